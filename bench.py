@@ -203,6 +203,23 @@ def timed_regions(h, sync, steps, warmup, repeats, pre, post, classes=("residual
     return times, prof, norms
 
 
+DUMP_BYTES = 32 << 20       # --dump-outputs: largest iterate written whole (a sample of it above)
+DUMP_SEED = 20251015
+
+
+def dump_outputs(out_dir, x, norm):
+    """--dump-outputs: the iterate after the last timed V-cycle (x.npy, in the levels' precision) and that cycle's
+    residual norm (residual_norm.npy, float64).  An iterate larger than DUMP_BYTES is written as the entries at a fixed
+    set of positions (DUMP_SEED, sorted), so runs with the same arguments write the same positions."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    k = DUMP_BYTES // x.itemsize
+    if x.size > k:
+        x = x[np.sort(np.random.default_rng(DUMP_SEED).choice(x.size, k, replace=False))]
+    np.save(os.path.join(out_dir, "x.npy"), x)
+    np.save(os.path.join(out_dir, "residual_norm.npy"), np.array([norm], dtype=np.float64))
+
+
 def residual_launch_bytes(h, meta, w):
     """The fine-grid residual launch r = b - A x of the set-by-set schedule: rows it covers, SURVEY 8(d)'s
     CSR bytes, and the bytes it has to move with the operator in its device format."""
@@ -510,7 +527,7 @@ def config1_leg(steps, warmup, repeats, sync_of):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--steps", type=int, default=30, help="V-cycles in each timed region (ms_per_step: one of them)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=11,
                     help="timed regions of --steps cycles each; value = steps / median region time (BASELINE.md §3)")
@@ -538,7 +555,11 @@ def main():
                     help="multi-GPU: grids handled across ranks (the last of them and all below run replicated)")
     ap.add_argument("--cpu-size", type=int, default=256, help="CPU baseline leg: grid extent (default: the full workload)")
     ap.add_argument("--cpu-cycles", type=int, default=4)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="single GPU: after the timed regions, write what the last timed V-cycle computed (the iterate, a fixed seeded sample of it above %d MiB, and its residual norm) as DIR/<name>.npy" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or args.dist or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--dump-outputs: the single-GPU run only")
 
     # identity of the sources, resolved BEFORE anything initialises the GPU (no fork from a GPU process) and
     # handed to the children of a multi-GPU launch
@@ -587,6 +608,8 @@ def main():
     times, timed, region_norms = timed_regions(h, syncer(h), args.steps, args.warmup, repeats, pre, post,
                                                () if args.graph else (roof_class,), graph=bool(args.graph))
     elapsed = statistics.median(times)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, h.resident_fetch().astype(np_dtype), region_norms[-1])
     norm = h.resident_cycle(pre, post, want_norm=True)          # untimed: read the norm back once
 
     # Second, untimed region: every level-0 kernel class, for the per-kernel table.

@@ -78,3 +78,55 @@ def test_pmc_traffic_is_tied_to_the_kernel_sources_it_was_measured_on(rnd):
         assert d["config"]["kernel_src_sha"] == p["kernel_src_sha"]
         assert abs(d["roofline"]["traffic"] - p["traffic_bytes"]) <= 1e-3 * p["traffic_bytes"]
         assert "NOT measured in this run" in d["roofline"]["traffic_source"]
+
+
+def test_dump_outputs_are_float_arrays_within_the_budget_and_the_same_sample_every_run(tmp_path):
+    """--dump-outputs: x.npy and residual_norm.npy in float32 / float64, 64 MB at most in all; an iterate above the budget
+    as the entries at one fixed, sorted set of positions (two runs: the same file), a small one whole."""
+    import numpy as np
+    x = np.arange(3 * bench.DUMP_BYTES // 8 + 5, dtype=np.float64)           # entry i holds i: the positions written
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), x, 0.25)
+    files = sorted(os.listdir(str(tmp_path / "a")))
+    assert files == ["residual_norm.npy", "x.npy"]
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in files) <= 64e6
+    got = np.load(str(tmp_path / "a" / "x.npy"))
+    assert got.dtype == np.float64 and got.size == bench.DUMP_BYTES // 8
+    assert np.all(np.diff(got) > 0) and got[0] >= 0 and got[-1] < x.size
+    assert np.array_equal(got, np.load(str(tmp_path / "b" / "x.npy")))
+    assert np.load(str(tmp_path / "a" / "residual_norm.npy")).tolist() == [0.25]
+    small = np.random.default_rng(3).random(1000).astype(np.float32)
+    bench.dump_outputs(str(tmp_path / "c"), small, 1.5)
+    got = np.load(str(tmp_path / "c" / "x.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, small)
+
+
+@pytest.mark.gpu
+def test_dump_outputs_hold_the_iterate_and_norm_of_the_last_timed_cycle(tmp_path):
+    """`bench.py --dump-outputs DIR` at 32^3: x.npy and residual_norm.npy have the bits of the same warm-up and timed cycles
+    run here on a hierarchy of bench.py's problem; the line counts exactly --steps cycles per timed region."""
+    import subprocess
+    import sys
+    import numpy as np
+    from openmg_amd import _hip, operators
+    size, grids, steps, warmup, repeats = 32, 3, 3, 2, 2
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--size", str(size), "--grids", str(grids),
+                        "--steps", str(steps), "--warmup", str(warmup), "--repeats", str(repeats), "--no-cpu", "--no-plain",
+                        "--no-sets", "--no-lex", "--no-dropin", "--no-config4", "--no-config1", "--dump-outputs", str(tmp_path)],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = json.loads(p.stdout.strip().splitlines()[-1])
+    assert d["steps"] == steps and d["ms_per_step"] > 0 and len(d["config"]["ms_per_step_all"]) == repeats
+    shape = (size,) * 3
+    A0 = operators.stencil_poisson(shape)
+    b = A0 @ np.random.default_rng(12345).random(A0.shape[0])
+    R = operators.restrictionList(shape, grids - 2, 8)
+    with _hip.Hierarchy(operators.coeffecientList(A0, R), R, smoother="colour") as h:
+        h.resident_load(b)
+        h.resident_cycles(1, 1, warmup)
+        for _ in range(repeats):
+            norms = h.resident_cycles(1, 1, steps)
+        x = h.resident_fetch()
+    got = np.load(str(tmp_path / "x.npy"))
+    assert got.dtype == np.float64 and np.array_equal(got, x), int(np.sum(got != x))
+    assert np.load(str(tmp_path / "residual_norm.npy")).tolist() == [norms[-1]]
