@@ -223,6 +223,16 @@ int omg_resident_fetch(omg_hierarchy *h, double *x);
 /* Fine-grid SpMV y = A[0] x (tools.flexibleMmult, openmg/tools.py:26) on the resident
  * operator, `reps` back-to-back launches inside one hipEvent bracket; *avg_ms per launch. */
 int omg_resident_spmv_time(omg_hierarchy *h, int reps, double *avg_ms);
+/* Flexible preconditioned conjugate gradients (FCG(1), Polak-Ribiere) on the resident level 0, one zero-start V-cycle
+ * V(pre, post) as the preconditioner per iteration.  Starts from the resident iterate (omg_resident_load[_dev]); stops
+ * at the first iteration whose recurrence norm ||r||_2 is below threshold (> 0), or after max_iter (>= 1).  Afterwards
+ * the resident iterate is the solution and the resident right-hand side b again (omg_resident_fetch[_dev]; a later
+ * omg_resident_cycle continues from it).  *iterations: iterations done; norms[max_iter] (nullable): the recurrence norm
+ * of each; *true_norm: ||b - A x||_2 once at the end; *breakdown: 1 when (p, q) <= 0 or a scalar was not finite — the
+ * last finite iterate stays resident and the call still returns OMG_OK.  Dots and scalars in double for either dtype;
+ * the reductions are deterministic (same bits from run to run, with or without omg_resident_use_graph). */
+int omg_resident_pcg(omg_hierarchy *h, int pre, int post, int max_iter, double threshold, int *iterations,
+                     double *norms /* nullable */, double *true_norm, int *breakdown);
 /* Capture one resident cycle into a hipGraph and replay it on later omg_resident_cycle
  * calls with the same (pre, post).  enable = 0 drops the graph.                          */
 int omg_resident_use_graph(omg_hierarchy *h, int enable);

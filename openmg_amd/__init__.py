@@ -11,6 +11,11 @@ Extra keys understood in the `parameters` dict (ignored by the reference):
     'smoother'  'gs' (default: the reference's lexicographic Gauss-Seidel iterate),
                 'colour' (multi-colour GS; red-black on 5/7-point stencils) or 'jacobi'
     'omega'     relaxation weight for 'jacobi' (default 2/3)
+    'accel'     mgSolve only: None (default: plain V-cycles, the reference's loop) or 'cg': flexible preconditioned
+                conjugate gradients (FCG(1)) on the finest level with one zero-start V-cycle as the preconditioner per
+                iteration — 'cycles' then caps the CG iterations, 'threshold' is the target of the recurrence residual
+                norm, infoDict['cycle'] counts iterations and infoDict['norm'] is the true ||b - A u||; a CG breakdown
+                (an indefinite operator or preconditioner) raises RuntimeError.  Any other value raises ValueError
     'dtype'     'float64' (default, the reference's precision) or 'float32': the precision the
                 levels are stored and computed in on the device (inputs / outputs stay float64)
     'trustOperators'  mgCycle only, default False: when the caller passes the SAME list members (object identity) it
@@ -156,6 +161,9 @@ def mgSolve(A_in, b, parameters):
     Returns u, or (u, infoDict) when parameters['giveInfo'] is true; infoDict holds
     'cycle', 'norm', and the hierarchies 'R' and 'A' as SciPy CSR lists.
     """
+    accel = parameters.get("accel")
+    if accel not in (None, "cg"):
+        raise ValueError("parameters['accel'] must be None or 'cg', not %r" % (accel,))
     problemShape = parameters["problemShape"]
     gridLevels = parameters["gridLevels"]
     defaults["coarsestLevel"] = gridLevels - 1
@@ -190,33 +198,10 @@ def mgSolve(A_in, b, parameters):
             hierarchy.resident_load_dev(_devarray.address(b, hierarchy.sizes[0], "b"))
         else:
             hierarchy.resident_load(np.asarray(b, dtype=np.float64).reshape(-1))
-        if verbose:
-            _announce_descent(depth)
-        norm = hierarchy.resident_cycle(pre, post)
-        cycle = 1
-        if verbose:
-            print("Residual norm from cycle %d is %f." % (cycle, norm))
-        if parameters["threshold"] <= 0 and parameters["cycles"] <= 0:
-            raise ValueError("Either parameters['threshold'] or parameters['cycles'] must be > 0.")
-
-        def finished():
-            by_count = parameters.get("cycles", 0) > 0 and cycle >= parameters["cycles"]
-            by_norm = "threshold" in parameters and parameters["threshold"] > 0 and norm < parameters["threshold"]
-            return by_count or by_norm
-
-        if (not verbose and parameters.get("cycles", 0) > cycle and not parameters.get("threshold", 0) > 0):
-            # stop rule = cycle count only: the remaining cycles go to the device in one call (every
-            # cycle's norm is still computed; only the last one is observable here)
-            norm = hierarchy.resident_cycles(pre, post, parameters["cycles"] - cycle)[-1]
-            cycle = parameters["cycles"]
-        while not finished():
-            if verbose:
-                print("cycle %i < cycles %i" % (cycle, parameters["cycles"]))
-                _announce_descent(depth)
-            cycle += 1
-            norm = hierarchy.resident_cycle(pre, post)
-            if verbose:
-                print("Residual norm from cycle %d is %f." % (cycle, norm))
+        if accel == "cg":
+            cycle, norm = _solve_cg(hierarchy, parameters, pre, post, depth, verbose)
+        else:
+            cycle, norm = _solve_cycles(hierarchy, parameters, pre, post, depth, verbose)
         if b_on_device:
             result = _devarray.empty_like(b, hierarchy.sizes[0])
             hierarchy.resident_fetch_dev(_devarray.address(result, hierarchy.sizes[0], "result"))
@@ -231,6 +216,64 @@ def mgSolve(A_in, b, parameters):
     if parameters["giveInfo"]:
         return result, infoDict
     return result
+
+
+# CG iterations per omg_resident_pcg call when only 'threshold' stops the solve (the next call restarts from the iterate)
+_CG_CHUNK = 10000
+
+
+def _solve_cg(hierarchy, parameters, pre, post, depth, verbose):
+    """mgSolve's loop with parameters['accel'] == 'cg': FCG on the resident iterate; returns (iterations, true norm)."""
+    cycles, threshold = parameters["cycles"], parameters["threshold"]
+    both_off = threshold <= 0 and cycles <= 0
+    done = 0
+    while True:
+        max_iter = 1 if both_off else (cycles - done if cycles > 0 else _CG_CHUNK)
+        its, norms, norm, breakdown = hierarchy.resident_pcg(pre, post, max_iter, threshold if threshold > 0 else 0.0)
+        if verbose:
+            for k, nk in enumerate(norms):
+                _announce_descent(depth)
+                print("Residual norm from cycle %d is %f." % (done + k + 1, nk))
+        if breakdown:
+            raise RuntimeError("mgSolve accel='cg': conjugate gradients broke down in iteration %d (the operator or the "
+                               "V-cycle is not positive definite)" % (done + its + 1))
+        done += its
+        if both_off:
+            raise ValueError("Either parameters['threshold'] or parameters['cycles'] must be > 0.")
+        if (cycles > 0 and done >= cycles) or (threshold > 0 and len(norms) and norms[-1] < threshold):
+            return done, norm
+
+
+def _solve_cycles(hierarchy, parameters, pre, post, depth, verbose):
+    """mgSolve's loop of plain V-cycles (openmg/__init__.py:112-138); returns (cycles, norm)."""
+    if verbose:
+        _announce_descent(depth)
+    norm = hierarchy.resident_cycle(pre, post)
+    cycle = 1
+    if verbose:
+        print("Residual norm from cycle %d is %f." % (cycle, norm))
+    if parameters["threshold"] <= 0 and parameters["cycles"] <= 0:
+        raise ValueError("Either parameters['threshold'] or parameters['cycles'] must be > 0.")
+
+    def finished():
+        by_count = parameters.get("cycles", 0) > 0 and cycle >= parameters["cycles"]
+        by_norm = "threshold" in parameters and parameters["threshold"] > 0 and norm < parameters["threshold"]
+        return by_count or by_norm
+
+    if (not verbose and parameters.get("cycles", 0) > cycle and not parameters.get("threshold", 0) > 0):
+        # stop rule = cycle count only: the remaining cycles go to the device in one call (every
+        # cycle's norm is still computed; only the last one is observable here)
+        norm = hierarchy.resident_cycles(pre, post, parameters["cycles"] - cycle)[-1]
+        cycle = parameters["cycles"]
+    while not finished():
+        if verbose:
+            print("cycle %i < cycles %i" % (cycle, parameters["cycles"]))
+            _announce_descent(depth)
+        cycle += 1
+        norm = hierarchy.resident_cycle(pre, post)
+        if verbose:
+            print("Residual norm from cycle %d is %f." % (cycle, norm))
+    return cycle, norm
 
 
 def _device_setup_depth(A_in, problemShape, parameters):

@@ -86,6 +86,7 @@ SIGNATURES = {
     "omg_resident_fetch": (_I, [_P, _P]),
     "omg_resident_spmv_time": (_I, [_P, _I, _DP]),
     "omg_resident_use_graph": (_I, [_P, _I]),
+    "omg_resident_pcg": (_I, [_P, _I, _I, _I, _D, _IP, _DP, _DP, _IP]),
     "omg_profile_enable": (_I, [_P, _I]),
     "omg_profile_read": (_I, [_P, _I64P, _DP]),
     "omg_level_smooth": (_I, [_P, _I, _P, _P, _I]),
@@ -440,6 +441,19 @@ class Hierarchy:
         x = np.empty(self.sizes[0], dtype=np.float64)
         check(lib().omg_resident_fetch(self._h, x.ctypes.data))
         return x
+
+    def resident_pcg(self, pre, post, max_iter, threshold=0.0):
+        """Flexible CG preconditioned by one zero-start V(pre, post) cycle per iteration, from the resident iterate
+        (omg_resident_pcg).  Returns (iterations, norms ndarray of the recurrence norm per iteration, true_norm, breakdown);
+        the solution stays resident (resident_fetch)."""
+        max_iter = int(max_iter)
+        if max_iter < 1:
+            raise ValueError("max_iter must be >= 1")
+        norms = np.zeros(max_iter, dtype=np.float64)
+        it, tn, bd = ctypes.c_int(0), ctypes.c_double(0.0), ctypes.c_int(0)
+        check(lib().omg_resident_pcg(self._h, int(pre), int(post), max_iter, float(threshold), ctypes.byref(it),
+                                     norms.ctypes.data_as(_DP), ctypes.byref(tn), ctypes.byref(bd)))
+        return int(it.value), norms[:it.value].copy(), float(tn.value), bool(bd.value)
 
     def spmv_time(self, reps=20):
         """Average milliseconds of one fine-grid y = A[0] x launch on the resident operator."""

@@ -903,4 +903,39 @@ struct Stencil27Plan {
     void rap_from(const int32_t *indptr, const double *vals, bool write_fine, double *coarse_dense, Stencil27Plan<V> *coarse, hipStream_t s);
 };
 
+// ---- flexible preconditioned CG on a hierarchy's finest level (pcg.hip; driven by hierarchy.hip omg_resident_pcg) -----
+// The iteration's scalars: one device array of PCG_NSC doubles.  PCG_DONE set (converged, breakdown) turns every
+// pcg_* launch after it into a no-op.
+enum { PCG_RHO = 0, PCG_ALPHA = 1, PCG_BETA = 2, PCG_DONE = 3, PCG_BREAK = 4, PCG_ITERS = 5, PCG_NSC = 8 };
+constexpr int PCG_MAX_WG = 2048;      // workgroups of a pcg launch at most (grid stride beyond): partials per reduction
+// a plane level's operator (PlanePlan: red-black layout, nr = n / 2 red slots first, hx = nx / 2 cells per colour and line)
+struct PcgPlane {
+    int nx, ny, nz, hx;
+    int64_t nr;
+    double c[7];                      // -K, -J, -I, diagonal, +I, +J, +K
+};
+template <typename V>
+int pcg_wgs(int64_t n);               // workgroups (= partials) of the streaming launches over n values
+// (r, z) -> part[0, nwg), (z, q) -> part[nwg, 2 nwg)
+template <typename V>
+void pcg_dots(const V *r, const V *z, const V *q, int64_t n, double *part, const double *sc, hipStream_t s);
+template <typename V>
+void pcg_dot(const V *a, const V *b, int64_t n, double *part, const double *sc, hipStream_t s);
+// p2 = z + beta p
+template <typename V>
+void pcg_pupdate(const V *z, const V *p, V *p2, int64_t n, const double *sc, hipStream_t s);
+// x += alpha p ; r -= alpha q ; ||r||^2 partials
+template <typename V>
+void pcg_update(V *x, const V *p, V *r, const V *q, int64_t n, double *part, const double *sc, hipStream_t s);
+// r = b - q (r nullable) and ||b - q||^2 partials; runs whatever PCG_DONE says
+template <typename V>
+void pcg_residual(const V *b, const V *q, V *r, int64_t n, double *part, hipStream_t s);
+// p2 = z + beta p ; q = A p2 ; (p2, q) partials, matrix-free on a plane level; returns the partials' count
+template <typename V>
+int pcg_plane_step(const PcgPlane &g, const V *z, const V *p, V *p2, V *q, double *part, const double *sc, hipStream_t s);
+void pcg_fold_beta(const double *part, int nwg, double *sc, bool first, hipStream_t s);
+void pcg_fold_alpha(const double *part, int nwg, double *sc, hipStream_t s);
+void pcg_fold_norm(const double *part, int nwg, double *sc, double *norms, int k, double threshold, hipStream_t s);
+void pcg_fold_sqrt(const double *part, int nwg, double *out, hipStream_t s);
+
 }  // namespace omg

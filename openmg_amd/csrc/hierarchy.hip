@@ -192,6 +192,10 @@ struct Hier {
     int pre_level = -1;
     DevBuf<double> norms_dev;      // omg_resident_cycles: one norm per cycle of the batch
     DevBuf<double> batch_partials; // ... and the block partials of up to 64 deferred norms
+    // omg_resident_pcg (level 0, its numbering): a copy of b, the iterate x, the search direction p and its successor p2, q = A p;
+    // the scalars (PCG_NSC, then PCG_NSC zeros: beta = 0, not done), the workgroup partials, one norm per iteration
+    DevBuf<V> pcg_b, pcg_x, pcg_p, pcg_p2, pcg_q;
+    DevBuf<double> pcg_sc, pcg_part, pcg_norms;
     int smoother = OMG_SMOOTH_GS_LEX;
     double omega = 1.0;
     hipStream_t own = nullptr, stream = nullptr;
@@ -1670,6 +1674,144 @@ void with(const omg_hierarchy *h, F &&f) {
 template <typename HP>
 using value_of = typename std::remove_cv<typename std::remove_pointer<HP>::type>::type::value_type;
 
+// One level-0 V-cycle from a zero iterate: the right-hand side in L.b, the result left in L.xp (openmg/__init__.py:191-192;
+// omg_hierarchy_cycle_dev, and the preconditioner of omg_resident_pcg)
+template <typename V>
+void zero_start_cycle(Hier<V> *hh, int pre, int post) {
+    Level<V> &L = hh->lv[0];
+    bool first = false, zero_in = false;
+    if (hh->lv.size() > 1) {
+        zero_in = (use_plane(hh, L, pre, post) && pre == 1) || (use_s27(hh, L) && pre >= 1) || (use_var7(hh, L) && pre == 1);   // the down pass / first sweep does not read a zero iterate
+        if (!zero_in) {
+            // x starts from zero: the first relaxation launch is a pointwise b / diag (restrict_level).  The
+            // diagonal comes from the row-kernel format, which a plane level builds on first use: BEFORE it
+            // (with the format still pending the diagonal stayed uninitialised)
+            if (pre > 0) {
+                ensure_format(hh, 0);
+                if (!L.diag.p && !getenv_flag("OMG_NO_FIRST_SWEEP")) {
+                    L.diag.alloc(std::max<int64_t>(L.n, 1));
+                    launch_diagonal(L.A, L.diag.p, hh->stream);
+                }
+            }
+            first = pre > 0 && first_sweep_in_restrict(hh, L, pre);
+            if (first) {
+                const bool jac = hh->smoother == OMG_SMOOTH_JACOBI;
+                launch_first_relaxation<V>(L.b.p, L.diag.p, L.xp, L.n, jac ? L.n : L.A.sets[1], jac, hh->omega, hh->stream);
+            } else {
+                OMG_HIP(hipMemsetAsync(L.xp, 0, L.n * sizeof(V), hh->stream));
+            }
+        }
+    }
+    cycle_body(hh, 0, pre, post, false, nullptr, first, nullptr, zero_in);
+}
+
+// ---- omg_resident_pcg: flexible CG on level 0 with the zero-start V-cycle as its preconditioner (pcg.hip) ---------------
+// r lives where the cycle reads its right-hand side (L.b), z where it leaves its iterate (L.xp); x, p, p2, q and a copy
+// of b are the hierarchy's own.  A plane level (red-black, whole grid) forms p2 = z + beta p, q = A p2 and (p2, q) in one
+// launch; any other level updates p, runs the level's SpMV and the dot as three.
+template <typename V>
+bool pcg_fused_plane(const Hier<V> *hh, const Level<V> &L) {
+    return hh->lv.size() > 1 && use_plane(hh, L, 1, 1) && !L.plane->g.jacobi && L.plane->g.z_base == 0 && L.plane->g.z_end == L.plane->g.nz;
+}
+
+template <typename V>
+PcgPlane pcg_plane_of(const Level<V> &L) {
+    const PlaneGeom &g = L.plane->g;
+    PcgPlane pg;
+    pg.nx = g.nx; pg.ny = g.ny; pg.nz = g.nz; pg.hx = g.hx;
+    pg.nr = L.n / 2;
+    for (int i = 0; i < 7; ++i) pg.c[i] = g.c[i];
+    return pg;
+}
+
+// q = A v on level 0 (v in its numbering); sc0: the zero scalars (the fused launch with beta = 0 and nothing done; p2 scratch)
+template <typename V>
+void pcg_apply(Hier<V> *hh, const V *v, V *q, V *scratch, const double *sc0) {
+    Level<V> &L = hh->lv[0];
+    if (pcg_fused_plane(hh, L)) {
+        pcg_plane_step<V>(pcg_plane_of(L), v, v, scratch, q, hh->pcg_part.p, sc0, hh->stream);
+        return;
+    }
+    ensure_format(hh, 0);
+    RowArgsT<V> a;
+    a.x = const_cast<V *>(v);
+    a.y = q;
+    launch_rows(L.A, ROW_SPMV, -1, a, hh->stream);
+}
+
+template <typename V>
+void resident_pcg(Hier<V> *hh, int pre, int post, int max_iter, double threshold, int *iterations, double *norms, double *true_norm,
+                  int *breakdown) {
+    Level<V> &L = hh->lv[0];
+    const int64_t n = L.n;
+    hipStream_t s = hh->stream;
+    const size_t vn = size_t(std::max<int64_t>(n, 1));
+    for (DevBuf<V> *b : {&hh->pcg_b, &hh->pcg_x, &hh->pcg_p, &hh->pcg_p2, &hh->pcg_q})
+        if (b->n < vn) b->alloc(vn);
+    if (hh->pcg_sc.n < size_t(2 * PCG_NSC)) hh->pcg_sc.alloc(2 * PCG_NSC);
+    if (hh->pcg_part.n < size_t(2 * PCG_MAX_WG)) hh->pcg_part.alloc(2 * PCG_MAX_WG);
+    if (hh->pcg_norms.n < size_t(max_iter)) hh->pcg_norms.alloc(size_t(max_iter));
+    double *sc = hh->pcg_sc.p, *sc0 = hh->pcg_sc.p + PCG_NSC, *part = hh->pcg_part.p;
+    V *B = hh->pcg_b.p, *X = hh->pcg_x.p, *Q = hh->pcg_q.p;
+    V *P = hh->pcg_p.p, *P2 = hh->pcg_p2.p;
+    const bool fused = pcg_fused_plane(hh, L);
+    const PcgPlane pg = fused ? pcg_plane_of(L) : PcgPlane{};
+    if (!fused) ensure_format(hh, 0);
+    const int nwg = pcg_wgs<V>(n);
+    OMG_HIP(hipMemsetAsync(sc, 0, 2 * PCG_NSC * sizeof(double), s));
+    OMG_HIP(hipMemcpyAsync(B, L.b.p, size_t(n) * sizeof(V), hipMemcpyDeviceToDevice, s));
+    OMG_HIP(hipMemcpyAsync(X, L.xp, size_t(n) * sizeof(V), hipMemcpyDeviceToDevice, s));
+    OMG_HIP(hipMemsetAsync(P, 0, size_t(n) * sizeof(V), s));       // (beta = 0 in the first iteration multiplies it)
+    pcg_apply(hh, X, Q, P2, sc0);
+    pcg_residual<V>(B, Q, L.b.p, n, part, s);                      // r = b - A x0
+    constexpr int BATCH = 16;
+    double hs[PCG_NSC] = {0};
+    int k = 0;
+    while (k < max_iter) {
+        const int cnt = std::min(BATCH, max_iter - k);
+        for (int j = 0; j < cnt; ++j, ++k) {
+            zero_start_cycle(hh, pre, post);                       // z = M(r)
+            V *Z = L.xp, *R = L.b.p;
+            pcg_dots<V>(R, Z, Q, n, part, sc, s);
+            pcg_fold_beta(part, nwg, sc, k == 0, s);
+            int nwg2 = nwg;
+            if (fused) {
+                nwg2 = pcg_plane_step<V>(pg, Z, P, P2, Q, part, sc, s);
+            } else {
+                pcg_pupdate<V>(Z, P, P2, n, sc, s);
+                RowArgsT<V> a;
+                a.x = P2;
+                a.y = Q;
+                launch_rows(L.A, ROW_SPMV, -1, a, s);
+                pcg_dot<V>(P2, Q, n, part, sc, s);
+            }
+            std::swap(P, P2);
+            pcg_fold_alpha(part, nwg2, sc, s);
+            pcg_update<V>(X, P, R, Q, n, part, sc, s);
+            pcg_fold_norm(part, nwg, sc, hh->pcg_norms.p, k, threshold, s);
+        }
+        OMG_HIP(hipMemcpyAsync(hs, sc, sizeof(hs), hipMemcpyDeviceToHost, s));
+        OMG_HIP(hipStreamSynchronize(s));
+        check_march(hh);
+        if (hs[PCG_DONE] != 0.0) break;
+    }
+    const int iters = int(hs[PCG_ITERS]);
+    if (norms && iters > 0) OMG_HIP(hipMemcpyAsync(norms, hh->pcg_norms.p, size_t(iters) * sizeof(double), hipMemcpyDeviceToHost, s));
+    // the resident state: x as the iterate, b as the right-hand side; the true residual once
+    OMG_HIP(hipMemcpyAsync(L.xp, X, size_t(n) * sizeof(V), hipMemcpyDeviceToDevice, s));
+    OMG_HIP(hipMemcpyAsync(L.b.p, B, size_t(n) * sizeof(V), hipMemcpyDeviceToDevice, s));
+    pcg_apply(hh, X, Q, P2, sc0);
+    pcg_residual<V>(B, Q, static_cast<V *>(nullptr), n, part, s);
+    pcg_fold_sqrt(part, nwg, sc0 + PCG_ITERS, s);
+    double tn = 0.0;
+    OMG_HIP(hipMemcpyAsync(&tn, sc0 + PCG_ITERS, sizeof(double), hipMemcpyDeviceToHost, s));
+    OMG_HIP(hipStreamSynchronize(s));
+    check_march(hh);
+    if (iterations) *iterations = iters;
+    if (true_norm) *true_norm = tn;
+    if (breakdown) *breakdown = hs[PCG_BREAK] != 0.0 ? 1 : 0;
+}
+
 }  // namespace
 }  // namespace omg
 
@@ -2038,30 +2180,7 @@ int omg_hierarchy_cycle_dev(omg_hierarchy *h, const double *b_dev, double *x_dev
                 const int32_t *perm = L.ord.identity ? nullptr : L.perm.p;
                 if (direct_io(L)) OMG_HIP(hipMemcpyAsync(L.b.p, b_dev, L.n * sizeof(double), hipMemcpyDeviceToDevice, hh->stream));
                 else launch_gather<double, V>(b_dev, perm, L.b.p, L.n, hh->stream);
-                bool first = false, zero_in = false;
-                if (hh->lv.size() > 1) {
-                    zero_in = (use_plane(hh, L, pre, post) && pre == 1) || (use_s27(hh, L) && pre >= 1) || (use_var7(hh, L) && pre == 1);   // the down pass / first sweep does not read a zero iterate
-                    if (!zero_in) {
-                        // x starts from zero: the first relaxation launch is a pointwise b / diag (restrict_level).  The
-                        // diagonal comes from the row-kernel format, which a plane level builds on first use: BEFORE it
-                        // (with the format still pending the diagonal stayed uninitialised)
-                        if (pre > 0) {
-                            ensure_format(hh, 0);
-                            if (!L.diag.p && !getenv_flag("OMG_NO_FIRST_SWEEP")) {
-                                L.diag.alloc(std::max<int64_t>(L.n, 1));
-                                launch_diagonal(L.A, L.diag.p, hh->stream);
-                            }
-                        }
-                        first = pre > 0 && first_sweep_in_restrict(hh, L, pre);
-                        if (first) {
-                            const bool jac = hh->smoother == OMG_SMOOTH_JACOBI;
-                            launch_first_relaxation<V>(L.b.p, L.diag.p, L.xp, L.n, jac ? L.n : L.A.sets[1], jac, hh->omega, hh->stream);
-                        } else {
-                            OMG_HIP(hipMemsetAsync(L.xp, 0, L.n * sizeof(V), hh->stream));
-                        }
-                    }
-                }
-                cycle_body(hh, 0, pre, post, false, nullptr, first, nullptr, zero_in);
+                zero_start_cycle(hh, pre, post);
                 if (direct_io(L)) OMG_HIP(hipMemcpyAsync(x_dev, L.xp, L.n * sizeof(double), hipMemcpyDeviceToDevice, hh->stream));
                 else launch_scatter<V, double>(L.xp, perm, x_dev, L.n, hh->stream);
             } catch (...) {
@@ -2261,6 +2380,19 @@ int omg_resident_fetch(omg_hierarchy *h, double *x) {
             check_level(hh, 0);
             OMG_REQUIRE(hh->resident && x, "nothing resident / x is null");
             fetch_vec<V>(hh, 0, hh->lv[0].xp, x);
+        });
+    });
+}
+
+int omg_resident_pcg(omg_hierarchy *h, int pre, int post, int max_iter, double threshold, int *iterations, double *norms,
+                     double *true_norm, int *breakdown) {
+    return guarded([&] {
+        with(h, [&](auto *hh) {
+            check_level(hh, 0);
+            OMG_REQUIRE(hh->resident, "omg_resident_load has not been called");
+            OMG_REQUIRE(pre >= 0 && post >= 0 && max_iter >= 1, "negative sweep count / max_iter < 1");
+            OMG_REQUIRE(hh->lv.size() > 1, "a single-level hierarchy solves directly: nothing to accelerate");
+            resident_pcg(hh, pre, post, max_iter, threshold, iterations, norms, true_norm, breakdown);
         });
     });
 }

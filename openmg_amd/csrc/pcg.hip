@@ -1,0 +1,364 @@
+// Flexible preconditioned conjugate gradients on the finest level of a hierarchy (omg_resident_pcg; hierarchy.hip drives
+// it, common.h declares the launchers).  Notay's FCG(1) in the Polak-Ribiere form, one zero-start V-cycle as the
+// preconditioner per iteration:
+//
+//   r = b - A x ; z = M(r) ; p = z ; rho = (r, z)
+//   loop:  q = A p ; alpha = rho / (p, q) ; x += alpha p ; r -= alpha q ; stop on ||r||
+//          z = M(r) ; beta = -alpha (z, q) / rho ; rho = (r, z) ; p = z + beta p
+//
+// Every vector is in the level's own numbering (inner products do not depend on the order).  The scalars live on the
+// device (PCG_* slots of one double array): every reduction leaves one partial per workgroup in a fixed slot, and a
+// one-workgroup fold adds the slots in a fixed order and derives alpha / beta from them — the same bits from run to run,
+// no host round trip per iteration, no float atomics.  A fold that meets convergence or a breakdown raises PCG_DONE;
+// every kernel here returns at once when it is set, so the iterate stays that of the first converged iteration.
+#include <algorithm>
+#include <cmath>
+
+#include "common.h"
+
+namespace omg {
+namespace {
+
+constexpr int PCG_WG = 256;
+
+// deterministic sum of the 256 values of a workgroup (fixed tree)
+__device__ __forceinline__ double block_sum(double v, double *sh) {
+    const int t = int(threadIdx.x);
+    sh[t] = v;
+    __syncthreads();
+#pragma unroll
+    for (int s = PCG_WG / 2; s > 0; s >>= 1) {
+        if (t < s) sh[t] += sh[t + s];
+        __syncthreads();
+    }
+    return sh[0];
+}
+
+// element chunks of 16 bytes (VW values) where every pointer is 16-byte aligned, single values otherwise
+template <typename V, int VW>
+struct Chunk {
+    V v[VW];
+};
+template <typename V, int VW>
+__device__ __forceinline__ Chunk<V, VW> ld(const V *p, int64_t c) {
+    return reinterpret_cast<const Chunk<V, VW> *>(p)[c];
+}
+template <typename V, int VW>
+__device__ __forceinline__ void st(V *p, int64_t c, const Chunk<V, VW> &v) {
+    reinterpret_cast<Chunk<V, VW> *>(p)[c] = v;
+}
+
+__device__ __forceinline__ bool pcg_done(const double *sc) { return sc[PCG_DONE] != 0.0; }
+
+// (r, z) -> part[wg], (z, q) -> part[nwg + wg]
+template <typename V, int VW>
+__global__ __launch_bounds__(PCG_WG) void dots_kernel(const V *__restrict__ r, const V *__restrict__ z, const V *__restrict__ q,
+                                                      int64_t n, double *__restrict__ part, const double *__restrict__ sc) {
+    __shared__ double sh[PCG_WG];
+    if (pcg_done(sc)) return;
+    const int64_t nc = n / VW, stride = int64_t(gridDim.x) * PCG_WG;
+    double rz = 0.0, zq = 0.0;
+    for (int64_t c = int64_t(blockIdx.x) * PCG_WG + threadIdx.x; c < nc; c += stride) {
+        const Chunk<V, VW> a = ld<V, VW>(r, c), b = ld<V, VW>(z, c), d = ld<V, VW>(q, c);
+#pragma unroll
+        for (int e = 0; e < VW; ++e) {
+            rz = fma(double(a.v[e]), double(b.v[e]), rz);
+            zq = fma(double(b.v[e]), double(d.v[e]), zq);
+        }
+    }
+    if (blockIdx.x == 0)
+        for (int64_t i = nc * VW + threadIdx.x; i < n; i += PCG_WG) {
+            rz = fma(double(r[i]), double(z[i]), rz);
+            zq = fma(double(z[i]), double(q[i]), zq);
+        }
+    rz = block_sum(rz, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = rz;
+    __syncthreads();
+    zq = block_sum(zq, sh);
+    if (threadIdx.x == 0) part[gridDim.x + blockIdx.x] = zq;
+}
+
+// (a, b) -> part[wg]
+template <typename V, int VW>
+__global__ __launch_bounds__(PCG_WG) void dot_kernel(const V *__restrict__ a, const V *__restrict__ b, int64_t n,
+                                                     double *__restrict__ part, const double *__restrict__ sc) {
+    __shared__ double sh[PCG_WG];
+    if (pcg_done(sc)) return;
+    const int64_t nc = n / VW, stride = int64_t(gridDim.x) * PCG_WG;
+    double s = 0.0;
+    for (int64_t c = int64_t(blockIdx.x) * PCG_WG + threadIdx.x; c < nc; c += stride) {
+        const Chunk<V, VW> u = ld<V, VW>(a, c), w = ld<V, VW>(b, c);
+#pragma unroll
+        for (int e = 0; e < VW; ++e) s = fma(double(u.v[e]), double(w.v[e]), s);
+    }
+    if (blockIdx.x == 0)
+        for (int64_t i = nc * VW + threadIdx.x; i < n; i += PCG_WG) s = fma(double(a[i]), double(b[i]), s);
+    s = block_sum(s, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// p2 = z + beta p
+template <typename V, int VW>
+__global__ __launch_bounds__(PCG_WG) void pupdate_kernel(const V *__restrict__ z, const V *__restrict__ p, V *__restrict__ p2,
+                                                         int64_t n, const double *__restrict__ sc) {
+    if (pcg_done(sc)) return;
+    const double beta = sc[PCG_BETA];
+    const int64_t nc = n / VW, stride = int64_t(gridDim.x) * PCG_WG;
+    for (int64_t c = int64_t(blockIdx.x) * PCG_WG + threadIdx.x; c < nc; c += stride) {
+        const Chunk<V, VW> u = ld<V, VW>(z, c), w = ld<V, VW>(p, c);
+        Chunk<V, VW> o;
+#pragma unroll
+        for (int e = 0; e < VW; ++e) o.v[e] = V(fma(beta, double(w.v[e]), double(u.v[e])));
+        st<V, VW>(p2, c, o);
+    }
+    if (blockIdx.x == 0)
+        for (int64_t i = nc * VW + threadIdx.x; i < n; i += PCG_WG) p2[i] = V(fma(beta, double(p[i]), double(z[i])));
+}
+
+// x += alpha p ; r -= alpha q ; ||r||^2 -> part[wg]
+template <typename V, int VW>
+__global__ __launch_bounds__(PCG_WG) void update_kernel(V *__restrict__ x, const V *__restrict__ p, V *__restrict__ r,
+                                                        const V *__restrict__ q, int64_t n, double *__restrict__ part,
+                                                        const double *__restrict__ sc) {
+    __shared__ double sh[PCG_WG];
+    if (pcg_done(sc)) return;
+    const double alpha = sc[PCG_ALPHA];
+    const int64_t nc = n / VW, stride = int64_t(gridDim.x) * PCG_WG;
+    double rr = 0.0;
+    for (int64_t c = int64_t(blockIdx.x) * PCG_WG + threadIdx.x; c < nc; c += stride) {
+        Chunk<V, VW> xv = ld<V, VW>(x, c), rv = ld<V, VW>(r, c);
+        const Chunk<V, VW> pv = ld<V, VW>(p, c), qv = ld<V, VW>(q, c);
+#pragma unroll
+        for (int e = 0; e < VW; ++e) {
+            xv.v[e] = V(fma(alpha, double(pv.v[e]), double(xv.v[e])));
+            rv.v[e] = V(fma(-alpha, double(qv.v[e]), double(rv.v[e])));
+            rr = fma(double(rv.v[e]), double(rv.v[e]), rr);
+        }
+        st<V, VW>(x, c, xv);
+        st<V, VW>(r, c, rv);
+    }
+    if (blockIdx.x == 0)
+        for (int64_t i = nc * VW + threadIdx.x; i < n; i += PCG_WG) {
+            x[i] = V(fma(alpha, double(p[i]), double(x[i])));
+            r[i] = V(fma(-alpha, double(q[i]), double(r[i])));
+            rr = fma(double(r[i]), double(r[i]), rr);
+        }
+    rr = block_sum(rr, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = rr;
+}
+
+// r = b - q (r nullable) ; ||b - q||^2 -> part[wg].  Not gated by PCG_DONE (the set-up and the final true residual).
+template <typename V, int VW>
+__global__ __launch_bounds__(PCG_WG) void residual_kernel(const V *__restrict__ b, const V *__restrict__ q, V *__restrict__ r,
+                                                          int64_t n, double *__restrict__ part) {
+    __shared__ double sh[PCG_WG];
+    const int64_t nc = n / VW, stride = int64_t(gridDim.x) * PCG_WG;
+    double rr = 0.0;
+    for (int64_t c = int64_t(blockIdx.x) * PCG_WG + threadIdx.x; c < nc; c += stride) {
+        const Chunk<V, VW> bv = ld<V, VW>(b, c), qv = ld<V, VW>(q, c);
+        Chunk<V, VW> o;
+#pragma unroll
+        for (int e = 0; e < VW; ++e) {
+            o.v[e] = bv.v[e] - qv.v[e];
+            rr = fma(double(o.v[e]), double(o.v[e]), rr);
+        }
+        if (r) st<V, VW>(r, c, o);
+    }
+    if (blockIdx.x == 0)
+        for (int64_t i = nc * VW + threadIdx.x; i < n; i += PCG_WG) {
+            const V o = b[i] - q[i];
+            if (r) r[i] = o;
+            rr = fma(double(o), double(o), rr);
+        }
+    rr = block_sum(rr, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = rr;
+}
+
+// p2 = z + beta p, q = A p2 and (p2, q) -> part[wg] on a plane level: the constant-coefficient 7-point operator in the
+// plane passes' red-black layout (plane.hip: cell (i, j, k) of colour c = (i + j + k) & 1 sits at slot
+// c nr + k ny hx + j hx + i / 2).  One output slot per thread; the neighbours' p2 (all of the other colour) is formed from
+// their z and p again, so p2 goes to a buffer of its own.  Each row is the row kernels' fma chain in column order from +0
+// (-K, -J, -I, diagonal, +I, +J, +K); a neighbour outside the grid contributes c * 0.
+template <typename V>
+__global__ __launch_bounds__(PCG_WG) void plane_step_kernel(const V *__restrict__ z, const V *__restrict__ p, V *__restrict__ p2,
+                                                            V *__restrict__ q, PcgPlane g, double *__restrict__ part,
+                                                            const double *__restrict__ sc) {
+    __shared__ double sh[PCG_WG];
+    if (pcg_done(sc)) return;
+    const V beta = V(sc[PCG_BETA]);
+    const V c0 = V(g.c[0]), c1 = V(g.c[1]), c2 = V(g.c[2]), c3 = V(g.c[3]), c4 = V(g.c[4]), c5 = V(g.c[5]), c6 = V(g.c[6]);
+    const int64_t ps = int64_t(g.ny) * g.hx, n = 2 * g.nr, stride = int64_t(gridDim.x) * PCG_WG;
+    auto pv = [&](int64_t s) -> V { return V(fma(double(beta), double(p[s]), double(z[s]))); };
+    double pq = 0.0;
+    for (int64_t s = int64_t(blockIdx.x) * PCG_WG + threadIdx.x; s < n; s += stride) {
+        const int colour = s >= g.nr ? 1 : 0;
+        const int64_t u = s - (colour ? g.nr : 0);
+        const int k = int(u / ps);
+        const int64_t rem = u - int64_t(k) * ps;
+        const int j = int(rem / g.hx), h = int(rem - int64_t(j) * g.hx);
+        const int par = (j + k) & 1;
+        const int i = 2 * h + (colour ? 1 - par : par);
+        const int64_t ob = colour ? 0 : g.nr;                         // the other colour's first slot
+        const int64_t line = ob + int64_t(k) * ps + int64_t(j) * g.hx;
+        const V km = k > 0 ? pv(line - ps + (i >> 1)) : V(0);
+        const V jm = j > 0 ? pv(line - g.hx + (i >> 1)) : V(0);
+        const V im = i > 0 ? pv(line + ((i - 1) >> 1)) : V(0);
+        const V d = pv(s);
+        const V ip = i + 1 < g.nx ? pv(line + ((i + 1) >> 1)) : V(0);
+        const V jp = j + 1 < g.ny ? pv(line + g.hx + (i >> 1)) : V(0);
+        const V kp = k + 1 < g.nz ? pv(line + ps + (i >> 1)) : V(0);
+        V a = fma(c0, km, V(0));
+        a = fma(c1, jm, a);
+        a = fma(c2, im, a);
+        a = fma(c3, d, a);
+        a = fma(c4, ip, a);
+        a = fma(c5, jp, a);
+        a = fma(c6, kp, a);
+        p2[s] = d;
+        q[s] = a;
+        pq = fma(double(d), double(a), pq);
+    }
+    pq = block_sum(pq, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = pq;
+}
+
+// One workgroup: thread t adds slots t, t + 256, ... in order, then the fixed tree.
+__device__ __forceinline__ double fold(const double *part, int nwg, double *sh) {
+    double a = 0.0;
+    for (int i = int(threadIdx.x); i < nwg; i += PCG_WG) a += part[i];
+    return block_sum(a, sh);
+}
+
+__device__ __forceinline__ void pcg_break(double *sc) {
+    sc[PCG_BREAK] = 1.0;
+    sc[PCG_DONE] = 1.0;
+}
+
+// rho_new = (r, z); beta = -alpha (z, q) / rho_old (0 in the first iteration)
+__global__ __launch_bounds__(PCG_WG) void fold_beta_kernel(const double *__restrict__ part, int nwg, double *__restrict__ sc, int first) {
+    __shared__ double sh[PCG_WG];
+    if (pcg_done(sc)) return;
+    const double rz = fold(part, nwg, sh);
+    __syncthreads();
+    const double zq = fold(part + nwg, nwg, sh);
+    if (threadIdx.x != 0) return;
+    const double beta = first ? 0.0 : -sc[PCG_ALPHA] * zq / sc[PCG_RHO];
+    if (!std::isfinite(rz) || !std::isfinite(beta)) { pcg_break(sc); return; }
+    sc[PCG_BETA] = beta;
+    sc[PCG_RHO] = rz;
+}
+
+// alpha = rho / (p, q); (p, q) <= 0 or anything not finite: breakdown
+__global__ __launch_bounds__(PCG_WG) void fold_alpha_kernel(const double *__restrict__ part, int nwg, double *__restrict__ sc) {
+    __shared__ double sh[PCG_WG];
+    if (pcg_done(sc)) return;
+    const double pq = fold(part, nwg, sh);
+    if (threadIdx.x != 0) return;
+    const double alpha = sc[PCG_RHO] / pq;
+    if (!(pq > 0.0) || !std::isfinite(pq) || !std::isfinite(alpha)) { pcg_break(sc); return; }
+    sc[PCG_ALPHA] = alpha;
+}
+
+// ||r|| of iteration k -> norms[k]; PCG_ITERS = k + 1; done when below the threshold (> 0)
+__global__ __launch_bounds__(PCG_WG) void fold_norm_kernel(const double *__restrict__ part, int nwg, double *__restrict__ sc,
+                                                           double *__restrict__ norms, int k, double threshold) {
+    __shared__ double sh[PCG_WG];
+    if (pcg_done(sc)) return;
+    const double nr = sqrt(fold(part, nwg, sh));
+    if (threadIdx.x != 0) return;
+    norms[k] = nr;
+    sc[PCG_ITERS] = double(k + 1);
+    if (!std::isfinite(nr)) pcg_break(sc);
+    else if (threshold > 0.0 && nr < threshold) sc[PCG_DONE] = 1.0;
+}
+
+__global__ __launch_bounds__(PCG_WG) void fold_sqrt_kernel(const double *__restrict__ part, int nwg, double *__restrict__ out) {
+    __shared__ double sh[PCG_WG];
+    const double s = fold(part, nwg, sh);
+    if (threadIdx.x == 0) *out = sqrt(s);
+}
+
+template <typename V>
+constexpr int vec_width() { return int(16 / sizeof(V)); }
+
+bool aligned16(const void *a) { return (reinterpret_cast<uintptr_t>(a) & 15u) == 0; }
+
+}  // namespace
+
+template <typename V>
+int pcg_wgs(int64_t n) {
+    const int64_t chunks = (n + vec_width<V>() - 1) / vec_width<V>();
+    return int(std::max<int64_t>(1, std::min<int64_t>(PCG_MAX_WG, (chunks + PCG_WG - 1) / PCG_WG)));
+}
+
+// (each launcher picks the 16-byte form when every vector it touches is 16-byte aligned: the same sums either way
+// only up to the order inside a thread, so the choice is made from the pointers alone and repeats from run to run)
+#define PCG_LAUNCH(kern, ok, ...)                                                                                           \
+    do {                                                                                                                \
+        const int nwg_ = pcg_wgs<V>(n);                                                                                 \
+        if (ok) hipLaunchKernelGGL((kern<V, vec_width<V>()>), dim3(unsigned(nwg_)), dim3(PCG_WG), 0, s, __VA_ARGS__);  \
+        else hipLaunchKernelGGL((kern<V, 1>), dim3(unsigned(nwg_)), dim3(PCG_WG), 0, s, __VA_ARGS__);                  \
+        OMG_HIP(hipGetLastError());                                                                                     \
+    } while (0)
+
+template <typename V>
+void pcg_dots(const V *r, const V *z, const V *q, int64_t n, double *part, const double *sc, hipStream_t s) {
+    PCG_LAUNCH(dots_kernel, aligned16(r) && aligned16(z) && aligned16(q), r, z, q, n, part, sc);
+}
+template <typename V>
+void pcg_dot(const V *a, const V *b, int64_t n, double *part, const double *sc, hipStream_t s) {
+    PCG_LAUNCH(dot_kernel, aligned16(a) && aligned16(b), a, b, n, part, sc);
+}
+template <typename V>
+void pcg_pupdate(const V *z, const V *p, V *p2, int64_t n, const double *sc, hipStream_t s) {
+    PCG_LAUNCH(pupdate_kernel, aligned16(z) && aligned16(p) && aligned16(p2), z, p, p2, n, sc);
+}
+template <typename V>
+void pcg_update(V *x, const V *p, V *r, const V *q, int64_t n, double *part, const double *sc, hipStream_t s) {
+    PCG_LAUNCH(update_kernel, aligned16(x) && aligned16(p) && aligned16(r) && aligned16(q), x, p, r, q, n, part, sc);
+}
+template <typename V>
+void pcg_residual(const V *b, const V *q, V *r, int64_t n, double *part, hipStream_t s) {
+    PCG_LAUNCH(residual_kernel, aligned16(b) && aligned16(q) && aligned16(r), b, q, r, n, part);
+}
+#undef PCG_LAUNCH
+
+template <typename V>
+int pcg_plane_step(const PcgPlane &g, const V *z, const V *p, V *p2, V *q, double *part, const double *sc, hipStream_t s) {
+    const int64_t n = 2 * g.nr;
+    const int nwg = int(std::max<int64_t>(1, std::min<int64_t>(PCG_MAX_WG, (n + PCG_WG - 1) / PCG_WG)));
+    hipLaunchKernelGGL((plane_step_kernel<V>), dim3(unsigned(nwg)), dim3(PCG_WG), 0, s, z, p, p2, q, g, part, sc);
+    OMG_HIP(hipGetLastError());
+    return nwg;
+}
+
+void pcg_fold_beta(const double *part, int nwg, double *sc, bool first, hipStream_t s) {
+    hipLaunchKernelGGL(fold_beta_kernel, dim3(1), dim3(PCG_WG), 0, s, part, nwg, sc, first ? 1 : 0);
+    OMG_HIP(hipGetLastError());
+}
+void pcg_fold_alpha(const double *part, int nwg, double *sc, hipStream_t s) {
+    hipLaunchKernelGGL(fold_alpha_kernel, dim3(1), dim3(PCG_WG), 0, s, part, nwg, sc);
+    OMG_HIP(hipGetLastError());
+}
+void pcg_fold_norm(const double *part, int nwg, double *sc, double *norms, int k, double threshold, hipStream_t s) {
+    hipLaunchKernelGGL(fold_norm_kernel, dim3(1), dim3(PCG_WG), 0, s, part, nwg, sc, norms, k, threshold);
+    OMG_HIP(hipGetLastError());
+}
+void pcg_fold_sqrt(const double *part, int nwg, double *out, hipStream_t s) {
+    hipLaunchKernelGGL(fold_sqrt_kernel, dim3(1), dim3(PCG_WG), 0, s, part, nwg, out);
+    OMG_HIP(hipGetLastError());
+}
+
+#define PCG_INST(V)                                                                                             \
+    template int pcg_wgs<V>(int64_t);                                                                           \
+    template void pcg_dots<V>(const V *, const V *, const V *, int64_t, double *, const double *, hipStream_t); \
+    template void pcg_dot<V>(const V *, const V *, int64_t, double *, const double *, hipStream_t);             \
+    template void pcg_pupdate<V>(const V *, const V *, V *, int64_t, const double *, hipStream_t);              \
+    template void pcg_update<V>(V *, const V *, V *, const V *, int64_t, double *, const double *, hipStream_t); \
+    template void pcg_residual<V>(const V *, const V *, V *, int64_t, double *, hipStream_t);                   \
+    template int pcg_plane_step<V>(const PcgPlane &, const V *, const V *, V *, V *, double *, const double *, hipStream_t);
+PCG_INST(double)
+PCG_INST(float)
+#undef PCG_INST
+
+}  // namespace omg
