@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the multigrid V-cycle hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 One "step" = one V-cycle (pre-smooth, residual, restrict, recurse, coarse solve, prolong +
 correct, post-smooth, residual norm — openmg/__init__.py:151-236) on a synthetic 3-D 7-point
@@ -13,7 +13,9 @@ one rank; started bare (`python bench.py --gpus N`) the parent launches the N ra
 itself (openmg_amd/launch.py) before it touches the GPU, relays rank 0's JSON line and returns
 the worst child exit code.
 
-Prints ONE JSON line: metric V-cycles/s (median of --repeats timed regions of K cycles), plus
+Prints ONE JSON line: metric V-cycles/s (median of --repeats timed regions of K cycles).  A plain run does only what
+that figure needs: set-up, warm-up, the timed regions, --dump-outputs, the line.  At N = 1 --full adds, after the
+timed regions (the --no-* options leave legs out of it):
   roofline      the dominant kernel — the plane-pipelined down pass of the fine grid (red-black
                 sweep + residual + restriction in one launch; without plane passes: the fine-grid
                 residual kernel r = b - A x): bytes the launch has to move / average launch time
@@ -539,6 +541,10 @@ def main():
     ap.add_argument("--stencil", default="7pt", choices=["7pt", "27var"],
                     help="multi-GPU leg only: 27var = BASELINE configs[4]'s 27-point variable-coefficient operator")
     ap.add_argument("--graph", type=int, default=0, help="replay every cycle of the timed regions from a hipGraph")
+    ap.add_argument("--full", action="store_true",
+                    help="single GPU: after the timed regions also measure the roofline and per-kernel figures, the other "
+                         "schedules, configurations and precisions, the drop-in calls and the CPU baseline (the --no-* options "
+                         "leave legs out); without it the line carries the headline and its configuration only")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--no-plain", action="store_true", help="skip the plain-CSR (OMG_COMPRESS=0) leg")
     ap.add_argument("--no-sets", action="store_true", help="skip the set-by-set schedule (OMG_PLANE=0) leg")
@@ -603,98 +609,103 @@ def main():
 
     # Timed regions.  Only the roofline kernel (one launch per cycle) is bracketed by hipEvents there:
     # every event pair opens a gap in the stream.  (A hipGraph replay cannot carry the events; with
-    # --graph 1 the kernel is timed in the second region below.)
+    # --graph 1 the kernel is timed in the second region below.)  The events stay in a plain run, which
+    # does not report them, so that its timed cycles are those of a --full run.
     roof_class = "plane_down" if plane else "residual"
     times, timed, region_norms = timed_regions(h, syncer(h), args.steps, args.warmup, repeats, pre, post,
                                                () if args.graph else (roof_class,), graph=bool(args.graph))
     elapsed = statistics.median(times)
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, h.resident_fetch().astype(np_dtype), region_norms[-1])
-    norm = h.resident_cycle(pre, post, want_norm=True)          # untimed: read the norm back once
 
-    # Second, untimed region: every level-0 kernel class, for the per-kernel table.
-    h.use_graph(False)
-    h.profile_enable(True)
-    for _ in range(args.steps):
-        h.resident_cycle(pre, post, want_norm=False)
-    prof = h.profile_read()
-    h.profile_enable(False)
-    if timed is None:
-        timed = prof
-    # The metric's "fine-grid SpMV GB/s": plain y = A x over the whole level-0 operator as it
-    # sits in HBM for the cycle, 20 back-to-back launches in one hipEvent bracket (untimed region).
-    spmv_ms = h.spmv_time(20)
-    spmv_csr = spmv_bytes(n, nnz, w)
-    if plane:
-        # a plane level applies its operator matrix-free, like its cycle does: x read once, y written once
-        spmv_fmt = 2 * w * n
-        spmv_kernel = "y = A x, all rows of the fine grid (plane_spmv_kernel: matrix-free, the level's seven coefficients)"
-    else:
-        fmt_all = h.format_info(0, "A")
-        spmv_fmt = fmt_all["format_bytes"] + 2 * w * n          # operator in its device format + x read + y written
-        spmv_kernel = "y = A x, all rows of the fine grid (%s)" % kernel_name(fmt_all, "ROW_SPMV", h.level_flags(0)["union_walk"])
-    fine_spmv = {"kernel": spmv_kernel,
-                 "avg_launch_us": round(spmv_ms * 1e3, 2),
-                 "bytes_per_launch": spmv_fmt, "achieved": round(spmv_fmt / spmv_ms / 1e6, 1),
-                 "frac": round(spmv_fmt / spmv_ms / 1e6 / HBM_PEAK_GBS, 4),
-                 "csr_equiv_bytes": spmv_csr, "csr_equiv_GBps": round(spmv_csr / spmv_ms / 1e6, 1)}
+    # From here on only --full measures anything; a plain run closes the hierarchy and prints the line.
+    norm = roofline = fine_spmv = spmv_csr = None
+    if args.full:
+        norm = h.resident_cycle(pre, post, want_norm=True)          # untimed: read the norm back once
 
-    fmt_b, csr_b = class_bytes(h, meta, w)
-    kernels = kernel_table(prof, args.steps, fmt_b, csr_b)
-    launches, ms = timed[roof_class]
-    avg_s = (ms / launches) * 1e-3
-    if plane:
-        # The dominant kernel of the cycle: the plane-pipelined DOWN pass of the fine grid — red-black sweep,
-        # residual and restriction of openmg/__init__.py:201-210 in one launch.  Algorithmic bytes per unit
-        # (DESIGN.md §5): per fine unknown 3 w (x read, b read, x written), per coarse unknown w (its right-hand
-        # side) + 4 (its slot in the coarse ordering).  The operator itself costs nothing: seven coefficients.
-        bytes_roof = fmt_b["plane_down"]
-        traffic, traffic_src, rocprof_us = pmc_traffic("r06_pmc_plane_down.json", bytes_roof, w)
-        achieved = bytes_roof / avg_s / 1e9
-        roofline = {"bound": "hbm", "kernel": "plane_kernel<down>: fine-grid red-black sweep + residual + restriction in one launch (plane.hip)",
-                    "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                    "bytes_per_launch": int(bytes_roof),
-                    "bytes_definition": "per fine unknown: x read, b read, x written (3 w); per coarse unknown: right-hand side written (w) "
-                                        "+ its slot in the coarse ordering read (4)",
-                    "avg_launch_us": round(avg_s * 1e6, 2), "avg_launch_us_source": "hipEvents on the kernel's own stream inside the timed regions",
-                    "avg_launch_us_rocprof": rocprof_us,
-                    "avg_launch_us_rocprof_source": "NOT measured in this run: rocprofv3's average duration of the same kernel of the same build "
-                                                    "(profiles/r06_pmc_plane_down.json; per grid size over a whole bench run: "
-                                                    "profiles/r06_bench_kernel_stats_by_grid.txt)" if rocprof_us else None,
-                    "launches_timed": launches,
-                    "csr_equiv_bytes": int(csr_b["plane_down"]), "csr_equiv_GBps": round(csr_b["plane_down"] / avg_s / 1e9, 1),
-                    "tiling": h.plane_info(0),
-                    "level0_kernels": kernels}
-    else:
-        rows_c, nnz_c, res_csr, res_fmt, fmt_cov = residual_launch_bytes(h, meta, w)
-        traffic, traffic_src, _ = pmc_traffic("r02_pmc_residual.json", res_fmt, w)
-        achieved = res_fmt / avg_s / 1e9
-        roofline = {"bound": "hbm", "kernel": "fine grid r = b - A x (%s)" % kernel_name(fmt_cov, "ROW_RESIDUAL", h.level_flags(0)["union_walk"]),
-                    "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                    "bytes_per_launch": res_fmt,
-                    "bytes_definition": "operator bytes as stored in HBM (device format, DESIGN.md §4) + b and r of the covered rows + x once",
-                    "avg_launch_us": round(avg_s * 1e6, 2), "launches_timed": launches,
-                    "csr_equiv_bytes": res_csr, "csr_equiv_GBps": round(res_csr / avg_s / 1e9, 1),
-                    "device_format": {"row_pattern_rows": fmt_cov["pattern_rows"], "rows": fmt_cov["rows"],
-                                      "column_coded_nnz": fmt_cov["coldict_nnz"], "value_coded_nnz": fmt_cov["valdict_nnz"],
-                                      "nnz": fmt_cov["nnz"], "OMG_COMPRESS": os.environ.get("OMG_COMPRESS", "15 (default)")},
-                    "rows_covered": rows_c, "nnz_covered": nnz_c, "fused_last_set": h.level_fused(0),
-                    "level0_kernels": kernels}
+        # Second, untimed region: every level-0 kernel class, for the per-kernel table.
+        h.use_graph(False)
+        h.profile_enable(True)
+        for _ in range(args.steps):
+            h.resident_cycle(pre, post, want_norm=False)
+        prof = h.profile_read()
+        h.profile_enable(False)
+        if timed is None:
+            timed = prof
+        # The metric's "fine-grid SpMV GB/s": plain y = A x over the whole level-0 operator as it
+        # sits in HBM for the cycle, 20 back-to-back launches in one hipEvent bracket (untimed region).
+        spmv_ms = h.spmv_time(20)
+        spmv_csr = spmv_bytes(n, nnz, w)
+        if plane:
+            # a plane level applies its operator matrix-free, like its cycle does: x read once, y written once
+            spmv_fmt = 2 * w * n
+            spmv_kernel = "y = A x, all rows of the fine grid (plane_spmv_kernel: matrix-free, the level's seven coefficients)"
+        else:
+            fmt_all = h.format_info(0, "A")
+            spmv_fmt = fmt_all["format_bytes"] + 2 * w * n          # operator in its device format + x read + y written
+            spmv_kernel = "y = A x, all rows of the fine grid (%s)" % kernel_name(fmt_all, "ROW_SPMV", h.level_flags(0)["union_walk"])
+        fine_spmv = {"kernel": spmv_kernel,
+                     "avg_launch_us": round(spmv_ms * 1e3, 2),
+                     "bytes_per_launch": spmv_fmt, "achieved": round(spmv_fmt / spmv_ms / 1e6, 1),
+                     "frac": round(spmv_fmt / spmv_ms / 1e6 / HBM_PEAK_GBS, 4),
+                     "csr_equiv_bytes": spmv_csr, "csr_equiv_GBps": round(spmv_csr / spmv_ms / 1e6, 1)}
+
+        fmt_b, csr_b = class_bytes(h, meta, w)
+        kernels = kernel_table(prof, args.steps, fmt_b, csr_b)
+        launches, ms = timed[roof_class]
+        avg_s = (ms / launches) * 1e-3
+        if plane:
+            # The dominant kernel of the cycle: the plane-pipelined DOWN pass of the fine grid — red-black sweep,
+            # residual and restriction of openmg/__init__.py:201-210 in one launch.  Algorithmic bytes per unit
+            # (DESIGN.md §5): per fine unknown 3 w (x read, b read, x written), per coarse unknown w (its right-hand
+            # side) + 4 (its slot in the coarse ordering).  The operator itself costs nothing: seven coefficients.
+            bytes_roof = fmt_b["plane_down"]
+            traffic, traffic_src, rocprof_us = pmc_traffic("r06_pmc_plane_down.json", bytes_roof, w)
+            achieved = bytes_roof / avg_s / 1e9
+            roofline = {"bound": "hbm", "kernel": "plane_kernel<down>: fine-grid red-black sweep + residual + restriction in one launch (plane.hip)",
+                        "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
+                        "bytes_per_launch": int(bytes_roof),
+                        "bytes_definition": "per fine unknown: x read, b read, x written (3 w); per coarse unknown: right-hand side written (w) "
+                                            "+ its slot in the coarse ordering read (4)",
+                        "avg_launch_us": round(avg_s * 1e6, 2), "avg_launch_us_source": "hipEvents on the kernel's own stream inside the timed regions",
+                        "avg_launch_us_rocprof": rocprof_us,
+                        "avg_launch_us_rocprof_source": "NOT measured in this run: rocprofv3's average duration of the same kernel of the same build "
+                                                        "(profiles/r06_pmc_plane_down.json; per grid size over a whole bench run: "
+                                                        "profiles/r06_bench_kernel_stats_by_grid.txt)" if rocprof_us else None,
+                        "launches_timed": launches,
+                        "csr_equiv_bytes": int(csr_b["plane_down"]), "csr_equiv_GBps": round(csr_b["plane_down"] / avg_s / 1e9, 1),
+                        "tiling": h.plane_info(0),
+                        "level0_kernels": kernels}
+        else:
+            rows_c, nnz_c, res_csr, res_fmt, fmt_cov = residual_launch_bytes(h, meta, w)
+            traffic, traffic_src, _ = pmc_traffic("r02_pmc_residual.json", res_fmt, w)
+            achieved = res_fmt / avg_s / 1e9
+            roofline = {"bound": "hbm", "kernel": "fine grid r = b - A x (%s)" % kernel_name(fmt_cov, "ROW_RESIDUAL", h.level_flags(0)["union_walk"]),
+                        "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
+                        "bytes_per_launch": res_fmt,
+                        "bytes_definition": "operator bytes as stored in HBM (device format, DESIGN.md §4) + b and r of the covered rows + x once",
+                        "avg_launch_us": round(avg_s * 1e6, 2), "launches_timed": launches,
+                        "csr_equiv_bytes": res_csr, "csr_equiv_GBps": round(res_csr / avg_s / 1e9, 1),
+                        "device_format": {"row_pattern_rows": fmt_cov["pattern_rows"], "rows": fmt_cov["rows"],
+                                          "column_coded_nnz": fmt_cov["coldict_nnz"], "value_coded_nnz": fmt_cov["valdict_nnz"],
+                                          "nnz": fmt_cov["nnz"], "OMG_COMPRESS": os.environ.get("OMG_COMPRESS", "15 (default)")},
+                        "rows_covered": rows_c, "nnz_covered": nnz_c, "fused_last_set": h.level_fused(0),
+                        "level0_kernels": kernels}
     # The reference's OWN parameter dict: preIterations 1, postIterations 0 (openmg/__init__.py:22-23), same hierarchy
     # and loop: the up pass then runs without its relaxation (prolongation + correction + the norm's squares).
     # the same setup kept on the device (omg_hierarchy_create_from_fine: what mgSolve runs when the caller does not ask
     # for the operator lists): upload of the fine operator, restrictions, Galerkin products, qualification, tilings
     setup_device_s = None
-    if args.smoother == "colour":
+    if args.full and args.smoother == "colour":
         from openmg_amd import _hip as _h
         t_s = time.perf_counter()
         h_dev = _h.Hierarchy.from_fine(_PROBLEM[(args.size, args.grids)][0], (args.size,) * 3, args.grids - 1, smoother=args.smoother, dtype=np_dtype)
         setup_device_s = time.perf_counter() - t_s
         h_dev.close()
     default_cycle = None
-    if plane and args.smoother == "colour":
+    if args.full and plane and args.smoother == "colour":
         h.resident_load(b)
         t_d, _, n_d = timed_regions(h, syncer(h), args.steps, min(args.warmup, 3), min(repeats, 7), 1, 0, ())
         e_d = statistics.median(t_d)
@@ -708,7 +719,7 @@ def main():
     # What a caller of the DROP-IN pays (north star: "openmg.mg_cycle(A, b, ...) is a drop-in"): mgCycle is handed the
     # A / R lists and host vectors on every call (openmg/__init__.py:151), mgSolve builds the hierarchy itself (:103-109).
     dropin = None
-    if not args.no_dropin and args.smoother == "colour":
+    if args.full and not args.no_dropin and args.smoother == "colour":
         import numpy as np
         import openmg_amd
         A0, b_h, R_l, A_l = _PROBLEM[(args.size, args.grids)][:4]
@@ -799,7 +810,7 @@ def main():
 
     # The set-by-set schedule the plane passes replace (round 2's headline path): eight level-0 launches per cycle.
     set_path = None
-    if plane and not args.no_sets:
+    if args.full and plane and not args.no_sets:
         set_path = leg({"OMG_PLANE": "0"}, args.smoother,
                        "same problem and timed loop, set-by-set schedule (OMG_PLANE=0): operators in the lossless device "
                        "format, eight level-0 launches per cycle; same iterate bit for bit", min(repeats, 3), False)
@@ -807,14 +818,14 @@ def main():
     # (OMG_PLANE=0) — what the north star's "CSR SpMV ... >= 50 % of the HBM roofline on the fine-grid SpMV"
     # describes — timed with the same loop.
     csr_path = None
-    if not args.no_plain and os.environ.get("OMG_COMPRESS", "15") != "0":
+    if args.full and not args.no_plain and os.environ.get("OMG_COMPRESS", "15") != "0":
         csr_path = leg({"OMG_COMPRESS": "0", "OMG_PLANE": "0"}, args.smoother,
                        "same problem and timed loop, every operator held as plain int32 CSR and walked by the CSR row kernels "
                        "(OMG_COMPRESS=0, OMG_PLANE=0)", repeats, True)
     # The same problem with the reference's OWN smoother — in-place lexicographic Gauss-Seidel
     # (openmg/solvers.py:56-68) — instead of the red-black ordering: same loop, fewer repeats.
     lex_path = None
-    if not args.no_lex and args.smoother == "colour":
+    if args.full and not args.no_lex and args.smoother == "colour":
         lex_path = leg({}, "gs",
                        "same problem and timed loop with the reference's lexicographic Gauss-Seidel (openmg/solvers.py:56-68) "
                        "as the smoother; grid star stencils run a sweep as one wavefront launch (march.hip, "
@@ -830,21 +841,21 @@ def main():
         lex_path["line_scan"]["norm_rel_diff_from_the_wavefront_kernel"] = abs(na - nb) / max(abs(na), 1e-300)
 
     config4 = None
-    if not args.no_config4 and args.dtype == "f64" and args.smoother == "colour":
+    if args.full and not args.no_config4 and args.dtype == "f64" and args.smoother == "colour":
         _PROBLEM.clear()                               # (the 256^3 7-point operator: 1.9 GB of host memory)
         config4 = config4_leg(args.config4_size, args.grids, max(10, args.steps), 3, min(repeats, 7), syncer)
     var7 = None
-    if not args.no_config1 and args.dtype == "f64" and args.smoother == "colour":
+    if args.full and not args.no_config1 and args.dtype == "f64" and args.smoother == "colour":
         var7 = var7_leg(args.size, args.grids, args.steps, 3, min(repeats, 5), syncer)
     config0 = None
-    if not args.no_config1 and args.dtype == "f64":
+    if args.full and not args.no_config1 and args.dtype == "f64":
         config0 = config0_leg(args.steps, 3, min(repeats, 5), syncer)
     config1 = None
-    if not args.no_config1 and args.dtype == "f64" and args.smoother == "colour":
+    if args.full and not args.no_config1 and args.dtype == "f64" and args.smoother == "colour":
         config1 = config1_leg(args.steps, 3, min(repeats, 9), syncer)
 
     cpu = None
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         rate, dt, cpu_spmv = cpu_baseline(args.cpu_size, args.grids, args.cpu_cycles)
         scale = (args.cpu_size / float(args.size)) ** 3
         cpu = {"value": round(rate * scale, 5), "unit": "V-cycles/s", "cores": 1, "kind": "port",
@@ -861,29 +872,30 @@ def main():
     #  * SURVEY 8(d) as it is worded — the fine-grid SpMV over plain int32 CSR (1 740 111 876 B at 256^3), the `csr_path` leg;
     #  * the cycle with the reference's own (lexicographic) smoother; BASELINE configs[4]'s cycle and its sweep's fraction;
     #  * traffic_ratio: HBM bytes the PMC passes counted for the roofline kernel over the bytes it has to move.
-    if csr_path is not None and "fine_grid_spmv" in csr_path:
-        roofline["csr_spmv_bytes"] = csr_path["fine_grid_spmv"]["bytes_per_launch"]
-        roofline["csr_spmv_us"] = csr_path["fine_grid_spmv"]["avg_launch_us"]
-        roofline["csr_spmv_frac"] = csr_path["fine_grid_spmv"]["frac"]
-        roofline["csr_cycle_vcycles_per_s"] = csr_path["vcycles_per_s"]
-    roofline["matrix_free_spmv_frac"] = fine_spmv["frac"]
-    roofline["matrix_free_spmv_us"] = fine_spmv["avg_launch_us"]
-    if dropin is not None:
-        roofline["mgcycle_host_arrays_call_ms"] = dropin["mgcycle_call_ms"]
-        roofline["mgcycle_device_arrays_call_ms"] = dropin["mgcycle_device_arrays_call_ms"]
-    if lex_path is not None:
-        roofline["reference_smoother_vcycles_per_s"] = lex_path["vcycles_per_s"]
-        roofline["reference_smoother_line_scan_vcycles_per_s"] = lex_path["line_scan"]["vcycles_per_s"]
-    if var7 is not None:
-        roofline["var7_vcycles_per_s"] = var7["vcycles_per_s"]
-        roofline["var7_set_schedule_vcycles_per_s"] = var7["set_schedule_vcycles_per_s"]
-        roofline["var7_reference_smoother_vcycles_per_s"] = var7["reference_smoother"]["vcycles_per_s"]
-        roofline["var7_mgsolve_20_cycles_s"] = var7["mgsolve_20_cycles_s"]
-    if config4 is not None:
-        roofline["config4_vcycles_per_s"] = config4.get("vcycles_per_s")
-        roofline["config4_sweep_frac"] = (config4.get("roofline") or {}).get("frac")
-    if roofline.get("traffic") and roofline.get("bytes_per_launch"):
-        roofline["traffic_ratio"] = round(roofline["traffic"] / float(roofline["bytes_per_launch"]), 4)
+    if args.full:
+        if csr_path is not None and "fine_grid_spmv" in csr_path:
+            roofline["csr_spmv_bytes"] = csr_path["fine_grid_spmv"]["bytes_per_launch"]
+            roofline["csr_spmv_us"] = csr_path["fine_grid_spmv"]["avg_launch_us"]
+            roofline["csr_spmv_frac"] = csr_path["fine_grid_spmv"]["frac"]
+            roofline["csr_cycle_vcycles_per_s"] = csr_path["vcycles_per_s"]
+        roofline["matrix_free_spmv_frac"] = fine_spmv["frac"]
+        roofline["matrix_free_spmv_us"] = fine_spmv["avg_launch_us"]
+        if dropin is not None:
+            roofline["mgcycle_host_arrays_call_ms"] = dropin["mgcycle_call_ms"]
+            roofline["mgcycle_device_arrays_call_ms"] = dropin["mgcycle_device_arrays_call_ms"]
+        if lex_path is not None:
+            roofline["reference_smoother_vcycles_per_s"] = lex_path["vcycles_per_s"]
+            roofline["reference_smoother_line_scan_vcycles_per_s"] = lex_path["line_scan"]["vcycles_per_s"]
+        if var7 is not None:
+            roofline["var7_vcycles_per_s"] = var7["vcycles_per_s"]
+            roofline["var7_set_schedule_vcycles_per_s"] = var7["set_schedule_vcycles_per_s"]
+            roofline["var7_reference_smoother_vcycles_per_s"] = var7["reference_smoother"]["vcycles_per_s"]
+            roofline["var7_mgsolve_20_cycles_s"] = var7["mgsolve_20_cycles_s"]
+        if config4 is not None:
+            roofline["config4_vcycles_per_s"] = config4.get("vcycles_per_s")
+            roofline["config4_sweep_frac"] = (config4.get("roofline") or {}).get("frac")
+        if roofline.get("traffic") and roofline.get("bytes_per_launch"):
+            roofline["traffic_ratio"] = round(roofline["traffic"] / float(roofline["bytes_per_launch"]), 4)
     steady_ms = round(1e3 * min(times[len(times) // 2:]) / args.steps, 4)
     headline_shape = args.size == 256 and w == 8 and plane
     population = ("fast" if steady_ms <= 0.272 else "slow") if headline_shape else None
@@ -912,7 +924,7 @@ def main():
                                   "`value_set_schedule`: the same cycle set by set on the lossless device format" if plane else
                                   "operators in the lossless device format (row patterns)"),
                    "unknowns": n, "nnz": nnz, "grids": meta["grids"], "pre": pre, "post": post,
-                   "smoother": args.smoother, "hipgraph": bool(args.graph),
+                   "smoother": args.smoother, "hipgraph": bool(args.graph), "full": args.full,
                    "plane_levels": [bool(f) for f in meta.get("plane_levels", [])],
                    "repeats": repeats, "ms_per_step_all": [round(1e3 * t / args.steps, 4) for t in times],
                    # the two kinds of allocation of the finest level's vectors (the level's passes ~7 % apart;

@@ -130,3 +130,27 @@ def test_dump_outputs_hold_the_iterate_and_norm_of_the_last_timed_cycle(tmp_path
     got = np.load(str(tmp_path / "x.npy"))
     assert got.dtype == np.float64 and np.array_equal(got, x), int(np.sum(got != x))
     assert np.load(str(tmp_path / "residual_norm.npy")).tolist() == [norms[-1]]
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_alone_and_full_adds_the_legs():
+    """A plain run at 32^3 measures nothing after its timed regions: the legs, the roofline and the CPU baseline are null.
+    The same run with --full (configs[1] / [4] left out, the CPU baseline at 32^3) fills them in."""
+    import subprocess
+    import sys
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--size", "32", "--grids", "3", "--steps", "3",
+            "--warmup", "2", "--repeats", "3"]
+    legs = ("roofline", "fine_grid_spmv", "dropin", "csr_path", "reference_smoother", "cpu_baseline")
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-config4", "--no-config1", "--cpu-size", "32", "--cpu-cycles", "1"])):
+        p = subprocess.run(base + extra, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert p.returncode == 0, (mode, p.stderr[-3000:])
+        lines[mode] = d = json.loads(p.stdout.strip().splitlines()[-1])
+        assert d["unit"] == "V-cycles/s" and d["higher_is_better"] is True and d["dtype"] == "f64" and d["steps"] == 3
+        assert abs(d["value"] - 1e3 / d["ms_per_step"]) / d["value"] < 1e-3 and len(d["config"]["ms_per_step_all"]) == 3
+        assert d["config"]["full"] is (mode == "full")
+    plain, full = lines["plain"], lines["full"]
+    assert all(plain[k] is None for k in legs + ("set_schedule", "default_cycle", "config0", "config1", "config4", "var7"))
+    assert plain["config"]["final_residual_norm"] is None and plain["config"]["setup_device_s"] is None
+    assert all(isinstance(full[k], dict) for k in legs), [k for k in legs if not isinstance(full[k], dict)]
+    assert full["roofline"]["level0_kernels"] and full["cpu_baseline"]["value"] > 0 and full["config"]["final_residual_norm"] > 0

@@ -10,7 +10,7 @@ rm -rf "$out"; mkdir -p "$out"
 cd "$root"
 last() { tail -1 "$1" > "$2"; }
 # the PMC passes first: the bench line quotes their traffic (profiles/${p}_pmc_*.json) while the kernel sources hash to it
-timeout 300 python bench.py --no-cpu --no-plain --no-lex --no-sets --no-dropin --no-config4 --no-config1 > $out/quick.log 2>/dev/null; last $out/quick.log $out/quick.json
+timeout 300 python bench.py --full --no-cpu --no-plain --no-lex --no-sets --no-dropin --no-config4 --no-config1 > $out/quick.log 2>/dev/null; last $out/quick.log $out/quick.json
 PASSES="1 2 4 5 6 7" bash tools/pmc_plane.sh gpurun_out/fin/pmc > $out/pmc.log 2>&1
 python tools/pmc_any.py gpurun_out/fin/pmc > $out/${p}_pmc_plane_kernels.txt 2>&1
 python tools/pmc_plane_json.py gpurun_out/fin/pmc $out/quick.json $out/${p}_pmc_plane_down.json \
@@ -22,9 +22,9 @@ python tools/pmc_any.py gpurun_out/fin/pmc27 > $out/${p}_pmc_s27_kernels.txt 2>&
 python tools/pmc_s27_json.py gpurun_out/fin/pmc27 $out/${p}_pmc_s27_sweep.json \
   "tools/pmc_s27.sh passes 5 and 6 (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, --kernel-include-regex s27_, tools/prof_config4.py --steps 2 --batched 0), table in profiles/${p}_pmc_s27_kernels.txt" > $out/pmc27_json.log 2>&1
 cp $out/${p}_pmc_s27_sweep.json $root/profiles/${p}_pmc_s27_sweep.json
-timeout 900 python bench.py > $out/bench.log 2>$out/bench.err; last $out/bench.log $out/${p}_bench.json
-timeout 300 python bench.py --graph 1 --no-cpu --no-plain --no-lex --no-sets --no-dropin --no-config4 --no-config1 > $out/graph.log 2>/dev/null; last $out/graph.log $out/${p}_bench_hipgraph.json
-timeout 300 python bench.py --no-cpu --no-plain --no-lex --no-dropin --no-config4 --no-config1 --dtype f32 > $out/f32.log 2>/dev/null; last $out/f32.log $out/${p}_bench_f32.json
+timeout 900 python bench.py --full > $out/bench.log 2>$out/bench.err; last $out/bench.log $out/${p}_bench.json
+timeout 300 python bench.py --full --graph 1 --no-cpu --no-plain --no-lex --no-sets --no-dropin --no-config4 --no-config1 > $out/graph.log 2>/dev/null; last $out/graph.log $out/${p}_bench_hipgraph.json
+timeout 300 python bench.py --full --no-cpu --no-plain --no-lex --no-dropin --no-config4 --no-config1 --dtype f32 > $out/f32.log 2>/dev/null; last $out/f32.log $out/${p}_bench_f32.json
 OMG_DIST_P2P=0 timeout 300 python bench.py --dist 1 --no-cpu > $out/dist1.log 2>/dev/null; last $out/dist1.log $out/${p}_bench_dist1.json
 OMG_DIST_P2P=1 timeout 300 python bench.py --dist 1 --no-cpu > $out/dist1p.log 2>/dev/null; last $out/dist1p.log $out/${p}_bench_dist1_peer.json
 PYTHONPATH=$root timeout 300 python tools/exchange_probe.py > $out/${p}_exchange_probe.txt 2>/dev/null
@@ -37,7 +37,7 @@ OMG_SETUP_TIMING=1 timeout 120 python tools/setup_timing.py > $out/${p}_setup_ti
 OMG_SETUP_TIMING=1 timeout 200 python tools/setup_breakdown.py > $out/${p}_setup_breakdown.txt 2>&1
 python tools/hostmem_probe.py > $out/${p}_hostmem_probe.txt 2>&1
 cd /tmp && export TMPDIR=/tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o b -- python3 $root/bench.py --no-cpu > $out/under.log 2>/dev/null
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o b -- python3 $root/bench.py --full --no-cpu > $out/under.log 2>/dev/null
 last $out/under.log $out/${p}_bench_under_rocprof.json
 cp $out/trace/b_kernel_stats.csv $out/${p}_bench_kernel_stats.csv
 python3 $root/tools/trace_stats.py $out/trace/b_kernel_trace.csv > $out/${p}_bench_kernel_stats_by_grid.txt 2>&1
