@@ -111,7 +111,10 @@ int omg_hierarchy_create_from_fine(const omg_csr *A_in, int dim, const int64_t *
  * operators.coeffecientList again, openmg/operators.py:144-188): data = the CSR's value array in the SAME pattern, nnz
  * doubles, in host memory or — on_device != 0 — already in HBM.  Level 0 is re-tiled, every Galerkin product re-formed
  * on the device in one pass per level (closed form of the aggregation on a grid, SciPy's accumulation order: the bits of
- * a fresh setup), the coarsest operator factorised anew.  The resident right-hand side and iterate stay. */
+ * a fresh setup), the coarsest operator factorised anew.  The resident right-hand side and iterate stay.  It also takes
+ * such a hierarchy whose level 0 runs the 7-point per-row-coefficient passes (var7) and whose smoothed levels are each var7
+ * or one of the small host-coded levels below them: the products are re-formed the same way, the host-coded levels
+ * rebuilt from theirs.  Any other hierarchy: OMG_ERR_INVALID. */
 int omg_hierarchy_update_fine(omg_hierarchy *h, const double *data, int64_t nnz, int on_device);
 int omg_hierarchy_dtype(const omg_hierarchy *h, int *dtype);
 int omg_hierarchy_destroy(omg_hierarchy *h);

@@ -339,7 +339,9 @@ class Hierarchy:
 
     def update_fine(self, data, on_device=False):
         """New values for the fine operator, same pattern (omg_hierarchy_update_fine).  data: the CSR's value array as a
-        float64 NumPy array, or — on_device — (device pointer, number of entries)."""
+        float64 NumPy array, or — on_device — (device pointer, number of entries).  Takes a from_fine hierarchy whose
+        smoothed levels all run the 27-point kernels, or whose level 0 runs the 7-point var7 passes and whose smoothed levels
+        are var7 or host-coded; afterwards it is the hierarchy from_fine builds from the new operator, bit for bit."""
         if on_device:
             ptr, nnz = data
             check(lib().omg_hierarchy_update_fine(self._h, ctypes.c_void_p(int(ptr)), int(nnz), 1))

@@ -818,7 +818,22 @@ struct Var7Plan {
     // sweep = false: the pass without its relaxation (down leaves x_new untouched: the iterate stays in x_old)
     void down(const V *x_old, V *x_new, const V *b, bool x_zero, const Coarse &c, hipStream_t s, bool sweep = true) const;
     void up(const V *x_old, V *x_new, const V *b, const Coarse &c, double *out, hipStream_t s, bool sweep = true) const;
+    // omg_hierarchy_update_fine: the Galerkin product of this level in closed form (var7_rap below); write_fine: the input is
+    // the caller's fine CSR (indptr, vals) and its coefficients go into this level's seven arrays as well
+    void rap_from(const int32_t *indptr, const double *vals, bool write_fine, double *coarse_dense, Var7Plan<V> *coarse,
+                  unsigned long long *err, hipStream_t s);
 };
+
+// R A R^T of a 7-point level on an nx x ny x nz grid (even extents) under the plain 2 x 2 x 2 aggregation with weight w, in
+// SciPy's order (the bits of setup_device.hip rap_aggregation_kernel): one thread per coarse row.  Input: a CSR in the exact
+// 7-point pattern with ascending columns (indptr non-null; fine != null: its values also go into fine's seven arrays), or a
+// dense [row][7] double array (slots -K, -J, -I, D, +I, +J, +K; zero where the neighbour is outside the grid).  Output: the
+// coarse rows as such a dense array and, where coarse != null, into the coarse level's seven arrays (as V).  err[0]: smallest
+// row (+ 1; bit 62: a coarse row) whose diagonal is exactly zero; err[1]: the same for a value that a fresh var7 level would
+// not take (not finite as V, a zero diagonal as V, a coarse coupling inside the grid that is exactly zero).  Enqueued only.
+template <typename V>
+void var7_rap(const int32_t *indptr, const double *vals, int nx, int ny, int nz, double w, Var7Plan<V> *fine, Var7Plan<V> *coarse,
+              double *coarse_dense, unsigned long long *err, hipStream_t s);
 
 // ---- 27-point grid stencils with per-row coefficients: BASELINE configs[4] (stencil27.hip) ----------------
 // A level whose operator holds, in every row, exactly the in-grid neighbours of a 27-point stencil on a

@@ -205,6 +205,14 @@ struct Hier {
     DevBuf<int32_t> indptr0;
     int64_t nnz0 = 0;
     std::vector<DevBuf<double>> dense27;
+    // ... or a hierarchy from create_from_fine whose level 0 runs the 7-point per-row-coefficient passes (var7) and whose
+    // smoothed levels are each var7 or coded by the host (its small levels): indptr0 / nnz0 as above (a var7 level 0 holds
+    // exactly the in-grid neighbours, columns ascending: the row pointers place every value), the fine grid (nx, ny, nz), and
+    // per level >= 1 the Galerkin operator as a dense [row][7] double array (made at the first update) — the next product's
+    // input, and the operator of a host level or the coarsest level
+    bool upd7 = false;
+    int g7[3] = {0, 0, 0};
+    std::vector<DevBuf<double>> dense7;
     // resident state
     bool resident = false;
     // OMG_NO_FUSE=1: never fuse the last smoother set with the residual / norm (A/B switch;
@@ -1486,12 +1494,19 @@ std::unique_ptr<Hier<V>> create_from_fine(const omg_csr &A0, int dim, const int6
     });
     struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{inverter};
     {
-        // (new coefficients later: omg_hierarchy_update_fine needs the fine pattern's row pointers, nothing else of the operators)
+        // (new coefficients later: omg_hierarchy_update_fine needs the fine pattern's row pointers, nothing else of the operators;
+        // 27-point levels throughout, or 7-point var7 levels with host-coded levels below them)
         bool all27 = dim == 3;
         for (int l = 0; l + 1 < n_levels; ++l) all27 = all27 && bool(h->lv[size_t(l)].s27);
-        if (all27) {
+        bool all7 = dim == 3 && bool(h->lv[0].var7);
+        for (int l = 0; l + 1 < n_levels; ++l) all7 = all7 && (h->lv[size_t(l)].var7 || host_level[size_t(l)]);
+        if (all27 || all7) {
             h->indptr0 = std::move(dA[0].indptr);
             h->nnz0 = dA[0].nnz;
+        }
+        if (all7) {
+            h->upd7 = true;
+            h->g7[0] = int(shape[2]); h->g7[1] = int(shape[1]); h->g7[2] = int(shape[0]);
         }
     }
     dA.clear();                                                    // (the fused paths hold what they need of the operators)
@@ -1565,13 +1580,160 @@ std::unique_ptr<Hier<V>> create_from_fine(const omg_csr &A0, int dim, const int6
     return h;
 }
 
+// A 7-point level's operator from its dense [row][7] form (slots -K, -J, -I, D, +I, +J, +K): the in-grid neighbours whose value
+// is not exactly zero, columns ascending — what the Galerkin chain hands create_from_fine (SciPy drops exact zeros).
+HostCsr csr_from_dense7(const std::vector<double> &d, int nx, int ny, int nz) {
+    const int64_t n = int64_t(nx) * ny * nz, sj = nx, sk = int64_t(nx) * ny;
+    HostCsr A;
+    A.n_rows = A.n_cols = n;
+    A.indptr.resize(size_t(n) + 1);
+    A.indices.reserve(size_t(n) * 7);
+    A.data.reserve(size_t(n) * 7);
+    for (int64_t r = 0; r < n; ++r) {
+        A.indptr[size_t(r)] = int32_t(A.indices.size());
+        const int64_t i = r % nx, j = (r / nx) % ny, k = r / sk;
+        const int64_t col[7] = {r - sk, r - sj, r - 1, r, r + 1, r + sj, r + sk};
+        const bool in[7] = {k > 0, j > 0, i > 0, true, i + 1 < nx, j + 1 < ny, k + 1 < nz};
+        for (int e = 0; e < 7; ++e) {
+            const double v = d[size_t(r) * 7 + size_t(e)];
+            if (!in[e] || v == 0.0) continue;
+            A.indices.push_back(int32_t(col[e]));
+            A.data.push_back(v);
+        }
+    }
+    A.indptr[size_t(n)] = int32_t(A.indices.size());
+    A.nnz = int64_t(A.indices.size());
+    return A;
+}
+
+// The plain 2 x 2 x 2 aggregation of an nx x ny x nz grid, weight 1/8, columns ascending (setup_device.hip restriction_kernel
+// for a grid whose first and last extents are equal)
+HostCsr aggregation_csr(int nx, int ny, int nz) {
+    const int64_t n = int64_t(nx) * ny * nz, hx = nx / 2, hy = ny / 2, nc = n / 8;
+    HostCsr R;
+    R.n_rows = nc;
+    R.n_cols = n;
+    R.nnz = n;
+    R.indptr.resize(size_t(nc) + 1);
+    R.indices.resize(size_t(n));
+    R.data.assign(size_t(n), 1.0 / 8);
+    for (int64_t cr = 0; cr <= nc; ++cr) R.indptr[size_t(cr)] = int32_t(8 * cr);
+    for (int64_t cr = 0; cr < nc; ++cr) {
+        const int64_t I = cr % hx, J = (cr / hx) % hy, K = cr / (hx * hy);
+        int64_t p = 8 * cr;
+        for (int dk = 0; dk < 2; ++dk)
+            for (int dj = 0; dj < 2; ++dj)
+                for (int di = 0; di < 2; ++di, ++p) R.indices[size_t(p)] = int32_t(((2 * K + dk) * ny + 2 * J + dj) * nx + 2 * I + di);
+    }
+    (void)nz;
+    return R;
+}
+
+// New coefficients for the fine operator of a hierarchy that create_from_fine set up with a var7 level 0 (Hier::upd7): every
+// Galerkin product re-formed in HBM by var7_rap — level 0's seven arrays written in the same pass that reads the new values,
+// each var7 level's arrays as the coarse side of the pass above it, every product in double as a dense [row][7] array —; a
+// host-coded level is then rebuilt in full from its product, as create_from_fine codes it: its greedy colouring (and with it
+// its ordering, its format, the slot map of the level above) follows the pattern, and an exact zero of the new product
+// changes the pattern.  The coarsest operator is factorised anew.  The result is the hierarchy a fresh setup of the new
+// operator gives, bit for bit.
+template <typename V>
+void update_fine_var7(Hier<V> *h, const double *vals, int64_t nnz, bool on_device) {
+    OMG_REQUIRE(vals && nnz == h->nnz0, "omg_hierarchy_update_fine: the value array must have the fine operator's number of entries");
+    const int last = (int)h->lv.size() - 1;
+    OMG_HIP(hipStreamSynchronize(h->stream));
+    drop_graph(h);
+    DevBuf<double> up;
+    if (!on_device) {
+        SetupTimer tm("update: upload the new values");
+        up.alloc(size_t(nnz));
+        OMG_HIP(hipMemcpyAsync(up.p, vals, size_t(nnz) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        vals = up.p;
+    }
+    if (h->dense7.size() != h->lv.size()) h->dense7.resize(h->lv.size());
+    DevBuf<unsigned long long> d_err(size_t(2 * last));
+    std::vector<unsigned long long> err(size_t(2 * last));
+    {
+        SetupTimer tm("update: Galerkin products of the 7-point chain (one pass per level)");
+        OMG_HIP(hipMemsetAsync(d_err.p, 0xFF, err.size() * sizeof(unsigned long long), h->stream));
+        for (int l = 0; l < last; ++l) {
+            Level<V> &L = h->lv[size_t(l)];
+            DevBuf<double> &out = h->dense7[size_t(l) + 1];
+            const size_t need = size_t(h->lv[size_t(l) + 1].n) * 7;
+            if (out.n < need) out.alloc(need);
+            Var7Plan<V> *C = l + 1 < last ? h->lv[size_t(l) + 1].var7.get() : nullptr;
+            var7_rap<V>(l == 0 ? h->indptr0.p : nullptr, l == 0 ? vals : h->dense7[size_t(l)].p, h->g7[0] >> l, h->g7[1] >> l, h->g7[2] >> l,
+                        1.0 / 8, l == 0 ? L.var7.get() : nullptr, C, out.p, d_err.p + 2 * l, h->stream);
+            if (L.var7) L.format_pending = true;                   // (its row-kernel side, if it was ever built, is of the old operator)
+        }
+        OMG_HIP(hipMemcpyAsync(err.data(), d_err.p, err.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+        OMG_HIP(hipStreamSynchronize(h->stream));
+    }
+    h->lv[0].diag.release();                                       // (made from the row-kernel format on first use: of the old operator)
+    for (int l = 0; l < last; ++l)
+        for (int q = 0; q < 2; ++q) {
+            const unsigned long long e = err[size_t(2 * l + q)];
+            if (e == ~0ull) continue;
+            const int lev = (e >> 62) ? l + 1 : l;
+            const std::string where = "omg_hierarchy_update_fine: level " + std::to_string(lev) + ": row " + std::to_string((e & ~(3ull << 62)) - 1);
+            // (what a fresh setup of this operator raises: a zero diagonal is a missing one; any other value a var7 level does
+            // not take makes the level one of another kind, which an update cannot turn this one into)
+            if (q == 0) throw Error(OMG_ERR_NO_DIAGONAL, where + " has no nonzero diagonal entry");
+            throw Error(OMG_ERR_INVALID, where + ": a value that is not finite in the level's precision, a diagonal that rounds to zero "
+                                                 "there, or a coupling that is exactly zero (a fresh setup would not run this level as var7)");
+        }
+    std::vector<HostCsr> hA(size_t(last) + 1);
+    {
+        SetupTimer tm("update: host-coded levels' and the coarsest operators, from their products");
+        for (int l = 1; l <= last; ++l) {
+            if (l < last && h->lv[size_t(l)].var7) continue;
+            std::vector<double> d(size_t(h->lv[size_t(l)].n) * 7);
+            OMG_HIP(hipMemcpyAsync(d.data(), h->dense7[size_t(l)].p, d.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            OMG_HIP(hipStreamSynchronize(h->stream));
+            hA[size_t(l)] = csr_from_dense7(d, h->g7[0] >> l, h->g7[1] >> l, h->g7[2] >> l);
+            check_diagonal(view(hA[size_t(l)]), l);
+        }
+    }
+    for (int l = 1; l < last; ++l) {
+        Level<V> &L = h->lv[size_t(l)], &U = h->lv[size_t(l) - 1];
+        if (L.var7) continue;
+        SetupTimer tm("update: a host-coded level's ordering");
+        order_level(L, view(hA[size_t(l)]), h->smoother, h->stream);
+        if (L.ord.identity) {
+            L.perm.release();
+            U.r_out.release();
+        } else {
+            if (L.perm.n != size_t(L.n)) L.perm.alloc(size_t(L.n));
+            L.perm.upload(L.ord.perm.data(), size_t(L.n), h->stream);
+            if (U.r_out.n != size_t(L.n)) U.r_out.alloc(size_t(L.n));
+            U.r_out.upload(L.ord.inv.data(), size_t(L.n), h->stream);          // (the restriction of the level above writes through it)
+        }
+        OMG_HIP(hipStreamSynchronize(h->stream));
+    }
+    for (int l = 1; l < last; ++l) {
+        if (h->lv[size_t(l)].var7) continue;
+        SetupTimer tm("update: a host-coded level's format");
+        const HostCsr R = aggregation_csr(h->g7[0] >> l, h->g7[1] >> l, h->g7[2] >> l);
+        materialise_ordering(h->lv[size_t(l) + 1].ord);
+        build_format(h, l, view(hA[size_t(l)]), view(R));
+    }
+    Level<V> &Lc = h->lv.back();
+    {
+        SetupTimer tm("update: coarse factorisation");
+        Lc.A.upload(hA[size_t(last)], Lc.ord.sets, h->stream);
+        h->coarse.retain_workspace = true;                          // (a hierarchy that is updated once is updated again)
+        h->coarse.build(hA[size_t(last)], h->stream);
+    }
+    OMG_HIP(hipStreamSynchronize(h->stream));
+}
+
 // New coefficients for the fine operator of a hierarchy that create_from_fine set up with 27-point levels throughout (same
 // pattern, new values: BASELINE configs[4]'s "Galerkin RAP rebuilt on-device"; openmg/operators.py:144-188 is what the
 // reference would run again): level 0 is re-tiled and every Galerkin product re-formed in HBM by s27_rap_kernel — each
 // operator of the chain read once —, the coarsest operator factorised anew.  vals: the CSR's data array, host or device.
 template <typename V>
 void update_fine(Hier<V> *h, const double *vals, int64_t nnz, bool on_device) {
-    OMG_REQUIRE(h->indptr0.p, "omg_hierarchy_update_fine: needs a hierarchy made by omg_hierarchy_create_from_fine whose smoothed levels all run the 27-point kernels");
+    if (h->upd7) { update_fine_var7(h, vals, nnz, on_device); return; }
+    OMG_REQUIRE(h->indptr0.p, "omg_hierarchy_update_fine: needs a hierarchy made by omg_hierarchy_create_from_fine whose smoothed levels all run the 27-point kernels, or whose level 0 runs the 7-point var7 passes and whose smoothed levels are var7 or host-coded");
     OMG_REQUIRE(vals && nnz == h->nnz0, "omg_hierarchy_update_fine: the value array must have the fine operator's number of entries");
     const int last = (int)h->lv.size() - 1;
     OMG_HIP(hipStreamSynchronize(h->stream));

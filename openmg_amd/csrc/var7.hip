@@ -771,6 +771,189 @@ void Var7Plan<V>::up(const V *x_old, V *x_new, const V *b, const Coarse &c, doub
     run(*this, a, false, s);
 }
 
+// ---- new coefficients into an existing hierarchy: the Galerkin product in closed form (omg_hierarchy_update_fine) --------
+// openmg/operators.py:184-186 for the plain 2 x 2 x 2 aggregation of a 7-point level, with the additions of SciPy's
+// csr_matmat in its order (as setup_device.hip rap_aggregation_kernel forms them): (R A)(I, j) = sum over the fine rows k
+// of aggregate I, ascending, of w a(k, j); A_c(I, J) = sum over the cells j of aggregate J, ascending, of (R A)(I, j) w.
+// On a 7-point grid the j of a coarse row are its eight children (each fed by itself and its three neighbours inside the
+// aggregate, four terms) and the 24 cells behind the aggregate's six faces (one term each, from the child on the face);
+// R A R^T is again 7-point.  Children in ascending row order: c = di + 2 dj + 4 dk.  Face slot m of the cells behind a face
+// is the index of the feeding child among the face's four, ascending — which is their cells' ascending order as well.
+// The sums start at 0.0 and take every term, zeros included: a term that SciPy drops is +-0, which changes no sum (a running
+// sum that starts at +0 is never -0), and an entry that SciPy drops is one whose sum is zero, a zero coefficient here.
+//
+// Loads: for one (dj, dk) a thread's two children are consecutive rows, at most 14 consecutive values of the input, and the
+// chunks of consecutive threads (consecutive I of one line) follow one another in memory.  The wave fetches its 64 chunks
+// together — lane l of load u takes value 64 u + l of the chunks laid end to end, 14 slots each (unit stride where the
+// chunks are contiguous) — through LDS, and every thread then reads its own 14 (as s27_rap_kernel does for 27 points:
+// lanes that walked their own rows cost 2x there).
+namespace {
+constexpr int V7RAP_WAVES = 4, V7RAP_CHUNK = 14;
+
+template <typename V>
+struct Var7RapArgs {
+    const int32_t *indptr;           // CSR input (level 0: the caller's operator); null: dense [row][7] input
+    const double *vals;
+    int nx, ny, nz;                  // the fine grid
+    V *f[7];                         // the fine level's arrays in slot order -K, -J, -I, D, +I, +J, +K (null: not written)
+    V *c[7];                         // the coarse level's (null: the coarse level is not a var7 level)
+    double *cdense;                  // [coarse row][7]
+    double w;
+    unsigned long long *err;         // [2]: see var7_rap (common.h)
+};
+
+template <typename V, bool CSR_IN>
+__global__ __launch_bounds__(64 * V7RAP_WAVES) void var7_rap_kernel(const Var7RapArgs<V> a) {
+    __shared__ double s_stage[V7RAP_WAVES][64 * V7RAP_CHUNK];
+    __shared__ int64_t s_base[V7RAP_WAVES][64];
+    __shared__ int s_len[V7RAP_WAVES][64];
+    const int hx = a.nx / 2, hy = a.ny / 2, hz = a.nz / 2;
+    const int64_t nc = int64_t(hx) * hy * hz;
+    const int wv = int(threadIdx.x) >> 6, ln = int(threadIdx.x) & 63;
+    const int64_t crow = int64_t(blockIdx.x) * (64 * V7RAP_WAVES) + threadIdx.x;
+    const bool valid = crow < nc;                      // (a thread behind the last row fetches nothing, but takes part in the wave's steps)
+    const int I = int(crow % hx);
+    const int64_t line = crow / hx;
+    const int J = int(line % hy), K = int(line / hy);
+    const int64_t nh = int64_t(a.nx) * a.ny * a.nz / 2;
+    const double w = a.w;
+    double inner[8], face[7][4];                       // (R A)(I, j): the children; the cells behind face e (slots 0, 1, 2, 4, 5, 6)
+#pragma unroll
+    for (int q = 0; q < 8; ++q) inner[q] = 0.0;
+#pragma unroll
+    for (int q = 0; q < 28; ++q) face[q / 4][q % 4] = 0.0;
+    unsigned long long bad0 = ~0ull, bad1 = ~0ull;     // smallest offending fine row + 1: zero diagonal / otherwise not a var7 value
+    auto wave_sync = [] {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
+#pragma unroll
+    for (int pair = 0; pair < 4; ++pair) {
+        const int dj = pair & 1, dk = pair >> 1;
+        const int j = 2 * J + dj, k = 2 * K + dk;
+        const int64_t row0 = (int64_t(k) * a.ny + j) * a.nx + 2 * I;
+        const bool has[7] = {k > 0, j > 0, I > 0, true, true, j + 1 < a.ny, k + 1 < a.nz};   // child 0; child 1: -I always, +I iff I < hx - 1
+        wave_sync();                                   // (the previous pair's readers are done with the stage)
+        int64_t base = 0;
+        int len = 0;
+        if (valid) {
+            if (CSR_IN) { base = a.indptr[row0]; len = a.indptr[row0 + 2] - int(base); }
+            else { base = row0 * 7; len = 14; }
+        }
+        s_base[wv][ln] = base;
+        s_len[wv][ln] = len;
+        wave_sync();
+        double got[V7RAP_CHUNK];
+#pragma unroll
+        for (int u = 0; u < V7RAP_CHUNK; ++u) {
+            const int f = 64 * u + ln, owner = f / V7RAP_CHUNK, o = f - V7RAP_CHUNK * owner;
+            got[u] = o < s_len[wv][owner] ? a.vals[s_base[wv][owner] + o] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < V7RAP_CHUNK; ++u) s_stage[wv][64 * u + ln] = got[u];
+        wave_sync();
+        const double *const src = &s_stage[wv][V7RAP_CHUNK * ln];
+        int p = 0;
+#pragma unroll
+        for (int di = 0; di < 2; ++di) {
+            const int c = di + 2 * pair;
+            const int64_t slot = int64_t((di + j + k) & 1) * nh + (int64_t(k) * a.ny + j) * hx + I;     // the child's place in the colour layout
+#pragma unroll
+            for (int e = 0; e < 7; ++e) {
+                const bool present = e == 2 ? (di == 1 || has[2]) : e == 4 ? (di == 0 || I + 1 < hx) : has[e];
+                double v;
+                if (CSR_IN) { v = present ? src[p] : 0.0; p += present ? 1 : 0; }
+                else v = src[7 * di + e];
+                if (CSR_IN && a.f[0] && valid) {
+                    const V t = V(v);
+                    a.f[e][slot] = t;
+                    const unsigned long long rr = (unsigned long long)(row0 + di + 1);
+                    if (e == 3 && v == 0.0 && rr < bad0) bad0 = rr;
+                    if ((!isfinite(t) || (e == 3 && t == V(0))) && rr < bad1) bad1 = rr;
+                }
+                const double t = __dmul_rn(w, v);
+                // the cell this value couples child c to: inside the aggregate (or the child itself), or behind a face
+                if (e == 3) inner[c] = __dadd_rn(inner[c], t);
+                else if (e == 2) { if (di == 1) inner[c - 1] = __dadd_rn(inner[c - 1], t); else face[2][pair] = t; }
+                else if (e == 4) { if (di == 0) inner[c + 1] = __dadd_rn(inner[c + 1], t); else face[4][pair] = t; }
+                else if (e == 1) { if (dj == 1) inner[c - 2] = __dadd_rn(inner[c - 2], t); else face[1][di + 2 * dk] = t; }
+                else if (e == 5) { if (dj == 0) inner[c + 2] = __dadd_rn(inner[c + 2], t); else face[5][di + 2 * dk] = t; }
+                else if (e == 0) { if (dk == 1) inner[c - 4] = __dadd_rn(inner[c - 4], t); else face[0][di + 2 * dj] = t; }
+                else { if (dk == 0) inner[c + 4] = __dadd_rn(inner[c + 4], t); else face[6][di + 2 * dj] = t; }
+            }
+        }
+    }
+    if (!valid) return;
+    if (bad0 != ~0ull) atomicMin(&a.err[0], bad0);
+    if (bad1 != ~0ull) atomicMin(&a.err[1], bad1);
+    // the coarse row, slot by slot
+    const bool chas[7] = {K > 0, J > 0, I > 0, true, I + 1 < hx, J + 1 < hy, K + 1 < hz};
+    const int64_t cslot = int64_t((I + J + K) & 1) * (nc / 2) + crow / 2;
+    const unsigned long long cr = (1ull << 62) | (unsigned long long)(crow + 1);
+#pragma unroll
+    for (int e = 0; e < 7; ++e) {
+        double sum = 0.0;
+        if (e == 3) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) sum = __dadd_rn(sum, __dmul_rn(inner[q], w));
+        } else {
+#pragma unroll
+            for (int m = 0; m < 4; ++m) sum = __dadd_rn(sum, __dmul_rn(face[e][m], w));
+        }
+        if (!chas[e]) sum = 0.0;
+        a.cdense[crow * 7 + e] = sum;
+        if (a.c[0]) {
+            // what var7_scatter_kernel takes on a fresh level: every coupling inside the grid stored (nonzero), finite as V,
+            // a diagonal that is not zero as V
+            const V cv = V(sum);
+            if (e == 3 && sum == 0.0) atomicMin(&a.err[0], cr);
+            if (chas[e] && (sum == 0.0 || !isfinite(cv) || (e == 3 && cv == V(0)))) atomicMin(&a.err[1], cr);
+            a.c[e][cslot] = cv;
+        }
+    }
+}
+
+}  // namespace
+
+template <typename V>
+void var7_rap(const int32_t *indptr, const double *vals, int nx, int ny, int nz, double w, Var7Plan<V> *fine, Var7Plan<V> *coarse,
+              double *coarse_dense, unsigned long long *err, hipStream_t s) {
+    OMG_REQUIRE(nx >= 2 && ny >= 2 && nz >= 2 && !(nx & 1) && !(ny & 1) && !(nz & 1), "internal: var7_rap needs even extents");
+    OMG_REQUIRE(!fine || (indptr && fine->nx == nx && fine->ny == ny && fine->nz == nz && !fine->sym), "internal: var7_rap: the fine level is not this grid's");
+    OMG_REQUIRE(!coarse || (coarse->nx == nx / 2 && coarse->ny == ny / 2 && coarse->nz == nz / 2 && !coarse->sym),
+                "internal: var7_rap: the coarse var7 level does not sit under this grid");
+    Var7RapArgs<V> a;
+    std::memset(&a, 0, sizeof(a));
+    a.indptr = indptr; a.vals = vals;
+    a.nx = nx; a.ny = ny; a.nz = nz;
+    auto arrays = [](Var7Plan<V> *P, V **out) {
+        V *const t[7] = {P->cM[2].p, P->cM[1].p, P->cM[0].p, P->cD.p, P->cP[0].p, P->cP[1].p, P->cP[2].p};
+        for (int e = 0; e < 7; ++e) out[e] = t[e];
+    };
+    if (fine) arrays(fine, a.f);
+    if (coarse) arrays(coarse, a.c);
+    a.cdense = coarse_dense;
+    a.w = w;
+    a.err = err;
+    const int64_t nc = int64_t(nx / 2) * (ny / 2) * (nz / 2);
+    constexpr int T = 64 * V7RAP_WAVES;
+    const dim3 grid(unsigned((nc + T - 1) / T));
+    if (indptr) hipLaunchKernelGGL((var7_rap_kernel<V, true>), grid, dim3(T), 0, s, a);
+    else hipLaunchKernelGGL((var7_rap_kernel<V, false>), grid, dim3(T), 0, s, a);
+    OMG_HIP(hipGetLastError());
+}
+
+template <typename V>
+void Var7Plan<V>::rap_from(const int32_t *indptr, const double *vals, bool write_fine, double *coarse_dense, Var7Plan<V> *coarse,
+                           unsigned long long *err, hipStream_t s) {
+    var7_rap<V>(indptr, vals, nx, ny, nz, w, write_fine ? this : nullptr, coarse, coarse_dense, err, s);
+}
+
+template void var7_rap<double>(const int32_t *, const double *, int, int, int, double, Var7Plan<double> *, Var7Plan<double> *, double *,
+                               unsigned long long *, hipStream_t);
+template void var7_rap<float>(const int32_t *, const double *, int, int, int, double, Var7Plan<float> *, Var7Plan<float> *, double *,
+                              unsigned long long *, hipStream_t);
 template struct Var7Plan<double>;
 template struct Var7Plan<float>;
 
