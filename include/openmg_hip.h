@@ -92,6 +92,14 @@ int omg_hierarchy_create(int n_levels, const omg_csr *A, const omg_csr *R,
  * "within single-precision rounding of the fp64 iterate", stated per test.               */
 #define OMG_DTYPE_F64 0
 #define OMG_DTYPE_F32 1
+/* Mixed precision: the levels exactly as OMG_DTYPE_F32, plus level 0's outer state in double — its operator taken from
+ * the caller's double A[0] (never the float copy), the resident b and iterate, the CG vectors.  The resident entries then
+ * iterate in double around the fp32 V-cycle: omg_resident_cycle[s] run defect correction (r = b - A x in double, one
+ * zero-start fp32 V-cycle on fl32(r), x += its result; the norm is ||b - A x|| in double after the correction) and
+ * omg_resident_pcg runs FCG with z = M(fl32(r)), everything else double — answers to fp64 accuracy with fp32 cycles.
+ * omg_vcycle, omg_vcycle_ex, omg_vcycle_dev, omg_solve and omg_hierarchy_cycle_dev return OMG_ERR_UNSUPPORTED on such a
+ * hierarchy; the per-level operations act on its fp32 levels.  omg_hierarchy_dtype reports it. */
+#define OMG_DTYPE_MIXED 2
 int omg_hierarchy_create_ex(int n_levels, const omg_csr *A, const omg_csr *R, int smoother,
                             double omega, int dtype, omg_hierarchy **out);
 /* replaces: the setup of openmg.mgSolve — operators.restrictionList(problemShape, ...) + operators.coeffecientList(A_in, R)

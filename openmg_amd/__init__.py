@@ -17,7 +17,11 @@ Extra keys understood in the `parameters` dict (ignored by the reference):
                 norm, infoDict['cycle'] counts iterations and infoDict['norm'] is the true ||b - A u||; a CG breakdown
                 (an indefinite operator or preconditioner) raises RuntimeError.  Any other value raises ValueError
     'dtype'     'float64' (default, the reference's precision) or 'float32': the precision the
-                levels are stored and computed in on the device (inputs / outputs stay float64)
+                levels are stored and computed in on the device (inputs / outputs stay float64).
+                mgSolve only: 'mixed' — fp32 levels and V-cycles inside fp64 iterations on the finest level (its
+                operator, iterate, residual and CG vectors in fp64, each cycle run on fl32(r)): with accel None every
+                cycle is a defect correction x += M(fl32(b - A x)), with accel 'cg' FCG uses z = M(fl32(r)); u and
+                every norm are fp64 and converge to the fp64 solution at fp32 cycle cost.  mgCycle raises ValueError
     'trustOperators'  mgCycle only, default False: when the caller passes the SAME list members (object identity) it
                 passed on an earlier call — e.g. infoDict['A'] / infoDict['R'] handed back unchanged — the per-call
                 checksum of every byte of the lists (what recognises an operator edited in place) is skipped
@@ -329,6 +333,9 @@ def mgCycle(A, b, level, R, parameters, initial=None):
     of matching shapes work).  Returns (uOut, {'norm': ||b - A[level] uOut||_2}); the norm
     is 0 when `level` is the coarsest.  The device copy of the hierarchy is cached between
     calls (see clear_cache)."""
+    if parameters.get("dtype", "float64") == "mixed":
+        raise ValueError("parameters['dtype'] = 'mixed' is for mgSolve only (fp64 iterations around fp32 V-cycles); "
+                         "mgCycle runs one cycle: use 'float32' or 'float64'")
     coarsest = parameters["coarsestLevel"]
     if coarsest >= len(A) or coarsest > len(R):
         raise IndexError("parameters['coarsestLevel'] = %d but only %d operators / %d restrictions given"

@@ -238,13 +238,15 @@ def smoother_code(kind):
         raise ValueError("unknown smoother %r (choose from %s)" % (kind, sorted(set(SMOOTHERS))))
 
 
-DTYPE_F64, DTYPE_F32 = 0, 1
+DTYPE_F64, DTYPE_F32, DTYPE_MIXED = 0, 1, 2
 
 
 def dtype_code(dtype):
-    """OMG_DTYPE_* for a numpy dtype / name."""
-    if isinstance(dtype, int) and not isinstance(dtype, bool) and dtype in (DTYPE_F64, DTYPE_F32):
+    """OMG_DTYPE_* for a numpy dtype / name; 'mixed' is OMG_DTYPE_MIXED (fp32 levels, fp64 outer state of level 0)."""
+    if isinstance(dtype, int) and not isinstance(dtype, bool) and dtype in (DTYPE_F64, DTYPE_F32, DTYPE_MIXED):
         return dtype
+    if isinstance(dtype, str) and dtype == "mixed":
+        return DTYPE_MIXED
     dt = np.dtype(dtype)
     if dt == np.float64:
         return DTYPE_F64
@@ -297,7 +299,8 @@ class Hierarchy:
 
     def __init__(self, A_list, R_list, smoother="gs", omega=1.0, dtype="float64"):
         """dtype: precision the levels are stored and computed in on the device ("float64", the
-        reference's, or "float32"); host vectors are float64 either way."""
+        reference's, or "float32"; "mixed": float32 levels with level 0's outer state in float64, for the resident
+        entries); host vectors are float64 either way."""
         if len(R_list) != len(A_list) - 1:
             raise ValueError("need len(R) == len(A) - 1")
         self._A = [as_csr(M) for M in A_list]
@@ -473,10 +476,10 @@ class Hierarchy:
         check(lib().omg_hierarchy_sync(self._h))
 
     def device_dtype(self):
-        """np.dtype the levels are held in on the device (omg_hierarchy_dtype)."""
+        """np.dtype the levels are held in on the device (omg_hierarchy_dtype): float32 for a mixed hierarchy too."""
         code = ctypes.c_int(-1)
         check(lib().omg_hierarchy_dtype(self._h, ctypes.byref(code)))
-        return np.dtype(np.float32 if code.value == DTYPE_F32 else np.float64)
+        return np.dtype(np.float32 if code.value in (DTYPE_F32, DTYPE_MIXED) else np.float64)
 
     def level_sets(self, level):
         v = ctypes.c_int64(0)

@@ -245,6 +245,9 @@ HostCsr permute_csr(const omg_csr &A, const int32_t *row_perm /* new->old or nul
 // distributed runs need keys that agree across ranks.  Empty sets are kept.
 Ordering ordering_from_keys(const int32_t *keys, int64_t n, int32_t n_sets);
 HostCsr transpose_csr(const HostCsr &A);
+// P A P^T with the columns of every row ascending (row_perm new->old, col_inv old->new; null: identity); src[e]: the index
+// in A of entry e of the result
+HostCsr renumber_sorted(const omg_csr &A, const int32_t *row_perm, const int32_t *col_inv, std::vector<int32_t> &src);
 // Row blocks for the streaming kernels: greedy split of each set into blocks of at most
 // `max_rows` rows and `max_nnz` entries (a single longer row gets a block of its own).
 void make_row_blocks(const IndexVec &indptr, const std::vector<int64_t> &sets,
@@ -300,7 +303,7 @@ struct HostFormat {
     bool union_failed = false;                  // encode_csr's several-rows-per-thread attempt (union walk) did not qualify
 };
 template <typename V>
-HostFormat<V> encode_csr(const HostCsr &A, const std::vector<int64_t> &sets);
+HostFormat<V> encode_csr(const HostCsr &A, const std::vector<int64_t> &sets, int mode = -1);   // mode: OMG_COMPRESS bits (-1: from the environment)
 // encode -> decode -> compare bit for bit (throws on a mismatch); out: OMG_FORMAT_FIELDS statistics
 template <typename V>
 void format_selftest(const omg_csr &A, int64_t *out);
@@ -370,7 +373,7 @@ struct DevCsrT {
     int union_max = 0;                 // longest union of any block (picks the kernel instantiation)
     int union_blocks = 0;              // 1: blocks of rows_cap > 256 rows made for rows_union_kernel (not SHORT rows)
     int lanes_per_row = 1;             // 4 for operators with long rows (avg > 16 entries)
-    void upload(const HostCsr &A, const std::vector<int64_t> &sets, hipStream_t s);   // converts to V
+    void upload(const HostCsr &A, const std::vector<int64_t> &sets, hipStream_t s, bool plain = false);   // converts to V; plain: int32 CSR only (OMG_COMPRESS=0)
     size_t n_sets() const { return sets.empty() ? 0 : sets.size() - 1; }
     bool all_pattern() const {         // every (non-empty) set can run rows_pattern_kernel
         if (set_pattern.empty() || union_blocks) return false;
@@ -931,23 +934,31 @@ struct PcgPlane {
 };
 template <typename V>
 int pcg_wgs(int64_t n);               // workgroups (= partials) of the streaming launches over n values
+// Z: the element type of z = M(r) and of the cycle's right-hand side — V itself, or float under an fp64 outer iteration
+// (OMG_DTYPE_MIXED); rlo (Z != V only, otherwise ignored): fl32(r) goes there as well
 // (r, z) -> part[0, nwg), (z, q) -> part[nwg, 2 nwg)
-template <typename V>
-void pcg_dots(const V *r, const V *z, const V *q, int64_t n, double *part, const double *sc, hipStream_t s);
+template <typename V, typename Z>
+void pcg_dots(const V *r, const Z *z, const V *q, int64_t n, double *part, const double *sc, hipStream_t s);
 template <typename V>
 void pcg_dot(const V *a, const V *b, int64_t n, double *part, const double *sc, hipStream_t s);
 // p2 = z + beta p
-template <typename V>
-void pcg_pupdate(const V *z, const V *p, V *p2, int64_t n, const double *sc, hipStream_t s);
-// x += alpha p ; r -= alpha q ; ||r||^2 partials
-template <typename V>
-void pcg_update(V *x, const V *p, V *r, const V *q, int64_t n, double *part, const double *sc, hipStream_t s);
-// r = b - q (r nullable) and ||b - q||^2 partials; runs whatever PCG_DONE says
-template <typename V>
-void pcg_residual(const V *b, const V *q, V *r, int64_t n, double *part, hipStream_t s);
+template <typename V, typename Z>
+void pcg_pupdate(const Z *z, const V *p, V *p2, int64_t n, const double *sc, hipStream_t s);
+// x += alpha p ; r -= alpha q ; ||r||^2 partials ; rlo = fl32(r)
+template <typename V, typename Z>
+void pcg_update(V *x, const V *p, V *r, const V *q, Z *rlo, int64_t n, double *part, const double *sc, hipStream_t s);
+// r = b - q (r nullable) and ||b - q||^2 partials ; rlo = fl32(b - q) (nullable); runs whatever PCG_DONE says
+template <typename V, typename Z>
+void pcg_residual(const V *b, const V *q, V *r, Z *rlo, int64_t n, double *part, hipStream_t s);
 // p2 = z + beta p ; q = A p2 ; (p2, q) partials, matrix-free on a plane level; returns the partials' count
-template <typename V>
-int pcg_plane_step(const PcgPlane &g, const V *z, const V *p, V *p2, V *q, double *part, const double *sc, hipStream_t s);
+template <typename V, typename Z>
+int pcg_plane_step(const PcgPlane &g, const Z *z, const V *p, V *p2, V *q, double *part, const double *sc, hipStream_t s);
+// the mixed plain cycle's defect correction (not gated by PCG_DONE): x += z ...
+template <typename V, typename Z>
+void pcg_defect_add(V *x, const Z *z, int64_t n, hipStream_t s);
+// ... or on a plane level in one launch: x2 = x + z ; rlo = fl32(b - A x2) ; ||b - A x2||^2 partials (returns their count)
+template <typename V, typename Z>
+int pcg_defect_plane(const PcgPlane &g, const V *x, const Z *z, V *x2, const V *b, Z *rlo, double *part, hipStream_t s);
 void pcg_fold_beta(const double *part, int nwg, double *sc, bool first, hipStream_t s);
 void pcg_fold_alpha(const double *part, int nwg, double *sc, hipStream_t s);
 void pcg_fold_norm(const double *part, int nwg, double *sc, double *norms, int k, double threshold, hipStream_t s);

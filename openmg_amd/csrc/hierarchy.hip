@@ -196,6 +196,19 @@ struct Hier {
     // the scalars (PCG_NSC, then PCG_NSC zeros: beta = 0, not done), the workgroup partials, one norm per iteration
     DevBuf<V> pcg_b, pcg_x, pcg_p, pcg_p2, pcg_q;
     DevBuf<double> pcg_sc, pcg_part, pcg_norms;
+    // OMG_DTYPE_MIXED (a float hierarchy): the levels as for OMG_DTYPE_F32, and level 0's outer state in double — what the
+    // resident entries iterate on (mixed_* below), in the level's numbering.  The operator: on a plane level (pcg_fused_plane)
+    // its seven constants taken from the caller's double CSR; otherwise the caller's CSR renumbered into the level's ordering,
+    // columns ascending, plain int32 CSR (src: entry e came from the caller's entry src[e] — omg_hierarchy_update_fine).
+    // x / x2: the iterate and the out-of-place target of the plane defect correction (swapped); r, p, p2, q: FCG's
+    bool mixed = false;
+    struct Mixed {
+        bool plane = false;
+        PcgPlane pg{};
+        DevCsrT<double> A;
+        DevBuf<int32_t> src;
+        DevBuf<double> b, x, x2, r, p, p2, q;
+    } mx;
     int smoother = OMG_SMOOTH_GS_LEX;
     double omega = 1.0;
     hipStream_t own = nullptr, stream = nullptr;
@@ -1891,7 +1904,7 @@ template <typename V>
 void pcg_apply(Hier<V> *hh, const V *v, V *q, V *scratch, const double *sc0) {
     Level<V> &L = hh->lv[0];
     if (pcg_fused_plane(hh, L)) {
-        pcg_plane_step<V>(pcg_plane_of(L), v, v, scratch, q, hh->pcg_part.p, sc0, hh->stream);
+        pcg_plane_step<V, V>(pcg_plane_of(L), v, v, scratch, q, hh->pcg_part.p, sc0, hh->stream);
         return;
     }
     ensure_format(hh, 0);
@@ -1925,7 +1938,7 @@ void resident_pcg(Hier<V> *hh, int pre, int post, int max_iter, double threshold
     OMG_HIP(hipMemcpyAsync(X, L.xp, size_t(n) * sizeof(V), hipMemcpyDeviceToDevice, s));
     OMG_HIP(hipMemsetAsync(P, 0, size_t(n) * sizeof(V), s));       // (beta = 0 in the first iteration multiplies it)
     pcg_apply(hh, X, Q, P2, sc0);
-    pcg_residual<V>(B, Q, L.b.p, n, part, s);                      // r = b - A x0
+    pcg_residual<V, V>(B, Q, L.b.p, static_cast<V *>(nullptr), n, part, s);                      // r = b - A x0
     constexpr int BATCH = 16;
     double hs[PCG_NSC] = {0};
     int k = 0;
@@ -1934,13 +1947,13 @@ void resident_pcg(Hier<V> *hh, int pre, int post, int max_iter, double threshold
         for (int j = 0; j < cnt; ++j, ++k) {
             zero_start_cycle(hh, pre, post);                       // z = M(r)
             V *Z = L.xp, *R = L.b.p;
-            pcg_dots<V>(R, Z, Q, n, part, sc, s);
+            pcg_dots<V, V>(R, Z, Q, n, part, sc, s);
             pcg_fold_beta(part, nwg, sc, k == 0, s);
             int nwg2 = nwg;
             if (fused) {
-                nwg2 = pcg_plane_step<V>(pg, Z, P, P2, Q, part, sc, s);
+                nwg2 = pcg_plane_step<V, V>(pg, Z, P, P2, Q, part, sc, s);
             } else {
-                pcg_pupdate<V>(Z, P, P2, n, sc, s);
+                pcg_pupdate<V, V>(Z, P, P2, n, sc, s);
                 RowArgsT<V> a;
                 a.x = P2;
                 a.y = Q;
@@ -1949,7 +1962,7 @@ void resident_pcg(Hier<V> *hh, int pre, int post, int max_iter, double threshold
             }
             std::swap(P, P2);
             pcg_fold_alpha(part, nwg2, sc, s);
-            pcg_update<V>(X, P, R, Q, n, part, sc, s);
+            pcg_update<V, V>(X, P, R, Q, static_cast<V *>(nullptr), n, part, sc, s);
             pcg_fold_norm(part, nwg, sc, hh->pcg_norms.p, k, threshold, s);
         }
         OMG_HIP(hipMemcpyAsync(hs, sc, sizeof(hs), hipMemcpyDeviceToHost, s));
@@ -1963,7 +1976,7 @@ void resident_pcg(Hier<V> *hh, int pre, int post, int max_iter, double threshold
     OMG_HIP(hipMemcpyAsync(L.xp, X, size_t(n) * sizeof(V), hipMemcpyDeviceToDevice, s));
     OMG_HIP(hipMemcpyAsync(L.b.p, B, size_t(n) * sizeof(V), hipMemcpyDeviceToDevice, s));
     pcg_apply(hh, X, Q, P2, sc0);
-    pcg_residual<V>(B, Q, static_cast<V *>(nullptr), n, part, s);
+    pcg_residual<V, V>(B, Q, static_cast<V *>(nullptr), static_cast<V *>(nullptr), n, part, s);
     pcg_fold_sqrt(part, nwg, sc0 + PCG_ITERS, s);
     double tn = 0.0;
     OMG_HIP(hipMemcpyAsync(&tn, sc0 + PCG_ITERS, sizeof(double), hipMemcpyDeviceToHost, s));
@@ -1974,6 +1987,222 @@ void resident_pcg(Hier<V> *hh, int pre, int post, int max_iter, double threshold
     if (breakdown) *breakdown = hs[PCG_BREAK] != 0.0 ? 1 : 0;
 }
 
+// ---- OMG_DTYPE_MIXED: fp64 iterations around the fp32 zero-start V-cycle (pcg.hip kernels with Z = float) --------------
+// Every iteration crosses the precision boundary once each way: the cycle reads fl32(r) from L.b and leaves z in L.xp
+// (float); x, r, p, q, b, the operator and every norm stay double.  Plain cycles are defect correction
+// (x += M(fl32(b - A x)), the norm that of b - A x after the correction), PCG is the FCG of resident_pcg.  The fp64 x and
+// b are the resident state; L.b is formed again from them at the start of every call.  Neither runs from a hipGraph.
+
+// the seven constants of a plane level 0 (-K, -J, -I, diagonal, +I, +J, +K) in double from the caller's CSR (natural
+// numbering: r = (k ny + j) nx + i): for each direction the value at that offset in the row of the first cell that has
+// such a neighbour — the plan checked that every row agrees; an absent direction (2-D: K) is 0
+void plane_constants(const omg_csr &A, PcgPlane &g) {
+    const int64_t nx = g.nx, ny = g.ny, nz = g.nz, sj = nx, sk = nx * ny;
+    const int64_t off[7] = {-sk, -sj, -1, 0, 1, sj, sk};
+    const int64_t ext[7] = {nz, ny, nx, 1, nx, ny, nz};
+    for (int e = 0; e < 7; ++e) {
+        g.c[e] = 0.0;
+        if (e != 3 && ext[e] < 2) continue;
+        const int64_t r = e == 0 ? sk : e == 1 ? sj : e == 2 ? 1 : 0;     // minus directions: the cell one step in
+        const int64_t c = r + off[e];
+        for (int64_t p = A.indptr[r]; p < A.indptr[r + 1]; ++p)
+            if (A.indices[p] == c) g.c[e] = A.data[p];
+    }
+}
+
+template <typename V>
+void build_mixed(Hier<V> *h, const omg_csr &A0) {
+    Level<V> &L = h->lv[0];
+    auto &m = h->mx;
+    OMG_REQUIRE(A0.n_rows == L.n, "internal: the mixed outer operator has the wrong size");
+    SetupTimer tm("mixed precision: level 0's fp64 outer operator and vectors");
+    m.plane = pcg_fused_plane(h, L);
+    if (m.plane) {
+        m.pg = pcg_plane_of(L);
+        plane_constants(A0, m.pg);
+    } else {
+        materialise_ordering(L.ord);
+        const bool id = L.ord.identity;
+        std::vector<int32_t> src;
+        HostCsr Ap = renumber_sorted(A0, id ? nullptr : L.ord.perm.data(), id ? nullptr : L.ord.inv.data(), src);
+        m.A.upload(Ap, {0, L.n}, h->stream, true);
+        m.src.alloc(std::max<size_t>(src.size(), 1));
+        m.src.upload(src.data(), src.size(), h->stream);
+    }
+    const size_t vn = size_t(std::max<int64_t>(L.n, 1));
+    for (DevBuf<double> *b : {&m.b, &m.x, &m.r, &m.p, &m.p2, &m.q}) { b->alloc(vn); b->zero(h->stream); }
+    if (m.plane) { m.x2.alloc(vn); m.x2.zero(h->stream); }
+    if (h->pcg_sc.n < size_t(2 * PCG_NSC)) h->pcg_sc.alloc(2 * PCG_NSC);
+    if (h->pcg_part.n < size_t(2 * PCG_MAX_WG)) h->pcg_part.alloc(2 * PCG_MAX_WG);
+    OMG_HIP(hipStreamSynchronize(h->stream));
+    h->mixed = true;
+}
+
+// the entries that would hand back an fp32-accurate answer refuse a mixed hierarchy
+template <typename V>
+void refuse_mixed(const Hier<V> *h, const char *entry) {
+    if (h->mixed)
+        throw Error(OMG_ERR_UNSUPPORTED, std::string(entry) + ": a mixed-precision hierarchy solves through the resident entries "
+                                         "(omg_resident_load[_dev], omg_resident_cycle[s], omg_resident_pcg, omg_resident_fetch[_dev])");
+}
+
+// q = A v in double (sc0: zero scalars for the plane launch, scratch: its p2)
+template <typename V>
+void mixed_apply(Hier<V> *h, const double *v, double *q, double *scratch, const double *sc0) {
+    auto &m = h->mx;
+    if (m.plane) {
+        pcg_plane_step<double, double>(m.pg, v, v, scratch, q, h->pcg_part.p, sc0, h->stream);
+        return;
+    }
+    RowArgsT<double> a;
+    a.x = const_cast<double *>(v);
+    a.y = q;
+    launch_rows(m.A, ROW_SPMV, -1, a, h->stream);
+}
+
+// r = b - A x (r64 nullable) and fl32(r) into the cycle's right-hand side L.b; ||r||^2 partials (pcg_wgs<double>(n) of them).
+// Uses q and p2.
+template <typename V>
+void mixed_residual(Hier<V> *h, double *r64) {
+    auto &m = h->mx;
+    Level<V> &L = h->lv[0];
+    mixed_apply(h, m.x.p, m.q.p, m.p2.p, h->pcg_sc.p + PCG_NSC);
+    pcg_residual<double, V>(m.b.p, m.q.p, r64, L.b.p, L.n, h->pcg_part.p, h->stream);
+}
+
+// n_cycles defect-correction cycles; the norm of cycle k to out[k] (device)
+template <typename V>
+void mixed_cycles(Hier<V> *h, int pre, int post, int n_cycles, double *out) {
+    auto &m = h->mx;
+    Level<V> &L = h->lv[0];
+    const int64_t n = L.n;
+    hipStream_t s = h->stream;
+    double *part = h->pcg_part.p;
+    OMG_HIP(hipMemsetAsync(h->pcg_sc.p, 0, 2 * PCG_NSC * sizeof(double), s));
+    mixed_residual(h, static_cast<double *>(nullptr));
+    for (int k = 0; k < n_cycles; ++k) {
+        zero_start_cycle(h, pre, post);                            // z = M(fl32(r)) in L.xp
+        int nwg;
+        if (m.plane) {
+            nwg = pcg_defect_plane<double, V>(m.pg, m.x.p, L.xp, m.x2.p, m.b.p, L.b.p, part, s);
+            std::swap(m.x, m.x2);
+        } else {
+            pcg_defect_add<double, V>(m.x.p, L.xp, n, s);
+            RowArgsT<double> a;
+            a.x = m.x.p;
+            a.y = m.q.p;
+            launch_rows(m.A, ROW_SPMV, -1, a, s);
+            pcg_residual<double, V>(m.b.p, m.q.p, static_cast<double *>(nullptr), L.b.p, n, part, s);
+            nwg = pcg_wgs<double>(n);
+        }
+        pcg_fold_sqrt(part, nwg, out + k, s);
+    }
+}
+
+// resident_pcg with x, r, p, p2, q, b in double and z = M(fl32(r)) in float
+template <typename V>
+void mixed_pcg(Hier<V> *hh, int pre, int post, int max_iter, double threshold, int *iterations, double *norms, double *true_norm,
+               int *breakdown) {
+    auto &m = hh->mx;
+    Level<V> &L = hh->lv[0];
+    const int64_t n = L.n;
+    hipStream_t s = hh->stream;
+    if (hh->pcg_norms.n < size_t(max_iter)) hh->pcg_norms.alloc(size_t(max_iter));
+    double *sc = hh->pcg_sc.p, *sc0 = hh->pcg_sc.p + PCG_NSC, *part = hh->pcg_part.p;
+    double *X = m.x.p, *R = m.r.p, *Q = m.q.p, *P = m.p.p, *P2 = m.p2.p;
+    const int nwg = pcg_wgs<double>(n);
+    OMG_HIP(hipMemsetAsync(sc, 0, 2 * PCG_NSC * sizeof(double), s));
+    mixed_residual(hh, R);                                          // r = b - A x0, fl32(r) -> L.b
+    OMG_HIP(hipMemsetAsync(P, 0, size_t(n) * sizeof(double), s));  // (beta = 0 in the first iteration multiplies it)
+    constexpr int BATCH = 16;
+    double hs[PCG_NSC] = {0};
+    int k = 0;
+    while (k < max_iter) {
+        const int cnt = std::min(BATCH, max_iter - k);
+        for (int j = 0; j < cnt; ++j, ++k) {
+            zero_start_cycle(hh, pre, post);                       // z = M(fl32(r))
+            const V *Z = L.xp;
+            pcg_dots<double, V>(R, Z, Q, n, part, sc, s);
+            pcg_fold_beta(part, nwg, sc, k == 0, s);
+            int nwg2 = nwg;
+            if (m.plane) {
+                nwg2 = pcg_plane_step<double, V>(m.pg, Z, P, P2, Q, part, sc, s);
+            } else {
+                pcg_pupdate<double, V>(Z, P, P2, n, sc, s);
+                RowArgsT<double> a;
+                a.x = P2;
+                a.y = Q;
+                launch_rows(m.A, ROW_SPMV, -1, a, s);
+                pcg_dot<double>(P2, Q, n, part, sc, s);
+            }
+            std::swap(P, P2);
+            pcg_fold_alpha(part, nwg2, sc, s);
+            pcg_update<double, V>(X, P, R, Q, L.b.p, n, part, sc, s);
+            pcg_fold_norm(part, nwg, sc, hh->pcg_norms.p, k, threshold, s);
+        }
+        OMG_HIP(hipMemcpyAsync(hs, sc, sizeof(hs), hipMemcpyDeviceToHost, s));
+        OMG_HIP(hipStreamSynchronize(s));
+        check_march(hh);
+        if (hs[PCG_DONE] != 0.0) break;
+    }
+    const int iters = int(hs[PCG_ITERS]);
+    if (norms && iters > 0) OMG_HIP(hipMemcpyAsync(norms, hh->pcg_norms.p, size_t(iters) * sizeof(double), hipMemcpyDeviceToHost, s));
+    mixed_residual(hh, static_cast<double *>(nullptr));            // the true residual once
+    pcg_fold_sqrt(part, nwg, sc0 + PCG_ITERS, s);
+    double tn = 0.0;
+    OMG_HIP(hipMemcpyAsync(&tn, sc0 + PCG_ITERS, sizeof(double), hipMemcpyDeviceToHost, s));
+    OMG_HIP(hipStreamSynchronize(s));
+    check_march(hh);
+    if (iterations) *iterations = iters;
+    if (true_norm) *true_norm = tn;
+    if (breakdown) *breakdown = hs[PCG_BREAK] != 0.0 ? 1 : 0;
+}
+
+// the fp64 resident vectors from / to natural numbering (host or device double arrays)
+template <typename V>
+void mixed_load(Hier<V> *h, const double *b, const double *x0, bool dev) {
+    auto &m = h->mx;
+    Level<V> &L = h->lv[0];
+    const int32_t *perm = L.ord.identity ? nullptr : L.perm.p;
+    auto put = [&](const double *src, double *dst) {
+        if (!dev) {
+            ensure_nat(h, 0);
+            L.nat.upload(src, L.n, h->stream);
+            src = L.nat.p;
+        }
+        launch_gather<double, double>(src, perm, dst, L.n, h->stream);
+    };
+    put(b, m.b.p);
+    if (x0) put(x0, m.x.p);
+    else OMG_HIP(hipMemsetAsync(m.x.p, 0, size_t(L.n) * sizeof(double), h->stream));
+    OMG_HIP(hipStreamSynchronize(h->stream));
+}
+
+template <typename V>
+void mixed_fetch(Hier<V> *h, double *x, bool dev) {
+    Level<V> &L = h->lv[0];
+    const int32_t *perm = L.ord.identity ? nullptr : L.perm.p;
+    if (dev) {
+        launch_scatter<double, double>(h->mx.x.p, perm, x, L.n, h->stream);
+        OMG_HIP(hipStreamSynchronize(h->stream));
+    } else {
+        ensure_nat(h, 0);
+        launch_scatter<double, double>(h->mx.x.p, perm, L.nat.p, L.n, h->stream);
+        download_staged(x, L.nat.p, size_t(L.n) * sizeof(double), h->stream);
+    }
+    check_march(h);
+}
+
+// omg_hierarchy_update_fine on a mixed hierarchy, after the fp32 levels: the outer operator's values gathered from the new
+// ones through src (its pattern is the caller's operator's, renumbered)
+template <typename V>
+void mixed_update_values(Hier<V> *h, const double *vals_dev, int64_t nnz) {
+    auto &m = h->mx;
+    OMG_REQUIRE(!m.plane && m.A.nnz == nnz, "internal: the mixed outer operator does not match the update");
+    launch_gather<double, double>(vals_dev, m.src.p, m.A.data.p, nnz, h->stream);
+    OMG_HIP(hipStreamSynchronize(h->stream));
+}
+
 }  // namespace
 }  // namespace omg
 
@@ -1982,7 +2211,7 @@ using namespace omg;
 extern "C" {
 
 const char *omg_last_error(void) { return g_last_error.c_str(); }
-const char *omg_version(void) { return "openmg_hip 0.2 (gfx950; f64, f32)"; }
+const char *omg_version(void) { return "openmg_hip 0.2 (gfx950; f64, f32, mixed)"; }
 
 int omg_device_count(int *count) {
     return guarded([&] {
@@ -2017,10 +2246,11 @@ int omg_hierarchy_create_ex(int n_levels, const omg_csr *A, const omg_csr *R, in
     return guarded([&] {
         OMG_REQUIRE(out, "out is null");
         *out = nullptr;
-        OMG_REQUIRE(dtype == OMG_DTYPE_F64 || dtype == OMG_DTYPE_F32, "unknown dtype");
+        OMG_REQUIRE(dtype == OMG_DTYPE_F64 || dtype == OMG_DTYPE_F32 || dtype == OMG_DTYPE_MIXED, "unknown dtype");
         std::unique_ptr<omg_hierarchy> h(new omg_hierarchy);
-        if (dtype == OMG_DTYPE_F32) h->f = create<float>(n_levels, A, R, smoother, omega);
+        if (dtype != OMG_DTYPE_F64) h->f = create<float>(n_levels, A, R, smoother, omega);
         else h->d = create<double>(n_levels, A, R, smoother, omega);
+        if (dtype == OMG_DTYPE_MIXED) build_mixed(h->f.get(), A[0]);
         *out = h.release();
     });
 }
@@ -2035,24 +2265,40 @@ int omg_hierarchy_create_from_fine(const omg_csr *A_in, int dim, const int64_t *
     return guarded([&] {
         OMG_REQUIRE(out && A_in, "null argument");
         *out = nullptr;
-        OMG_REQUIRE(dtype == OMG_DTYPE_F64 || dtype == OMG_DTYPE_F32, "unknown dtype");
+        OMG_REQUIRE(dtype == OMG_DTYPE_F64 || dtype == OMG_DTYPE_F32 || dtype == OMG_DTYPE_MIXED, "unknown dtype");
         std::unique_ptr<omg_hierarchy> h(new omg_hierarchy);
-        if (dtype == OMG_DTYPE_F32) h->f = create_from_fine<float>(*A_in, dim, shape, n_restrictions, smoother, omega);
+        if (dtype != OMG_DTYPE_F64) h->f = create_from_fine<float>(*A_in, dim, shape, n_restrictions, smoother, omega);
         else h->d = create_from_fine<double>(*A_in, dim, shape, n_restrictions, smoother, omega);
+        if (dtype == OMG_DTYPE_MIXED) build_mixed(h->f.get(), *A_in);
         *out = h.release();
     });
 }
 
 int omg_hierarchy_update_fine(omg_hierarchy *h, const double *data, int64_t nnz, int on_device) {
     return guarded([&] {
-        with(h, [&](auto *hh) { update_fine(hh, data, nnz, on_device != 0); });
+        with(h, [&](auto *hh) {
+            if (!hh->mixed) {
+                update_fine(hh, data, nnz, on_device != 0);
+                return;
+            }
+            // (the new values once in HBM for both the fp32 levels and the fp64 outer operator)
+            DevBuf<double> up;
+            const double *dev = data;
+            if (!on_device && data && nnz > 0) {
+                up.alloc(size_t(nnz));
+                OMG_HIP(hipMemcpyAsync(up.p, data, size_t(nnz) * sizeof(double), hipMemcpyHostToDevice, hh->stream));
+                dev = up.p;
+            }
+            update_fine(hh, dev, nnz, true);
+            mixed_update_values(hh, dev, nnz);
+        });
     });
 }
 
 int omg_hierarchy_dtype(const omg_hierarchy *h, int *dtype) {
     return guarded([&] {
         OMG_REQUIRE(h && dtype, "null argument");
-        *dtype = h->f ? OMG_DTYPE_F32 : OMG_DTYPE_F64;
+        *dtype = h->f ? (h->f->mixed ? OMG_DTYPE_MIXED : OMG_DTYPE_F32) : OMG_DTYPE_F64;
     });
 }
 
@@ -2189,6 +2435,7 @@ int omg_vcycle(omg_hierarchy *h, int level, const double *b, double *x, int pre,
                double *norm) {
     return guarded([&] {
         with(h, [&](auto *hh) {
+            refuse_mixed(hh, "omg_vcycle");
             using V = value_of<decltype(hh)>;
             check_level(hh, level);
             OMG_REQUIRE(b && x, "b / x is null");
@@ -2214,6 +2461,7 @@ int omg_vcycle_ex(omg_hierarchy *h, int level, const double *b, const double *x_
                   int pre, int post, double *norm) {
     return guarded([&] {
         with(h, [&](auto *hh) {
+            refuse_mixed(hh, "omg_vcycle_ex");
             using V = value_of<decltype(hh)>;
             check_level(hh, level);
             OMG_REQUIRE(b && x_out, "b / x_out is null");
@@ -2258,6 +2506,7 @@ int omg_vcycle_dev(omg_hierarchy *h, int level, const double *b_dev, const doubl
                    int pre, int post, double *norm) {
     return guarded([&] {
         with(h, [&](auto *hh) {
+            refuse_mixed(hh, "omg_vcycle_dev");
             using V = value_of<decltype(hh)>;
             check_level(hh, level);
             OMG_REQUIRE(b_dev && x_out_dev, "b / x_out is null");
@@ -2300,6 +2549,11 @@ int omg_resident_load_dev(omg_hierarchy *h, const double *b_dev, const double *x
             using V = value_of<decltype(hh)>;
             check_level(hh, 0);
             OMG_REQUIRE(b_dev, "b is null");
+            if (hh->mixed) {
+                mixed_load(hh, b_dev, x0_dev, true);
+                hh->resident = true;
+                return;
+            }
             auto &L = hh->lv[0];
             load_vec_dev(hh, 0, b_dev, L.b.p);
             if (x0_dev) load_vec_dev(hh, 0, x0_dev, L.xp);
@@ -2316,6 +2570,10 @@ int omg_resident_fetch_dev(omg_hierarchy *h, double *x_dev) {
             using V = value_of<decltype(hh)>;
             check_level(hh, 0);
             OMG_REQUIRE(hh->resident && x_dev, "nothing resident / x is null");
+            if (hh->mixed) {
+                mixed_fetch(hh, x_dev, true);
+                return;
+            }
             fetch_vec_dev<V>(hh, 0, hh->lv[0].xp, x_dev);
             OMG_HIP(hipStreamSynchronize(hh->stream));
             check_march(hh);
@@ -2331,6 +2589,7 @@ int omg_hierarchy_cycle_dev(omg_hierarchy *h, const double *b_dev, double *x_dev
                             void *hip_stream) {
     return guarded([&] {
         with(h, [&](auto *hh) {
+            refuse_mixed(hh, "omg_hierarchy_cycle_dev");
             using V = value_of<decltype(hh)>;
             check_level(hh, 0);
             OMG_REQUIRE(b_dev && x_dev && pre >= 0 && post >= 0, "bad argument");
@@ -2360,6 +2619,11 @@ int omg_resident_load(omg_hierarchy *h, const double *b, const double *x0) {
             using V = value_of<decltype(hh)>;
             check_level(hh, 0);
             OMG_REQUIRE(b, "b is null");
+            if (hh->mixed) {
+                mixed_load(hh, b, x0, false);
+                hh->resident = true;
+                return;
+            }
             auto &L = hh->lv[0];
             load_vec(hh, 0, b, L.b.p);
             if (x0) load_vec(hh, 0, x0, L.xp);
@@ -2376,6 +2640,12 @@ int omg_resident_cycle(omg_hierarchy *h, int pre, int post, double *norm) {
             check_level(hh, 0);
             OMG_REQUIRE(hh->resident, "omg_resident_load has not been called");
             OMG_REQUIRE(pre >= 0 && post >= 0, "negative sweep count");
+            if (hh->mixed) {
+                mixed_cycles(hh, pre, post, 1, hh->norm_dev.p);
+                const double nv = read_norm(hh);
+                if (norm) *norm = nv;
+                return;
+            }
             run_cycle0(hh, pre, post);
             if (norm) *norm = read_norm(hh);
         });
@@ -2394,6 +2664,13 @@ int omg_resident_cycles(omg_hierarchy *h, int pre, int post, int n_cycles, doubl
             OMG_REQUIRE(pre >= 0 && post >= 0 && n_cycles >= 0, "negative argument");
             if (n_cycles == 0) return;
             if (hh->norms_dev.n < size_t(n_cycles)) hh->norms_dev.alloc(size_t(n_cycles));
+            if (hh->mixed) {
+                mixed_cycles(hh, pre, post, n_cycles, hh->norms_dev.p);
+                if (norms) OMG_HIP(hipMemcpyAsync(norms, hh->norms_dev.p, size_t(n_cycles) * sizeof(double), hipMemcpyDeviceToHost, hh->stream));
+                OMG_HIP(hipStreamSynchronize(hh->stream));
+                check_march(hh);
+                return;
+            }
             const bool single = hh->lv.size() == 1;
             if (!single && use_plane(hh, hh->lv[0], pre, post) && post <= 1) {
                 // every cycle's up pass leaves its workgroup partials in a slot of the batch buffer; one
@@ -2541,6 +2818,10 @@ int omg_resident_fetch(omg_hierarchy *h, double *x) {
             using V = value_of<decltype(hh)>;
             check_level(hh, 0);
             OMG_REQUIRE(hh->resident && x, "nothing resident / x is null");
+            if (hh->mixed) {
+                mixed_fetch(hh, x, false);
+                return;
+            }
             fetch_vec<V>(hh, 0, hh->lv[0].xp, x);
         });
     });
@@ -2554,7 +2835,8 @@ int omg_resident_pcg(omg_hierarchy *h, int pre, int post, int max_iter, double t
             OMG_REQUIRE(hh->resident, "omg_resident_load has not been called");
             OMG_REQUIRE(pre >= 0 && post >= 0 && max_iter >= 1, "negative sweep count / max_iter < 1");
             OMG_REQUIRE(hh->lv.size() > 1, "a single-level hierarchy solves directly: nothing to accelerate");
-            resident_pcg(hh, pre, post, max_iter, threshold, iterations, norms, true_norm, breakdown);
+            if (hh->mixed) mixed_pcg(hh, pre, post, max_iter, threshold, iterations, norms, true_norm, breakdown);
+            else resident_pcg(hh, pre, post, max_iter, threshold, iterations, norms, true_norm, breakdown);
         });
     });
 }
@@ -2573,6 +2855,7 @@ int omg_solve(omg_hierarchy *h, const double *b, double *x, int pre, int post, i
               double threshold, int *cycles_done, double *norm) {
     return guarded([&] {
         with(h, [&](auto *hh) {
+            refuse_mixed(hh, "omg_solve");
             using V = value_of<decltype(hh)>;
             check_level(hh, 0);
             OMG_REQUIRE(b && x, "b / x is null");

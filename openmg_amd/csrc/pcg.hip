@@ -11,7 +11,13 @@
 // one-workgroup fold adds the slots in a fixed order and derives alpha / beta from them — the same bits from run to run,
 // no host round trip per iteration, no float atomics.  A fold that meets convergence or a breakdown raises PCG_DONE;
 // every kernel here returns at once when it is set, so the iterate stays that of the first converged iteration.
+//
+// Mixed precision (OMG_DTYPE_MIXED): the same kernels with a second element type Z for what the cycle reads and writes
+// — z = M(r) arrives as float, and the update / residual kernels also leave fl32(r) in the cycle's right-hand side —
+// while x, r, p, q, b and every scalar stay double.  With Z = V (the fp64 and fp32 hierarchies) they compute what they
+// always computed.  The defect-correction kernels at the end (x += z, r = b - A x) serve the mixed plain cycle.
 #include <algorithm>
+#include <type_traits>
 #include <cmath>
 
 #include "common.h"
@@ -51,15 +57,16 @@ __device__ __forceinline__ void st(V *p, int64_t c, const Chunk<V, VW> &v) {
 __device__ __forceinline__ bool pcg_done(const double *sc) { return sc[PCG_DONE] != 0.0; }
 
 // (r, z) -> part[wg], (z, q) -> part[nwg + wg]
-template <typename V, int VW>
-__global__ __launch_bounds__(PCG_WG) void dots_kernel(const V *__restrict__ r, const V *__restrict__ z, const V *__restrict__ q,
+template <typename V, typename Z, int VW>
+__global__ __launch_bounds__(PCG_WG) void dots_kernel(const V *__restrict__ r, const Z *__restrict__ z, const V *__restrict__ q,
                                                       int64_t n, double *__restrict__ part, const double *__restrict__ sc) {
     __shared__ double sh[PCG_WG];
     if (pcg_done(sc)) return;
     const int64_t nc = n / VW, stride = int64_t(gridDim.x) * PCG_WG;
     double rz = 0.0, zq = 0.0;
     for (int64_t c = int64_t(blockIdx.x) * PCG_WG + threadIdx.x; c < nc; c += stride) {
-        const Chunk<V, VW> a = ld<V, VW>(r, c), b = ld<V, VW>(z, c), d = ld<V, VW>(q, c);
+        const Chunk<V, VW> a = ld<V, VW>(r, c), d = ld<V, VW>(q, c);
+        const Chunk<Z, VW> b = ld<Z, VW>(z, c);
 #pragma unroll
         for (int e = 0; e < VW; ++e) {
             rz = fma(double(a.v[e]), double(b.v[e]), rz);
@@ -98,14 +105,15 @@ __global__ __launch_bounds__(PCG_WG) void dot_kernel(const V *__restrict__ a, co
 }
 
 // p2 = z + beta p
-template <typename V, int VW>
-__global__ __launch_bounds__(PCG_WG) void pupdate_kernel(const V *__restrict__ z, const V *__restrict__ p, V *__restrict__ p2,
+template <typename V, typename Z, int VW>
+__global__ __launch_bounds__(PCG_WG) void pupdate_kernel(const Z *__restrict__ z, const V *__restrict__ p, V *__restrict__ p2,
                                                          int64_t n, const double *__restrict__ sc) {
     if (pcg_done(sc)) return;
     const double beta = sc[PCG_BETA];
     const int64_t nc = n / VW, stride = int64_t(gridDim.x) * PCG_WG;
     for (int64_t c = int64_t(blockIdx.x) * PCG_WG + threadIdx.x; c < nc; c += stride) {
-        const Chunk<V, VW> u = ld<V, VW>(z, c), w = ld<V, VW>(p, c);
+        const Chunk<Z, VW> u = ld<Z, VW>(z, c);
+        const Chunk<V, VW> w = ld<V, VW>(p, c);
         Chunk<V, VW> o;
 #pragma unroll
         for (int e = 0; e < VW; ++e) o.v[e] = V(fma(beta, double(w.v[e]), double(u.v[e])));
@@ -115,11 +123,12 @@ __global__ __launch_bounds__(PCG_WG) void pupdate_kernel(const V *__restrict__ z
         for (int64_t i = nc * VW + threadIdx.x; i < n; i += PCG_WG) p2[i] = V(fma(beta, double(p[i]), double(z[i])));
 }
 
-// x += alpha p ; r -= alpha q ; ||r||^2 -> part[wg]
-template <typename V, int VW>
+// x += alpha p ; r -= alpha q ; ||r||^2 -> part[wg]; Z != V: also rlo = fl32(r), the cycle's right-hand side
+template <typename V, typename Z, int VW>
 __global__ __launch_bounds__(PCG_WG) void update_kernel(V *__restrict__ x, const V *__restrict__ p, V *__restrict__ r,
-                                                        const V *__restrict__ q, int64_t n, double *__restrict__ part,
-                                                        const double *__restrict__ sc) {
+                                                        const V *__restrict__ q, Z *__restrict__ rlo, int64_t n,
+                                                        double *__restrict__ part, const double *__restrict__ sc) {
+    constexpr bool LO = !std::is_same<V, Z>::value;
     __shared__ double sh[PCG_WG];
     if (pcg_done(sc)) return;
     const double alpha = sc[PCG_ALPHA];
@@ -136,21 +145,30 @@ __global__ __launch_bounds__(PCG_WG) void update_kernel(V *__restrict__ x, const
         }
         st<V, VW>(x, c, xv);
         st<V, VW>(r, c, rv);
+        if constexpr (LO) {
+            Chunk<Z, VW> lo;
+#pragma unroll
+            for (int e = 0; e < VW; ++e) lo.v[e] = Z(rv.v[e]);
+            st<Z, VW>(rlo, c, lo);
+        }
     }
     if (blockIdx.x == 0)
         for (int64_t i = nc * VW + threadIdx.x; i < n; i += PCG_WG) {
             x[i] = V(fma(alpha, double(p[i]), double(x[i])));
             r[i] = V(fma(-alpha, double(q[i]), double(r[i])));
             rr = fma(double(r[i]), double(r[i]), rr);
+            if constexpr (LO) rlo[i] = Z(r[i]);
         }
     rr = block_sum(rr, sh);
     if (threadIdx.x == 0) part[blockIdx.x] = rr;
 }
 
 // r = b - q (r nullable) ; ||b - q||^2 -> part[wg].  Not gated by PCG_DONE (the set-up and the final true residual).
-template <typename V, int VW>
+// Z != V: also rlo = fl32(b - q) (nullable)
+template <typename V, typename Z, int VW>
 __global__ __launch_bounds__(PCG_WG) void residual_kernel(const V *__restrict__ b, const V *__restrict__ q, V *__restrict__ r,
-                                                          int64_t n, double *__restrict__ part) {
+                                                          Z *__restrict__ rlo, int64_t n, double *__restrict__ part) {
+    constexpr bool LO = !std::is_same<V, Z>::value;
     __shared__ double sh[PCG_WG];
     const int64_t nc = n / VW, stride = int64_t(gridDim.x) * PCG_WG;
     double rr = 0.0;
@@ -163,11 +181,20 @@ __global__ __launch_bounds__(PCG_WG) void residual_kernel(const V *__restrict__ 
             rr = fma(double(o.v[e]), double(o.v[e]), rr);
         }
         if (r) st<V, VW>(r, c, o);
+        if constexpr (LO) {
+            if (rlo) {
+                Chunk<Z, VW> lo;
+#pragma unroll
+                for (int e = 0; e < VW; ++e) lo.v[e] = Z(o.v[e]);
+                st<Z, VW>(rlo, c, lo);
+            }
+        }
     }
     if (blockIdx.x == 0)
         for (int64_t i = nc * VW + threadIdx.x; i < n; i += PCG_WG) {
             const V o = b[i] - q[i];
             if (r) r[i] = o;
+            if constexpr (LO) { if (rlo) rlo[i] = Z(o); }
             rr = fma(double(o), double(o), rr);
         }
     rr = block_sum(rr, sh);
@@ -179,8 +206,8 @@ __global__ __launch_bounds__(PCG_WG) void residual_kernel(const V *__restrict__ 
 // c nr + k ny hx + j hx + i / 2).  One output slot per thread; the neighbours' p2 (all of the other colour) is formed from
 // their z and p again, so p2 goes to a buffer of its own.  Each row is the row kernels' fma chain in column order from +0
 // (-K, -J, -I, diagonal, +I, +J, +K); a neighbour outside the grid contributes c * 0.
-template <typename V>
-__global__ __launch_bounds__(PCG_WG) void plane_step_kernel(const V *__restrict__ z, const V *__restrict__ p, V *__restrict__ p2,
+template <typename V, typename Z>
+__global__ __launch_bounds__(PCG_WG) void plane_step_kernel(const Z *__restrict__ z, const V *__restrict__ p, V *__restrict__ p2,
                                                             V *__restrict__ q, PcgPlane g, double *__restrict__ part,
                                                             const double *__restrict__ sc) {
     __shared__ double sh[PCG_WG];
@@ -220,6 +247,67 @@ __global__ __launch_bounds__(PCG_WG) void plane_step_kernel(const V *__restrict_
     }
     pq = block_sum(pq, sh);
     if (threadIdx.x == 0) part[blockIdx.x] = pq;
+}
+
+// ---- defect correction of the mixed plain cycle: x' = x + z, r = b - A x', fl32(r) for the next cycle, ||r||^2 ----------
+
+// x += z (any level); the fp64 SpMV and residual_kernel follow
+template <typename V, typename Z, int VW>
+__global__ __launch_bounds__(PCG_WG) void defect_add_kernel(V *__restrict__ x, const Z *__restrict__ z, int64_t n) {
+    const int64_t nc = n / VW, stride = int64_t(gridDim.x) * PCG_WG;
+    for (int64_t c = int64_t(blockIdx.x) * PCG_WG + threadIdx.x; c < nc; c += stride) {
+        Chunk<V, VW> xv = ld<V, VW>(x, c);
+        const Chunk<Z, VW> zv = ld<Z, VW>(z, c);
+#pragma unroll
+        for (int e = 0; e < VW; ++e) xv.v[e] = xv.v[e] + V(zv.v[e]);
+        st<V, VW>(x, c, xv);
+    }
+    if (blockIdx.x == 0)
+        for (int64_t i = nc * VW + threadIdx.x; i < n; i += PCG_WG) x[i] = x[i] + V(z[i]);
+}
+
+// On a plane level (the layout of plane_step_kernel): x2 = x + z, r = b - A x2 with the neighbours' x2 formed again from their
+// x and z (so x2 is a buffer of its own), rlo = fl32(r), ||r||^2 -> part[wg].  A x2 is plane_step_kernel's fma chain.
+template <typename V, typename Z>
+__global__ __launch_bounds__(PCG_WG) void defect_plane_kernel(const V *__restrict__ x, const Z *__restrict__ z, V *__restrict__ x2,
+                                                              const V *__restrict__ b, Z *__restrict__ rlo, PcgPlane g,
+                                                              double *__restrict__ part) {
+    __shared__ double sh[PCG_WG];
+    const V c0 = V(g.c[0]), c1 = V(g.c[1]), c2 = V(g.c[2]), c3 = V(g.c[3]), c4 = V(g.c[4]), c5 = V(g.c[5]), c6 = V(g.c[6]);
+    const int64_t ps = int64_t(g.ny) * g.hx, n = 2 * g.nr, stride = int64_t(gridDim.x) * PCG_WG;
+    auto xv = [&](int64_t s) -> V { return x[s] + V(z[s]); };
+    double rr = 0.0;
+    for (int64_t s = int64_t(blockIdx.x) * PCG_WG + threadIdx.x; s < n; s += stride) {
+        const int colour = s >= g.nr ? 1 : 0;
+        const int64_t u = s - (colour ? g.nr : 0);
+        const int k = int(u / ps);
+        const int64_t rem = u - int64_t(k) * ps;
+        const int j = int(rem / g.hx), h = int(rem - int64_t(j) * g.hx);
+        const int par = (j + k) & 1;
+        const int i = 2 * h + (colour ? 1 - par : par);
+        const int64_t ob = colour ? 0 : g.nr;
+        const int64_t line = ob + int64_t(k) * ps + int64_t(j) * g.hx;
+        const V km = k > 0 ? xv(line - ps + (i >> 1)) : V(0);
+        const V jm = j > 0 ? xv(line - g.hx + (i >> 1)) : V(0);
+        const V im = i > 0 ? xv(line + ((i - 1) >> 1)) : V(0);
+        const V d = xv(s);
+        const V ip = i + 1 < g.nx ? xv(line + ((i + 1) >> 1)) : V(0);
+        const V jp = j + 1 < g.ny ? xv(line + g.hx + (i >> 1)) : V(0);
+        const V kp = k + 1 < g.nz ? xv(line + ps + (i >> 1)) : V(0);
+        V a = fma(c0, km, V(0));
+        a = fma(c1, jm, a);
+        a = fma(c2, im, a);
+        a = fma(c3, d, a);
+        a = fma(c4, ip, a);
+        a = fma(c5, jp, a);
+        a = fma(c6, kp, a);
+        const V r = b[s] - a;
+        x2[s] = d;
+        rlo[s] = Z(r);
+        rr = fma(double(r), double(r), rr);
+    }
+    rr = block_sum(rr, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = rr;
 }
 
 // One workgroup: thread t adds slots t, t + 256, ... in order, then the fixed tree.
@@ -296,38 +384,54 @@ int pcg_wgs(int64_t n) {
 #define PCG_LAUNCH(kern, ok, ...)                                                                                           \
     do {                                                                                                                \
         const int nwg_ = pcg_wgs<V>(n);                                                                                 \
-        if (ok) hipLaunchKernelGGL((kern<V, vec_width<V>()>), dim3(unsigned(nwg_)), dim3(PCG_WG), 0, s, __VA_ARGS__);  \
-        else hipLaunchKernelGGL((kern<V, 1>), dim3(unsigned(nwg_)), dim3(PCG_WG), 0, s, __VA_ARGS__);                  \
+        if (ok) hipLaunchKernelGGL((kern<V, Z, vec_width<V>()>), dim3(unsigned(nwg_)), dim3(PCG_WG), 0, s, __VA_ARGS__); \
+        else hipLaunchKernelGGL((kern<V, Z, 1>), dim3(unsigned(nwg_)), dim3(PCG_WG), 0, s, __VA_ARGS__);                 \
         OMG_HIP(hipGetLastError());                                                                                     \
     } while (0)
 
-template <typename V>
-void pcg_dots(const V *r, const V *z, const V *q, int64_t n, double *part, const double *sc, hipStream_t s) {
+template <typename V, typename Z>
+void pcg_dots(const V *r, const Z *z, const V *q, int64_t n, double *part, const double *sc, hipStream_t s) {
     PCG_LAUNCH(dots_kernel, aligned16(r) && aligned16(z) && aligned16(q), r, z, q, n, part, sc);
 }
 template <typename V>
 void pcg_dot(const V *a, const V *b, int64_t n, double *part, const double *sc, hipStream_t s) {
-    PCG_LAUNCH(dot_kernel, aligned16(a) && aligned16(b), a, b, n, part, sc);
+    const int nwg = pcg_wgs<V>(n);
+    if (aligned16(a) && aligned16(b)) hipLaunchKernelGGL((dot_kernel<V, vec_width<V>()>), dim3(unsigned(nwg)), dim3(PCG_WG), 0, s, a, b, n, part, sc);
+    else hipLaunchKernelGGL((dot_kernel<V, 1>), dim3(unsigned(nwg)), dim3(PCG_WG), 0, s, a, b, n, part, sc);
+    OMG_HIP(hipGetLastError());
 }
-template <typename V>
-void pcg_pupdate(const V *z, const V *p, V *p2, int64_t n, const double *sc, hipStream_t s) {
+template <typename V, typename Z>
+void pcg_pupdate(const Z *z, const V *p, V *p2, int64_t n, const double *sc, hipStream_t s) {
     PCG_LAUNCH(pupdate_kernel, aligned16(z) && aligned16(p) && aligned16(p2), z, p, p2, n, sc);
 }
-template <typename V>
-void pcg_update(V *x, const V *p, V *r, const V *q, int64_t n, double *part, const double *sc, hipStream_t s) {
-    PCG_LAUNCH(update_kernel, aligned16(x) && aligned16(p) && aligned16(r) && aligned16(q), x, p, r, q, n, part, sc);
+template <typename V, typename Z>
+void pcg_update(V *x, const V *p, V *r, const V *q, Z *rlo, int64_t n, double *part, const double *sc, hipStream_t s) {
+    PCG_LAUNCH(update_kernel, aligned16(x) && aligned16(p) && aligned16(r) && aligned16(q) && aligned16(rlo), x, p, r, q, rlo, n, part, sc);
 }
-template <typename V>
-void pcg_residual(const V *b, const V *q, V *r, int64_t n, double *part, hipStream_t s) {
-    PCG_LAUNCH(residual_kernel, aligned16(b) && aligned16(q) && aligned16(r), b, q, r, n, part);
+template <typename V, typename Z>
+void pcg_residual(const V *b, const V *q, V *r, Z *rlo, int64_t n, double *part, hipStream_t s) {
+    PCG_LAUNCH(residual_kernel, aligned16(b) && aligned16(q) && aligned16(r) && aligned16(rlo), b, q, r, rlo, n, part);
+}
+template <typename V, typename Z>
+void pcg_defect_add(V *x, const Z *z, int64_t n, hipStream_t s) {
+    PCG_LAUNCH(defect_add_kernel, aligned16(x) && aligned16(z), x, z, n);
 }
 #undef PCG_LAUNCH
 
-template <typename V>
-int pcg_plane_step(const PcgPlane &g, const V *z, const V *p, V *p2, V *q, double *part, const double *sc, hipStream_t s) {
+template <typename V, typename Z>
+int pcg_plane_step(const PcgPlane &g, const Z *z, const V *p, V *p2, V *q, double *part, const double *sc, hipStream_t s) {
     const int64_t n = 2 * g.nr;
     const int nwg = int(std::max<int64_t>(1, std::min<int64_t>(PCG_MAX_WG, (n + PCG_WG - 1) / PCG_WG)));
-    hipLaunchKernelGGL((plane_step_kernel<V>), dim3(unsigned(nwg)), dim3(PCG_WG), 0, s, z, p, p2, q, g, part, sc);
+    hipLaunchKernelGGL((plane_step_kernel<V, Z>), dim3(unsigned(nwg)), dim3(PCG_WG), 0, s, z, p, p2, q, g, part, sc);
+    OMG_HIP(hipGetLastError());
+    return nwg;
+}
+
+template <typename V, typename Z>
+int pcg_defect_plane(const PcgPlane &g, const V *x, const Z *z, V *x2, const V *b, Z *rlo, double *part, hipStream_t s) {
+    const int64_t n = 2 * g.nr;
+    const int nwg = int(std::max<int64_t>(1, std::min<int64_t>(PCG_MAX_WG, (n + PCG_WG - 1) / PCG_WG)));
+    hipLaunchKernelGGL((defect_plane_kernel<V, Z>), dim3(unsigned(nwg)), dim3(PCG_WG), 0, s, x, z, x2, b, rlo, g, part);
     OMG_HIP(hipGetLastError());
     return nwg;
 }
@@ -349,16 +453,21 @@ void pcg_fold_sqrt(const double *part, int nwg, double *out, hipStream_t s) {
     OMG_HIP(hipGetLastError());
 }
 
-#define PCG_INST(V)                                                                                             \
-    template int pcg_wgs<V>(int64_t);                                                                           \
-    template void pcg_dots<V>(const V *, const V *, const V *, int64_t, double *, const double *, hipStream_t); \
-    template void pcg_dot<V>(const V *, const V *, int64_t, double *, const double *, hipStream_t);             \
-    template void pcg_pupdate<V>(const V *, const V *, V *, int64_t, const double *, hipStream_t);              \
-    template void pcg_update<V>(V *, const V *, V *, const V *, int64_t, double *, const double *, hipStream_t); \
-    template void pcg_residual<V>(const V *, const V *, V *, int64_t, double *, hipStream_t);                   \
-    template int pcg_plane_step<V>(const PcgPlane &, const V *, const V *, V *, V *, double *, const double *, hipStream_t);
-PCG_INST(double)
-PCG_INST(float)
+#define PCG_INST(V, Z)                                                                                                  \
+    template void pcg_dots<V, Z>(const V *, const Z *, const V *, int64_t, double *, const double *, hipStream_t);       \
+    template void pcg_pupdate<V, Z>(const Z *, const V *, V *, int64_t, const double *, hipStream_t);                    \
+    template void pcg_update<V, Z>(V *, const V *, V *, const V *, Z *, int64_t, double *, const double *, hipStream_t); \
+    template void pcg_residual<V, Z>(const V *, const V *, V *, Z *, int64_t, double *, hipStream_t);                    \
+    template int pcg_plane_step<V, Z>(const PcgPlane &, const Z *, const V *, V *, V *, double *, const double *, hipStream_t);   \
+    template void pcg_defect_add<V, Z>(V *, const Z *, int64_t, hipStream_t);                                            \
+    template int pcg_defect_plane<V, Z>(const PcgPlane &, const V *, const Z *, V *, const V *, Z *, double *, hipStream_t);
+PCG_INST(double, double)
+PCG_INST(float, float)
+PCG_INST(double, float)
 #undef PCG_INST
+template int pcg_wgs<double>(int64_t);
+template int pcg_wgs<float>(int64_t);
+template void pcg_dot<double>(const double *, const double *, int64_t, double *, const double *, hipStream_t);
+template void pcg_dot<float>(const float *, const float *, int64_t, double *, const double *, hipStream_t);
 
 }  // namespace omg

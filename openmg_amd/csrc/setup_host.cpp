@@ -204,6 +204,39 @@ HostCsr permute_csr(const omg_csr &A, const int32_t *row_perm, const int32_t *co
     return out;
 }
 
+HostCsr renumber_sorted(const omg_csr &A, const int32_t *row_perm, const int32_t *col_inv, std::vector<int32_t> &src) {
+    HostCsr out;
+    out.n_rows = A.n_rows;
+    out.n_cols = A.n_cols;
+    out.nnz = A.nnz;
+    out.indptr.resize(A.n_rows + 1);
+    out.indices.resize(A.nnz);
+    out.data.resize(A.nnz);
+    src.resize(size_t(A.nnz));
+    out.indptr[0] = 0;
+    for (int64_t i = 0; i < A.n_rows; ++i) {
+        const int64_t o = row_perm ? row_perm[i] : i;
+        out.indptr[i + 1] = out.indptr[i] + (A.indptr[o + 1] - A.indptr[o]);
+    }
+    parallel_rows(A.n_rows, [&](int64_t lo, int64_t hi) {
+        std::vector<std::pair<int32_t, int32_t>> row;
+        for (int64_t i = lo; i < hi; ++i) {
+            const int64_t o = row_perm ? row_perm[i] : i;
+            row.clear();
+            for (int32_t p = A.indptr[o]; p < A.indptr[o + 1]; ++p) row.emplace_back(col_inv ? col_inv[A.indices[p]] : A.indices[p], p);
+            std::stable_sort(row.begin(), row.end(), [](const std::pair<int32_t, int32_t> &a, const std::pair<int32_t, int32_t> &b) { return a.first < b.first; });
+            int32_t q = out.indptr[i];
+            for (const auto &e : row) {
+                out.indices[q] = e.first;
+                out.data[q] = A.data[e.second];
+                src[size_t(q)] = e.second;
+                ++q;
+            }
+        }
+    });
+    return out;
+}
+
 HostCsr transpose_csr(const HostCsr &A) {
     HostCsr T;
     T.n_rows = A.n_cols;
@@ -652,8 +685,8 @@ HostFormat<V> encode_with(const HostCsr &A, const std::vector<int64_t> &sets_in,
 }  // namespace
 
 template <typename V>
-HostFormat<V> encode_csr(const HostCsr &A, const std::vector<int64_t> &sets_in) {
-    int mode = compress_mode();
+HostFormat<V> encode_csr(const HostCsr &A, const std::vector<int64_t> &sets_in, int mode) {
+    if (mode < 0) mode = compress_mode();
     {   // OMG_PATTERN_KERNEL=0 (rows_kernel everywhere): no ELL blocks, rows_kernel cannot read them
         const char *e = getenv("OMG_PATTERN_KERNEL");
         if (e && e[0] == '0') mode &= ~8;
@@ -693,9 +726,9 @@ HostFormat<V> encode_csr(const HostCsr &A, const std::vector<int64_t> &sets_in) 
 }
 
 template <typename V>
-void DevCsrT<V>::upload(const HostCsr &A, const std::vector<int64_t> &sets_in, hipStream_t s) {
+void DevCsrT<V>::upload(const HostCsr &A, const std::vector<int64_t> &sets_in, hipStream_t s, bool plain) {
     HostFormat<V> F;
-    { SetupTimer tm("  encode_csr"); F = encode_csr<V>(A, sets_in); }       // host only (setup_host.cpp)
+    { SetupTimer tm("  encode_csr"); F = encode_csr<V>(A, sets_in, plain ? 0 : -1); }       // host only (setup_host.cpp)
     SetupTimer tm_up("  upload");
     n_rows = A.n_rows;
     n_cols = A.n_cols;
@@ -852,8 +885,8 @@ void format_selftest(const omg_csr &A, int64_t *out) {
     format_stats(F.info, F.set_blk, F.rows_cap, int64_t(sizeof(V)), -1, out);
 }
 
-template HostFormat<double> encode_csr<double>(const HostCsr &, const std::vector<int64_t> &);
-template HostFormat<float> encode_csr<float>(const HostCsr &, const std::vector<int64_t> &);
+template HostFormat<double> encode_csr<double>(const HostCsr &, const std::vector<int64_t> &, int);
+template HostFormat<float> encode_csr<float>(const HostCsr &, const std::vector<int64_t> &, int);
 template void format_selftest<double>(const omg_csr &, int64_t *);
 template void format_selftest<float>(const omg_csr &, int64_t *);
 template struct DevCsrT<double>;
