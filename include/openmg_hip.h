@@ -471,6 +471,13 @@ int omg_pdist_p2p_open(omg_pdist *d, int peer_rank, const void *handles64, int c
 int omg_pdist_p2p_local(omg_pdist *d, omg_pdist *other);
 int omg_pdist_p2p_enable(omg_pdist *d, int mode);
 int omg_pdist_p2p_status(omg_pdist *d, unsigned *status);
+/* Where the exported buffers sit in their allocations (tests, diagnostics).  omg_pdist_p2p_handles refuses, before the
+ * first handle, an export whose computed base is not the base of the allocation that contains the buffer, as the
+ * runtime reports it; this reports the same comparison.  out4: per buffer, in handle order, four values — the index of
+ * its allocation among the exported ones (buffers that share a handle share the index), the byte offset of its first
+ * element from the exported base, the allocation's size, and the distance of the exported base from the allocation's
+ * base (0: right).  mapped: per rank of the decomposition, how many allocations of it this rank has opened. */
+int omg_pdist_p2p_layout(omg_pdist *d, int64_t *out4, int capacity /* buffers */, int *mapped, int mapped_capacity);
 int omg_pdist_cycles_squares(omg_pdist *d, int n_cycles, double *squares);                         /* collective */
 /* all ranks in one process on one GPU, device copies in place of RCCL (verification) */
 int omg_pdist_group_create(int n, omg_pdist **ranks, omg_pdist_group **out);
@@ -522,6 +529,8 @@ int omg_sdist_p2p_open(omg_sdist *d, int peer_rank, const void *handles64, int c
 int omg_sdist_p2p_local(omg_sdist *d, omg_sdist *other);
 int omg_sdist_p2p_enable(omg_sdist *d, int mode /* 0 | 1 */);
 int omg_sdist_p2p_status(omg_sdist *d, unsigned *status);
+/* as omg_pdist_p2p_layout; mapped2: the allocations opened of rank - 1 and of rank + 1 */
+int omg_sdist_p2p_layout(omg_sdist *d, int64_t *out4, int capacity /* buffers */, int *mapped2);
 int omg_sdist_group_create(int n, omg_sdist **ranks, omg_sdist_group **out);
 int omg_sdist_group_destroy(omg_sdist_group *g);
 int omg_sdist_group_cycles(omg_sdist_group *g, int pre, int post, int n_cycles, double *norms /* nullable */);

@@ -126,6 +126,7 @@ SIGNATURES = {
     "omg_pdist_p2p_local": (_I, [_P, _P]),
     "omg_pdist_p2p_enable": (_I, [_P, _I]),
     "omg_pdist_p2p_status": (_I, [_P, _P]),
+    "omg_pdist_p2p_layout": (_I, [_P, _I64P, _I, _IP, _I]),
     "omg_pdist_cycles_squares": (_I, [_P, _I, _P]),
     "omg_pdist_rccl_ranks": (_I, [_P, _IP]),
     "omg_pdist_load": (_I, [_P, _P, _P]),
@@ -144,6 +145,7 @@ SIGNATURES = {
     "omg_sdist_p2p_local": (_I, [_P, _P]),
     "omg_sdist_p2p_enable": (_I, [_P, _I]),
     "omg_sdist_p2p_status": (_I, [_P, _P]),
+    "omg_sdist_p2p_layout": (_I, [_P, _I64P, _I, _IP]),
     "omg_pdist_group_create": (_I, [_I, _P, _PP]),
     "omg_pdist_group_destroy": (_I, [_P]),
     "omg_pdist_group_cycles": (_I, [_P, _I, _P]),

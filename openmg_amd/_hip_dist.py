@@ -191,6 +191,12 @@ class DistGroup:
 
 
 # ---- plane-pipelined slabs (omg_pdist_*) ------------------------------------------------------
+def _layout(out, n, mapped):
+    keys = ("alloc", "offset", "alloc_bytes", "base_delta")
+    return {"buffers": [dict(zip(keys, (int(out[4 * i + k]) for k in range(4)))) for i in range(n)],
+            "mapped": [int(v) for v in mapped]}
+
+
 def star_coefficients(A, shape):
     """The seven coefficients (-K, -J, -I, diagonal, +I, +J, +K) of a constant-coefficient star stencil on a
     C-ordered grid of `shape` (planes, lines, cells), read off the row of cell (1, 1, 1)."""
@@ -314,6 +320,17 @@ class PlaneDistRank:
         v = ctypes.c_uint(0)
         check(lib().omg_pdist_p2p_status(self._h, ctypes.byref(v)))
         return v.value
+
+    def p2p_layout(self):
+        """Where the exported buffers (flags, the two gathered right-hand sides, x / tmp / b per level) sit in their
+        allocations: dict(buffers=[dict(alloc, offset, alloc_bytes, base_delta)] in handle order, mapped=[allocations
+        opened of each rank]) — include/openmg_hip.h omg_pdist_p2p_layout."""
+        n = ctypes.c_int(0)
+        check(lib().omg_pdist_p2p_handle_count(self._h, ctypes.byref(n)))
+        out = (ctypes.c_int64 * (4 * n.value))()
+        mapped = (ctypes.c_int * self.n_ranks)()
+        check(lib().omg_pdist_p2p_layout(self._h, out, n.value, mapped, self.n_ranks))
+        return _layout(out, n.value, mapped)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -457,6 +474,17 @@ class Slab27Rank:
         v = ctypes.c_uint(0)
         check(lib().omg_sdist_p2p_status(self._h, ctypes.byref(v)))
         return v.value
+
+    def p2p_layout(self):
+        """Where the exported buffers (flags, then x / tmp / b per level) sit in their allocations: dict(buffers=
+        [dict(alloc, offset, alloc_bytes, base_delta)] in handle order, mapped=[allocations opened of rank - 1, of
+        rank + 1]) — include/openmg_hip.h omg_sdist_p2p_layout."""
+        n = ctypes.c_int(0)
+        check(lib().omg_sdist_p2p_handle_count(self._h, ctypes.byref(n)))
+        out = (ctypes.c_int64 * (4 * n.value))()
+        mapped = (ctypes.c_int * 2)()
+        check(lib().omg_sdist_p2p_layout(self._h, out, n.value, mapped))
+        return _layout(out, n.value, mapped)
 
     def close(self):
         if getattr(self, "_h", None):

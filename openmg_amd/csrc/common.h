@@ -105,14 +105,22 @@ struct DevBuf {
         return *this;
     }
     // count elements at ptr, inside an allocation somebody else owns and keeps alive (with the slack this type promises)
-    // (shift_bytes: how far behind the owner's first element the view starts — the allocation's base is then
-    // p - DEVBUF_SLACK - shift for views as for owners: dist.hip's IPC export)
+    // THE LAYOUT RULE (owners and views alike): the allocation's base is p - DEVBUF_SLACK - shift.  alloc() keeps it by
+    // construction; a view keeps it when shift_bytes is the byte distance of ptr from the owner's first element (plus the
+    // owner's own shift) — borrow_in() below computes both from one offset, so they cannot disagree.  The peer-store IPC
+    // exports (dist.hip, dist27.hip: ExportBuf below) hand p - DEVBUF_SLACK - shift to hipIpcGetMemHandle and the
+    // neighbour rebuilds mapped base + DEVBUF_SLACK + shift; a view borrowed with a shift that is not its distance
+    // would be exported at an interior pointer (export_guard refuses that before anything is stored).
     void borrow(T *ptr, size_t count, size_t shift_bytes = 0) {
         release();
         p = ptr;
         n = count;
         shift = shift_bytes;
         owned = false;
+    }
+    // the view of `count` elements that starts offset_bytes behind pool's first element
+    void borrow_in(const DevBuf<char> &pool, size_t offset_bytes, size_t count) {
+        borrow(reinterpret_cast<T *>(pool.p + offset_bytes), count, pool.shift + offset_bytes);
     }
     ~DevBuf() { release(); }
     // shift (bytes, a multiple of 64): the vector starts that much further into its allocation — large vectors that a
@@ -162,6 +170,62 @@ struct DevBuf {
     }
     void zero(hipStream_t s) { if (n) OMG_HIP(hipMemsetAsync(p, 0, n * sizeof(T), s)); }
 };
+
+// ---- what a rank exports to its neighbours over hipIpc (peer stores: dist.hip, dist27.hip) ----------------------------
+// A buffer as the export sees it: first element, shift (DevBuf's layout rule) and size.  export_base() is what goes to
+// hipIpcGetMemHandle, export_rebuild() what the opener makes of the mapping with ITS OWN buffer's shift (the vectors sit
+// in their allocations alike on every rank), export_guard() asks the runtime which allocation really contains the
+// buffer and refuses an export whose computed base is not that allocation's — on the host, before any kernel stores
+// through a pointer rebuilt from it.
+struct ExportBuf {
+    void *p = nullptr;
+    size_t shift = 0, bytes = 0;
+};
+template <typename T>
+inline ExportBuf export_buf(const DevBuf<T> &b) { return ExportBuf{b.p, b.shift, b.n * sizeof(T)}; }
+inline char *export_base(const ExportBuf &b) { return static_cast<char *>(b.p) - DEVBUF_SLACK - b.shift; }
+inline void *export_rebuild(void *mapped_base, const ExportBuf &own) { return static_cast<char *>(mapped_base) + DEVBUF_SLACK + own.shift; }
+// the allocation that contains b, as the runtime knows it
+inline void export_allocation(const ExportBuf &b, char *&base, size_t &bytes) {
+    hipDeviceptr_t rb = nullptr;
+    size_t rs = 0;
+    OMG_HIP(hipMemGetAddressRange(&rb, &rs, b.p));
+    base = static_cast<char *>(rb);
+    bytes = rs;
+}
+inline void export_guard(const ExportBuf &b, int index) {
+    char *rb = nullptr;
+    size_t rs = 0;
+    export_allocation(b, rb, rs);
+    const char *const first = static_cast<const char *>(b.p);
+    const long long delta = static_cast<long long>(export_base(b) - rb);
+    if (delta != 0 || first < rb + DEVBUF_SLACK || first + b.bytes + DEVBUF_SLACK > rb + rs) {
+        char msg[320];
+        snprintf(msg, sizeof msg, "peer export: buffer %d (%zu bytes at offset %lld of an allocation of %zu bytes): the exported base p - %zu - shift "
+                 "(shift %zu) is %+lld bytes from the allocation's base, or the buffer and its slack do not lie inside it",
+                 index, b.bytes, static_cast<long long>(first - rb), rs, DEVBUF_SLACK, b.shift, delta);
+        throw Error(OMG_ERR_INVALID, msg);
+    }
+}
+// per buffer four values: index of its exported base among the distinct ones (buffers with one base share a handle),
+// byte offset of its first element from that base, the size of the allocation that contains it and how far the
+// exported base lies from that allocation's base (0: the layout rule holds) — the last two are the runtime's answers
+inline void export_layout(const std::vector<ExportBuf> &bufs, int64_t *out4) {
+    std::vector<char *> bases;
+    for (size_t i = 0; i < bufs.size(); ++i) {
+        char *const base = export_base(bufs[i]);
+        size_t k = 0;
+        while (k < bases.size() && bases[k] != base) ++k;
+        if (k == bases.size()) bases.push_back(base);
+        char *rb = nullptr;
+        size_t rs = 0;
+        export_allocation(bufs[i], rb, rs);
+        out4[4 * i] = int64_t(k);
+        out4[4 * i + 1] = int64_t(static_cast<char *>(bufs[i].p) - base);
+        out4[4 * i + 2] = int64_t(rs);
+        out4[4 * i + 3] = int64_t(base - rb);
+    }
+}
 
 // How the k-th candidate of a placement search (hierarchy.hip place_finest_pool, Stencil27Plan::place_tiles, ...) is
 // allocated: 0 ordinary hipMalloc, n >= 2: scattered pieces of n MiB (DevBuf::alloc; 1: physically contiguous — an

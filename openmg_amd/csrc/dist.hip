@@ -1496,16 +1496,17 @@ std::unique_ptr<PlaneDist> pd_create(int rank, int n_ranks, int nx, int ny, int 
         {
             // OMG_DIST_VEC_POOL=1: one allocation for the three vectors the passes stream side by side, as hierarchy.hip
             // pooled_vectors does for whole grids (there: -2.6 % per cycle).  Measured on a slab with its ghost planes
-            // (`bench.py --dist 1`): 0.2944 against 0.2905 ms per cycle — slower, so three allocations stay the default here.
-            static const bool pool_on = [] { const char *e = experiment_env("OMG_DIST_VEC_POOL"); return e && e[0] == '1'; }();
+            // (`bench.py --dist 1`): 0.2944 against 0.2905 ms per cycle — slower, so three allocations stay the default here
+            // (a supported switch: tests/test_gpu_plane_dist.py runs the peer-store export of the pooled layout).
+            static const bool pool_on = [] { const char *e = getenv("OMG_DIST_VEC_POOL"); return e && e[0] == '1'; }();
             if (pool_on) {
                 const size_t MB2 = size_t(2) << 20, bytes = size_t(L.n_ext) * sizeof(double);
                 const size_t span = (bytes + 2 * DEVBUF_SLACK + vector_stagger(2) + MB2 - 1) / MB2 * MB2;
                 L.pool.alloc(3 * span);
                 // (order x, b, x's twin, as hierarchy.hip has it)
-                L.x.borrow(reinterpret_cast<double *>(L.pool.p), size_t(L.n_ext), 0);
-                L.b.borrow(reinterpret_cast<double *>(L.pool.p + span + vector_stagger(2)), size_t(L.n_ext), span + vector_stagger(2));
-                L.tmp.borrow(reinterpret_cast<double *>(L.pool.p + 2 * span + vector_stagger(1)), size_t(L.n_ext), 2 * span + vector_stagger(1));
+                L.x.borrow_in(L.pool, 0, size_t(L.n_ext));
+                L.b.borrow_in(L.pool, span + vector_stagger(2), size_t(L.n_ext));
+                L.tmp.borrow_in(L.pool, 2 * span + vector_stagger(1), size_t(L.n_ext));
             } else {
                 L.x.alloc(size_t(L.n_ext)); L.tmp.alloc(size_t(L.n_ext), vector_stagger(1)); L.b.alloc(size_t(L.n_ext), vector_stagger(2));
             }
@@ -1990,13 +1991,12 @@ int omg_pdist_rccl_ranks(omg_pdist *d, int *count) {
  * 2 = a one-workgroup wait launch before each pass (ranks that share a GPU: a pass that waited itself would hold the
  * compute units the neighbour's pass needs), 0 = back to RCCL.  Needs >= 4 planes per rank on every level. */
 // (with how far each vector starts into its allocation: common.h vector_stagger — the same on every rank)
-static void pd_own_buffers(PlaneDist *d, std::vector<void *> &out, std::vector<size_t> *shift = nullptr) {
-    out = {d->flags.p, d->full_b.p, d->full_b2.p};
-    if (shift) *shift = {d->flags.shift, d->full_b.shift, d->full_b2.shift};
+static std::vector<ExportBuf> pd_own_buffers(PlaneDist *d) {
+    std::vector<ExportBuf> out = {export_buf(d->flags), export_buf(d->full_b), export_buf(d->full_b2)};
     for (PDLevel &L : d->lv) {
-        out.push_back(L.x.p); out.push_back(L.tmp.p); out.push_back(L.b.p);
-        if (shift) { shift->push_back(L.x.shift); shift->push_back(L.tmp.shift); shift->push_back(L.b.shift); }
+        out.push_back(export_buf(L.x)); out.push_back(export_buf(L.tmp)); out.push_back(export_buf(L.b));
     }
+    return out;
 }
 static void pd_attach(PlaneDist *d, int peer_rank, const std::vector<void *> &bufs) {
     PDPeer &P = d->peers[size_t(peer_rank)];
@@ -2035,16 +2035,30 @@ int omg_pdist_p2p_handles(omg_pdist *d, void *handles64, int capacity) {
     return guarded([&] {
         OMG_REQUIRE(d && d->d && handles64, "null argument");
         static_assert(sizeof(hipIpcMemHandle_t) == 64, "IPC handle size");
-        std::vector<void *> bufs;
-        std::vector<size_t> shift;
-        pd_own_buffers(d->d.get(), bufs, &shift);
+        const std::vector<ExportBuf> bufs = pd_own_buffers(d->d.get());
         OMG_REQUIRE(capacity >= int(bufs.size()), "handle buffer too small");
         OMG_HIP(hipStreamSynchronize(d->d->stream));
+        for (size_t i = 0; i < bufs.size(); ++i) export_guard(bufs[i], int(i));          // (all of them, before the first handle)
         for (size_t i = 0; i < bufs.size(); ++i) {
             hipIpcMemHandle_t h;
-            OMG_HIP(hipIpcGetMemHandle(&h, static_cast<char *>(bufs[i]) - DEVBUF_SLACK - shift[i]));     // (the allocation's base)
+            OMG_HIP(hipIpcGetMemHandle(&h, export_base(bufs[i])));
             std::memcpy(static_cast<char *>(handles64) + 64 * i, &h, 64);
         }
+    });
+}
+
+/* Where the exported buffers sit (tests, diagnostics): per buffer, in handle order, four values — index of its handle's
+ * allocation, byte offset of its first element from the exported base, that allocation's size and the distance of
+ * the exported base from the allocation's base as the runtime reports them (common.h export_layout) —, and per rank
+ * of the decomposition how many of its allocations this rank has mapped (0: not opened, itself, or the same process). */
+int omg_pdist_p2p_layout(omg_pdist *d, int64_t *out4, int capacity, int *mapped, int mapped_capacity) {
+    return guarded([&] {
+        OMG_REQUIRE(d && d->d && out4 && mapped, "null argument");
+        PlaneDist *dd = d->d.get();
+        const std::vector<ExportBuf> bufs = pd_own_buffers(dd);
+        OMG_REQUIRE(capacity >= int(bufs.size()) && mapped_capacity >= dd->n_ranks, "layout buffer too small");
+        export_layout(bufs, out4);
+        for (int r = 0; r < dd->n_ranks; ++r) mapped[r] = int(dd->peers[size_t(r)].mapped.size());
     });
 }
 
@@ -2056,9 +2070,8 @@ int omg_pdist_p2p_open(omg_pdist *d, int peer_rank, const void *handles64, int c
         OMG_REQUIRE(count == 3 + 3 * int(dd->lv.size()), "handle count does not match the levels");
         PDPeer &P = dd->peers[size_t(peer_rank)];
         OMG_REQUIRE(P.mapped.empty(), "peer already opened");
-        std::vector<void *> bufs, own;
-        std::vector<size_t> shift;
-        pd_own_buffers(dd, own, &shift);                      // (the peer's vectors sit in their allocations as mine do)
+        std::vector<void *> bufs;
+        const std::vector<ExportBuf> own = pd_own_buffers(dd);          // (the peer's vectors sit in their allocations as mine do)
         // (vectors that share an allocation share a handle: it is opened once)
         std::vector<std::pair<std::array<char, 64>, void *>> opened;
         for (int i = 0; i < count; ++i) {
@@ -2074,7 +2087,7 @@ int omg_pdist_p2p_open(omg_pdist *d, int peer_rank, const void *handles64, int c
                 P.mapped.push_back(base);
                 opened.emplace_back(key, base);
             }
-            bufs.push_back(static_cast<char *>(base) + DEVBUF_SLACK + shift[size_t(i)]);
+            bufs.push_back(export_rebuild(base, own[size_t(i)]));
         }
         pd_attach(dd, peer_rank, bufs);
     });
@@ -2086,7 +2099,7 @@ int omg_pdist_p2p_local(omg_pdist *d, omg_pdist *other) {
         OMG_REQUIRE(other->d->n_ranks == d->d->n_ranks && other->d->lv.size() == d->d->lv.size() && other->d->rank != d->d->rank,
                     "not another rank of the same decomposition");
         std::vector<void *> bufs;
-        pd_own_buffers(other->d.get(), bufs);
+        for (const ExportBuf &e : pd_own_buffers(other->d.get())) bufs.push_back(e.p);
         pd_attach(d->d.get(), other->d->rank, bufs);
     });
 }

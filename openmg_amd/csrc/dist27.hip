@@ -277,14 +277,17 @@ std::unique_ptr<SDist<V>> sd_create(int rank, int n_ranks, int nx, int ny, int n
         {
             // the three vectors the sweeps stream side by side out of one allocation, each 2 MiB-aligned + its stagger, b in the
             // middle: what hierarchy.hip measured for whole grids (configs[4]: + 3 %); OMG_VEC_POOL=0: three allocations
-            static const bool pool_on = [] { const char *e = experiment_env("OMG_VEC_POOL"); return !(e && e[0] == '0'); }();
+            // (a supported switch: tests/test_gpu_dist27.py compares the two layouts bit for bit)
+            static const bool pool_on = [] { const char *e = getenv("OMG_VEC_POOL"); return !(e && e[0] == '0'); }();
             if (pool_on && nv >= (size_t(1) << 20)) {
                 const size_t MB2 = size_t(2) << 20, bytes = nv * sizeof(V);
                 const size_t span = (bytes + 2 * DEVBUF_SLACK + vector_stagger(2) + MB2 - 1) / MB2 * MB2;
                 L.pool.alloc(3 * span);
-                L.x.borrow(reinterpret_cast<V *>(L.pool.p + DEVBUF_SLACK), nv);
-                L.b.borrow(reinterpret_cast<V *>(L.pool.p + span + DEVBUF_SLACK + vector_stagger(2)), nv);
-                L.tmp.borrow(reinterpret_cast<V *>(L.pool.p + 2 * span + DEVBUF_SLACK + vector_stagger(1)), nv);
+                // (views by common.h's layout rule — their distance from the pool's first element is their shift, which the
+                // peer-store export and the neighbour that opens it go by; the addresses are the ones place_tiles has always seen)
+                L.x.borrow_in(L.pool, DEVBUF_SLACK, nv);
+                L.b.borrow_in(L.pool, span + DEVBUF_SLACK + vector_stagger(2), nv);
+                L.tmp.borrow_in(L.pool, 2 * span + DEVBUF_SLACK + vector_stagger(1), nv);
             } else {
                 L.x.alloc(nv); L.tmp.alloc(nv); L.b.alloc(nv);
             }
@@ -698,19 +701,19 @@ using value_of = typename std::remove_pointer<HP>::type::value_type;
 }  // namespace
 
 namespace {
+// what the neighbours store into, in handle order (common.h ExportBuf: where each sits in its allocation)
 template <typename V>
-void sd_own_buffers(SDist<V> *d, std::vector<void *> &out, std::vector<size_t> &shift) {
+std::vector<ExportBuf> sd_own_buffers(SDist<V> *d) {
     if (!d->pflags.p) {
         d->pflags.alloc(64);
         d->pflags.zero(d->stream);
         OMG_HIP(hipStreamSynchronize(d->stream));
     }
-    out = {d->pflags.p};
-    shift = {d->pflags.shift};
+    std::vector<ExportBuf> out = {export_buf(d->pflags)};
     for (auto &L : d->lv) {
-        out.push_back(L.x.p); out.push_back(L.tmp.p); out.push_back(L.b.p);
-        shift.push_back(L.x.shift); shift.push_back(L.tmp.shift); shift.push_back(L.b.shift);
+        out.push_back(export_buf(L.x)); out.push_back(export_buf(L.tmp)); out.push_back(export_buf(L.b));
     }
+    return out;
 }
 template <typename V>
 void sd_attach(SDist<V> *d, int peer_rank, const std::vector<void *> &bufs) {
@@ -897,14 +900,13 @@ int omg_sdist_p2p_handles(omg_sdist *d, void *handles64, int capacity) {
     return guarded([&] {
         OMG_REQUIRE(handles64, "null argument");
         with(d, [&](auto *dd) {
-            std::vector<void *> bufs;
-            std::vector<size_t> shift;
-            sd_own_buffers(dd, bufs, shift);
+            const std::vector<ExportBuf> bufs = sd_own_buffers(dd);
             OMG_REQUIRE(capacity >= int(bufs.size()), "handle buffer too small");
             OMG_HIP(hipStreamSynchronize(dd->stream));
+            for (size_t i = 0; i < bufs.size(); ++i) export_guard(bufs[i], int(i));      // (all of them, before the first handle)
             for (size_t i = 0; i < bufs.size(); ++i) {
                 hipIpcMemHandle_t h;
-                OMG_HIP(hipIpcGetMemHandle(&h, static_cast<char *>(bufs[i]) - DEVBUF_SLACK - shift[i]));     // (the allocation's base)
+                OMG_HIP(hipIpcGetMemHandle(&h, export_base(bufs[i])));
                 std::memcpy(static_cast<char *>(handles64) + 64 * i, &h, 64);
             }
         });
@@ -919,9 +921,9 @@ int omg_sdist_p2p_open(omg_sdist *d, int peer_rank, const void *handles64, int c
             OMG_REQUIRE(peer_rank >= 0 && peer_rank < dd->n_ranks && count == 1 + 3 * int(dd->lv.size()), "bad peer rank / handle count");
             auto &P = dd->peer[peer_rank == dd->rank - 1 ? 0 : 1];
             OMG_REQUIRE(P.mapped.empty(), "peer already opened");
-            std::vector<void *> own, bufs;
-            std::vector<size_t> shift;
-            sd_own_buffers(dd, own, shift);                  // (the neighbour's vectors sit in their allocations as mine do)
+            std::vector<void *> bufs;
+            const std::vector<ExportBuf> own = sd_own_buffers(dd);      // (the neighbour's vectors sit in their allocations as mine do)
+            // (vectors that share an allocation share a handle: it is opened once)
             std::vector<std::pair<std::array<char, 64>, void *>> opened;
             for (int i = 0; i < count; ++i) {
                 std::array<char, 64> key;
@@ -936,9 +938,25 @@ int omg_sdist_p2p_open(omg_sdist *d, int peer_rank, const void *handles64, int c
                     P.mapped.push_back(base);
                     opened.emplace_back(key, base);
                 }
-                bufs.push_back(static_cast<char *>(base) + DEVBUF_SLACK + shift[size_t(i)]);
+                bufs.push_back(export_rebuild(base, own[size_t(i)]));
             }
             sd_attach(dd, peer_rank, bufs);
+        });
+    });
+}
+
+/* Where the exported buffers sit (tests, diagnostics): per buffer, in handle order, four values — index of its handle's
+ * allocation, byte offset of its first element from the exported base, that allocation's size and the distance of
+ * the exported base from the allocation's base as the runtime reports them (common.h export_layout) —, and how many
+ * allocations of rank - 1 / rank + 1 this rank has mapped (0: not opened, or a rank of the same process). */
+int omg_sdist_p2p_layout(omg_sdist *d, int64_t *out4, int capacity, int *mapped2) {
+    return guarded([&] {
+        OMG_REQUIRE(out4 && mapped2, "null argument");
+        with(d, [&](auto *dd) {
+            const std::vector<ExportBuf> bufs = sd_own_buffers(dd);
+            OMG_REQUIRE(capacity >= int(bufs.size()), "layout buffer too small");
+            export_layout(bufs, out4);
+            for (int k = 0; k < 2; ++k) mapped2[k] = int(dd->peer[k].mapped.size());
         });
     });
 }
@@ -953,8 +971,7 @@ int omg_sdist_p2p_local(omg_sdist *d, omg_sdist *other) {
             else oo = other->f.get();
             OMG_REQUIRE(oo && oo->n_ranks == dd->n_ranks && oo->lv.size() == dd->lv.size(), "not another rank of the same decomposition");
             std::vector<void *> bufs;
-            std::vector<size_t> shift;
-            sd_own_buffers(oo, bufs, shift);
+            for (const ExportBuf &e : sd_own_buffers(oo)) bufs.push_back(e.p);
             sd_attach(dd, oo->rank, bufs);
         });
     });
@@ -965,9 +982,7 @@ int omg_sdist_p2p_enable(omg_sdist *d, int mode) {
         OMG_REQUIRE(mode == 0 || mode == 1, "bad argument");
         with(d, [&](auto *dd) {
             if (mode) {
-                std::vector<void *> bufs;
-                std::vector<size_t> shift;
-                sd_own_buffers(dd, bufs, shift);                // (my own flag words exist)
+                (void)sd_own_buffers(dd);                       // (my own flag words exist)
                 if (dd->rank > 0) OMG_REQUIRE(dd->peer[0].flags, "peer mode: rank - 1's buffers have not been opened");
                 if (dd->rank + 1 < dd->n_ranks) OMG_REQUIRE(dd->peer[1].flags, "peer mode: rank + 1's buffers have not been opened");
                 if (const char *e = getenv("OMG_P2P_SPIN")) dd->p2p_spin = uint32_t(std::max(1l, atol(e)));

@@ -536,7 +536,7 @@ PoolLayout pool_layout(int64_t n) {
 constexpr int64_t POOL_TRIAL_MIN = int64_t(1) << 23;       // levels from 8 M unknowns: the placement of their pool is timed (place_finest_pool)
 template <typename V>
 bool pooled_vectors(Level<V> &L) {
-    static const bool on = [] { const char *e = experiment_env("OMG_VEC_POOL"); return !(e && e[0] == '0'); }();
+    static const bool on = [] { const char *e = getenv("OMG_VEC_POOL"); return !(e && e[0] == '0'); }();
     if (!on || !(L.plane || L.s27) || L.n < (int64_t(1) << 20)) return false;
     if (L.pool.p || L.x.p) return true;
     const PoolLayout q = pool_layout<V>(L.n);

@@ -1,6 +1,12 @@
 """One rank of the peer-mode test (tests/test_gpu_plane_dist.py): WORLD processes share cuda:0, every rank opens the
-others' IPC handles and the cycle's exchanges are stores into the other PROCESSES' memory, ordered by flags."""
+others' IPC handles and the cycle's exchanges are stores into the other PROCESSES' memory, ordered by flags.
+Every rank also saves its p2p_layout() (where the exported buffers sit, what it mapped).
+
+argv: rank world port out_dir shape grids n_dist
+  or: loopback world mode out_dir shape grids n_dist — all ranks in THIS process with peer stores between them (a process
+      of its own because OMG_DIST_VEC_POOL is read once per process); writes loopback.npz."""
 import datetime
+import json
 import os
 import sys
 
@@ -10,7 +16,25 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
+def loopback():
+    world, mode, out_dir = int(sys.argv[2]), int(sys.argv[3]), sys.argv[4]
+    shape, grids, n_dist = tuple(int(v) for v in sys.argv[5].split("x")), int(sys.argv[6]), int(sys.argv[7])
+    from openmg_amd import _hip_dist
+    from test_gpu_plane_dist import problem, slabs
+    A, R, b, x0 = problem(shape, grids)
+    g = _hip_dist.PlaneDistGroup(slabs(A, R, shape, world, n_dist, b, x0), p2p=mode)
+    try:
+        layouts = [r.p2p_layout() for r in g.ranks]
+        norms = g.cycles(3) + g.cycles(1)
+        x = np.concatenate([r.fetch() for r in g.ranks])
+    finally:
+        g.close()
+    np.savez(os.path.join(out_dir, "loopback.npz"), x=x, norms=np.array(norms), layouts=json.dumps(layouts))
+
+
 def main():
+    if sys.argv[1] == "loopback":
+        return loopback()
     rank, world, port, out_dir = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3]), sys.argv[4]
     shape, grids, n_dist = tuple(int(v) for v in sys.argv[5].split("x")), int(sys.argv[6]), int(sys.argv[7])
     import torch
@@ -40,7 +64,7 @@ def main():
 
     norms = d.cycles(2, reduce) + d.cycles(1, reduce)
     x = d.fetch()
-    np.savez(os.path.join(out_dir, "rank%d.npz" % rank), x=x, norms=np.array(norms))
+    np.savez(os.path.join(out_dir, "rank%d.npz" % rank), x=x, norms=np.array(norms), layout=json.dumps(d.p2p_layout()))
     td.barrier()                                           # nobody unmaps what a neighbour may still be writing
     d.close()
     tail.close()

@@ -1,6 +1,11 @@
 """Run by tests/test_gpu_poison.py in a process of its own with OMG_POISON=1: every fresh device allocation is filled
 with NaN patterns (common.h DevBuf::alloc), so a kernel that reads what nobody wrote — harmless in a young process,
-where the allocator hands out zeros — shows up as NaNs or as a difference from the set-by-set schedule."""
+where the allocator hands out zeros — shows up as NaNs or as a difference from the set-by-set schedule.
+
+`poison_worker.py slab27 OUT.npz SHAPE WORLD N_LEVELS GRIDS DTYPE P2P` (tests/test_gpu_poison.py, tests/test_gpu_dist27.py):
+a loopback group of 27-point slabs in a process of its own — for OMG_POISON=1, and for OMG_VEC_POOL=0, which like every
+such switch is read once per process — writes the iterates and norms of three sweep-count pairs and the ranks'
+p2p_layout()."""
 import json
 import os
 import sys
@@ -71,7 +76,30 @@ def both_ways(A, R, dtype, flag, sweeps, smoother="colour"):
     return out
 
 
+def slab27(out, shape, world, n_levels, grids, dtype, p2p):
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from test_gpu_dist27 import slab_group, slab_problem
+    b, x0 = slab_problem(shape, world, dtype)
+    g, tails, _ = slab_group(shape, world, n_levels, grids, dtype, p2p=p2p)
+    res = {"layouts": json.dumps([r.p2p_layout() for r in g.ranks])}
+    per = b.size // world
+    norms = []
+    for pre, post in ((1, 1), (1, 0), (2, 1)):
+        for r in g.ranks:
+            r.load(b[r.rank * per:(r.rank + 1) * per], x0[r.rank * per:(r.rank + 1) * per])
+        norms += g.cycles(pre, post, 3)
+        res["x%d%d" % (pre, post)] = np.concatenate([r.fetch() for r in g.ranks])
+    res["norms"] = np.array(norms)
+    np.savez(out, **res)
+    g.close()
+    for t in tails:
+        t.close()
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "slab27":
+        return slab27(sys.argv[2], tuple(int(v) for v in sys.argv[3].split("x")), int(sys.argv[4]), int(sys.argv[5]), int(sys.argv[6]),
+                      sys.argv[7], int(sys.argv[8]))
     report = {}
     for dtype in ("float64", "float32"):
         A, R = hierarchy27((32, 32, 32), 4)

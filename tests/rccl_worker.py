@@ -5,10 +5,12 @@ test-only stand-in tests/fake_rccl (OMG_RCCL_LIB) — RCCL itself refuses two ra
 argv: mode out_dir shape grids n_dist dtype extra        (RANK / WORLD_SIZE / MASTER_PORT: launch.child_env)
 modes: plane  — plane-pipelined slabs (omg_pdist_*), 7-point red-black fp64;  extra = "gate" switches the gated passes on
        sets   — the set-by-set runner (omg_dist_*);                           extra = smoother
-       slab27 — 27-point slabs (omg_sdist_*);                                 extra = unused
-Writes rank<r>.npz: the rank's part of the iterate, every norm, the communicator's size, the shim's status."""
+       slab27 — 27-point slabs (omg_sdist_*);                                 extra = "p2p": peer stores between the processes
+Writes rank<r>.npz: the rank's part of the iterate, every norm, the communicator's size, the shim's status; slab27 also
+the rank's p2p_layout() (JSON) and, with peer stores, its p2p_status() after the cycles."""
 import ctypes
 import datetime
+import json
 import os
 import sys
 
@@ -82,7 +84,8 @@ def main():
         A_rows = dist.stencil27_variable_rows(shape, rank * per, (rank + 1) * per)
         r = _hip_dist.Slab27Rank(rank, world, shape, A_rows, n_dist, 0.125, dtype)
         coarse = dist.assemble_coarse(all_gather(r.coarse_rows()))
-        tail = dist.make_tail(coarse, tuple(s >> n_dist for s in shape), grids - n_dist, smoother="colour", dtype=dtype)
+        from test_gpu_dist27 import make_tail              # (dist.make_tail, or its plain-aggregation twin where shape[0] != shape[2])
+        tail = make_tail(coarse, tuple(s >> n_dist for s in shape), grids - n_dist, dtype)
         tails.append(tail)
         r.set_tail(tail)
         r.connect(ids(1)[0])                              # (collective: also the neighbours' coefficient rows)
@@ -106,6 +109,8 @@ def main():
             norms += r.cycles(pre, post, 3)
             result["x%d%d" % (pre, post)] = r.fetch()
         result["exchanges"] = r.info()["exchanges_last_call"]
+        result["layout"] = json.dumps(r.p2p_layout())
+        result["p2p_status"] = r.p2p_status() if extra == "p2p" else 0
     elif mode == "stall":
         # a schedule that would DEADLOCK RCCL — rank 1 never posts the receives rank 0's sends wait for — must end as an
         # error after the stand-in's bounded wait (FRCCL_TIMEOUT_S), not as a hung GPU: rank 0 runs one cycle alone

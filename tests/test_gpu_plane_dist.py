@@ -239,26 +239,52 @@ def test_peer_store_wait_gives_up_instead_of_hanging():
             r.close()
 
 
-@pytest.mark.parametrize("world,shape,grids,n_dist", [(2, (32, 32, 32), 4, 2), (4, (64, 32, 48), 4, 2)])
-def test_peer_stores_between_processes(tmp_path, world, shape, grids, n_dist):
-    """Real concurrency: one PROCESS per rank (all on this GPU), hipIpc mappings of each other's vectors and flags,
-    gloo only as the control plane.  The iterate must have the bits of the single-GPU cycle."""
+def assert_export_layout(layouts, head, level_bytes, pooled):
+    """What every peer-store test asserts of the ranks' p2p_layout() (one dict per rank; `head` buffers in front of the
+    levels' x / tmp / b; level_bytes[l]: a level-l vector's size; pooled[l]: whether that level keeps its three vectors
+    in one allocation): the exported base IS the allocation's base as the runtime reports it, a pooled level's vectors
+    share one allocation index without overlapping, everything else has an allocation of its own, every vector and its
+    64 bytes of slack on either side fit the allocation, and every rank has the same indices and offsets (the rank that
+    opens a neighbour's handles rebuilds the pointers from its OWN layout).  Returns the number of distinct allocations
+    a rank exports = what a neighbour must have mapped of it."""
+    first = [(b["alloc"], b["offset"]) for b in layouts[0]["buffers"]]
+    distinct = head + sum(1 if p else 3 for p in pooled)
+    for rank, lay in enumerate(layouts):
+        bufs = lay["buffers"]
+        assert len(bufs) == head + 3 * len(level_bytes), (rank, len(bufs))
+        assert [(b["alloc"], b["offset"]) for b in bufs] == first, (rank, bufs, first)
+        assert all(b["base_delta"] == 0 for b in bufs), (rank, bufs)
+        assert len({b["alloc"] for b in bufs}) == distinct and max(b["alloc"] for b in bufs) == distinct - 1, (rank, bufs)
+        assert len({b["alloc"] for b in bufs[:head]}) == head
+        for l, nbytes in enumerate(level_bytes):
+            trio = bufs[head + 3 * l:head + 3 * l + 3]
+            assert len({t["alloc"] for t in trio}) == (1 if pooled[l] else 3), (rank, l, trio)
+            for t in trio:
+                assert t["offset"] >= 64 and t["offset"] + nbytes + 64 <= t["alloc_bytes"], (rank, l, t, nbytes)
+            if pooled[l]:
+                offs = sorted(t["offset"] for t in trio)
+                assert offs[1] - offs[0] >= nbytes + 128 and offs[2] - offs[1] >= nbytes + 128, (rank, l, offs, nbytes)
+                assert len({t["alloc_bytes"] for t in trio}) == 1
+    return distinct
+
+
+def plane_level_bytes(shape, world, n_dist):
+    """bytes of a rank's x / tmp / b per distributed level: its planes and four ghost planes on either side (dist.hip PD_GHOST)"""
+    return [8 * (shape[1] >> l) * (shape[2] >> l) * ((shape[0] >> l) // world + 8) for l in range(n_dist)]
+
+
+def run_rank_processes(tmp_path, world, shape, grids, n_dist, env=None):
     import os
     import socket
     import subprocess
     import sys
-    A, R, b, x0 = problem(shape, grids)
-    with _hip.Hierarchy(A, R, smoother="colour") as h:
-        h.resident_load(b, x0)
-        want_norms = [h.resident_cycle(1, 1) for _ in range(3)]
-        want = h.resident_fetch()
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
     worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "p2p_worker.py")
     procs = [subprocess.Popen([sys.executable, worker, str(r), str(world), str(port), str(tmp_path), "x".join(map(str, shape)), str(grids), str(n_dist)],
-                              stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for r in range(world)]
+                              stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env) for r in range(world)]
     for r, p in enumerate(procs):
         try:
             o, e = p.communicate(timeout=240)
@@ -267,10 +293,79 @@ def test_peer_stores_between_processes(tmp_path, world, shape, grids, n_dist):
                 q.kill()
             raise
         assert p.returncode == 0, (r, e[-3000:])
-    got = np.concatenate([np.load(os.path.join(str(tmp_path), "rank%d.npz" % r))["x"] for r in range(world)])
+    return [dict(np.load(os.path.join(str(tmp_path), "rank%d.npz" % r))) for r in range(world)]
+
+
+def test_pooled_slab_vectors_between_processes(tmp_path):
+    """OMG_DIST_VEC_POOL=1 (read once per process; the rank processes inherit it): x, b and tmp of every level are views
+    into one allocation, borrowed with their distance from its first element as shift — the layout rule of common.h that
+    the 27-point slabs' pools copy.  Four rank processes, peer stores through hipIpc mappings: the bits of the single-GPU
+    cycle, one handle per level, 3 + n_dist allocations mapped per peer.  (MI355X: 3.1 s.)"""
+    import json
+    import os
+    world, shape, grids, n_dist = 4, (64, 32, 48), 4, 2
+    A, R, b, x0 = problem(shape, grids)
+    with _hip.Hierarchy(A, R, smoother="colour") as h:
+        h.resident_load(b, x0)
+        want_norms = [h.resident_cycle(1, 1) for _ in range(3)]
+        want = h.resident_fetch()
+    out = run_rank_processes(tmp_path, world, shape, grids, n_dist, env=dict(os.environ, OMG_DIST_VEC_POOL="1"))
+    got = np.concatenate([o["x"] for o in out])
     assert np.array_equal(got, want), int(np.sum(got != want))
-    for r in range(world):
-        np.testing.assert_allclose(np.load(os.path.join(str(tmp_path), "rank%d.npz" % r))["norms"], want_norms, rtol=1e-13)
+    for o in out:
+        np.testing.assert_allclose(o["norms"], want_norms, rtol=1e-13)
+    layouts = [json.loads(str(o["layout"])) for o in out]
+    distinct = assert_export_layout(layouts, 3, plane_level_bytes(shape, world, n_dist), [True] * n_dist)
+    assert distinct == 3 + n_dist
+    for r, lay in enumerate(layouts):
+        assert lay["mapped"] == [0 if q == r else distinct for q in range(world)], (r, lay["mapped"])
+
+
+def test_pooled_slab_vectors_in_one_process(tmp_path):
+    """As above with all four ranks in ONE process (peer stores through plain pointers, mode 1), a process of its own
+    because the switch is a per-process static.  (MI355X: 1.0 s.)"""
+    import json
+    import os
+    import subprocess
+    import sys
+    world, shape, grids, n_dist = 4, (64, 32, 48), 4, 2
+    A, R, b, x0 = problem(shape, grids)
+    with _hip.Hierarchy(A, R, smoother="colour") as h:
+        h.resident_load(b, x0)
+        want_norms = [h.resident_cycle(1, 1) for _ in range(4)]
+        want = h.resident_fetch()
+    worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "p2p_worker.py")
+    run = subprocess.run([sys.executable, worker, "loopback", str(world), "1", str(tmp_path), "x".join(map(str, shape)), str(grids), str(n_dist)],
+                         env=dict(os.environ, OMG_DIST_VEC_POOL="1"), capture_output=True, text=True, timeout=240)
+    assert run.returncode == 0, run.stderr[-3000:]
+    o = dict(np.load(os.path.join(str(tmp_path), "loopback.npz")))
+    assert np.array_equal(o["x"], want), int(np.sum(o["x"] != want))
+    np.testing.assert_allclose(o["norms"], want_norms, rtol=1e-13)
+    layouts = json.loads(str(o["layouts"]))
+    assert assert_export_layout(layouts, 3, plane_level_bytes(shape, world, n_dist), [True] * n_dist) == 3 + n_dist
+    assert all(lay["mapped"] == [0] * world for lay in layouts)          # (one process: nothing is opened)
+
+
+@pytest.mark.parametrize("world,shape,grids,n_dist", [(2, (32, 32, 32), 4, 2), (4, (64, 32, 48), 4, 2)])
+def test_peer_stores_between_processes(tmp_path, world, shape, grids, n_dist):
+    """Real concurrency: one PROCESS per rank (all on this GPU), hipIpc mappings of each other's vectors and flags,
+    gloo only as the control plane.  The iterate must have the bits of the single-GPU cycle."""
+    import json
+    A, R, b, x0 = problem(shape, grids)
+    with _hip.Hierarchy(A, R, smoother="colour") as h:
+        h.resident_load(b, x0)
+        want_norms = [h.resident_cycle(1, 1) for _ in range(3)]
+        want = h.resident_fetch()
+    out = run_rank_processes(tmp_path, world, shape, grids, n_dist)
+    got = np.concatenate([o["x"] for o in out])
+    assert np.array_equal(got, want), int(np.sum(got != want))
+    for o in out:
+        np.testing.assert_allclose(o["norms"], want_norms, rtol=1e-13)
+    # (three allocations per level, the default: every buffer has a handle of its own)
+    layouts = [json.loads(str(o["layout"])) for o in out]
+    distinct = assert_export_layout(layouts, 3, plane_level_bytes(shape, world, n_dist), [False] * n_dist)
+    for r, lay in enumerate(layouts):
+        assert lay["mapped"] == [0 if q == r else distinct for q in range(world)], (r, lay["mapped"])
 
 
 def test_bench_gpus_2_rehearsal_on_one_gpu():
