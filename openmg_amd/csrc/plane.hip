@@ -590,6 +590,10 @@ __global__ __launch_bounds__(MAXT) void plane_kernel(const PlaneKArgs<V> a) {
 
     // ---- prologue: the state step s0 = z0 - 2 expects ---------------------------------------------
     const int s0 = z0 - 2;
+    constexpr bool RES = MODE == 0 || NORM;          // the pass forms residuals
+    // Planes that only skipped stages would read (the live-step table) are not loaded: the registers get
+    // zeros.  Without residuals the red sweep of plane z0 - 2 is skipped, and with it goes the first plane of black x
+    // and of red x and b; the black right-hand side no pass needs before plane z0 - 1 (stage C starts there at the earliest).
     {
         P2<V> em = zero2;
         if (MODE == 1) {
@@ -602,7 +606,7 @@ __global__ __launch_bounds__(MAXT) void plane_kernel(const PlaneKArgs<V> a) {
 #pragma unroll
         for (int l = 0; l < 2; ++l) {
             XB[0][l] = fetch_x(1, s0, l);            // becomes XB[1] at the first shift
-            XB[1][l] = fetch_x(1, s0 - 1, l);        // becomes XB[2]
+            XB[1][l] = RES ? fetch_x(1, s0 - 1, l) : zero2;   // becomes XB[2]
             if (MODE == 1) {
                 XB[0][l] = prolonged(XB[0][l], E0);
                 XB[1][l] = prolonged(XB[1][l], em);
@@ -610,9 +614,9 @@ __global__ __launch_bounds__(MAXT) void plane_kernel(const PlaneKArgs<V> a) {
 #pragma unroll
             for (int d = 0; d < LA; ++d) {            // what steps s0 (, s0 + 1) take at their top
                 LXB[d][l] = fetch_x(1, s0 + d + 1, l);
-                LXR[d][l] = fetch_x(0, s0 + d, l);
-                LBR[d][l] = fetch(bs, 0, s0 + d, l);
-                LBB[d][l] = fetch(bs, 1, s0 + d - 1, l);
+                LXR[d][l] = (RES || d > 0) ? fetch_x(0, s0 + d, l) : zero2;
+                LBR[d][l] = (RES || d > 0) ? fetch(bs, 0, s0 + d, l) : zero2;
+                LBB[d][l] = zero2;                    // (planes z0 - 3, z0 - 2)
             }
             if (live) lds_put(lds + (0 * 2 + (s0 & 1)) * BUF + idx[l], XB[0][l]);
         }
@@ -728,6 +732,14 @@ __global__ __launch_bounds__(MAXT) void plane_kernel(const PlaneKArgs<V> a) {
         }
         {
             unsigned pXB = plane_off(1, s + LA + 1), pR = plane_off(0, s + LA), pBB = plane_off(1, s + LA - 1);
+            {
+                // what no live stage takes (uniform): the planes past the last red sweep's reach — the loads of the
+                // march's last LA steps — and the black right-hand side outside the planes stage C works on
+                const bool past = s + LA > z1 + (RES ? 1 : 0);
+                const int cfirst = z0 - ((RES && SWEEP) ? 1 : 0), clast = z1 - ((RES && SWEEP) ? 0 : 1);
+                if (past) { pXB = unsigned(OOB); pR = unsigned(OOB); }
+                if (s + LA - 1 < cfirst || s + LA - 1 > clast) pBB = unsigned(OOB);
+            }
             asm volatile("" : "+s"(pXB), "+s"(pR), "+s"(pBB));
 #ifdef OMG_PLANE_DBG_ON
             if (a.dbg & 16) {                                     // (timing experiment: the chunk's fill planes — those of its neighbours in z — not loaded)
@@ -773,8 +785,16 @@ __global__ __launch_bounds__(MAXT) void plane_kernel(const PlaneKArgs<V> a) {
             const V *const E2 = lds + (1 * 2 + par) * BUF;        // red, new, plane s - 1
             const V *const E3 = lds + (2 * 2 + par) * BUF;        // black, new, plane s - 2
             const bool pvB = s >= a.kv0 && s < a.kv1, pvC = s - 1 >= a.kv0 && s - 1 < a.kv1;
+            // The chunk's fill and drain steps (s < z0 + 2, s > z1) run only the stages whose results reach an owned
+            // plane's iterate, a coarse slot or a square (the live-step table); uniform conditions on the
+            // march index, one body per parity.  Everything that carries state — the shifts, the loads, the images, the
+            // counts, RB = rb, the stores — runs in every step.  What a skipped stage leaves behind (a plane of the
+            // neighbour chunk not relaxed, a zero residual) is read by skipped stages only.
+            const bool liveT = s > z0 && s <= z1;                 // plane s - 1 is the chunk's own
+            const bool liveB = RES || (s >= z0 - 1 && s <= z1);   // red of s feeds the black sweeps of s - 1, s + 1 (, the residuals beyond)
+            const bool liveC = SWEEP ? (RES ? s >= z0 : liveT) : liveT;   // (no sweep: C's chain is the residual of the chunk's own rows)
             // B: red sweep of plane s
-            if (SWEEP) {
+            if (SWEEP && liveB) {
                 const P2<V> jm = lds_pair(E1 + idx[0] - S), jp = lds_pair(E1 + idx[1] + S);
                 const P2<V> o0 = XB[1][0], o1 = XB[1][1];
                 V num[4], quo[4];
@@ -807,7 +827,7 @@ __global__ __launch_bounds__(MAXT) void plane_kernel(const PlaneKArgs<V> a) {
             }
             PLANE_STAMP(st_B)
             // C: black sweep of plane s - 1, and the residual of the rows it has just relaxed
-            {
+            if (liveC) {
                 const P2<V> jm = lds_pair(E2 + idx[0] - S), jp = lds_pair(E2 + idx[1] + S);
                 const P2<V> o0 = XR[1][0], o1 = XR[1][1];
                 V num[4], quo[4], hd[4];
@@ -834,15 +854,18 @@ __global__ __launch_bounds__(MAXT) void plane_kernel(const PlaneKArgs<V> a) {
                         rb[l].y = num[2 * l + 1];
                         continue;
                     }
-                    const int rule = (l + par + (MIRROR ? 1 : 0)) & 1;    // (par, not s: a constant in the two-steps form)
-                    const P2<V> Bv = BB[l], Kp = XR[MIRROR ? 2 : 0][l];
-                    const V nx_ = XB[2][l].x + quo[2 * l];
-                    const V ny_ = XB[2][l].y + quo[2 * l + 1];
-                    // the same chain with the new x_i: what a residual pass over the updated vector computes
-                    rb[l].x = Bv.x - tail(l, 0, rule, hd[2 * l], nx_, nl[l].ipx, Jp[l].x, Kp.x);
-                    rb[l].y = Bv.y - tail(l, 1, rule, hd[2 * l + 1], ny_, nl[l].ipy, Jp[l].y, Kp.y);
-                    XB[2][l].x = nx_;
-                    XB[2][l].y = ny_;
+                    XB[2][l].x = XB[2][l].x + quo[2 * l];
+                    XB[2][l].y = XB[2][l].y + quo[2 * l + 1];
+                }
+                if (SWEEP && RES && liveT) {
+#pragma unroll
+                    for (int l = 0; l < 2; ++l) {
+                        const int rule = (l + par + (MIRROR ? 1 : 0)) & 1;    // (par, not s: a constant in the two-steps form)
+                        const P2<V> Bv = BB[l], Kp = XR[MIRROR ? 2 : 0][l];
+                        // the same chain with the new x_i: what a residual pass over the updated vector computes
+                        rb[l].x = Bv.x - tail(l, 0, rule, hd[2 * l], XB[2][l].x, nl[l].ipx, Jp[l].x, Kp.x);
+                        rb[l].y = Bv.y - tail(l, 1, rule, hd[2 * l + 1], XB[2][l].y, nl[l].ipy, Jp[l].y, Kp.y);
+                    }
                 }
                 if (!pvC) {                                       // (uniform)
                     asm volatile("" ::: "memory");
@@ -883,8 +906,8 @@ __global__ __launch_bounds__(MAXT) void plane_kernel(const PlaneKArgs<V> a) {
         if (live) {
             // D: residual of the red rows of plane s - 2 (of a plane outside the grid: a finite value that ends in no coarse
             // slot and no norm)
-            P2<V> rr[2];
-            {
+            P2<V> rr[2] = {zero2, zero2};
+            if (RES && s >= z0 + 2) {                             // (plane s - 2 is the chunk's own; s <= z1 + 1 always)
                 const P2<V> jm = d_jm, jp = d_jp;
                 const P2<V> o0 = XB[3][0], o1 = XB[3][1];
 #pragma unroll
