@@ -158,6 +158,24 @@ int omg_hierarchy_level_flags(const omg_hierarchy *h, int level, int *flags);
  * by set (same iterate, bit for bit; the norm's partial sums are associated differently).  A/B only.
  * OMG_PLANE=0 in the environment at creation never builds them.                                      */
 int omg_hierarchy_use_plane(omg_hierarchy *h, int enable);
+/* The shape of the cycles run on this hierarchy and their over-correction factor.  A cycle entered at level l with
+ * shape k smooths, restricts the residual, visits level l + 1 — once for V (and wherever l + 1 is the coarsest level:
+ * its direct solve is exact), twice otherwise, the second visit starting from the first one's result with the same
+ * right-hand side: F = an F-cycle then a V-cycle, W = two W-cycles —, adds over_correction * R^T e and smooths.
+ * Level l, 1 <= l < coarsest, is visited l + 1 times by an F-cycle and 2^l times by a W-cycle.  The factor is applied
+ * as the prolongation's weight: every stored entry of R^T times the factor, rounded once to the level's precision; the
+ * product with e is then rounded and added as before, and the restriction keeps R.  (OMG_CYCLE_V, 1.0), the default,
+ * is the cycle of openmg/__init__.py:151-236.  A factor > 1 repairs the too-stiff Galerkin operators of plain
+ * aggregation under F and W; under V the overshoot compounds down the levels and the iteration may diverge.
+ * Every entry that runs cycles on the hierarchy obeys the setting (omg_vcycle*, omg_solve, omg_resident_cycle(s),
+ * omg_resident_pcg, omg_hierarchy_cycle_dev, the OMG_DTYPE_MIXED entries); the multi-GPU runners are V only.  A call
+ * that changes the setting drops the captured graphs; one that repeats it does nothing.  An unknown shape or a factor
+ * that is not finite and positive: OMG_ERR_INVALID.                                                   */
+#define OMG_CYCLE_V 0
+#define OMG_CYCLE_F 1
+#define OMG_CYCLE_W 2
+int omg_hierarchy_set_cycle(omg_hierarchy *h, int shape, double over_correction);
+int omg_hierarchy_get_cycle(const omg_hierarchy *h, int *shape, double *over_correction);
 /* Tiling of a level's plane-pipelined passes: out[8] = cells per line, lines per plane, planes, a
  * workgroup's interior cells in x / lines / planes, workgroups, threads per workgroup (all 0 when the
  * level has none).                                                                                   */

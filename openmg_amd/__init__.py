@@ -16,6 +16,16 @@ Extra keys understood in the `parameters` dict (ignored by the reference):
                 iteration — 'cycles' then caps the CG iterations, 'threshold' is the target of the recurrence residual
                 norm, infoDict['cycle'] counts iterations and infoDict['norm'] is the true ||b - A u||; a CG breakdown
                 (an indefinite operator or preconditioner) raises RuntimeError.  Any other value raises ValueError
+    'cycle'     'V' (default: the reference's cycle), 'F' or 'W': how often a cycle visits the coarse levels.  A cycle over
+                level l visits level l + 1 once ('V', and wherever l + 1 is the coarsest level: its direct solve is exact)
+                or twice, the second visit starting from the first one's result: 'F' = an F- then a V-cycle, 'W' = two
+                W-cycles.  Level l >= 1 is visited l + 1 ('F') or 2**l ('W') times per cycle.  The plain aggregation's
+                Galerkin operators are about twice too stiff, so a V-cycle's factor degrades with depth; F and W repair it
+    'overCorrection'  a finite float > 0, default 1.0: the coarse correction is added as alpha * R^T e.  The factor is applied
+                as the prolongation's weight (every entry of R^T times alpha, rounded once to the levels' precision).
+                1.5 .. 1.8 with 'F' or 'W' is the standard repair for plain aggregation; with 'V' the overshoot compounds
+                down the levels and alpha > 1 CAN DIVERGE.  Both keys hold for mgSolve (with every 'accel' and 'dtype') and
+                mgCycle (from the level it is entered at downward); anything else raises ValueError before any device work
     'dtype'     'float64' (default, the reference's precision) or 'float32': the precision the
                 levels are stored and computed in on the device (inputs / outputs stay float64).
                 mgSolve only: 'mixed' — fp32 levels and V-cycles inside fp64 iterations on the finest level (its
@@ -68,6 +78,18 @@ def _smoother_of(parameters):
 
 def _dtype_of(parameters):
     return _hip.dtype_code(parameters.get("dtype", "float64"))
+
+
+def _cycle_of(parameters):
+    """(shape, over-correction factor) of parameters['cycle'] / ['overCorrection']; ValueError for anything else."""
+    shape = parameters.get("cycle", "V")
+    if not isinstance(shape, str) or shape not in _hip.CYCLES:
+        raise ValueError("parameters['cycle'] must be 'V', 'F' or 'W', not %r" % (shape,))
+    try:
+        alpha = _hip.over_correction_of(parameters.get("overCorrection", 1.0))
+    except ValueError:
+        raise ValueError("parameters['overCorrection'] must be a finite float > 0, not %r" % (parameters.get("overCorrection"),))
+    return shape, alpha
 
 
 # ---- device hierarchy cache for repeated mgCycle calls ---------------------------------------
@@ -168,6 +190,7 @@ def mgSolve(A_in, b, parameters):
     accel = parameters.get("accel")
     if accel not in (None, "cg"):
         raise ValueError("parameters['accel'] must be None or 'cg', not %r" % (accel,))
+    shape, alpha = _cycle_of(parameters)
     problemShape = parameters["problemShape"]
     gridLevels = parameters["gridLevels"]
     defaults["coarsestLevel"] = gridLevels - 1
@@ -197,15 +220,16 @@ def mgSolve(A_in, b, parameters):
     depth = parameters["coarsestLevel"]
     b_on_device = _devarray.is_device_array(b)
     try:
+        hierarchy.set_cycle(shape, alpha)
         if b_on_device:
             _devarray.synchronize()
             hierarchy.resident_load_dev(_devarray.address(b, hierarchy.sizes[0], "b"))
         else:
             hierarchy.resident_load(np.asarray(b, dtype=np.float64).reshape(-1))
         if accel == "cg":
-            cycle, norm = _solve_cg(hierarchy, parameters, pre, post, depth, verbose)
+            cycle, norm = _solve_cg(hierarchy, parameters, pre, post, depth, verbose, shape)
         else:
-            cycle, norm = _solve_cycles(hierarchy, parameters, pre, post, depth, verbose)
+            cycle, norm = _solve_cycles(hierarchy, parameters, pre, post, depth, verbose, shape)
         if b_on_device:
             result = _devarray.empty_like(b, hierarchy.sizes[0])
             hierarchy.resident_fetch_dev(_devarray.address(result, hierarchy.sizes[0], "result"))
@@ -226,7 +250,7 @@ def mgSolve(A_in, b, parameters):
 _CG_CHUNK = 10000
 
 
-def _solve_cg(hierarchy, parameters, pre, post, depth, verbose):
+def _solve_cg(hierarchy, parameters, pre, post, depth, verbose, shape="V"):
     """mgSolve's loop with parameters['accel'] == 'cg': FCG on the resident iterate; returns (iterations, true norm)."""
     cycles, threshold = parameters["cycles"], parameters["threshold"]
     both_off = threshold <= 0 and cycles <= 0
@@ -236,7 +260,7 @@ def _solve_cg(hierarchy, parameters, pre, post, depth, verbose):
         its, norms, norm, breakdown = hierarchy.resident_pcg(pre, post, max_iter, threshold if threshold > 0 else 0.0)
         if verbose:
             for k, nk in enumerate(norms):
-                _announce_descent(depth)
+                _announce_descent(depth, shape)
                 print("Residual norm from cycle %d is %f." % (done + k + 1, nk))
         if breakdown:
             raise RuntimeError("mgSolve accel='cg': conjugate gradients broke down in iteration %d (the operator or the "
@@ -248,10 +272,10 @@ def _solve_cg(hierarchy, parameters, pre, post, depth, verbose):
             return done, norm
 
 
-def _solve_cycles(hierarchy, parameters, pre, post, depth, verbose):
+def _solve_cycles(hierarchy, parameters, pre, post, depth, verbose, shape="V"):
     """mgSolve's loop of plain V-cycles (openmg/__init__.py:112-138); returns (cycles, norm)."""
     if verbose:
-        _announce_descent(depth)
+        _announce_descent(depth, shape)
     norm = hierarchy.resident_cycle(pre, post)
     cycle = 1
     if verbose:
@@ -272,7 +296,7 @@ def _solve_cycles(hierarchy, parameters, pre, post, depth, verbose):
     while not finished():
         if verbose:
             print("cycle %i < cycles %i" % (cycle, parameters["cycles"]))
-            _announce_descent(depth)
+            _announce_descent(depth, shape)
         cycle += 1
         norm = hierarchy.resident_cycle(pre, post)
         if verbose:
@@ -318,14 +342,19 @@ def _device_setup_depth(A_in, problemShape, parameters):
     return n
 
 
-def _announce_descent(depth):
-    for level in range(depth):
-        print(level * " " + "calling mgCycle at level %i" % level)
-    print(depth * " " + "direct solving at level %i" % depth)
+def _announce_descent(depth, shape="V", level=0):
+    """The reference's progress lines for one cycle of `shape` entered at `level`, in the order of the recursion."""
+    if level >= depth:
+        print(depth * " " + "direct solving at level %i" % depth)
+        return
+    print(level * " " + "calling mgCycle at level %i" % level)
+    visits = [shape] if (shape == "V" or level + 1 >= depth) else (["F", "V"] if shape == "F" else ["W", "W"])
+    for s in visits:
+        _announce_descent(depth, s, level + 1)
 
 
 def mgCycle(A, b, level, R, parameters, initial=None):
-    """One V-cycle entered at `level`; same contract as openmg.mgCycle
+    """One cycle (parameters['cycle'], default a V-cycle) entered at `level`; same contract as openmg.mgCycle
     (openmg/__init__.py:151-236): pre-smooth, restrict the residual, recurse, prolong and
     correct, post-smooth; direct solve at parameters['coarsestLevel'].
 
@@ -336,6 +365,7 @@ def mgCycle(A, b, level, R, parameters, initial=None):
     if parameters.get("dtype", "float64") == "mixed":
         raise ValueError("parameters['dtype'] = 'mixed' is for mgSolve only (fp64 iterations around fp32 V-cycles); "
                          "mgCycle runs one cycle: use 'float32' or 'float64'")
+    shape, alpha = _cycle_of(parameters)
     coarsest = parameters["coarsestLevel"]
     if coarsest >= len(A) or coarsest > len(R):
         raise IndexError("parameters['coarsestLevel'] = %d but only %d operators / %d restrictions given"
@@ -352,10 +382,9 @@ def mgCycle(A, b, level, R, parameters, initial=None):
             raise ValueError("mgCycle at the coarsest level with device arrays: use solvers.coarseSolve on host arrays")
         return solvers.coarseSolve(A[level], b), {"norm": 0}
     hierarchy = _hierarchy_for(A, R, coarsest + 1, code, omega, _dtype_of(parameters), trust=bool(parameters.get("trustOperators", False)))
+    hierarchy.set_cycle(shape, alpha)          # (the cached hierarchy may have run another setting: a no-op when unchanged)
     if parameters.get("verbose", False):
-        for l in range(level, coarsest):
-            print(l * " " + "calling mgCycle at level %i" % l)
-        print(coarsest * " " + "direct solving at level %i" % coarsest)
+        _announce_descent(coarsest, shape, level)
     pre = parameters["preIterations"]
     if on_device:
         # b, initial, uOut in HBM: only the norm crosses PCIe (omg_vcycle_dev).  Q2 as on the host: with pre-smoothing the

@@ -69,6 +69,8 @@ SIGNATURES = {
     "omg_hierarchy_level_fused": (_I, [_P, _I, _IP]),
     "omg_hierarchy_level_flags": (_I, [_P, _I, _IP]),
     "omg_hierarchy_use_plane": (_I, [_P, _I]),
+    "omg_hierarchy_set_cycle": (_I, [_P, _I, _D]),
+    "omg_hierarchy_get_cycle": (_I, [_P, _IP, _DP]),
     "omg_hierarchy_plane_info": (_I, [_P, _I, _I64P]),
     "omg_hierarchy_format_info": (_I, [_P, _I, _I, _I, _I64P]),
     "omg_format_selftest": (_I, [_CSR, _I, _I64P]),
@@ -238,6 +240,31 @@ def smoother_code(kind):
         return SMOOTHERS[kind]
     except KeyError:
         raise ValueError("unknown smoother %r (choose from %s)" % (kind, sorted(set(SMOOTHERS))))
+
+
+CYCLE_V, CYCLE_F, CYCLE_W = 0, 1, 2
+CYCLES = {"V": CYCLE_V, "F": CYCLE_F, "W": CYCLE_W}
+
+
+def cycle_code(shape):
+    """OMG_CYCLE_* for 'V' / 'F' / 'W' (or the code itself)."""
+    if isinstance(shape, int) and not isinstance(shape, bool) and shape in CYCLES.values():
+        return shape
+    try:
+        return CYCLES[shape]
+    except (KeyError, TypeError):
+        raise ValueError("unknown cycle shape %r (choose from 'V', 'F', 'W')" % (shape,))
+
+
+def over_correction_of(value):
+    """The over-correction factor as a float; ValueError unless it is finite and > 0."""
+    try:
+        alpha = float(value)
+    except (TypeError, ValueError):
+        raise ValueError("the over-correction factor must be a number, not %r" % (value,))
+    if not np.isfinite(alpha) or alpha <= 0.0:
+        raise ValueError("the over-correction factor must be finite and > 0, not %r" % (value,))
+    return alpha
 
 
 DTYPE_F64, DTYPE_F32, DTYPE_MIXED = 0, 1, 2
@@ -505,6 +532,17 @@ class Hierarchy:
     def use_plane(self, enable=True):
         """Plane-pipelined passes on / off (omg_hierarchy_use_plane; same iterate either way)."""
         check(lib().omg_hierarchy_use_plane(self._h, 1 if enable else 0))
+
+    def set_cycle(self, shape="V", over_correction=1.0):
+        """Shape ('V', 'F', 'W') and over-correction factor of every cycle run on this hierarchy from now on
+        (omg_hierarchy_set_cycle); repeating the current setting does nothing."""
+        check(lib().omg_hierarchy_set_cycle(self._h, cycle_code(shape), over_correction_of(over_correction)))
+
+    def get_cycle(self):
+        """(shape, over-correction factor) as set: ('V', 1.0) unless set_cycle has been called."""
+        code, alpha = ctypes.c_int(-1), ctypes.c_double(0.0)
+        check(lib().omg_hierarchy_get_cycle(self._h, ctypes.byref(code), ctypes.byref(alpha)))
+        return {v: k for k, v in CYCLES.items()}[code.value], alpha.value
 
     PLANE_FIELDS = ("nx", "ny", "nz", "tile_x", "tile_y", "tile_z", "workgroups", "threads")
 

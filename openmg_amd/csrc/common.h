@@ -493,6 +493,14 @@ constexpr bool mode_prenorm(int m) { return m == ROW_GS_PRENORM || m == ROW_JACO
 constexpr bool mode_relaxes(int m) { return m == ROW_GS || m == ROW_JACOBI || mode_fused(m) || mode_prenorm(m); }   // needs x_i and the diagonal
 constexpr bool mode_norm(int m) { return m == ROW_RESNORM || m == ROW_NORM_ONLY || m == ROW_GS_NORM || mode_prenorm(m); }
 
+// The four value arrays of a DevCsrT (plain values, value dictionaries, pattern values, block-transposed values) in a second
+// edition: the same operator with other stored values behind the same codes and patterns (an over-corrected prolongation:
+// every entry times the factor, rounded once)
+template <typename V>
+struct RowValues {
+    const V *data = nullptr, *vdict = nullptr, *pval = nullptr, *vell = nullptr;
+};
+
 template <typename V>
 struct RowArgsT {
     const V *x = nullptr;        // gathered vector
@@ -511,6 +519,7 @@ struct RowArgsT {
     const V *first_diag = nullptr;
     int first_end = 0;
     bool first_jacobi = false;
+    const RowValues<V> *values = nullptr;   // read the operator's values from these arrays instead of its own (null: its own)
 };
 using RowArgs = RowArgsT<double>;
 
@@ -546,6 +555,9 @@ void launch_scatter(const S *src, const int32_t *idx, D *dst, int64_t n, hipStre
 // relaxation kernels form it (plain CSR arrays of the operator, which stay on the device)
 template <typename V>
 void launch_diagonal(const DevCsrT<V> &A, V *diag, hipStream_t s);
+// out[i] = factor * in[i], rounded once to V
+template <typename V>
+void launch_scale_values(const V *in, V *out, int64_t n, double factor, hipStream_t s);
 // x[i] = i < first_end ? 0 + scale_q((b[i] - 0) / diag[i]) : 0 — the first relaxation launch of a
 // zero iterate (first Gauss-Seidel set, or with jacobi a whole weighted-Jacobi sweep), spelled like
 // the row kernels' epilogues
@@ -731,6 +743,7 @@ struct PlaneGeom {
     size_t lds_bytes = 0;
     double c[7] = {0, 0, 0, 0, 0, 0, 0};   // -K, -J, -I, diagonal, +I, +J, +K
     double w = 0.0;                   // the restriction's weight
+    double over = 1.0;                // over-correction: the prolongation's weight is over * w, rounded once to V
     // small levels (set when the plan is built, from OMG_PLANE_BLOCK / OMG_PLANE_BLOCK_CELLS / OMG_PLANE_LA2):
     bool dim2 = false;                // nz == 1: a 2-D grid (five-point stencil, 2 x 2 aggregation): tile2d_kernel
     bool jacobi = false;              // ... smoothed with weighted Jacobi (weight omega) in its natural ordering instead of red-black
@@ -859,6 +872,7 @@ template <typename V>
 struct Var7Plan {
     int nx = 0, ny = 0, nz = 0;
     double w = 0.0;                   // the aggregation's one weight
+    double over = 1.0;                // over-correction: the prolongation's weight is over * w, rounded once to V
     bool sym = false;                 // a(i, j) == a(j, i) bit for bit: the "-" arrays are not kept
     int tx = 0, ty = 0, lz = 0, ntx = 0, nty = 0, ntz = 0, threads = 0;
     int64_t n_wg = 0;
@@ -934,6 +948,7 @@ struct S27Geom {
     int wpb = 4;                      // waves per workgroup (1 on small levels)
     int n_wg = 0;                     // workgroups
     double w = 0.0;                   // the restriction's weight
+    double over = 1.0;                // over-correction: the prolongation's weight is over * w, rounded once to V
 };
 template <typename V>
 struct Stencil27Plan {

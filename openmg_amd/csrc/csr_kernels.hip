@@ -1178,6 +1178,7 @@ KArgs<V> make_kargs(const DevCsrT<V> &A, const RowArgsT<V> &args) {
     k.pval = A.pval.p;
     k.pbeg = A.pbeg.p;
     k.vell = A.vell.p;
+    if (args.values) { k.data = args.values->data; k.vdict = args.values->vdict; k.pval = args.values->pval; k.vell = args.values->vell; }
     k.x = args.x;
     k.b = args.b;
     k.y = args.y;
@@ -1510,6 +1511,21 @@ void launch_first_relaxation(const V *b, const V *diag, V *x, int64_t n, int64_t
     OMG_HIP(hipGetLastError());
 }
 
+// out[i] = fl(factor * in[i]): every stored value of a prolongation operator times the over-correction factor, rounded
+// once to V (RowArgsT::values)
+template <typename V>
+__global__ void scale_values_kernel(const V *__restrict__ in, V *__restrict__ out, int64_t n, double factor) {
+    const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = V(factor * double(in[i]));
+}
+
+template <typename V>
+void launch_scale_values(const V *in, V *out, int64_t n, double factor, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL((scale_values_kernel<V>), dim3(grid_for(n, 256)), dim3(256), 0, s, in, out, n, factor);
+    OMG_HIP(hipGetLastError());
+}
+
 template <typename V>
 void launch_dense_gemv(const V *M, const V *v, V *out, int64_t n, hipStream_t s) {
     launch_dense_gemv_rows(M, v, out, n, n, s);
@@ -1529,6 +1545,7 @@ void launch_dense_gemv_rows(const V *M, const V *v, V *out, int64_t rows, int64_
     template void launch_gs_serial<V>(const DevCsrT<V> &, int, int, const RowArgsT<V> &, hipStream_t);    \
     template void launch_dense_gemv<V>(const V *, const V *, V *, int64_t, hipStream_t);                   \
     template void launch_diagonal<V>(const DevCsrT<V> &, V *, hipStream_t);                               \
+    template void launch_scale_values<V>(const V *, V *, int64_t, double, hipStream_t);                   \
     template void launch_first_relaxation<V>(const V *, const V *, V *, int64_t, int64_t, bool, double, hipStream_t); \
     template void launch_dense_gemv_rows<V>(const V *, const V *, V *, int64_t, int64_t, hipStream_t);
 OMG_INSTANTIATE(double)

@@ -149,6 +149,12 @@ struct Level {
     // explicit transpose P: possible when no two rows of R share a column (aggregation) and R
     // is row-pattern coded; reads 1 byte per COARSE row instead of ~9 per fine row
     bool scatter_prolong = false;
+    // over-correction (Hier::over != 1) on the row-kernel path: the prolongation operator's stored values (R's under
+    // scatter_prolong, P's otherwise) times the factor, each rounded once — a second edition of its value arrays, made by
+    // prolong_add_level on first use for the factor pw_factor (0: none made)
+    DevBuf<V> pw_data, pw_vdict, pw_pval, pw_vell;
+    RowValues<V> pw;
+    double pw_factor = 0.0;
     // lexicographic Gauss-Seidel of a grid star stencil: one launch per sweep (common.h MarchPlan);
     // the level then keeps its natural ordering (one "set") for every other kernel
     std::unique_ptr<MarchPlan<V>> march;
@@ -211,6 +217,10 @@ struct Hier {
     } mx;
     int smoother = OMG_SMOOTH_GS_LEX;
     double omega = 1.0;
+    // omg_hierarchy_set_cycle: the shape of every cycle run on this hierarchy (cycle_body) and the over-correction factor —
+    // the prolongation's weight is over * (the restriction's weight), rounded once to V; the restriction keeps its own
+    int cycle_shape = OMG_CYCLE_V;
+    double over = 1.0;
     hipStream_t own = nullptr, stream = nullptr;
     // omg_hierarchy_update_fine (a hierarchy set up on the device whose smoothed levels all run the 27-point kernels): the
     // fine operator's row pointers (the values come with every update), its grid, and per level >= 1 the Galerkin
@@ -493,13 +503,35 @@ void restrict_level(Hier<V> *h, int l, const V *fine, V *coarse, V *clear = null
     launch_rows(L.R, ROW_SPMV, -1, a, h->stream);
 }
 
+// fine += R^T coarse with every stored entry of R times `factor`, rounded once (1: the entries themselves)
 template <typename V>
-void prolong_add_level(Hier<V> *h, int l, const V *coarse, V *fine) {
+void ensure_prolong_values(Hier<V> *h, int l, double factor) {
+    Level<V> &L = h->lv[l];
+    if (factor != 1.0 && L.pw_factor != factor) {
+        const DevCsrT<V> &T = L.scatter_prolong ? L.R : L.P;
+        auto scaled = [&](const DevBuf<V> &src, DevBuf<V> &dst) -> const V * {
+            if (!src.p || !src.n) return src.p;
+            if (dst.n != src.n) dst.alloc(src.n);
+            launch_scale_values<V>(src.p, dst.p, int64_t(src.n), factor, h->stream);
+            return dst.p;
+        };
+        L.pw.data = scaled(T.data, L.pw_data);
+        L.pw.vdict = scaled(T.vdict, L.pw_vdict);
+        L.pw.pval = scaled(T.pval, L.pw_pval);
+        L.pw.vell = scaled(T.vell, L.pw_vell);
+        L.pw_factor = factor;
+    }
+}
+
+template <typename V>
+void prolong_add_level(Hier<V> *h, int l, const V *coarse, V *fine, double factor) {
     ensure_format(h, l);
     Level<V> &L = h->lv[l];
+    ensure_prolong_values(h, l, factor);
     Prof<V> p(h, l, 3);
     RowArgsT<V> a;
     a.x = coarse; a.y = fine;
+    if (factor != 1.0) a.values = &L.pw;
     if (L.scatter_prolong) {
         a.ymap = L.r_out.p;                   // R's rows are in natural coarse order (create())
         launch_rows(L.R, ROW_SCATTER, -1, a, h->stream);
@@ -782,9 +814,27 @@ bool use_plane(const Hier<V> *h, const Level<V> &L, int pre, int post) {
 // plane-pipelined up pass has left ALL of it in its workgroup partials (post_slot, or the plan's own
 // array: finish_plane_norm).
 // x_zero: the level's iterate is zero and has not been written (plane levels only).
+// shape: OMG_CYCLE_V / F / W from this level downward (-1, what every entry passes: the hierarchy's setting).
 template <typename V>
 int cycle_body(Hier<V> *h, int l, int pre, int post, bool want_norm = false, double *pre_slot = nullptr,
-               bool first_done = false, double *post_slot = nullptr, bool x_zero = false) {
+               bool first_done = false, double *post_slot = nullptr, bool x_zero = false, int shape = -1);
+
+// The coarse-grid correction of a cycle of `shape` over level l: level l + 1 is visited once (V; or it is the coarsest
+// level, whose direct solve is exact), or twice — F: an F-cycle, then a V-cycle; W: two W-cycles.  The first visit is the
+// one a V-cycle makes, with its shortcuts (first_done, x_zero: what the parent has made of the child's zero iterate).  The
+// second enters the child with its iterate as the first left it and its right-hand side untouched: nothing cleared, no
+// launch skipped, and every path of cycle_body builds the format it needs itself.
+template <typename V>
+void cycle_children(Hier<V> *h, int l, int pre, int post, int shape, bool first_done, bool x_zero) {
+    cycle_body(h, l + 1, pre, post, false, nullptr, first_done, nullptr, x_zero, shape);
+    if (shape != OMG_CYCLE_V && l + 1 < (int)h->lv.size() - 1)
+        cycle_body(h, l + 1, pre, post, false, nullptr, false, nullptr, false, shape == OMG_CYCLE_F ? OMG_CYCLE_V : OMG_CYCLE_W);
+}
+
+template <typename V>
+int cycle_body(Hier<V> *h, int l, int pre, int post, bool want_norm, double *pre_slot, bool first_done, double *post_slot, bool x_zero,
+               int shape) {
+    if (shape < 0) shape = h->cycle_shape;
     const int last = (int)h->lv.size() - 1;
     if (l >= last) {
         coarse_solve_level(h);
@@ -816,7 +866,7 @@ int cycle_body(Hier<V> *h, int l, int pre, int post, bool want_norm = false, dou
             Prof<V> p(h, l, 1);
             P.residual_restrict(L.xp, L.b.p, pre >= 1, L.r_out.p, C.b.p, h->stream);                  // :209, :210
         }
-        cycle_body(h, l + 1, pre, post, false, nullptr, false, nullptr, child_zero);                   // :213
+        cycle_children(h, l, pre, post, shape, false, child_zero);                                     // :213
         {
             Prof<V> p(h, l, 3);
             P.prolong(L.xp, C.xp, L.r_out.p, h->stream);                                               // :214, :220 / :224
@@ -838,7 +888,7 @@ int cycle_body(Hier<V> *h, int l, int pre, int post, bool want_norm = false, dou
         if (l + 1 < last) ensure_format(h, l + 1);
         const bool child_first = l + 1 < last && first_sweep_in_restrict(h, C, pre);
         restrict_level<V>(h, l, L.r.p, C.b.p, l + 1 < last ? C.xp : nullptr, child_first);
-        cycle_body(h, l + 1, pre, post, false, nullptr, child_first);
+        cycle_children(h, l, pre, post, shape, child_first, false);
         typename PlanePlan<V>::Coarse c;
         c.map = L.r_out.p;
         c.e = C.xp;
@@ -861,8 +911,8 @@ int cycle_body(Hier<V> *h, int l, int pre, int post, bool want_norm = false, dou
         c.first_end = child_first ? int(C.A.sets[1]) : 0;
         L.plane->down(L.xp, L.tp, L.b.p, x_zero, c, h->stream);
         std::swap(L.xp, L.tp);
-        cycle_body(h, l + 1, pre, post, false, nullptr, child_first);
-        prolong_add_level<V>(h, l, C.xp, L.xp);
+        cycle_children(h, l, pre, post, shape, child_first, false);
+        prolong_add_level<V>(h, l, C.xp, L.xp, h->over);
         return smooth_level(h, l, post, want_norm ? FUSE_NORM : FUSE_NONE, nullptr, false, post_slot) ? NORM_LAST_SET : NORM_NONE;
     }
     if (use_plane(h, L, pre, post)) {
@@ -886,7 +936,7 @@ int cycle_body(Hier<V> *h, int l, int pre, int post, bool want_norm = false, dou
         }
         if (pre >= 1) std::swap(L.xp, L.tp);
         if (l == h->pre_level) OMG_HIP(hipMemcpyAsync(h->pre_buf.p, L.xp, size_t(L.n) * sizeof(V), hipMemcpyDeviceToDevice, h->stream));
-        cycle_body(h, l + 1, pre, post, false, nullptr, child_first, nullptr, child_zero);   // :213
+        cycle_children(h, l, pre, post, shape, child_first, child_zero);                     // :213
         c.e = C.xp;
         double *out = (want_norm && post <= 1) ? (post_slot ? post_slot : L.plane->partials.p) : nullptr;
         {
@@ -918,7 +968,7 @@ int cycle_body(Hier<V> *h, int l, int pre, int post, bool want_norm = false, dou
         if (pre >= 1) std::swap(L.xp, L.tp);
         else if (x_zero) OMG_HIP(hipMemsetAsync(L.xp, 0, size_t(L.n) * sizeof(V), h->stream));
         if (l == h->pre_level) OMG_HIP(hipMemcpyAsync(h->pre_buf.p, L.xp, size_t(L.n) * sizeof(V), hipMemcpyDeviceToDevice, h->stream));
-        cycle_body(h, l + 1, pre, post, false, nullptr, false, nullptr, child_zero);      // :213
+        cycle_children(h, l, pre, post, shape, false, child_zero);                        // :213
         c.e = C.xp;
         double *out = (want_norm && post <= 1) ? (post_slot ? post_slot : P.partials.p) : nullptr;
         {
@@ -937,10 +987,11 @@ int cycle_body(Hier<V> *h, int l, int pre, int post, bool want_norm = false, dou
     // or already relaxed once (first_sweep_in_restrict)
     const bool child_zero = l + 1 < last && ((use_plane(h, C, pre, post) && pre == 1 && halves == 3) || (use_s27(h, C) && pre >= 1));
     if (l + 1 < last && !child_zero && !use_s27(h, C)) ensure_format(h, l + 1);
-    const bool child_first = l + 1 < last && !child_zero && !use_s27(h, C) && first_sweep_in_restrict(h, C, pre);
+    // (a var7 child's down pass holds its whole first sweep: it cannot skip a launch already applied)
+    const bool child_first = l + 1 < last && !child_zero && !use_s27(h, C) && !use_var7(h, C) && first_sweep_in_restrict(h, C, pre);
     restrict_level<V>(h, l, L.r.p, C.b.p, (l + 1 < last && !child_zero) ? C.xp : nullptr, child_first);
-    cycle_body(h, l + 1, pre, post, false, nullptr, child_first, nullptr, child_zero);   // :213
-    prolong_add_level<V>(h, l, C.xp, L.xp);                         // :214, :220/:224
+    cycle_children(h, l, pre, post, shape, child_first, child_zero);                     // :213
+    prolong_add_level<V>(h, l, C.xp, L.xp, h->over);                // :214, :220/:224
     if (post > 0)
         return smooth_level(h, l, post, want_norm ? FUSE_NORM : FUSE_NONE, nullptr, false, post_slot) ? NORM_LAST_SET : NORM_NONE;   // :216-222
     return NORM_NONE;
@@ -1187,6 +1238,7 @@ void build_format(Hier<V> *h, int l, const omg_csr &A, const omg_csr &R) {
         HostCsr Pt = transpose_csr(Rp);
         L.P.upload(Pt, {}, h->stream);
     }
+    L.pw_factor = 0.0;                                             // (a second edition of the prolongation's values belongs to the arrays just replaced)
     L.r.alloc(L.n);
     if (h->smoother == OMG_SMOOTH_JACOBI && !L.tmp.p) { L.tmp.alloc(L.n); L.tp = L.tmp.p; }
     L.partials.alloc(L.A.n_blocks() + SUM_FOLD);
@@ -2380,6 +2432,35 @@ int omg_hierarchy_use_plane(omg_hierarchy *h, int enable) {
     });
 }
 
+int omg_hierarchy_set_cycle(omg_hierarchy *h, int shape, double over_correction) {
+    return guarded([&] {
+        OMG_REQUIRE(shape == OMG_CYCLE_V || shape == OMG_CYCLE_F || shape == OMG_CYCLE_W, "unknown cycle shape");
+        OMG_REQUIRE(std::isfinite(over_correction) && over_correction > 0.0, "the over-correction factor must be finite and positive");
+        with(h, [&](auto *hh) {
+            if (hh->cycle_shape == shape && hh->over == over_correction) return;
+            OMG_HIP(hipStreamSynchronize(hh->stream));
+            drop_graph(hh);                                        // (a captured cycle has the shape's launches and the weight baked in)
+            hh->cycle_shape = shape;
+            hh->over = over_correction;
+            for (int l = 0; l + 1 < (int)hh->lv.size(); ++l) {
+                auto &L = hh->lv[l];
+                if (L.plane) L.plane->g.over = over_correction;
+                if (L.var7) L.var7->over = over_correction;
+                if (L.s27) L.s27->g.over = over_correction;
+                // (the row kernels' edition of the prolongation's values: now where the format exists, else when it is built)
+                if (!L.format_pending) ensure_prolong_values(hh, l, over_correction);
+            }
+        });
+    });
+}
+
+int omg_hierarchy_get_cycle(const omg_hierarchy *h, int *shape, double *over_correction) {
+    return guarded([&] {
+        OMG_REQUIRE(shape && over_correction, "null argument");
+        with(h, [&](auto *hh) { *shape = hh->cycle_shape; *over_correction = hh->over; });
+    });
+}
+
 int omg_hierarchy_plane_info(const omg_hierarchy *h, int level, int64_t *out8) {
     return guarded([&] {
         with(h, [&](auto *hh) {
@@ -3010,7 +3091,7 @@ int omg_level_prolong_add(omg_hierarchy *h, int level, const double *coarse, dou
             hh->resident = false;
             load_vec(hh, level + 1, coarse, C.xp);
             load_vec(hh, level, fine_inout, L.xp);
-            prolong_add_level<V>(hh, level, C.xp, L.xp);
+            prolong_add_level<V>(hh, level, C.xp, L.xp, 1.0);      // (the operator R^T itself: no over-correction)
             fetch_vec<V>(hh, level, L.xp, fine_inout);
         });
     });

@@ -186,6 +186,7 @@ struct PlaneKArgs {
     // first and last PLANE_EDGE planes, and wait for wait_flag[] before they read anything.  0: no such launch
     int edge_wg0;
     V c0, c1, c2, c3, c4, c5, c6, w;
+    V wp;                            // the prolongation's weight: the over-correction factor times w, rounded once (PlaneGeom::over)
     int x_zero;
     int fast_div;                    // the diagonal's exponent is within 2^-400 .. 2^400 (quotients())
     // coarse level
@@ -496,7 +497,7 @@ __global__ __launch_bounds__(MAXT) void plane_kernel(const PlaneKArgs<V> a) {
     auto coarse_vals = [&](const v2u &sl) -> P2<V> { return {bload1(es, int(sl.x), V(0)), bload1(es, int(sl.y), V(0))}; };
     auto prolonged = [&](const P2<V> &x, const P2<V> &e) -> P2<V> {
         // openmg/__init__.py:214,220: x + R^T e — the product rounded, then added (ROW_SCATTER's two roundings)
-        return {x.x + madd(a.w, e.x, V(0)), x.y + madd(a.w, e.y, V(0))};
+        return {x.x + madd(a.wp, e.x, V(0)), x.y + madd(a.wp, e.y, V(0))};
     };
 
     const V rc3 = refined_rcp(a.c3);
@@ -1158,6 +1159,7 @@ struct BlockKArgs {
     int nx, ny, nz, nr;
     int nbx, nby;
     V c0, c1, c2, c3, c4, c5, c6, w;
+    V wp;                            // the prolongation's weight: the over-correction factor times w, rounded once (PlaneGeom::over)
     int fast_div;
     int nxc, nyc;
     const int32_t *cmap;
@@ -1247,7 +1249,7 @@ __global__ __launch_bounds__(256) void block_kernel(const BlockKArgs<V> a) {
             const int c = t + n * NT;
             const int li = c % EX, lj = (c / EX) % EY, lk = c / (EX * EY);
             if (c < vol && in_grid(i0 + li, j0 + lj, k0 + lk))
-                X[c] = xv[n] + madd(a.w, E[((lk >> 1) * CY + (lj >> 1)) * CX + (li >> 1)], V(0));
+                X[c] = xv[n] + madd(a.wp, E[((lk >> 1) * CY + (lj >> 1)) * CX + (li >> 1)], V(0));
         }
         __syncthreads();
     }
@@ -1353,6 +1355,7 @@ struct Tile2KArgs {
     int nx, ny, nr;
     int nbx;
     V c1, c2, c3, c4, c5, w, omega;
+    V wp;                            // the prolongation's weight (PlaneGeom::over)
     int fast_div;
     int nxc, nyc;
     const int32_t *cmap;
@@ -1413,7 +1416,7 @@ __global__ __launch_bounds__(256) void tile2d_kernel(const Tile2KArgs<V> a) {
         for (int n = 0; n < NL; ++n) {
             const int c = t + n * NT;
             const int gi = i0 + c % EX, gj = j0 + c / EX;
-            if (c < vol && in_grid(gi, gj)) xv[n] = xv[n] + madd(a.w, E[((gj >> 1) - cj0) * CW + ((gi >> 1) - ci0)], V(0));
+            if (c < vol && in_grid(gi, gj)) xv[n] = xv[n] + madd(a.wp, E[((gj >> 1) - cj0) * CW + ((gi >> 1) - ci0)], V(0));
         }
         __syncthreads();
     }
@@ -2111,6 +2114,7 @@ PlaneKArgs<V> plane_args(const PlaneGeom &g, const V *x_old, V *x_new, const V *
     k.TXq = g.TX / 4; k.TY = g.TY; k.LZ = g.LZ; k.PX = g.PX; k.PY = g.PY; k.ntx = g.ntx; k.nty = g.nty; k.ntz = g.ntz;
     k.c0 = V(g.c[0]); k.c1 = V(g.c[1]); k.c2 = V(g.c[2]); k.c3 = V(g.c[3]); k.c4 = V(g.c[4]); k.c5 = V(g.c[5]); k.c6 = V(g.c[6]);
     k.w = V(g.w);
+    k.wp = V(g.over * g.w);
     k.fast_div = (std::fabs(g.c[3]) >= 0x1p-400 && std::fabs(g.c[3]) <= 0x1p400) ? 1 : 0;
     k.nxc = g.nx / 2; k.nyc = g.ny / 2; k.nzc = g.nzc;
     const int64_t nc = int64_t(k.nxc) * k.nyc * k.nzc;
@@ -2221,6 +2225,7 @@ void launch_block(const PlaneGeom &g, const V *x_old, V *x_new, const V *b, cons
     a.nbx = k.nbx; a.nby = k.nby;
     a.c0 = V(g.c[0]); a.c1 = V(g.c[1]); a.c2 = V(g.c[2]); a.c3 = V(g.c[3]); a.c4 = V(g.c[4]); a.c5 = V(g.c[5]); a.c6 = V(g.c[6]);
     a.w = V(g.w);
+    a.wp = V(g.over * g.w);
     a.fast_div = (std::fabs(g.c[3]) >= 0x1p-400 && std::fabs(g.c[3]) <= 0x1p400) ? 1 : 0;
     a.nxc = g.nx / 2; a.nyc = g.ny / 2;
     a.cmap = c.map; a.bc = c.b; a.ec = c.e;
@@ -2243,6 +2248,7 @@ void launch_tile2d(const PlaneGeom &g, const V *x_old, V *x_new, const V *b, con
     a.nbx = g.ntx;
     a.c1 = V(g.c[1]); a.c2 = V(g.c[2]); a.c3 = V(g.c[3]); a.c4 = V(g.c[4]); a.c5 = V(g.c[5]);
     a.w = V(g.w);
+    a.wp = V(g.over * g.w);
     a.omega = V(g.omega);
     a.fast_div = (std::fabs(g.c[3]) >= 0x1p-400 && std::fabs(g.c[3]) <= 0x1p400) ? 1 : 0;
     a.nxc = g.nx / 2; a.nyc = g.ny / 2;

@@ -163,6 +163,7 @@ struct S27KArgs {
     int line_lo, line_hi, sq_lo, sq_hi;
     unsigned vec_bytes, coef_bytes;  // 8 na sizeof(V); bytes of ONE colour's coefficients
     V w;
+    V wp;                            // the prolongation's weight (S27Geom::over)
 };
 
 // the neighbour of a cell with parity bits (px, py, pz) at slot s: its colour and the shift of its aggregate
@@ -572,7 +573,7 @@ __global__ __launch_bounds__(256) void s27_prolong_kernel(const S27KArgs<V> a) {
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
 #pragma unroll
-        for (int r = 0; r < RG; ++r) x[c].v[r] = x[c].v[r] + madd(a.w, e.v[r], V(0));
+        for (int r = 0; r < RG; ++r) x[c].v[r] = x[c].v[r] + madd(a.wp, e.v[r], V(0));
         stv(xs, c * a.na + t.a0, x[c], t.mask);
     }
 }
@@ -632,6 +633,7 @@ S27KArgs<V> base_args(const Stencil27Plan<V> &P) {
     k.vec_bytes = unsigned(size_t(8) * size_t(g.na) * sizeof(V));
     k.coef_bytes = unsigned(size_t(g.ng) * 27 * 64 * size_t(g.rg) * sizeof(V));
     k.w = V(g.w);
+    k.wp = V(g.over * g.w);
     k.line_lo = int(P.live_lo); k.line_hi = int(P.live_hi);
     k.sq_lo = int(P.live_lo); k.sq_hi = int(P.live_hi);
     return k;

@@ -42,6 +42,7 @@ struct Var7Args {
     V *cb;
     const V *e;
     V w;
+    V wp;                         // the prolongation's weight (Var7Plan::over)
     double *partials;
     int ntx, nty, lz;
     int sweep, x_zero;
@@ -171,7 +172,7 @@ __global__ __launch_bounds__(NT) void var7_pass_kernel(const Var7Args<V> a) {
                 const int c = t + u * NIO;
                 if (c < PLANE) {
                     V val = v[u];
-                    if (!DOWN && k_on && f_on[u]) val = val + v7_madd(a.w, ec[f_ec[u]], V(0));   // :214 as the row kernels' y += R^T e
+                    if (!DOWN && k_on && f_on[u]) val = val + v7_madd(a.wp, ec[f_ec[u]], V(0));   // :214 as the row kernels' y += R^T e
                     dst[c] = val;
                 }
             }
@@ -741,6 +742,7 @@ void run(const Var7Plan<V> &P, Var7Args<V> a, bool down, hipStream_t s) {
     a.cP0 = P.cP[0].p; a.cP1 = P.cP[1].p; a.cP2 = P.cP[2].p;
     a.cM0 = P.cM[0].p; a.cM1 = P.cM[1].p; a.cM2 = P.cM[2].p;
     a.w = V(P.w);
+    a.wp = V(P.over * P.w);
     a.ntx = P.ntx; a.nty = P.nty; a.lz = P.lz;
     if (const char *e = experiment_env("OMG_VAR7_DBG")) a.dbg = atoi(e);      // (tools/var7_dbg.py; a build with -DOMG_EXPERIMENTS)
     if (P.tx == 64) launch_pass<V, 64, 16, 1024>(a, down, P.sym, P.n_wg, s);
