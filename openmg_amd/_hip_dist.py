@@ -33,10 +33,87 @@ def rccl_unique_id():
     return buf.raw
 
 
-class DistRank:
+class _Handle:
+    """Owns the C handle self._h: close() gives it to the library function `_destroy` names, once."""
+    _destroy = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(lib(), self._destroy)(self._h)
+            self._h = None
+
+
+class _Rank(_Handle):
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _Group(_Handle):
+    """A loopback group: its own handle goes first, then its ranks."""
+
+    def close(self):
+        super().close()
+        for r in self.ranks:
+            r.close()
+
+
+class _PeerMode:
+    """The p2p_* methods of a rank whose entry points are lib().<_prefix>p2p_* (include/openmg_hip.h).  _p2p_mapped: how
+    many `mapped` entries <_prefix>p2p_layout fills and takes no capacity for (None: one per rank, capacity passed)."""
+    p2p_mode = 0
+    _prefix, _p2p_mapped = None, None
+
+    def _p2p(self, name, *args):
+        check(getattr(lib(), self._prefix + "p2p_" + name)(self._h, *args))
+
+    def _p2p_handle_count(self):
+        n = ctypes.c_int(0)
+        self._p2p("handle_count", ctypes.byref(n))
+        return n.value
+
+    def p2p_handles(self):
+        """bytes: this rank's IPC handles, for the p2p_open of the ranks that store into it."""
+        n = self._p2p_handle_count()
+        buf = ctypes.create_string_buffer(64 * n)
+        self._p2p("handles", buf, n)
+        return bytes(buf.raw)
+
+    def p2p_open(self, peer_rank, handles):
+        buf = ctypes.create_string_buffer(bytes(handles), len(handles))
+        self._p2p("open", int(peer_rank), buf, len(handles) // 64)
+
+    def p2p_local(self, other):
+        self._p2p("local", other._h)
+
+    def p2p_enable(self, mode):
+        self._p2p("enable", int(mode))
+        self.p2p_mode = int(mode)
+
+    def p2p_status(self):
+        v = ctypes.c_uint(0)
+        self._p2p("status", ctypes.byref(v))
+        return v.value
+
+    def p2p_layout(self):
+        """Where the exported buffers (flags, for plane slabs the two gathered right-hand sides, then x / tmp / b per level)
+        sit in their allocations: dict(buffers=[dict(alloc, offset, alloc_bytes, base_delta)] in handle order, mapped=
+        [allocations opened of each rank (plane slabs) / of rank - 1, of rank + 1 (27-point slabs)]) —
+        include/openmg_hip.h omg_pdist_p2p_layout, omg_sdist_p2p_layout."""
+        n = self._p2p_handle_count()
+        out = (ctypes.c_int64 * (4 * n))()
+        mapped = (ctypes.c_int * (self._p2p_mapped or self.n_ranks))()
+        self._p2p("layout", out, n, mapped, *(() if self._p2p_mapped else (self.n_ranks,)))
+        return _layout(out, n, mapped)
+
+
+class DistRank(_Rank):
     """One rank's slab of a row-partitioned hierarchy (omg_dist).  `levels` is the list made
     by openmg_amd.dist: dicts with A, R (CSR, local column numbering), n_halo, keys, n_sets,
     peers, send_off, send_idx, recv_off."""
+    _destroy = "omg_dist_destroy"
 
     def __init__(self, rank, n_ranks, levels, coarse_global, coarse_counts, smoother="colour", omega=1.0,
                  tail=None, dtype="float64"):
@@ -91,18 +168,10 @@ class DistRank:
         del keep
 
     def close(self):
-        if getattr(self, "_h", None):
-            lib().omg_dist_destroy(self._h)
-            self._h = None
+        super().close()
         if getattr(self, "_tail", None) is not None:
             self._tail.close()
             self._tail = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def connect(self, unique_id):
         check(lib().omg_dist_connect(self._h, ctypes.c_char_p(unique_id)))
@@ -162,32 +231,26 @@ class DistRank:
         return dict(zip(Hierarchy.FORMAT_FIELDS, [int(v) for v in out]))
 
 
-class DistGroup:
+class DistGroup(_Group):
     """Loopback group: every rank of a decomposition inside this process, on one GPU."""
+    _destroy = "omg_dist_group_destroy"
 
     def __init__(self, ranks):
         self.ranks = list(ranks)
         arr = (ctypes.c_void_p * len(self.ranks))(*[r._h for r in self.ranks])
         g = ctypes.c_void_p()
         check(lib().omg_dist_group_create(len(self.ranks), arr, ctypes.byref(g)))
-        self._g = g
+        self._h = g
 
     def cycle(self, pre, post, want_norm=True):
         norm = ctypes.c_double(0.0)
-        check(lib().omg_dist_group_cycle(self._g, int(pre), int(post), ctypes.byref(norm) if want_norm else None))
+        check(lib().omg_dist_group_cycle(self._h, int(pre), int(post), ctypes.byref(norm) if want_norm else None))
         return norm.value if want_norm else None
 
     def cycles(self, pre, post, n_cycles):
         norms = (ctypes.c_double * max(int(n_cycles), 1))()
-        check(lib().omg_dist_group_cycles(self._g, int(pre), int(post), int(n_cycles), norms))
+        check(lib().omg_dist_group_cycles(self._h, int(pre), int(post), int(n_cycles), norms))
         return [float(norms[k]) for k in range(int(n_cycles))]
-
-    def close(self):
-        if getattr(self, "_g", None):
-            lib().omg_dist_group_destroy(self._g)
-            self._g = None
-        for r in self.ranks:
-            r.close()
 
 
 # ---- plane-pipelined slabs (omg_pdist_*) ------------------------------------------------------
@@ -211,10 +274,11 @@ def star_coefficients(A, shape):
     return [float(v) for v in vals]
 
 
-class PlaneDistRank:
+class PlaneDistRank(_PeerMode, _Rank):
     """One rank's slab of a constant-coefficient 7-point hierarchy run as plane-pipelined passes (omg_pdist).
     shape: the GLOBAL finest grid (planes, lines, cells); coefficients: seven per distributed level; tail: a
     _hip.Hierarchy over the levels below the slabs (kept alive here)."""
+    _destroy, _prefix = "omg_pdist_destroy", "omg_pdist_"        # (peer mode: include/openmg_hip.h omg_pdist_p2p_*)
 
     def __init__(self, rank, n_ranks, shape, coefficients, weight, tail):
         nz, ny, nx = (int(s) for s in shape)
@@ -294,58 +358,10 @@ class PlaneDistRank:
                                "results of this batch are not valid" % (self.rank, status))
         return out
 
-    # ---- peer mode (include/openmg_hip.h: omg_pdist_p2p_*) ----
-    p2p_mode = 0
 
-    def p2p_handles(self):
-        """bytes: this rank's IPC handles, for the other ranks' p2p_open."""
-        n = ctypes.c_int(0)
-        check(lib().omg_pdist_p2p_handle_count(self._h, ctypes.byref(n)))
-        buf = ctypes.create_string_buffer(64 * n.value)
-        check(lib().omg_pdist_p2p_handles(self._h, buf, n.value))
-        return bytes(buf.raw)
-
-    def p2p_open(self, peer_rank, handles):
-        buf = ctypes.create_string_buffer(bytes(handles), len(handles))
-        check(lib().omg_pdist_p2p_open(self._h, int(peer_rank), buf, len(handles) // 64))
-
-    def p2p_local(self, other):
-        check(lib().omg_pdist_p2p_local(self._h, other._h))
-
-    def p2p_enable(self, mode):
-        check(lib().omg_pdist_p2p_enable(self._h, int(mode)))
-        self.p2p_mode = int(mode)
-
-    def p2p_status(self):
-        v = ctypes.c_uint(0)
-        check(lib().omg_pdist_p2p_status(self._h, ctypes.byref(v)))
-        return v.value
-
-    def p2p_layout(self):
-        """Where the exported buffers (flags, the two gathered right-hand sides, x / tmp / b per level) sit in their
-        allocations: dict(buffers=[dict(alloc, offset, alloc_bytes, base_delta)] in handle order, mapped=[allocations
-        opened of each rank]) — include/openmg_hip.h omg_pdist_p2p_layout."""
-        n = ctypes.c_int(0)
-        check(lib().omg_pdist_p2p_handle_count(self._h, ctypes.byref(n)))
-        out = (ctypes.c_int64 * (4 * n.value))()
-        mapped = (ctypes.c_int * self.n_ranks)()
-        check(lib().omg_pdist_p2p_layout(self._h, out, n.value, mapped, self.n_ranks))
-        return _layout(out, n.value, mapped)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().omg_pdist_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class PlaneDistGroup:
+class PlaneDistGroup(_Group):
     """All ranks of a plane-slab decomposition in one process on one GPU (device copies in place of RCCL)."""
+    _destroy = "omg_pdist_group_destroy"
 
     def __init__(self, ranks, p2p=0):
         """p2p 1 / 2: the ranks store into each other's vectors (peer mode; 2: with wait launches) instead of copies."""
@@ -360,30 +376,24 @@ class PlaneDistGroup:
         arr = (ctypes.c_void_p * len(self.ranks))(*[r._h for r in self.ranks])
         g = ctypes.c_void_p()
         check(lib().omg_pdist_group_create(len(self.ranks), arr, ctypes.byref(g)))
-        self._g = g
+        self._h = g
 
     def cycles(self, n_cycles, pre=1, post=1):
         norms = (ctypes.c_double * max(int(n_cycles), 1))()
-        check(lib().omg_pdist_group_cycles_ex(self._g, int(pre), int(post), int(n_cycles), norms))
+        check(lib().omg_pdist_group_cycles_ex(self._h, int(pre), int(post), int(n_cycles), norms))
         for r in self.ranks:
             if r.p2p_status():
                 raise RuntimeError("rank %d: a bounded wait inside a pass gave up" % r.rank)
         return [float(norms[k]) for k in range(int(n_cycles))]
 
-    def close(self):
-        if getattr(self, "_g", None):
-            lib().omg_pdist_group_destroy(self._g)
-            self._g = None
-        for r in self.ranks:
-            r.close()
-
 
 # ---- 27-point slabs (omg_sdist_*) ----------------------------------------------------------------
-class Slab27Rank:
+class Slab27Rank(_PeerMode, _Rank):
     """One rank's slab of a 27-point hierarchy with per-row coefficients on the octant-layout kernels (omg_sdist).
     shape: the GLOBAL finest grid (planes, lines, cells); A_rows: this rank's rows of the finest operator with global
     columns (dist.stencil27_variable_rows); n_levels distributed levels; the Galerkin products are made on the device.
     After construction: coarse_rows() -> gather over the ranks -> a tail hierarchy -> set_tail()."""
+    _destroy, _prefix, _p2p_mapped = "omg_sdist_destroy", "omg_sdist_", 2     # (peer mode for the halo exchanges: omg_sdist_p2p_*)
 
     def __init__(self, rank, n_ranks, shape, A_rows, n_levels, weight=0.125, dtype="float64"):
         nz, ny, nx = (int(s) for s in shape)
@@ -448,58 +458,10 @@ class Slab27Rank:
                                "complete); the results of this batch are not valid" % self.rank)
         return out
 
-    # ---- peer mode for the halo exchanges (include/openmg_hip.h: omg_sdist_p2p_*) ----
-    p2p_mode = 0
 
-    def p2p_handles(self):
-        """bytes: this rank's IPC handles, for its neighbours' p2p_open."""
-        n = ctypes.c_int(0)
-        check(lib().omg_sdist_p2p_handle_count(self._h, ctypes.byref(n)))
-        buf = ctypes.create_string_buffer(64 * n.value)
-        check(lib().omg_sdist_p2p_handles(self._h, buf, n.value))
-        return bytes(buf.raw)
-
-    def p2p_open(self, peer_rank, handles):
-        buf = ctypes.create_string_buffer(bytes(handles), len(handles))
-        check(lib().omg_sdist_p2p_open(self._h, int(peer_rank), buf, len(handles) // 64))
-
-    def p2p_local(self, other):
-        check(lib().omg_sdist_p2p_local(self._h, other._h))
-
-    def p2p_enable(self, mode):
-        check(lib().omg_sdist_p2p_enable(self._h, int(mode)))
-        self.p2p_mode = int(mode)
-
-    def p2p_status(self):
-        v = ctypes.c_uint(0)
-        check(lib().omg_sdist_p2p_status(self._h, ctypes.byref(v)))
-        return v.value
-
-    def p2p_layout(self):
-        """Where the exported buffers (flags, then x / tmp / b per level) sit in their allocations: dict(buffers=
-        [dict(alloc, offset, alloc_bytes, base_delta)] in handle order, mapped=[allocations opened of rank - 1, of
-        rank + 1]) — include/openmg_hip.h omg_sdist_p2p_layout."""
-        n = ctypes.c_int(0)
-        check(lib().omg_sdist_p2p_handle_count(self._h, ctypes.byref(n)))
-        out = (ctypes.c_int64 * (4 * n.value))()
-        mapped = (ctypes.c_int * 2)()
-        check(lib().omg_sdist_p2p_layout(self._h, out, n.value, mapped))
-        return _layout(out, n.value, mapped)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().omg_sdist_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Slab27Group:
+class Slab27Group(_Group):
     """All ranks of a 27-point slab decomposition in one process on one GPU (device copies in place of RCCL)."""
+    _destroy = "omg_sdist_group_destroy"
 
     def __init__(self, ranks, p2p=0):
         """p2p 1: the ranks store into each other's ghost planes (peer mode) instead of the copies."""
@@ -514,19 +476,12 @@ class Slab27Group:
         arr = (ctypes.c_void_p * len(self.ranks))(*[r._h for r in self.ranks])
         g = ctypes.c_void_p()
         check(lib().omg_sdist_group_create(len(self.ranks), arr, ctypes.byref(g)))
-        self._g = g
+        self._h = g
 
     def cycles(self, pre, post, n_cycles):
         norms = (ctypes.c_double * max(int(n_cycles), 1))()
-        check(lib().omg_sdist_group_cycles(self._g, int(pre), int(post), int(n_cycles), norms))
+        check(lib().omg_sdist_group_cycles(self._h, int(pre), int(post), int(n_cycles), norms))
         for r in self.ranks:
             if r.p2p_mode and r.p2p_status():
                 raise RuntimeError("rank %d: a bounded wait for a neighbour's flag gave up" % r.rank)
         return [float(norms[k]) for k in range(int(n_cycles))]
-
-    def close(self):
-        if getattr(self, "_g", None):
-            lib().omg_sdist_group_destroy(self._g)
-            self._g = None
-        for r in self.ranks:
-            r.close()

@@ -2,12 +2,17 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <array>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <new>
 #include <stdexcept>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -57,6 +62,45 @@ void set_last_error(const std::string &m);
     } while (0)
 
 void require_device();   // throws OMG_ERR_NO_DEVICE when no GPU is visible
+
+// ---- the C ABI shell ------------------------------------------------------------------
+// Every entry point runs its body in guarded(): exceptions become OMG_ERR_* codes and the last-error text.
+template <typename F>
+int guarded(F &&f) {
+    try {
+        f();
+        return OMG_OK;
+    } catch (const Error &e) {
+        set_last_error(e.what());
+        return e.code;
+    } catch (const std::bad_alloc &) {
+        set_last_error("host allocation failed");
+        return OMG_ERR_ALLOC;
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        return OMG_ERR_INVALID;
+    }
+}
+// A handle struct holds its object as `d` (double) or `f` (float), two unique_ptrs of which one is set.  typed<V>(h) is
+// the V instantiation (null when the handle holds the other one; const for a const handle), with() runs f on whichever
+// the handle holds, value_of<decltype(p)> is the V of the pointer f receives.
+template <typename V, typename H>
+auto typed(H *h) {
+    auto *const p = [&] {
+        if constexpr (std::is_same<V, double>::value) return h->d.get();
+        else return h->f.get();
+    }();
+    using T = typename std::remove_pointer<decltype(p)>::type;
+    return static_cast<typename std::conditional<std::is_const<H>::value, const T, T>::type *>(p);
+}
+template <typename H, typename F>
+void with(H *h, const char *null_message, F &&f) {
+    OMG_REQUIRE(h != nullptr && (h->d || h->f), null_message);
+    if (h->f) f(typed<float>(h));
+    else f(typed<double>(h));
+}
+template <typename HP>
+using value_of = typename std::remove_cv<typename std::remove_pointer<HP>::type>::type::value_type;
 
 // OMG_SETUP_TIMING=1: phases of the hierarchy setup, with their wall time, on stderr
 struct SetupTimer {
@@ -176,7 +220,8 @@ struct DevBuf {
 // hipIpcGetMemHandle, export_rebuild() what the opener makes of the mapping with ITS OWN buffer's shift (the vectors sit
 // in their allocations alike on every rank), export_guard() asks the runtime which allocation really contains the
 // buffer and refuses an export whose computed base is not that allocation's — on the host, before any kernel stores
-// through a pointer rebuilt from it.
+// through a pointer rebuilt from it.  export_handles() writes a rank's IPC handles (every buffer guarded first),
+// open_handles() maps a neighbour's, each allocation once, and returns the neighbour's buffers.
 struct ExportBuf {
     void *p = nullptr;
     size_t shift = 0, bytes = 0;
@@ -225,6 +270,45 @@ inline void export_layout(const std::vector<ExportBuf> &bufs, int64_t *out4) {
         out4[4 * i + 2] = int64_t(rs);
         out4[4 * i + 3] = int64_t(base - rb);
     }
+}
+// the 64-byte IPC handles of bufs, in order, into handles64 (room for `capacity` of them)
+inline void export_handles(const std::vector<ExportBuf> &bufs, void *handles64, int capacity) {
+    static_assert(sizeof(hipIpcMemHandle_t) == 64, "IPC handle size");
+    OMG_REQUIRE(capacity >= int(bufs.size()), "handle buffer too small");
+    for (size_t i = 0; i < bufs.size(); ++i) export_guard(bufs[i], int(i));          // (all of them, before the first handle)
+    for (size_t i = 0; i < bufs.size(); ++i) {
+        hipIpcMemHandle_t h;
+        OMG_HIP(hipIpcGetMemHandle(&h, export_base(bufs[i])));
+        std::memcpy(static_cast<char *>(handles64) + 64 * i, &h, 64);
+    }
+}
+// A neighbour's `count` handles, opened: its buffers in handle order, rebuilt with the shifts of `own` (the neighbour's
+// vectors sit in their allocations as mine do); every new mapping is appended to `mapped` (the caller closes them).
+inline std::vector<void *> open_handles(const void *handles64, int count, const std::vector<ExportBuf> &own, std::vector<void *> &mapped) {
+    std::vector<void *> bufs;
+    // (vectors that share an allocation share a handle: it is opened once)
+    std::vector<std::pair<std::array<char, 64>, void *>> opened;
+    for (int i = 0; i < count; ++i) {
+        std::array<char, 64> key;
+        std::memcpy(key.data(), static_cast<const char *>(handles64) + 64 * i, 64);
+        void *base = nullptr;
+        for (const auto &o : opened)
+            if (o.first == key) base = o.second;
+        if (!base) {
+            hipIpcMemHandle_t h;
+            std::memcpy(&h, key.data(), 64);
+            OMG_HIP(hipIpcOpenMemHandle(&base, h, hipIpcMemLazyEnablePeerAccess));
+            mapped.push_back(base);
+            opened.emplace_back(key, base);
+        }
+        bufs.push_back(export_rebuild(base, own[size_t(i)]));
+    }
+    return bufs;
+}
+// OMG_P2P_SPIN: how many polls a wait for a neighbour's flag makes before it gives up (peer_wait.h); at least 1
+inline uint32_t p2p_spin_env(uint32_t otherwise) {
+    const char *e = getenv("OMG_P2P_SPIN");
+    return e ? uint32_t(std::max(1L, atol(e))) : otherwise;
 }
 
 // How the k-th candidate of a placement search (hierarchy.hip place_finest_pool, Stencil27Plan::place_tiles, ...) is

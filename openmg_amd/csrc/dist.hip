@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "peer_wait.h"
 #include "rccl_dyn.h"
 
 namespace omg {
@@ -747,33 +748,9 @@ struct Runner {
     }
 };
 
-template <typename F>
-int guarded(F &&f) {
-    try {
-        f();
-        return OMG_OK;
-    } catch (const Error &e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::bad_alloc &) {
-        set_last_error("host allocation failed");
-        return OMG_ERR_ALLOC;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return OMG_ERR_INVALID;
-    }
-}
-
 // Runs f(Dist<V> *) on whichever instantiation the handle holds.
 template <typename F>
-void with(omg_dist *d, F &&f) {
-    OMG_REQUIRE(d != nullptr && (d->d || d->f), "null handle");
-    if (d->f) f(d->f.get());
-    else f(d->d.get());
-}
-
-template <typename HP>
-using value_of = typename std::remove_pointer<HP>::type::value_type;
+void with(omg_dist *d, F &&f) { omg::with(d, "null handle", std::forward<F>(f)); }
 
 
 // ============================================================================================================
@@ -918,17 +895,9 @@ __global__ void pd_sqrt_batch_kernel(double *v, int n) {
 }
 
 // peer mode's own launches (the passes themselves store and wait in plane.hip)
-__device__ __forceinline__ void pd_spin(const uint32_t *flag, uint32_t seq, uint32_t *status, uint32_t spin) {
-    for (uint32_t n = 0;; ++n) {
-        if (int32_t(__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) - seq) >= 0) break;
-        if (n >= spin) { __hip_atomic_fetch_or(status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
-        __builtin_amdgcn_s_sleep(16);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-}
 // thread i waits for flags[first + i * stride] (i < count)
 __global__ void pd_wait_kernel(const uint32_t *flags, int first, int stride, int count, uint32_t seq, uint32_t *status, uint32_t spin) {
-    if (int(threadIdx.x) < count) pd_spin(flags + first + int(threadIdx.x) * stride, seq, status, spin);
+    if (int(threadIdx.x) < count) peer_wait(flags + first + int(threadIdx.x) * stride, seq, status, spin);
 }
 __global__ void pd_signal_kernel(uint32_t *f0, uint32_t *f1, uint32_t seq) {
     if (f0) __hip_atomic_store(f0, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -1543,7 +1512,7 @@ std::unique_ptr<PlaneDist> pd_create(int rank, int n_ranks, int nx, int ny, int 
     for (PDLevel &L : d->lv) L.plan.status = d->flags.p + PD_STATUS;       // (bit 1: a wave gave up waiting for its neighbour wave)
     d->full_b2.alloc(size_t(cplane * lz * n_ranks));
     d->peers.resize(size_t(n_ranks));
-    if (const char *e = getenv("OMG_P2P_SPIN")) d->spin = uint32_t(std::max(1L, atol(e)));
+    d->spin = p2p_spin_env(d->spin);
     OMG_HIP(hipHostMalloc(reinterpret_cast<void **>(&d->progress), sizeof(uint32_t), hipHostMallocDefault));
     *d->progress = 0;
     d->nat.alloc(size_t(int64_t(nx) * ny * (nz_global / n_ranks)));
@@ -1906,10 +1875,7 @@ int omg_dist_group_cycles(omg_dist_group *g, int pre, int post, int n_cycles, do
         with(g->ranks[0], [&](auto *first) {
             using V = value_of<decltype(first)>;
             Runner<V> r;
-            for (omg_dist *d : g->ranks) {
-                if constexpr (std::is_same<V, double>::value) r.rs.push_back(d->d.get());
-                else r.rs.push_back(d->f.get());
-            }
+            for (omg_dist *d : g->ranks) r.rs.push_back(typed<V>(d));
             r.rccl = false;
             r.run_batch(pre, post, n_cycles, norms);
         });
@@ -1922,10 +1888,7 @@ int omg_dist_group_cycle(omg_dist_group *g, int pre, int post, double *norm) {
         with(g->ranks[0], [&](auto *first) {
             using V = value_of<decltype(first)>;
             Runner<V> r;
-            for (omg_dist *d : g->ranks) {
-                if constexpr (std::is_same<V, double>::value) r.rs.push_back(d->d.get());
-                else r.rs.push_back(d->f.get());
-            }
+            for (omg_dist *d : g->ranks) r.rs.push_back(typed<V>(d));
             r.rccl = false;
             r.run(pre, post, norm);
         });
@@ -2034,16 +1997,9 @@ int omg_pdist_p2p_handle_count(omg_pdist *d, int *count) {
 int omg_pdist_p2p_handles(omg_pdist *d, void *handles64, int capacity) {
     return guarded([&] {
         OMG_REQUIRE(d && d->d && handles64, "null argument");
-        static_assert(sizeof(hipIpcMemHandle_t) == 64, "IPC handle size");
         const std::vector<ExportBuf> bufs = pd_own_buffers(d->d.get());
-        OMG_REQUIRE(capacity >= int(bufs.size()), "handle buffer too small");
         OMG_HIP(hipStreamSynchronize(d->d->stream));
-        for (size_t i = 0; i < bufs.size(); ++i) export_guard(bufs[i], int(i));          // (all of them, before the first handle)
-        for (size_t i = 0; i < bufs.size(); ++i) {
-            hipIpcMemHandle_t h;
-            OMG_HIP(hipIpcGetMemHandle(&h, export_base(bufs[i])));
-            std::memcpy(static_cast<char *>(handles64) + 64 * i, &h, 64);
-        }
+        export_handles(bufs, handles64, capacity);
     });
 }
 
@@ -2070,26 +2026,7 @@ int omg_pdist_p2p_open(omg_pdist *d, int peer_rank, const void *handles64, int c
         OMG_REQUIRE(count == 3 + 3 * int(dd->lv.size()), "handle count does not match the levels");
         PDPeer &P = dd->peers[size_t(peer_rank)];
         OMG_REQUIRE(P.mapped.empty(), "peer already opened");
-        std::vector<void *> bufs;
-        const std::vector<ExportBuf> own = pd_own_buffers(dd);          // (the peer's vectors sit in their allocations as mine do)
-        // (vectors that share an allocation share a handle: it is opened once)
-        std::vector<std::pair<std::array<char, 64>, void *>> opened;
-        for (int i = 0; i < count; ++i) {
-            std::array<char, 64> key;
-            std::memcpy(key.data(), static_cast<const char *>(handles64) + 64 * i, 64);
-            void *base = nullptr;
-            for (const auto &o : opened)
-                if (o.first == key) base = o.second;
-            if (!base) {
-                hipIpcMemHandle_t h;
-                std::memcpy(&h, key.data(), 64);
-                OMG_HIP(hipIpcOpenMemHandle(&base, h, hipIpcMemLazyEnablePeerAccess));
-                P.mapped.push_back(base);
-                opened.emplace_back(key, base);
-            }
-            bufs.push_back(export_rebuild(base, own[size_t(i)]));
-        }
-        pd_attach(dd, peer_rank, bufs);
+        pd_attach(dd, peer_rank, open_handles(handles64, count, pd_own_buffers(dd), P.mapped));
     });
 }
 

@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "peer_wait.h"
 #include "rccl_dyn.h"
 
 namespace omg {
@@ -166,16 +167,6 @@ __global__ void sqrt_arrays_kernel(const double *v, double *out, int n) {
 }
 
 // ---- peer-store exchange ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void sp_wait(const uint32_t *flag, uint32_t seq, uint32_t *status, uint32_t spin) {
-    if (!flag) return;
-    for (uint32_t n = 0;; ++n) {
-        const uint32_t v = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if (int32_t(v - seq) >= 0) break;
-        if (n >= spin) { __hip_atomic_fetch_or(status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
-        __builtin_amdgcn_s_sleep(16);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-}
 // "overwrite my ghost planes": everything this rank's stream has done before (all readers of the ghost values of the
 // previous exchange) is complete when this one-thread launch runs
 __global__ void sp_ack_kernel(uint32_t *lo, uint32_t *hi, uint32_t seq) {
@@ -202,7 +193,7 @@ struct SpPush {
 template <typename V>
 __global__ __launch_bounds__(256) void sp_push_kernel(const SpPush<V> a) {
     const int run = int(blockIdx.y);
-    if (threadIdx.x == 0) sp_wait(a.ack[a.dir[run]], a.seq, a.status, a.spin);
+    if (threadIdx.x == 0) peer_wait(a.ack[a.dir[run]], a.seq, a.status, a.spin);
     __syncthreads();
     const V *const src = a.src[run];
     V *const dst = a.dst[run];
@@ -221,8 +212,8 @@ __global__ __launch_bounds__(256) void sp_push_kernel(const SpPush<V> a) {
     }
 }
 __global__ void sp_wait_kernel(const uint32_t *lo, const uint32_t *hi, uint32_t seq, uint32_t *status, uint32_t spin) {
-    sp_wait(lo, seq, status, spin);
-    sp_wait(hi, seq, status, spin);
+    peer_wait(lo, seq, status, spin);
+    peer_wait(hi, seq, status, spin);
 }
 
 template <typename V>
@@ -659,23 +650,6 @@ struct SExchange {
     }
 };
 
-template <typename F>
-int guarded(F &&f) {
-    try {
-        f();
-        return OMG_OK;
-    } catch (const Error &e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::bad_alloc &) {
-        set_last_error("host allocation failed");
-        return OMG_ERR_ALLOC;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return OMG_ERR_INVALID;
-    }
-}
-
 }  // namespace
 }  // namespace omg
 
@@ -691,13 +665,7 @@ struct omg_sdist_group {
 
 namespace {
 template <typename F>
-void with(omg_sdist *d, F &&f) {
-    OMG_REQUIRE(d != nullptr && (d->d || d->f), "null handle");
-    if (d->f) f(d->f.get());
-    else f(d->d.get());
-}
-template <typename HP>
-using value_of = typename std::remove_pointer<HP>::type::value_type;
+void with(omg_sdist *d, F &&f) { omg::with(d, "null handle", std::forward<F>(f)); }
 }  // namespace
 
 namespace {
@@ -901,14 +869,8 @@ int omg_sdist_p2p_handles(omg_sdist *d, void *handles64, int capacity) {
         OMG_REQUIRE(handles64, "null argument");
         with(d, [&](auto *dd) {
             const std::vector<ExportBuf> bufs = sd_own_buffers(dd);
-            OMG_REQUIRE(capacity >= int(bufs.size()), "handle buffer too small");
             OMG_HIP(hipStreamSynchronize(dd->stream));
-            for (size_t i = 0; i < bufs.size(); ++i) export_guard(bufs[i], int(i));      // (all of them, before the first handle)
-            for (size_t i = 0; i < bufs.size(); ++i) {
-                hipIpcMemHandle_t h;
-                OMG_HIP(hipIpcGetMemHandle(&h, export_base(bufs[i])));
-                std::memcpy(static_cast<char *>(handles64) + 64 * i, &h, 64);
-            }
+            export_handles(bufs, handles64, capacity);
         });
     });
 }
@@ -921,26 +883,7 @@ int omg_sdist_p2p_open(omg_sdist *d, int peer_rank, const void *handles64, int c
             OMG_REQUIRE(peer_rank >= 0 && peer_rank < dd->n_ranks && count == 1 + 3 * int(dd->lv.size()), "bad peer rank / handle count");
             auto &P = dd->peer[peer_rank == dd->rank - 1 ? 0 : 1];
             OMG_REQUIRE(P.mapped.empty(), "peer already opened");
-            std::vector<void *> bufs;
-            const std::vector<ExportBuf> own = sd_own_buffers(dd);      // (the neighbour's vectors sit in their allocations as mine do)
-            // (vectors that share an allocation share a handle: it is opened once)
-            std::vector<std::pair<std::array<char, 64>, void *>> opened;
-            for (int i = 0; i < count; ++i) {
-                std::array<char, 64> key;
-                std::memcpy(key.data(), static_cast<const char *>(handles64) + 64 * i, 64);
-                void *base = nullptr;
-                for (const auto &o : opened)
-                    if (o.first == key) base = o.second;
-                if (!base) {
-                    hipIpcMemHandle_t h;
-                    std::memcpy(&h, key.data(), 64);
-                    OMG_HIP(hipIpcOpenMemHandle(&base, h, hipIpcMemLazyEnablePeerAccess));
-                    P.mapped.push_back(base);
-                    opened.emplace_back(key, base);
-                }
-                bufs.push_back(export_rebuild(base, own[size_t(i)]));
-            }
-            sd_attach(dd, peer_rank, bufs);
+            sd_attach(dd, peer_rank, open_handles(handles64, count, sd_own_buffers(dd), P.mapped));
         });
     });
 }
@@ -966,9 +909,7 @@ int omg_sdist_p2p_local(omg_sdist *d, omg_sdist *other) {
         OMG_REQUIRE(d && other && bool(d->f) == bool(other->f), "null argument / mixed dtypes");
         with(d, [&](auto *dd) {
             using V = value_of<decltype(dd)>;
-            SDist<V> *oo;
-            if constexpr (std::is_same<V, double>::value) oo = other->d.get();
-            else oo = other->f.get();
+            SDist<V> *oo = typed<V>(other);
             OMG_REQUIRE(oo && oo->n_ranks == dd->n_ranks && oo->lv.size() == dd->lv.size(), "not another rank of the same decomposition");
             std::vector<void *> bufs;
             for (const ExportBuf &e : sd_own_buffers(oo)) bufs.push_back(e.p);
@@ -985,7 +926,7 @@ int omg_sdist_p2p_enable(omg_sdist *d, int mode) {
                 (void)sd_own_buffers(dd);                       // (my own flag words exist)
                 if (dd->rank > 0) OMG_REQUIRE(dd->peer[0].flags, "peer mode: rank - 1's buffers have not been opened");
                 if (dd->rank + 1 < dd->n_ranks) OMG_REQUIRE(dd->peer[1].flags, "peer mode: rank + 1's buffers have not been opened");
-                if (const char *e = getenv("OMG_P2P_SPIN")) dd->p2p_spin = uint32_t(std::max(1l, atol(e)));
+                dd->p2p_spin = p2p_spin_env(dd->p2p_spin);
             }
             OMG_HIP(hipStreamSynchronize(dd->stream));
             dd->p2p = mode;
@@ -1025,9 +966,7 @@ int omg_sdist_group_create(int n, omg_sdist **ranks, omg_sdist_group **out) {
             SExchange<V> ex;
             ex.loopback = true;
             for (int r = 0; r < n; ++r) {
-                SDist<V> *dd;
-                if constexpr (std::is_same<V, double>::value) dd = g->ranks[size_t(r)]->d.get();
-                else dd = g->ranks[size_t(r)]->f.get();
+                SDist<V> *dd = typed<V>(g->ranks[size_t(r)]);
                 OMG_REQUIRE(dd->rank == r && dd->n_ranks == n && dd->lv.size() == first->lv.size(), "ranks must be 0 .. n-1 of an n-rank decomposition");
                 OMG_HIP(hipStreamSynchronize(dd->stream));
                 dd->stream = first->own;
@@ -1051,10 +990,7 @@ int omg_sdist_group_cycles(omg_sdist_group *g, int pre, int post, int n_cycles, 
             using V = value_of<decltype(first)>;
             SExchange<V> ex;
             ex.loopback = true;
-            for (omg_sdist *r : g->ranks) {
-                if constexpr (std::is_same<V, double>::value) ex.ranks.push_back(r->d.get());
-                else ex.ranks.push_back(r->f.get());
-            }
+            for (omg_sdist *r : g->ranks) ex.ranks.push_back(typed<V>(r));
             ex.run(pre, post, n_cycles, norms);
         });
     });

@@ -1866,40 +1866,9 @@ struct OneShot {
     ~OneShot() { if (s) (void)hipStreamDestroy(s); }
 };
 
-template <typename F>
-int guarded(F &&f) {
-    try {
-        f();
-        return OMG_OK;
-    } catch (const Error &e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::bad_alloc &) {
-        set_last_error("host allocation failed");
-        return OMG_ERR_ALLOC;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return OMG_ERR_INVALID;
-    }
-}
-
 // Runs f(Hier<V> *) on whichever instantiation the handle holds.
-template <typename F>
-void with(omg_hierarchy *h, F &&f) {
-    OMG_REQUIRE(h != nullptr && (h->d || h->f), "null hierarchy");
-    if (h->f) f(h->f.get());
-    else f(h->d.get());
-}
-
-template <typename F>
-void with(const omg_hierarchy *h, F &&f) {
-    OMG_REQUIRE(h != nullptr && (h->d || h->f), "null hierarchy");
-    if (h->f) f(static_cast<const Hier<float> *>(h->f.get()));
-    else f(static_cast<const Hier<double> *>(h->d.get()));
-}
-
-template <typename HP>
-using value_of = typename std::remove_cv<typename std::remove_pointer<HP>::type>::type::value_type;
+template <typename H, typename F>
+void with(H *h, F &&f) { omg::with(h, "null hierarchy", std::forward<F>(f)); }
 
 // One level-0 V-cycle from a zero iterate: the right-hand side in L.b, the result left in L.xp (openmg/__init__.py:191-192;
 // omg_hierarchy_cycle_dev, and the preconditioner of omg_resident_pcg)

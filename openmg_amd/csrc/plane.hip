@@ -40,6 +40,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "peer_wait.h"
 
 // -DOMG_PLANE_STAMPS: in-kernel cycle stamps per stage (tools/plane_stamps.py); -DOMG_PLANE_DBGARGS: only the switches
 // of OMG_PLANE_DBG that leave out part of a pass's memory traffic (tools/plane_dbg_times.py; wrong results, timing only)
@@ -287,22 +288,6 @@ __device__ __forceinline__ Inline<V> in_line(int rule, const P2<V> &O, V nb) {
     return r;
 }
 
-// Wait until a flag another GPU (or another process's kernel) stores into this GPU's memory holds at least seq
-// (wrapping compare): system-scope loads, a bounded number of them — a wait that gives up sets bit 0 of *status
-// and lets the caller run on (its results are then wrong and the host says so) instead of hanging the device.
-__device__ __forceinline__ void peer_wait(const uint32_t *flag, uint32_t seq, uint32_t *status, uint32_t spin) {
-    if (!flag) return;
-    for (uint32_t n = 0;; ++n) {
-        const uint32_t v = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if (int32_t(v - seq) >= 0) break;
-        if (n >= spin) {
-            if (status) __hip_atomic_fetch_or(status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            break;
-        }
-        __builtin_amdgcn_s_sleep(16);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");      // what the flag's writer stored before it: not from this CU's L1 / this XCD's L2
-}
 // the pass's workgroups are counted at its end; the last one tells the neighbours
 // (The stores into the neighbours are write-through — PEER_AUX — so "out" is their acknowledgement: a wait for the
 // wave's outstanding stores, NOT a release fence at system scope, which would also write this XCD's whole L2 back —

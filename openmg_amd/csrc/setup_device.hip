@@ -638,23 +638,6 @@ void galerkin_chain_device(const omg_csr &A0, int dim, const int64_t *shape, int
 
 namespace {
 
-template <typename F>
-int guarded(F &&f) {
-    try {
-        f();
-        return OMG_OK;
-    } catch (const Error &e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::bad_alloc &) {
-        set_last_error("host allocation failed");
-        return OMG_ERR_ALLOC;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return OMG_ERR_INVALID;
-    }
-}
-
 struct Stream {
     hipStream_t s = nullptr;
     Stream() { require_device(); OMG_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
