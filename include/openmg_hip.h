@@ -153,7 +153,13 @@ int omg_hierarchy_level_fused(const omg_hierarchy *h, int level, int *fused);
 #define OMG_LEVEL_STENCIL27        128 /* 27-point grid stencil with per-row coefficients under the 2x2x2 aggregation, 8-colour
                                         * Gauss-Seidel (BASELINE configs[4]): the cycle over this level runs the octant-layout
                                         * kernels of stencil27.hip — four launches per sweep, the coefficients streamed once each */
+#define OMG_LEVEL_TAIL_FUSED       1024 /* a V(1,1) cycle of the hierarchy's shape runs this level's up pass inside the fused
+                                        * tail launch: the 16 x 16 x 16 sine solve + the up passes of the block levels above it
+                                        * (OMG_TAIL_FUSE=0|1|2 when the hierarchy is made; plane.hip tail_up_kernel) */
 int omg_hierarchy_level_flags(const omg_hierarchy *h, int level, int *flags);
+/* The fused tail launch (OMG_LEVEL_TAIL_FUSED) as it actually ran: out[0] = launches of it put on the hierarchy's stream
+ * since the hierarchy was made, by any entry; out[1] = how many of those came from replaying a captured graph.         */
+int omg_hierarchy_tail_info(const omg_hierarchy *h, int64_t *out2);
 /* Switch the plane-pipelined passes of a hierarchy off (enable = 0) or back on: the cycle then runs set
  * by set (same iterate, bit for bit; the norm's partial sums are associated differently).  A/B only.
  * OMG_PLANE=0 in the environment at creation never builds them.                                      */

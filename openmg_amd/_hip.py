@@ -68,6 +68,7 @@ SIGNATURES = {
     "omg_hierarchy_set_info": (_I, [_P, _I, _I, _I64P, _I64P]),
     "omg_hierarchy_level_fused": (_I, [_P, _I, _IP]),
     "omg_hierarchy_level_flags": (_I, [_P, _I, _IP]),
+    "omg_hierarchy_tail_info": (_I, [_P, _I64P]),
     "omg_hierarchy_use_plane": (_I, [_P, _I]),
     "omg_hierarchy_set_cycle": (_I, [_P, _I, _D]),
     "omg_hierarchy_get_cycle": (_I, [_P, _IP, _DP]),
@@ -522,12 +523,19 @@ class Hierarchy:
 
     def level_flags(self, level):
         """dict(fused_last_set=bool, scatter_prolong=bool, union_walk=bool, march=bool, plane=bool, stencil27=bool, var7=bool,
-        march_scan=bool) of a smoothed level."""
+        march_scan=bool, tail_fused=bool) of a smoothed level.  tail_fused: a V(1,1) cycle of the hierarchy's shape runs this
+        level's up pass inside the fused tail launch (OMG_TAIL_FUSE)."""
         f = ctypes.c_int(0)
         check(lib().omg_hierarchy_level_flags(self._h, int(level), ctypes.byref(f)))
         return {"fused_last_set": bool(f.value & 1), "scatter_prolong": bool(f.value & 2), "union_walk": bool(f.value & 16),
                 "march": bool(f.value & 32), "plane": bool(f.value & 64), "stencil27": bool(f.value & 128), "var7": bool(f.value & 256),
-                "march_scan": bool(f.value & 512)}
+                "march_scan": bool(f.value & 512), "tail_fused": bool(f.value & 1024)}
+
+    def tail_info(self):
+        """(fused tail launches put on the stream so far, how many of them by replaying a graph): omg_hierarchy_tail_info"""
+        out = (ctypes.c_int64 * 2)()
+        check(lib().omg_hierarchy_tail_info(self._h, out))
+        return int(out[0]), int(out[1])
 
     def use_plane(self, enable=True):
         """Plane-pipelined passes on / off (omg_hierarchy_use_plane; same iterate either way)."""

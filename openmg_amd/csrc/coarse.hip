@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "sine_cube16.h"
 
 namespace omg {
 namespace {
@@ -208,7 +209,6 @@ constexpr int SINE_THREADS = 1024;
 // matrix cores earn their keep: v_mfma_f64_16x16x4 (A: lane 16 k + i holds S[i][k]; B: lane 16 k + j holds in[k][line j];
 // D: register r of lane l holds row 4 r + l / 16 of column l % 16).  A wave takes 16 lines at a time, all of their outputs, so a
 // pass works in place; one workgroup barrier per pass.  E (16 or 32) >= every extent: the tables' row stride.
-typedef double v4d __attribute__((ext_vector_type(4)));
 template <typename V, int E>
 __global__ __launch_bounds__(SINE_THREADS) void sine_solve_kernel(const V *__restrict__ b, V *__restrict__ x, int nx, int ny, int nz,
                                                                  const double *__restrict__ tables, const double *__restrict__ lambda) {
@@ -300,71 +300,13 @@ __global__ __launch_bounds__(SINE_THREADS) void sine_solve_kernel(const V *__res
 // v_mfma_f64_16x16x4 — register r of lane l: row 4 r + l / 16, column l % 16 — IS the B layout of k-step r).
 // Order of the six transforms: x y z | z x y (the general kernel: x y z | x y z) — the same sums, associated as before
 // within each transform; 15.5 -> see DESIGN.md section 5e.
-// Lanes of ONE wave exchange values through LDS: the stores of all lanes must be complete and visible before any lane's
-// loads of the transposed addresses (nothing kept the compiler from reordering the may-alias accesses).
-__device__ __forceinline__ void wave_lds_exchange() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
+// (the body: sine_cube16.h, shared with the fused tail of the V-cycle, plane.hip tail_up_kernel)
 template <typename V>
 __global__ __launch_bounds__(SINE_THREADS) void sine_cube16_kernel(const V *__restrict__ b, V *__restrict__ x, const double *__restrict__ tables,
                                                                    const double *__restrict__ lambda) {
-    constexpr int N = 16, PX = N + 1;
-    __shared__ double buf[N * N * PX];                 // (i, j, k) at (k N + j) PX + i
-    const int lane = int(threadIdx.x) & 63, w = int(threadIdx.x) >> 6;
-    const int c = lane & 15, k4 = lane >> 4;
-    // A operands: lane 16 k + i holds S[i][k]; k-step ks: k = 4 ks + k4
-    double sx[4], sy[4], sz[4], lam[4], rhs[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-        sx[ks] = tables[(0 * N + c) * N + 4 * ks + k4];
-        sy[ks] = tables[(1 * N + c) * N + 4 * ks + k4];
-        sz[ks] = tables[(2 * N + c) * N + 4 * ks + k4];
-        rhs[ks] = double(b[(w * N + c) * N + 4 * ks + k4]);                 // line (k = w, j = c), element i = 4 ks + k4
-        lam[ks] = lambda[((4 * ks + k4) * N + w) * N + c];                  // element (i = c, j = w, k = 4 ks + k4)
-    }
-    auto transform = [&](const double (&S)[4], const double (&in)[4]) -> v4d {
-        v4d acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(S[ks], in[ks], acc, 0, 0, 0);
-        return acc;
-    };
-    double in[4];
-    // ---- forward along x and y, plane k = w -------------------------------------------------------------------
-    v4d acc = transform(sx, rhs);                      // rows i' = 4 r + k4 of line j = c
-#pragma unroll
-    for (int r = 0; r < 4; ++r) buf[(w * N + c) * PX + 4 * r + k4] = acc[r];
-    wave_lds_exchange();
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) in[ks] = buf[(w * N + 4 * ks + k4) * PX + c];       // line (k = w, i = c), element j
-    acc = transform(sy, in);                           // rows j' = 4 r + k4 of line i = c
-#pragma unroll
-    for (int r = 0; r < 4; ++r) buf[(w * N + 4 * r + k4) * PX + c] = acc[r];
-    __syncthreads();
-    // ---- along z: forward, the division, inverse — lines (j = w, i = c), in registers -----------------------------
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) in[ks] = buf[((4 * ks + k4) * N + w) * PX + c];
-    acc = transform(sz, in);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) in[r] = acc[r] / lam[r];
-    acc = transform(sz, in);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) buf[((4 * r + k4) * N + w) * PX + c] = acc[r];
-    __syncthreads();
-    // ---- inverse along x and y, plane k = w; the result leaves from the matrix instruction's registers --------------
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) in[ks] = buf[(w * N + c) * PX + 4 * ks + k4];
-    acc = transform(sx, in);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) buf[(w * N + c) * PX + 4 * r + k4] = acc[r];
-    wave_lds_exchange();
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) in[ks] = buf[(w * N + 4 * ks + k4) * PX + c];
-    acc = transform(sy, in);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) x[(w * N + 4 * r + k4) * N + c] = V(acc[r]);
+    __shared__ double buf[SINE16_BUF];
+    const Sine16Operands o = sine_cube16_load(b, tables, lambda);
+    sine_cube16_solve(o, buf, [&](int i, int j, int k, double v) { x[(k * SINE16_N + j) * SINE16_N + i] = V(v); });
 }
 
 // Is A a constant-coefficient SYMMETRIC star stencil on a lexicographically numbered grid whose boundary rows
@@ -749,13 +691,18 @@ bool CoarseSolver<V>::build_sine(const HostCsr &A, hipStream_t s) {
 }
 
 template <typename V>
+bool CoarseSolver<V>::cube16() const {
+    static const bool on = [] { const char *e = experiment_env("OMG_SINE_CUBE16"); return !(e && e[0] == '0'); }();
+    return n != 0 && P == 0 && sx == 16 && sy == 16 && sz == 16 && on;
+}
+
+template <typename V>
 void CoarseSolver<V>::solve(const V *b, V *x, hipStream_t s) const {
     if (n == 0) return;
     if (P == 0) {
         const int E = std::max(sx, std::max(sy, sz)) <= 16 ? 16 : 32;
         const size_t lds = (size_t(sx + 1) * size_t(sy) * size_t(sz) + 2 + size_t(sx + sy + sz) * size_t(E)) * sizeof(double);
-        static const bool cube16 = [] { const char *e = experiment_env("OMG_SINE_CUBE16"); return !(e && e[0] == '0'); }();
-        if (E == 16 && sx == 16 && sy == 16 && sz == 16 && cube16) {
+        if (cube16()) {
             hipLaunchKernelGGL((sine_cube16_kernel<V>), dim3(1), dim3(SINE_THREADS), 0, s, b, x, sine.p, lambda.p);
         } else if (E == 16) {
             hipLaunchKernelGGL((sine_solve_kernel<V, 16>), dim3(1), dim3(SINE_THREADS), lds, s, b, x, sx, sy, sz, sine.p, lambda.p);

@@ -718,6 +718,7 @@ struct CoarseSolver {
     void build(const HostCsr &A, hipStream_t s);
     bool build_sine(const HostCsr &A, hipStream_t s);       // P = 0 when the operator qualifies
     void solve(const V *b, V *x, hipStream_t s) const;     // original numbering, device pointers
+    bool cube16() const;                                   // solve() is one launch of sine_cube16_kernel
 };
 
 // ---- lexicographic Gauss-Seidel of grid stencils (march.hip) ---------------------------------
@@ -938,6 +939,25 @@ struct PlanePlan {
     void up(const V *x_old, V *x_new, const V *b, const Coarse &c, double *out, hipStream_t s, const Peer *peer = nullptr,
             bool sweep = true, int part = PART_ALL, const Gate *gate = nullptr) const;
 };
+
+// The tail of a V-cycle on the way up as ONE launch (plane.hip tail_up_kernel): the 16 x 16 x 16 sine solve, repeated in
+// every workgroup, + the up pass of the block level above it (+ the up pass of the block level above that, mid != null: then
+// `top` is level last - 2 and `mid` level last - 1).  The bits of the separate launches.
+template <typename V>
+struct TailUp {
+    const PlaneGeom *top = nullptr, *mid = nullptr;
+    const V *x_old = nullptr, *b = nullptr, *mid_x_old = nullptr, *mid_b = nullptr;
+    V *x_new = nullptr, *mid_x_new = nullptr;
+    const int32_t *cmap = nullptr;    // of level last - 1: coarsest natural index -> slot (null: identity)
+    const V *cb = nullptr;            // the coarsest right-hand side and solution, CoarseSolver's tables and eigenvalues
+    V *cx = nullptr;
+    const double *tables = nullptr, *lambda = nullptr;
+    bool sweep = true;                // false: postIterations = 0
+};
+// can level g (whole grid, coarse extents as given) be one of the launch's levels?
+bool tail_up_level(const PlaneGeom &g, int nxc, int nyc, int nzc);
+template <typename V>
+void launch_tail_up(const TailUp<V> &u, hipStream_t s);
 
 // ---- 7-point grid stencils with PER-ROW coefficients (var7.hip) ---------------------------------------------------
 // The ordinary real input of mgSolve (openmg/__init__.py:28: any A_in; operators.py:178): -div(kappa grad u) on a grid.

@@ -243,6 +243,10 @@ struct Hier {
     bool no_fuse = [] { const char *e = getenv("OMG_NO_FUSE"); return e && e[0] == '1'; }();
     // OMG_PLANE=0 (at creation): no plane-pipelined passes; set by omg_hierarchy_use_plane afterwards
     bool no_plane = false;
+    // OMG_TAIL_FUSE=0|1|2 (at creation): the coarsest solve and the small levels' up passes in one launch (tail_fuse_depth)
+    // omg_hierarchy_tail_info: fused tail launches put on the stream so far, and how many of them by replaying a graph
+    int64_t tail_launches = 0, tail_replayed = 0;
+    int tail_fuse = [] { const char *e = getenv("OMG_TAIL_FUSE"); return (e && e[0] >= '0' && e[0] <= '2' && !e[1]) ? e[0] - '0' : 2; }();
     // graph: a captured cycle bakes the levels' current / scratch vector pointers in, and a cycle may leave them
     // swapped (out-of-place sweeps: Jacobi, the 27-point pair launches, the plane passes) — so a graph is keyed by the
     // pointer state it was captured FROM and records the state it leaves; a cycle with an odd number of swaps gets a
@@ -251,6 +255,7 @@ struct Hier {
         hipGraphExec_t exec = nullptr;
         int pre = -1, post = -1;
         std::vector<V *> before, after;      // xp, tp of every level
+        int64_t tail = 0;                    // fused tail launches (tail_up_kernel) the captured cycle holds
     };
     bool want_graph = false;
     std::vector<GraphSlot> graphs;
@@ -831,6 +836,61 @@ void cycle_children(Hier<V> *h, int l, int pre, int post, int shape, bool first_
         cycle_body(h, l + 1, pre, post, false, nullptr, false, nullptr, false, shape == OMG_CYCLE_F ? OMG_CYCLE_V : OMG_CYCLE_W);
 }
 
+// The way down over a plane level (cycle_body): all but the last pre-smoothing sweep set by set, then the down pass — the
+// last sweep, the residual and the restriction (openmg/__init__.py:201, :209, :210).  c: what the pass was given of the
+// child level (the up pass takes the same).  Returns what the child's own cycle may rely on.
+struct PlaneDown { bool child_first, child_zero; };
+template <typename V>
+PlaneDown plane_down_half(Hier<V> *h, int l, int pre, int post, bool x_zero, bool first_done, int halves, typename PlanePlan<V>::Coarse &c) {
+    const int last = (int)h->lv.size() - 1;
+    Level<V> &L = h->lv[l];
+    Level<V> &C = h->lv[l + 1];
+    // :201 all but the last pre-smoothing sweep set by set (in place); the last one inside the down pass
+    if (pre > 1) smooth_level(h, l, pre - 1, FUSE_NONE, nullptr, first_done);
+    const bool child_plane = l + 1 < last && use_plane(h, C, pre, post);
+    const bool child_zero = child_plane && pre <= 1 && halves == 3;       // the child's down pass never reads its zero iterate
+    if (l + 1 < last && !child_zero) ensure_format(h, l + 1);
+    const bool child_first = l + 1 < last && !child_zero && !use_s27(h, C) && !L.plane->g.dim2 && first_sweep_in_restrict(h, C, pre);
+    c.map = L.r_out.p;
+    c.b = C.b.p;
+    c.x = (l + 1 < last && !child_zero) ? C.xp : nullptr;
+    c.diag = child_first ? C.diag.p : nullptr;
+    c.first_end = child_first ? int(C.A.sets[1]) : 0;
+    // (pre = 0: the child's down pass does not write its iterate either, and its up pass reads it)
+    if (child_zero && pre == 0) OMG_HIP(hipMemsetAsync(C.xp, 0, size_t(C.n) * sizeof(V), h->stream));
+    {
+        Prof<V> p(h, l, 5);
+        L.plane->down(L.xp, L.tp, L.b.p, x_zero, c, h->stream, nullptr, pre >= 1);      // :201 (last sweep), :209, :210
+    }
+    if (pre >= 1) std::swap(L.xp, L.tp);
+    if (l == h->pre_level) OMG_HIP(hipMemcpyAsync(h->pre_buf.p, L.xp, size_t(L.n) * sizeof(V), hipMemcpyDeviceToDevice, h->stream));
+    return {child_first, child_zero};
+}
+
+// Does the cycle from plane level l downward end in the fused tail launch (plane.hip tail_up_kernel), and with how many
+// up passes in it?  2: l is level last - 2 — its child's down pass runs as ever, then ONE launch holds the coarsest solve
+// and both up passes; 1: l is level last - 1 — the solve and its up pass; 0: the separate launches.  Only V shapes (F and W
+// come back to the level), only post <= 1 (further sweeps run set by set behind the up pass of each level), only block
+// levels of a red-black 7-point hierarchy above the 16 x 16 x 16 sine solve, and never for an up pass that leaves a norm.
+// The shape that counts is the HIERARCHY's: the second visit of a level in an F-cycle is a V-cycle from there down
+// (cycle_children), but an F hierarchy keeps the separate launches on every visit, as omg_hierarchy_level_flags reports.
+// OMG_TAIL_FUSE=0|1|2 when the hierarchy is made: never / depth 1 only / depth 2 where it applies (the default).
+template <typename V>
+int tail_fuse_depth(const Hier<V> *h, int l, int post, int shape) {
+    const int last = (int)h->lv.size() - 1;
+    if (h->tail_fuse <= 0 || shape != OMG_CYCLE_V || h->cycle_shape != OMG_CYCLE_V || post > 1 || l < 0 || l >= last || !h->coarse.cube16()) return 0;
+    auto fits = [&](int k) {
+        const Level<V> &K = h->lv[k];
+        if (!use_plane(h, K, 1, post)) return false;
+        const Level<V> &D = h->lv[k + 1];
+        if (k + 1 == last) return tail_up_level(K.plane->g, 16, 16, 16);
+        return use_plane(h, D, 1, post) && tail_up_level(K.plane->g, D.plane->g.nx, D.plane->g.ny, D.plane->g.nz);
+    };
+    if (l == last - 1) return fits(l) ? 1 : 0;
+    if (l == last - 2 && h->tail_fuse >= 2) return fits(l) && fits(l + 1) ? 2 : 0;
+    return 0;
+}
+
 template <typename V>
 int cycle_body(Hier<V> *h, int l, int pre, int post, bool want_norm, double *pre_slot, bool first_done, double *post_slot, bool x_zero,
                int shape) {
@@ -916,29 +976,36 @@ int cycle_body(Hier<V> *h, int l, int pre, int post, bool want_norm, double *pre
         return smooth_level(h, l, post, want_norm ? FUSE_NORM : FUSE_NONE, nullptr, false, post_slot) ? NORM_LAST_SET : NORM_NONE;
     }
     if (use_plane(h, L, pre, post)) {
-        // :201 all but the last pre-smoothing sweep set by set (in place); the last one inside the down pass
-        if (pre > 1) smooth_level(h, l, pre - 1, FUSE_NONE, nullptr, first_done);
-        const bool child_plane = l + 1 < last && use_plane(h, C, pre, post);
-        const bool child_zero = child_plane && pre <= 1 && halves == 3;       // the child's down pass never reads its zero iterate
-        if (l + 1 < last && !child_zero) ensure_format(h, l + 1);
-        const bool child_first = l + 1 < last && !child_zero && !use_s27(h, C) && !L.plane->g.dim2 && first_sweep_in_restrict(h, C, pre);
         typename PlanePlan<V>::Coarse c;
-        c.map = L.r_out.p;
-        c.b = C.b.p;
-        c.x = (l + 1 < last && !child_zero) ? C.xp : nullptr;
-        c.diag = child_first ? C.diag.p : nullptr;
-        c.first_end = child_first ? int(C.A.sets[1]) : 0;
-        // (pre = 0: the child's down pass does not write its iterate either, and its up pass reads it)
-        if (child_zero && pre == 0) OMG_HIP(hipMemsetAsync(C.xp, 0, size_t(C.n) * sizeof(V), h->stream));
-        {
-            Prof<V> p(h, l, 5);
-            L.plane->down(L.xp, L.tp, L.b.p, x_zero, c, h->stream, nullptr, pre >= 1);      // :201 (last sweep), :209, :210
-        }
-        if (pre >= 1) std::swap(L.xp, L.tp);
-        if (l == h->pre_level) OMG_HIP(hipMemcpyAsync(h->pre_buf.p, L.xp, size_t(L.n) * sizeof(V), hipMemcpyDeviceToDevice, h->stream));
-        cycle_children(h, l, pre, post, shape, child_first, child_zero);                     // :213
-        c.e = C.xp;
+        const PlaneDown d = plane_down_half(h, l, pre, post, x_zero, first_done, halves, c);
         double *out = (want_norm && post <= 1) ? (post_slot ? post_slot : L.plane->partials.p) : nullptr;
+        const int fuse = halves == 3 && !out ? tail_fuse_depth(h, l, post, shape) : 0;
+        if (fuse) {
+            // the rest of the cycle below this level in one launch: (depth 2: the child's down pass as ever, then) the coarsest
+            // solve and the up passes of the levels above it (plane.hip tail_up_kernel)
+            TailUp<V> u;
+            u.top = &L.plane->g; u.x_old = L.xp; u.x_new = L.tp; u.b = L.b.p;
+            u.cmap = L.r_out.p;
+            if (fuse == 2) {
+                typename PlanePlan<V>::Coarse cc;
+                plane_down_half(h, l + 1, pre, post, d.child_zero, d.child_first, halves, cc);
+                u.mid = &C.plane->g; u.mid_x_old = C.xp; u.mid_x_new = C.tp; u.mid_b = C.b.p;
+                u.cmap = C.r_out.p;
+            }
+            Level<V> &Z = h->lv[last];
+            u.cb = Z.b.p; u.cx = Z.xp; u.tables = h->coarse.sine.p; u.lambda = h->coarse.lambda.p;
+            u.sweep = post >= 1;
+            {
+                Prof<V> p(h, l, 6);
+                launch_tail_up<V>(u, h->stream);
+                ++h->tail_launches;
+            }
+            if (fuse == 2) std::swap(C.xp, C.tp);
+            std::swap(L.xp, L.tp);
+            return NORM_NONE;
+        }
+        cycle_children(h, l, pre, post, shape, d.child_first, d.child_zero);                 // :213
+        c.e = C.xp;
         {
             Prof<V> p(h, l, 6);
             L.plane->up(L.xp, L.tp, L.b.p, c, out, h->stream, nullptr, post >= 1);           // :214, :220/:224, first sweep of :216-222 (, :227)
@@ -1148,6 +1215,7 @@ void run_cycle0(Hier<V> *h, int pre, int post) {
         // leaves — starts over)
         if (h->graphs.size() >= 2 || (!h->graphs.empty() && (h->graphs[0].pre != pre || h->graphs[0].post != post))) drop_graph(h);
         hipGraph_t g = nullptr;
+        const int64_t tail_before = h->tail_launches;
         OMG_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
         try {
             body();
@@ -1163,6 +1231,8 @@ void run_cycle0(Hier<V> *h, int pre, int post) {
         ns.post = post;
         ns.before = cur;
         ns.after = pointer_state(h);               // (the capture ran the host side of the cycle: the swaps are made)
+        ns.tail = h->tail_launches - tail_before;  // (captured, not run: counted with every replay)
+        h->tail_launches = tail_before;
         hipError_t e = hipGraphInstantiate(&ns.exec, g, nullptr, nullptr, 0);
         (void)hipGraphDestroy(g);
         if (e != hipSuccess) {
@@ -1173,6 +1243,8 @@ void run_cycle0(Hier<V> *h, int pre, int post) {
         slot = &h->graphs.back();
     }
     OMG_HIP(hipGraphLaunch(slot->exec, h->stream));
+    h->tail_launches += slot->tail;
+    h->tail_replayed += slot->tail;
     restore(slot->after);
 }
 
@@ -2386,7 +2458,9 @@ int omg_hierarchy_level_flags(const omg_hierarchy *h, int level, int *flags) {
                      ((smoothed && hh->lv[level].march && hh->lv[level].march->line_scan) ? OMG_LEVEL_MARCH_SCAN : 0) |
                      ((smoothed && hh->lv[level].plane && !hh->no_plane) ? OMG_LEVEL_PLANE : 0) |
                      ((smoothed && hh->lv[level].s27 && !hh->no_plane) ? OMG_LEVEL_STENCIL27 : 0) |
-                     ((smoothed && hh->lv[level].var7 && !hh->no_plane) ? OMG_LEVEL_VAR7 : 0);
+                     ((smoothed && hh->lv[level].var7 && !hh->no_plane) ? OMG_LEVEL_VAR7 : 0) |
+                     ((tail_fuse_depth(hh, level, 1, hh->cycle_shape) || tail_fuse_depth(hh, level - 1, 1, hh->cycle_shape) == 2)
+                          ? OMG_LEVEL_TAIL_FUSED : 0);
         });
     });
 }
@@ -2427,6 +2501,13 @@ int omg_hierarchy_get_cycle(const omg_hierarchy *h, int *shape, double *over_cor
     return guarded([&] {
         OMG_REQUIRE(shape && over_correction, "null argument");
         with(h, [&](auto *hh) { *shape = hh->cycle_shape; *over_correction = hh->over; });
+    });
+}
+
+int omg_hierarchy_tail_info(const omg_hierarchy *h, int64_t *out2) {
+    return guarded([&] {
+        OMG_REQUIRE(out2, "null");
+        with(h, [&](auto *hh) { out2[0] = hh->tail_launches; out2[1] = hh->tail_replayed; });
     });
 }
 

@@ -41,6 +41,7 @@
 
 #include "common.h"
 #include "peer_wait.h"
+#include "sine_cube16.h"
 
 // -DOMG_PLANE_STAMPS: in-kernel cycle stamps per stage (tools/plane_stamps.py); -DOMG_PLANE_DBGARGS: only the switches
 // of OMG_PLANE_DBG that leave out part of a pass's memory traffic (tools/plane_dbg_times.py; wrong results, timing only)
@@ -1323,6 +1324,190 @@ __global__ __launch_bounds__(256) void block_kernel(const BlockKArgs<V> a) {
     }
 }
 
+// ---- the tail of a V-cycle on the way up: coarsest solve + the up passes of the small levels in ONE launch ------------
+// Below the marching levels a cycle is a chain of launches that each take their floor (6 - 12 us) for a few microseconds'
+// work.  On the way up the chain needs no hand-over between workgroups: the prolongation is local (a fine cell takes its
+// parent's value) and a red-black sweep reaches two cells, so a workgroup can make everything its block needs ITSELF —
+//   every workgroup (16 waves) runs the whole 16^3 sine solve into LDS (sine_cube16.h: the operands are 70 KB that stay
+//       in L2; the compute units would idle during a launch of one workgroup anyway); workgroup 0 also stores the solution;
+//   DEPTH 2: the up pass of level last-1 on the cells under its block + 2 of level last-2, widened by two (14 x 10 x 10
+//       for a 16 x 8 x 8 block): x + w e on + 2, red on + 1, black on + 0, clipped to the grid, the result kept in LDS; the
+//       cells under the block itself are that level's new iterate and are stored (every cell by exactly one workgroup);
+//   the block's own up pass as block_kernel<.., 1, ..> runs it, the coarse correction taken from LDS.
+// Every cell gets block_kernel's and sine_cube16_kernel's operations on the same operands in the same order — the seven
+// slots in column order from +0, block_quotient, x + madd(wp, e, 0), cells outside the grid as zeros, the solution rounded
+// to V where the solve stores it — so the launch leaves the bits of the three launches it replaces
+// (tests/test_gpu_tail_fused.py).  The region of level last-1 starts at an ODD coordinate: colour and parent cell come from
+// grid coordinates (as in tile2d_kernel), not from block_kernel's even-origin shortcut.
+template <typename V>
+struct TailLevelArgs {
+    const V *x_old;
+    V *x_new;
+    const V *b;
+    int nx, ny, nz, nr;
+    V c0, c1, c2, c3, c4, c5, c6;
+    V wp;                            // the prolongation's weight (PlaneGeom::over)
+    int fast_div;
+};
+template <typename V>
+struct TailKArgs {
+    TailLevelArgs<V> top, mid;       // the block's level (last - DEPTH); DEPTH 2: level last - 1
+    int nbx, nby;
+    const int32_t *cmap;             // of level last - 1: coarsest natural index -> slot of the coarsest vectors (null: identity)
+    const V *cb;                     // coarsest right-hand side, solution
+    V *cx;
+    const double *tables, *lambda;   // CoarseSolver::sine, ::lambda
+};
+constexpr int TAIL_BX = 16, TAIL_BY = 8, TAIL_BZ = 8, TAIL_THREADS = 1024;
+
+// A region of RX x RY x RZ cells (its core + a ring of two) of one level, LDS cell (0, 0, 0) at grid cell (oi, oj, ok) of ANY parity
+template <typename V, int RX, int RY, int RZ>
+struct TailRegion {
+    static constexpr int vol = RX * RY * RZ, NT = TAIL_THREADS, NL = (vol + NT - 1) / NT;
+    const TailLevelArgs<V> &a;
+    const int oi, oj, ok;
+    V xv[NL], bv[NL];
+    int ps[NL];                      // parents_in_cube16: where this thread's cells' parents lie in the coarsest vectors
+    __device__ __forceinline__ TailRegion(const TailLevelArgs<V> &lv, int i, int j, int k) : a(lv), oi(i), oj(j), ok(k) {}
+    __device__ __forceinline__ bool in_grid(int gi, int gj, int gk) const {
+        return gi >= 0 && gi < a.nx && gj >= 0 && gj < a.ny && gk >= 0 && gk < a.nz;
+    }
+    __device__ __forceinline__ int slot_of(int gi, int gj, int gk) const {
+        return (((gi + gj + gk) & 1) ? a.nr : 0) + (((gk * a.ny + gj) * a.nx + gi) >> 1);
+    }
+    // the region's x and b requested (cells outside the grid are zeros and stay so)
+    __device__ __forceinline__ void load() {
+        const int t = int(threadIdx.x);
+#pragma unroll
+        for (int n = 0; n < NL; ++n) {
+            const int c = t + n * NT;
+            const int gi = oi + c % RX, gj = oj + (c / RX) % RY, gk = ok + c / (RX * RY);
+            const bool in = c < vol && in_grid(gi, gj, gk);
+            const int slot = in ? slot_of(gi, gj, gk) : 0;
+            bv[n] = a.b[slot];
+            xv[n] = a.x_old[slot];
+            if (!in) { bv[n] = V(0); xv[n] = V(0); }
+        }
+    }
+    // the level above the 16 x 16 x 16 coarsest one: the slots of the parents of this thread's cells
+    __device__ __forceinline__ void parents_in_cube16(const int32_t *cmap) {
+        const int t = int(threadIdx.x);
+#pragma unroll
+        for (int n = 0; n < NL; ++n) {
+            const int c = t + n * NT;
+            const int gi = oi + c % RX, gj = oj + (c / RX) % RY, gk = ok + c / (RX * RY);
+            const int ce = (c < vol && in_grid(gi, gj, gk)) ? ((gk >> 1) * SINE16_N + (gj >> 1)) * SINE16_N + (gi >> 1) : 0;
+            ps[n] = cmap ? cmap[ce] : ce;
+        }
+    }
+    // X = x + wp e (openmg/__init__.py:214,220: the product rounded, then added), then — SWEEP — red on the core + 1 and
+    // black on the core; parent(n, I, J, K): the coarse value under this thread's n-th cell, coarse cell (I, J, K).  Ends
+    // behind a barrier.
+    template <bool SWEEP, typename PARENT>
+    __device__ __forceinline__ void up(V *X, V *B, PARENT parent) {
+        const int t = int(threadIdx.x);
+#pragma unroll
+        for (int n = 0; n < NL; ++n) {
+            const int c = t + n * NT;
+            const int gi = oi + c % RX, gj = oj + (c / RX) % RY, gk = ok + c / (RX * RY);
+            if (c >= vol) continue;
+            V x = xv[n];
+            if (in_grid(gi, gj, gk)) x = xv[n] + madd(a.wp, parent(n, gi >> 1, gj >> 1, gk >> 1), V(0));
+            X[c] = x;
+            B[c] = bv[n];
+        }
+        __syncthreads();
+        if (!SWEEP) return;
+        const V rc3 = refined_rcp(a.c3);
+        const bool fast = a.fast_div != 0;
+        auto row = [&](int c) -> V {
+            V s = madd(a.c0, X[c - RX * RY], V(0));
+            s = madd(a.c1, X[c - RX], s);
+            s = madd(a.c2, X[c - 1], s);
+            s = madd(a.c3, X[c], s);
+            s = madd(a.c4, X[c + 1], s);
+            s = madd(a.c5, X[c + RX], s);
+            return madd(a.c6, X[c + RX * RY], s);
+        };
+#pragma unroll
+        for (int colour = 0; colour < 2; ++colour) {
+            // cells of one colour inside the core widened by `ring`, clipped to the grid; a thread takes PAIRS of cells along
+            // x and relaxes the one of the sweep's colour (by its GRID coordinates)
+            const int ring = 1 - colour, off = 2 - ring;
+            const int wx = RX - 2 * off, wy = RY - 2 * off, wz = RZ - 2 * off;
+            const int np = wx / 2 * wy * wz;
+#pragma unroll
+            for (int n = 0; n < ((RX - 2) / 2 * (RY - 2) * (RZ - 2) + NT - 1) / NT; ++n) {
+                const int p = t + n * NT;
+                const int lj = off + (p / (wx / 2)) % wy, lk = off + p / (wx / 2 * wy);
+                const int l0 = off + 2 * (p % (wx / 2));
+                const int li = l0 + ((oi + l0 + oj + lj + ok + lk + colour) & 1);
+                const int gi = oi + li, gj = oj + lj, gk = ok + lk;
+                if (p >= np || !in_grid(gi, gj, gk)) continue;
+                const int l = (lk * RY + lj) * RX + li;
+                // openmg/solvers.py:68   x[i] = x[i] + (b[i] - Aix) / A[i, i]
+                X[l] = X[l] + block_quotient(B[l] - row(l), a.c3, rc3, fast);
+            }
+            __syncthreads();
+        }
+    }
+    // the CX x CY x CZ cells from local cell (fx, fy, fz) on: the level's new iterate out
+    template <int CX, int CY, int CZ>
+    __device__ __forceinline__ void store(const V *X, int fx, int fy, int fz) const {
+        const int t = int(threadIdx.x);
+#pragma unroll
+        for (int n = 0; n < (CX * CY * CZ + NT - 1) / NT; ++n) {
+            const int c = t + n * NT;
+            const int li = fx + c % CX, lj = fy + (c / CX) % CY, lk = fz + c / (CX * CY);
+            const int gi = oi + li, gj = oj + lj, gk = ok + lk;
+            if (c >= CX * CY * CZ || !in_grid(gi, gj, gk)) continue;
+            a.x_new[slot_of(gi, gj, gk)] = X[(lk * RY + lj) * RX + li];
+        }
+    }
+};
+
+template <typename V, int DEPTH, bool SWEEP>
+__global__ __launch_bounds__(TAIL_THREADS) void tail_up_kernel(const TailKArgs<V> a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char plane_smem[];
+    constexpr int BX = TAIL_BX, BY = TAIL_BY, BZ = TAIL_BZ;
+    typedef TailRegion<V, BX + 4, BY + 4, BZ + 4> Top;                       // the block + 2
+    typedef TailRegion<V, BX / 2 + 6, BY / 2 + 6, BZ / 2 + 6> Mid;           // the cells of level last-1 under it, + 2
+    constexpr int MX = BX / 2 + 6, MY = BY / 2 + 6;
+    constexpr int N = SINE16_N, PX = SINE16_PX;
+    double *const sol = reinterpret_cast<double *>(plane_smem);             // the solve's buffer, then the solution (rounded to V)
+    V *const X = reinterpret_cast<V *>(sol + SINE16_BUF);
+    V *const B = X + Top::vol;
+    V *const XM = B + Top::vol;
+    V *const BM = XM + Mid::vol;
+    const int bi = int(blockIdx.x) % a.nbx, bj = (int(blockIdx.x) / a.nbx) % a.nby, bk = int(blockIdx.x) / (a.nbx * a.nby);
+    // ALL loads are requested before the first one is used: the solve's operands, both levels' x and b, the coarse slots
+    const Sine16Operands so = sine_cube16_load(a.cb, a.tables, a.lambda);
+    Top top(a.top, bi * BX - 2, bj * BY - 2, bk * BZ - 2);
+    Mid mid(a.mid, bi * (BX / 2) - 3, bj * (BY / 2) - 3, bk * (BZ / 2) - 3);
+    top.load();
+    if (DEPTH == 2) mid.load();
+    if (DEPTH == 2) mid.parents_in_cube16(a.cmap);
+    else top.parents_in_cube16(a.cmap);
+    // ---- the coarsest solve, whole, in every workgroup ----------------------------------------------------------------
+    const bool first = blockIdx.x == 0;
+    sine_cube16_solve(so, sol, [&](int i, int j, int k, double v) {
+        const V r = V(v);
+        if (first) a.cx[(k * N + j) * N + i] = r;
+        sol[(k * N + j) * PX + i] = double(r);           // (plane k is this wave's own: it has read all it needs of it)
+    });
+    __syncthreads();
+    auto solved = [&](int slot) -> V { return V(sol[(slot / (N * N) * N + slot / N % N) * PX + slot % N]); };
+    if (DEPTH == 2) {
+        mid.template up<SWEEP>(XM, BM, [&](int n, int, int, int) -> V { return solved(mid.ps[n]); });
+        mid.template store<BX / 2, BY / 2, BZ / 2>(XM, 3, 3, 3);
+        const int mi = mid.oi, mj = mid.oj, mk = mid.ok;
+        top.template up<SWEEP>(X, B, [&](int, int I, int J, int K) -> V { return XM[((K - mk) * MY + (J - mj)) * MX + (I - mi)]; });
+    } else {
+        top.template up<SWEEP>(X, B, [&](int n, int, int, int) -> V { return solved(top.ps[n]); });
+    }
+    top.template store<BX, BY, BZ>(X, 2, 2, 2);
+}
+
 // ---- 2-D levels (five-point stencils, 2 x 2 aggregation): a tile of the grid per workgroup, whole in LDS ---------
 // BASELINE configs[1]'s grids (1024^2 and its Galerkin products).  A 2-D level has nothing to march along, so each half
 // of the cycle is one launch of independent tiles: the workgroup loads its BX x BY cells with a ring of three (x; b: two),
@@ -2222,6 +2407,57 @@ void launch_block(const PlaneGeom &g, const V *x_old, V *x_new, const V *b, cons
     }
     OMG_HIP(hipGetLastError());
 }
+
+// the fused tail (tail_up_kernel): a block level exactly twice the extents of the level below it, red-black, whole grids
+template <typename V>
+TailLevelArgs<V> tail_level(const PlaneGeom &g, const V *x_old, V *x_new, const V *b) {
+    TailLevelArgs<V> a;
+    std::memset(&a, 0, sizeof(a));
+    a.x_old = x_old; a.x_new = x_new; a.b = b;
+    a.nx = g.nx; a.ny = g.ny; a.nz = g.nz; a.nr = int(int64_t(g.nx) * g.ny * g.nz / 2);
+    a.c0 = V(g.c[0]); a.c1 = V(g.c[1]); a.c2 = V(g.c[2]); a.c3 = V(g.c[3]); a.c4 = V(g.c[4]); a.c5 = V(g.c[5]); a.c6 = V(g.c[6]);
+    a.wp = V(g.over * g.w);
+    a.fast_div = (std::fabs(g.c[3]) >= 0x1p-400 && std::fabs(g.c[3]) <= 0x1p400) ? 1 : 0;
+    return a;
+}
+template <typename V, int DEPTH, bool SWEEP>
+void launch_tail_kernel(const TailKArgs<V> &a, int wgs, hipStream_t s) {
+    const size_t cells = size_t(TAIL_BX + 4) * (TAIL_BY + 4) * (TAIL_BZ + 4) +
+                         (DEPTH == 2 ? size_t(TAIL_BX / 2 + 6) * (TAIL_BY / 2 + 6) * (TAIL_BZ / 2 + 6) : 0);
+    const size_t lds = SINE16_BUF * sizeof(double) + 2 * cells * sizeof(V);
+    auto kernel = tail_up_kernel<V, DEPTH, SWEEP>;
+    allow_lds(kernel, lds);
+    hipLaunchKernelGGL(kernel, dim3(unsigned(wgs)), dim3(TAIL_THREADS), lds, s, a);
+    OMG_HIP(hipGetLastError());
+}
+
+bool tail_up_level(const PlaneGeom &g, int nxc, int nyc, int nzc) {
+    return g.block && !g.dim2 && !g.jacobi && g.z_base == 0 && g.z_end == g.nz && g.nx == 2 * nxc && g.ny == 2 * nyc && g.nz == 2 * nzc;
+}
+
+template <typename V>
+void launch_tail_up(const TailUp<V> &u, hipStream_t s) {
+    const PlaneGeom &g = *u.top;
+    OMG_REQUIRE(u.mid ? tail_up_level(g, u.mid->nx, u.mid->ny, u.mid->nz) && tail_up_level(*u.mid, SINE16_N, SINE16_N, SINE16_N)
+                      : tail_up_level(g, SINE16_N, SINE16_N, SINE16_N),
+                "fused tail: block levels of twice the extents of the level below, above a 16 x 16 x 16 coarsest grid");
+    TailKArgs<V> a;
+    std::memset(&a, 0, sizeof(a));
+    a.top = tail_level<V>(g, u.x_old, u.x_new, u.b);
+    if (u.mid) a.mid = tail_level<V>(*u.mid, u.mid_x_old, u.mid_x_new, u.mid_b);
+    a.nbx = (g.nx + TAIL_BX - 1) / TAIL_BX; a.nby = (g.ny + TAIL_BY - 1) / TAIL_BY;
+    const int wgs = a.nbx * a.nby * ((g.nz + TAIL_BZ - 1) / TAIL_BZ);
+    a.cmap = u.cmap; a.cb = u.cb; a.cx = u.cx; a.tables = u.tables; a.lambda = u.lambda;
+    if (u.mid) {
+        if (u.sweep) launch_tail_kernel<V, 2, true>(a, wgs, s);
+        else launch_tail_kernel<V, 2, false>(a, wgs, s);
+    } else {
+        if (u.sweep) launch_tail_kernel<V, 1, true>(a, wgs, s);
+        else launch_tail_kernel<V, 1, false>(a, wgs, s);
+    }
+}
+template void launch_tail_up<double>(const TailUp<double> &, hipStream_t);
+template void launch_tail_up<float>(const TailUp<float> &, hipStream_t);
 
 
 template <typename V, int MODE, bool XZ, bool NORM, bool SWEEP>
