@@ -113,6 +113,38 @@ int omg_hierarchy_create_ex(int n_levels, const omg_csr *A, const omg_csr *R, in
  * infoDict['A'], ['R'] are NOT kept: a caller with giveInfo takes the ordinary route.                                  */
 int omg_hierarchy_create_from_fine(const omg_csr *A_in, int dim, const int64_t *shape, int n_restrictions, int smoother, double omega,
                                    int dtype, omg_hierarchy **out);
+/* Singular operators whose null space is the constant vector (zero row and column sums: the pure-Neumann or periodic
+ * Poisson problem; no reference counterpart — openmg/solvers.py:16-26 hands such a coarsest operator to SuperLU, which
+ * raises or returns 1e18).  With OMG_NULLSPACE_CONSTANT
+ *   - the coarsest operator must have the null space itself: every row sum and every column sum at most 1e-10 times the
+ *     sum of the row's / column's absolute entries (Galerkin products of such an operator keep it to rounding), otherwise
+ *     OMG_ERR_INVALID; it is inverted as A + gamma 1 1^T, gamma = (mean diagonal) / n, in double, as one explicit inverse
+ *     (n > 16384: OMG_ERR_UNSUPPORTED; OMG_COARSE_BLOCKS / OMG_COARSE_CHAIN are ignored):
+ *     (A + gamma 1 1^T)^-1 b = pinv(A) b + mean(b) / (gamma n) 1 — the minimum-norm solution for a right-hand side free of
+ *     constants, and a rounding-level mean mapped to a rounding-level constant;
+ *   - omg_resident_load[_dev] subtract its mean from the resident right-hand side after loading it (the fp64 outer b of an
+ *     OMG_DTYPE_MIXED hierarchy; the caller's array and the initial iterate stay as they are: every norm reported
+ *     afterwards is that of the projected system), omg_resident_fetch[_dev] subtract its mean from the resident iterate,
+ *     in place, before copying it out (the null component of x does not enter the residual: a later cycle continues
+ *     unchanged to rounding), omg_solve is load, cycles, fetch;
+ *   - omg_vcycle, omg_vcycle_ex, omg_vcycle_dev and omg_hierarchy_cycle_dev do NOT project: they are the reference's
+ *     recursive building block, entered at any level with the caller's b;
+ *   - the multi-GPU runners refuse such a hierarchy as their tail (omg_*dist_set_tail: OMG_ERR_UNSUPPORTED).
+ * The sums of the projection are deterministic (fixed slots, fixed order: csrc/nullspace.hip).  omg_hierarchy_update_fine
+ * keeps the setting.  nullspace = OMG_NULLSPACE_NONE is omg_hierarchy_create_ex / omg_hierarchy_create_from_fine, bit for
+ * bit; any other value: OMG_ERR_INVALID. */
+#define OMG_NULLSPACE_NONE     0
+#define OMG_NULLSPACE_CONSTANT 1
+typedef struct { int smoother; double omega; int dtype; int nullspace; } omg_hierarchy_options;
+int omg_hierarchy_create_opt(int n_levels, const omg_csr *A, const omg_csr *R,
+                             const omg_hierarchy_options *opt, omg_hierarchy **out);
+int omg_hierarchy_create_from_fine_opt(const omg_csr *A_in, int dim, const int64_t *shape, int n_restrictions,
+                                       const omg_hierarchy_options *opt, omg_hierarchy **out);
+int omg_hierarchy_nullspace(const omg_hierarchy *h, int *kind);
+/* x <- x - mean(x) on one level's vector (host doubles in natural numbering, through the level's
+ * precision and ordering like omg_level_smooth); *mean (nullable) = the mean that was removed.
+ * Works on any hierarchy, whatever its nullspace setting. */
+int omg_level_project(omg_hierarchy *h, int level, double *x_inout, double *mean);
 
 /* New values for the fine operator of a hierarchy made by omg_hierarchy_create_from_fine whose smoothed levels all run the
  * 27-point kernels (BASELINE configs[4]: "Galerkin RAP rebuilt on-device"; what the reference would do is run

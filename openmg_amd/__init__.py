@@ -32,6 +32,15 @@ Extra keys understood in the `parameters` dict (ignored by the reference):
                 operator, iterate, residual and CG vectors in fp64, each cycle run on fl32(r)): with accel None every
                 cycle is a defect correction x += M(fl32(b - A x)), with accel 'cg' FCG uses z = M(fl32(r)); u and
                 every norm are fp64 and converge to the fp64 solution at fp32 cycle cost.  mgCycle raises ValueError
+    'nullspace' None (default) or 'constant': A_in is SINGULAR with the constant null space — zero row and column sums: the
+                pure-Neumann or periodic Poisson problem (the pressure equation of an incompressible flow step).  The
+                coarsest operator is then inverted on the complement of the constants (as A + gamma 1 1^T, an explicit
+                inverse: at most 16384 coarsest unknowns), mgSolve subtracts mean(b) from its copy of b (a b with a mean has
+                no solution; the caller's array is untouched and every norm is that of the projected system) and returns
+                the u with mean(u) = 0.  An operator without that null space (a Dirichlet boundary) raises HipError
+                (ERR_INVALID).  Works with every 'smoother', 'accel', 'dtype', 'cycle' and 'overCorrection' and with device
+                arrays.  mgCycle, the reference's recursive building block, projects nothing: only the coarse solve
+                changes (b and the iterate are the caller's).  Anything else raises ValueError before any device work
     'trustOperators'  mgCycle only, default False: when the caller passes the SAME list members (object identity) it
                 passed on an earlier call — e.g. infoDict['A'] / infoDict['R'] handed back unchanged — the per-call
                 checksum of every byte of the lists (what recognises an operator edited in place) is skipped
@@ -92,6 +101,14 @@ def _cycle_of(parameters):
     return shape, alpha
 
 
+def _nullspace_of(parameters):
+    """parameters['nullspace']: None or 'constant'; ValueError for anything else."""
+    kind = parameters.get("nullspace")
+    if kind is not None and not (isinstance(kind, str) and kind == "constant"):
+        raise ValueError("parameters['nullspace'] must be None or 'constant', not %r" % (kind,))
+    return kind
+
+
 # ---- device hierarchy cache for repeated mgCycle calls ---------------------------------------
 # mgCycle receives the A and R lists on every call (openmg/__init__.py:151); uploading
 # them each time would dominate.  A cache entry holds the device hierarchy TOGETHER WITH strong
@@ -135,33 +152,33 @@ def _as_csr_cached(M):
     return C
 
 
-def _fingerprint(A, R, n_levels, code, omega, dtype):
+def _fingerprint(A, R, n_levels, code, omega, dtype, nullspace=None):
     def one(M):
         if sp.issparse(M):
             M = _as_csr_cached(M)
             return (M.shape, M.nnz, _array_checksum(M.indptr), _array_checksum(M.indices), _array_checksum(M.data))
         M = np.asarray(M)
         return (M.shape, _array_checksum(M))
-    return (tuple(one(M) for M in A[:n_levels]), tuple(one(M) for M in R[:n_levels - 1]), code, omega, dtype)
+    return (tuple(one(M) for M in A[:n_levels]), tuple(one(M) for M in R[:n_levels - 1]), code, omega, dtype, nullspace)
 
 
-def _hierarchy_for(A, R, n_levels, code, omega, dtype=_hip.DTYPE_F64, trust=False):
+def _hierarchy_for(A, R, n_levels, code, omega, dtype=_hip.DTYPE_F64, trust=False, nullspace=None):
     if trust:
         # parameters['trustOperators']: the caller vouches that list members it has passed before are unchanged; an entry
         # built from the very same objects (identity, not equality) and the same smoother / precision is taken as it is
         for h, members, how in _cache.values():
-            if (how == (code, omega, dtype) and len(members[0]) == n_levels
+            if (how == (code, omega, dtype, nullspace) and len(members[0]) == n_levels
                     and all(a is m for a, m in zip(A[:n_levels], members[0]))
                     and all(r is m for r, m in zip(R[:n_levels - 1], members[1]))):
                 return h
-    key = _fingerprint(A, R, n_levels, code, omega, dtype)
+    key = _fingerprint(A, R, n_levels, code, omega, dtype, nullspace)
     entry = _cache.get(key)
     if entry is None:
         while len(_cache) >= _CACHE_SLOTS:
             _cache.pop(next(iter(_cache)))[0].close()
         members = (list(A[:n_levels]), list(R[:n_levels - 1]))
-        h = _hip.Hierarchy(members[0], members[1], smoother=code, omega=omega, dtype=dtype)
-        entry = _cache[key] = (h, members, (code, omega, dtype))
+        h = _hip.Hierarchy(members[0], members[1], smoother=code, omega=omega, dtype=dtype, nullspace=nullspace)
+        entry = _cache[key] = (h, members, (code, omega, dtype, nullspace))
     return entry[0]
 
 
@@ -191,6 +208,7 @@ def mgSolve(A_in, b, parameters):
     if accel not in (None, "cg"):
         raise ValueError("parameters['accel'] must be None or 'cg', not %r" % (accel,))
     shape, alpha = _cycle_of(parameters)
+    nullspace = _nullspace_of(parameters)
     problemShape = parameters["problemShape"]
     gridLevels = parameters["gridLevels"]
     defaults["coarsestLevel"] = gridLevels - 1
@@ -210,13 +228,14 @@ def mgSolve(A_in, b, parameters):
         # for the fused paths stay in HBM (omg_hierarchy_create_from_fine); same hierarchy, same results
         R = A = None
         parameters["coarsestLevel"] = n_fused
-        hierarchy = _hip.Hierarchy.from_fine(A_in, problemShape, n_fused, smoother=code, omega=omega, dtype=_dtype_of(parameters))
+        hierarchy = _hip.Hierarchy.from_fine(A_in, problemShape, n_fused, smoother=code, omega=omega, dtype=_dtype_of(parameters),
+                                             nullspace=nullspace)
     else:
         R = operators.restrictionList(problemShape, parameters["coarsestLevel"], parameters["minSize"],
                                       dense=dense, verbose=verbose)
         parameters["coarsestLevel"] = len(R)
         A = operators.coeffecientList(A_in, R, dense=dense, verbose=verbose)
-        hierarchy = _hip.Hierarchy(A, R, smoother=code, omega=omega, dtype=_dtype_of(parameters))
+        hierarchy = _hip.Hierarchy(A, R, smoother=code, omega=omega, dtype=_dtype_of(parameters), nullspace=nullspace)
     depth = parameters["coarsestLevel"]
     b_on_device = _devarray.is_device_array(b)
     try:
@@ -366,6 +385,7 @@ def mgCycle(A, b, level, R, parameters, initial=None):
         raise ValueError("parameters['dtype'] = 'mixed' is for mgSolve only (fp64 iterations around fp32 V-cycles); "
                          "mgCycle runs one cycle: use 'float32' or 'float64'")
     shape, alpha = _cycle_of(parameters)
+    nullspace = _nullspace_of(parameters)
     coarsest = parameters["coarsestLevel"]
     if coarsest >= len(A) or coarsest > len(R):
         raise IndexError("parameters['coarsestLevel'] = %d but only %d operators / %d restrictions given"
@@ -381,7 +401,8 @@ def mgCycle(A, b, level, R, parameters, initial=None):
         if on_device:
             raise ValueError("mgCycle at the coarsest level with device arrays: use solvers.coarseSolve on host arrays")
         return solvers.coarseSolve(A[level], b), {"norm": 0}
-    hierarchy = _hierarchy_for(A, R, coarsest + 1, code, omega, _dtype_of(parameters), trust=bool(parameters.get("trustOperators", False)))
+    hierarchy = _hierarchy_for(A, R, coarsest + 1, code, omega, _dtype_of(parameters), trust=bool(parameters.get("trustOperators", False)),
+                               nullspace=nullspace)
     hierarchy.set_cycle(shape, alpha)          # (the cached hierarchy may have run another setting: a no-op when unchanged)
     if parameters.get("verbose", False):
         _announce_descent(coarsest, shape, level)

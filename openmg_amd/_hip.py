@@ -39,6 +39,11 @@ class CsrView(ctypes.Structure):
                 ("indptr", ctypes.c_void_p), ("indices", ctypes.c_void_p), ("data", ctypes.c_void_p)]
 
 
+class HierarchyOptions(ctypes.Structure):
+    """omg_hierarchy_options in include/openmg_hip.h."""
+    _fields_ = [("smoother", ctypes.c_int), ("omega", ctypes.c_double), ("dtype", ctypes.c_int), ("nullspace", ctypes.c_int)]
+
+
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _D = ctypes.c_double
@@ -47,6 +52,7 @@ _CSR = ctypes.POINTER(CsrView)
 _I64P = ctypes.POINTER(ctypes.c_int64)
 _IP = ctypes.POINTER(ctypes.c_int)
 _DP = ctypes.POINTER(ctypes.c_double)
+_OPT = ctypes.POINTER(HierarchyOptions)
 
 # name -> (restype, argtypes).  Must list EVERY symbol include/openmg_hip.h declares
 # (tests/test_cabi_symbols.py checks that against the header).
@@ -58,6 +64,10 @@ SIGNATURES = {
     "omg_hierarchy_create": (_I, [_I, _CSR, _CSR, _I, _D, _PP]),
     "omg_hierarchy_create_ex": (_I, [_I, _CSR, _CSR, _I, _D, _I, _PP]),
     "omg_hierarchy_create_from_fine": (_I, [_CSR, _I, _I64P, _I, _I, _D, _I, _PP]),
+    "omg_hierarchy_create_opt": (_I, [_I, _CSR, _CSR, _OPT, _PP]),
+    "omg_hierarchy_create_from_fine_opt": (_I, [_CSR, _I, _I64P, _I, _OPT, _PP]),
+    "omg_hierarchy_nullspace": (_I, [_P, _IP]),
+    "omg_level_project": (_I, [_P, _I, _P, _DP]),
     "omg_hierarchy_dtype": (_I, [_P, _IP]),
     "omg_hierarchy_update_fine": (_I, [_P, _P, ctypes.c_int64, _I]),
     "omg_hierarchy_destroy": (_I, [_P]),
@@ -268,6 +278,17 @@ def over_correction_of(value):
     return alpha
 
 
+NULLSPACE_NONE, NULLSPACE_CONSTANT = 0, 1
+NULLSPACES = {None: NULLSPACE_NONE, "constant": NULLSPACE_CONSTANT}
+
+
+def nullspace_code(kind):
+    """OMG_NULLSPACE_* for None / 'constant'; ValueError for anything else."""
+    if kind is None or (isinstance(kind, str) and kind in NULLSPACES):
+        return NULLSPACES[kind]
+    raise ValueError("nullspace must be None or 'constant', not %r" % (kind,))
+
+
 DTYPE_F64, DTYPE_F32, DTYPE_MIXED = 0, 1, 2
 
 
@@ -327,12 +348,15 @@ def vec(x, n=None, copy=False):
 class Hierarchy:
     """Device-resident A/R hierarchy (omg_hierarchy)."""
 
-    def __init__(self, A_list, R_list, smoother="gs", omega=1.0, dtype="float64"):
+    def __init__(self, A_list, R_list, smoother="gs", omega=1.0, dtype="float64", nullspace=None):
         """dtype: precision the levels are stored and computed in on the device ("float64", the
         reference's, or "float32"; "mixed": float32 levels with level 0's outer state in float64, for the resident
-        entries); host vectors are float64 either way."""
+        entries); host vectors are float64 either way.  nullspace: None, or 'constant' for a singular operator with
+        zero row and column sums (pure Neumann, periodic): the coarsest operator is inverted on the complement of the
+        constants, resident_load projects the right-hand side and resident_fetch the iterate (OMG_NULLSPACE_CONSTANT)."""
         if len(R_list) != len(A_list) - 1:
             raise ValueError("need len(R) == len(A) - 1")
+        self.nullspace_kind = nullspace_code(nullspace)
         self._A = [as_csr(M) for M in A_list]
         self._R = [as_csr(M) for M in R_list]
         arrA = (CsrView * len(self._A))(*[csr_view(M) for M in self._A])
@@ -343,17 +367,19 @@ class Hierarchy:
         self.sizes = [M.shape[0] for M in self._A]
         h = ctypes.c_void_p()
         self.dtype = dtype_code(dtype)
-        check(lib().omg_hierarchy_create_ex(self.n_levels, arrA, arrR, self.smoother, self.omega, self.dtype,
-                                            ctypes.byref(h)))
+        opt = HierarchyOptions(self.smoother, self.omega, self.dtype, self.nullspace_kind)
+        check(lib().omg_hierarchy_create_opt(self.n_levels, arrA, arrR, ctypes.byref(opt), ctypes.byref(h)))
         self._h = h
         # the device copy is complete; the host copies are only kept for .sizes
         self._A = self._R = None
 
     @classmethod
-    def from_fine(cls, A_in, shape, n_restrictions, smoother="gs", omega=1.0, dtype="float64"):
-        """mgSolve's setup on the device (omg_hierarchy_create_from_fine): restrictions, Galerkin products and the
-        qualification of the levels all in HBM; len(sizes) = n_restrictions + 1."""
+    def from_fine(cls, A_in, shape, n_restrictions, smoother="gs", omega=1.0, dtype="float64", nullspace=None):
+        """mgSolve's setup on the device (omg_hierarchy_create_from_fine_opt): restrictions, Galerkin products and the
+        qualification of the levels all in HBM; len(sizes) = n_restrictions + 1.  nullspace: as for Hierarchy()."""
         self = cls.__new__(cls)
+        self._h = None
+        self.nullspace_kind = nullspace_code(nullspace)
         A0 = as_csr(A_in)
         shape = tuple(int(s) for s in shape)
         arr = (ctypes.c_int64 * len(shape))(*shape)
@@ -364,8 +390,9 @@ class Hierarchy:
         self.sizes = [A0.shape[0] // (2 ** len(shape)) ** l for l in range(self.n_levels)]
         h = ctypes.c_void_p()
         v = csr_view(A0)
-        check(lib().omg_hierarchy_create_from_fine(ctypes.byref(v), len(shape), arr, int(n_restrictions), self.smoother, self.omega,
-                                                   self.dtype, ctypes.byref(h)))
+        opt = HierarchyOptions(self.smoother, self.omega, self.dtype, self.nullspace_kind)
+        check(lib().omg_hierarchy_create_from_fine_opt(ctypes.byref(v), len(shape), arr, int(n_restrictions), ctypes.byref(opt),
+                                                       ctypes.byref(h)))
         self._h = h
         self._A = self._R = None
         return self
@@ -510,6 +537,21 @@ class Hierarchy:
         code = ctypes.c_int(-1)
         check(lib().omg_hierarchy_dtype(self._h, ctypes.byref(code)))
         return np.dtype(np.float32 if code.value in (DTYPE_F32, DTYPE_MIXED) else np.float64)
+
+    @property
+    def nullspace(self):
+        """None or 'constant': the null space the hierarchy was made for (omg_hierarchy_nullspace)."""
+        code = ctypes.c_int(-1)
+        check(lib().omg_hierarchy_nullspace(self._h, ctypes.byref(code)))
+        return {v: k for k, v in NULLSPACES.items()}[code.value]
+
+    def project(self, level, x):
+        """(x - mean(x), mean) of a vector of `level`, formed on the device in the level's precision and ordering
+        (omg_level_project: the projection kernels of a null-space hierarchy, on any hierarchy)."""
+        out = vec(x, self.sizes[level], copy=True)
+        mean = ctypes.c_double(0.0)
+        check(lib().omg_level_project(self._h, int(level), out.ctypes.data, ctypes.byref(mean)))
+        return out, mean.value
 
     def level_sets(self, level):
         v = ctypes.c_int64(0)

@@ -64,6 +64,47 @@ __global__ void narrow_kernel(const double *src, V *dst, int64_t n) {
         dst[i] = V(src[i]);
 }
 
+// W[r, c] += gamma over the left half of the augmented n x 2n matrix: A + gamma 1 1^T (CoarseSolver::nullspace)
+__global__ void add_constant_kernel(double *W, int64_t n, double gamma) {
+    const int64_t tot = n * n;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < tot; t += (int64_t)gridDim.x * blockDim.x)
+        W[(t / n) * (2 * n) + t % n] += gamma;
+}
+
+// OMG_NULLSPACE_CONSTANT: does A have the constant null space (on both sides)?  Every row sum and every column sum at most
+// 1e-10 times the sum of the row's / column's absolute entries — a condition, not a measurement: rounding leaves a few 1e-16
+// there, an operator with a Dirichlet boundary 0.3.  Returns gamma = (sum_i a_ii / n) / n; throws OMG_ERR_INVALID.
+double constant_nullspace_gamma(const HostCsr &A) {
+    const int64_t n = A.n_rows;
+    std::vector<double> csum(size_t(n), 0.0), cabs(size_t(n), 0.0);
+    double trace = 0.0;
+    auto refuse = [&](const char *what, int64_t i, double sum, double mag) {
+        char msg[320];
+        snprintf(msg, sizeof msg, "nullspace = constant: the coarsest operator does not have the constant null space: %s %lld sums to %.3e "
+                 "against %.3e of absolute entries (a Dirichlet boundary, or an operator that is not singular?)", what, (long long)i, sum, mag);
+        throw Error(OMG_ERR_INVALID, msg);
+    };
+    for (int64_t i = 0; i < n; ++i) {
+        double rsum = 0.0, rabs = 0.0;
+        for (int32_t p = A.indptr[i]; p < A.indptr[i + 1]; ++p) {
+            const double v = A.data[p];
+            const int32_t c = A.indices[p];
+            rsum += v;
+            rabs += std::fabs(v);
+            csum[size_t(c)] += v;
+            cabs[size_t(c)] += std::fabs(v);
+            if (c == i) trace += v;
+        }
+        if (!(std::fabs(rsum) <= 1e-10 * rabs)) refuse("row", i, rsum, rabs);
+    }
+    for (int64_t c = 0; c < n; ++c)
+        if (!(std::fabs(csum[size_t(c)]) <= 1e-10 * cabs[size_t(c)])) refuse("column", c, csum[size_t(c)], cabs[size_t(c)]);
+    const double gamma = (trace / double(n)) / double(n);
+    if (!std::isfinite(gamma) || gamma == 0.0)
+        throw Error(OMG_ERR_INVALID, "nullspace = constant: the coarsest operator's diagonal sums to zero or is not finite: nothing to regularise with");
+    return gamma;
+}
+
 // ---- the solve ---------------------------------------------------------------------------
 // y_k = B_k b_I_k: one wave per interior row, four rows of one block per workgroup.
 template <typename V>
@@ -364,7 +405,17 @@ void CoarseSolver<V>::build(const HostCsr &A, hipStream_t s) {
     OMG_REQUIRE(A.n_rows == A.n_cols, "coarse operator must be square");
     n = A.n_rows;
     if (n == 0) return;
-    {   // OMG_COARSE_BLOCKS forces the inverse / substructuring, OMG_COARSE_SINE=0 switches the sine solve off
+    OMG_REQUIRE(nullspace == OMG_NULLSPACE_NONE || nullspace == OMG_NULLSPACE_CONSTANT, "unknown nullspace kind");
+    // a singular operator with the constant null space: the explicit inverse of A + gamma 1 1^T and nothing else
+    const bool ns = nullspace == OMG_NULLSPACE_CONSTANT;
+    double gamma = 0.0;
+    if (ns) {
+        if (n > 16384)
+            throw Error(OMG_ERR_UNSUPPORTED, "nullspace = constant: coarsest level has " + std::to_string(n) +
+                                                 " unknowns; its regularised dense inverse is limited to 16384 — use more gridLevels");
+        gamma = constant_nullspace_gamma(A);
+    }
+    if (!ns) {   // OMG_COARSE_BLOCKS forces the inverse / substructuring, OMG_COARSE_SINE=0 switches the sine solve off
         const char *e = getenv("OMG_COARSE_BLOCKS"), *q = getenv("OMG_COARSE_SINE");
         if (!(e && atoi(e) > 0) && !(q && q[0] == '0') && build_sine(A, s)) return;
     }
@@ -376,7 +427,7 @@ void CoarseSolver<V>::build(const HostCsr &A, hipStream_t s) {
     // number of interior blocks: least stored bytes subject to the LDS limits of the solve kernels
     const int64_t lds_cap = LDS_DOUBLES * int64_t(sizeof(double) / sizeof(V));      // elements of V in 48 KB
     P = 1;
-    {
+    if (!ns) {
         const char *e = getenv("OMG_COARSE_BLOCKS");         // 1 forces the explicit inverse
         const int forced = e ? atoi(e) : 0;
         // Measured at 256^3 / 5 grids (n = 4096, w = 256): the inverse's one 134 MB mat-vec takes
@@ -402,7 +453,7 @@ void CoarseSolver<V>::build(const HostCsr &A, hipStream_t s) {
     put(d_ptr, plain_ptr, s);
     put(d_idx, A.indices, s);
     put(d_val, A.data, s);
-    {   // OMG_COARSE_CHAIN=1 forces the block chain (tests: small operators through the path large ones take)
+    if (!ns) {   // OMG_COARSE_CHAIN=1 forces the block chain (tests: small operators through the path large ones take)
         const char *e = getenv("OMG_COARSE_CHAIN");
         if ((P == 1 && n > 16384) || (e && e[0] == '1' && n >= 4)) {
             build_chain(A, d_ptr.p, d_idx.p, d_val.p, s);
@@ -421,6 +472,10 @@ void CoarseSolver<V>::build(const HostCsr &A, hipStream_t s) {
         if (inv64.n != nn) inv64.alloc(nn);
         if (retain_workspace && ws_keep.n != nn) ws_keep.alloc(nn);
         fill_augmented_from_csr(d_ptr.p, d_idx.p, d_val.p, n, d_map.p, d_map.p, n, W.p, s);
+        if (ns) {
+            hipLaunchKernelGGL(add_constant_kernel, dim3(grid1d(n * n)), dim3(256), 0, s, W.p, n, gamma);
+            OMG_HIP(hipGetLastError());
+        }
         gauss_jordan_inverse(W.p, n, inv64.p, s, retain_workspace ? ws_keep.p : nullptr);
         if (inv.n != nn) inv.alloc(nn);
         hipLaunchKernelGGL((narrow_kernel<V>), dim3(grid1d(n * n)), dim3(256), 0, s, inv64.p, inv.p, n * n);

@@ -102,6 +102,15 @@ void with(H *h, const char *null_message, F &&f) {
 template <typename HP>
 using value_of = typename std::remove_cv<typename std::remove_pointer<HP>::type>::type::value_type;
 
+// The multi-GPU runners (omg_dist_*, omg_pdist_*, omg_sdist_*) project nothing: a tail hierarchy made with a null space
+// (OMG_NULLSPACE_CONSTANT) is refused by their set_tail
+inline void refuse_nullspace_tail(const omg_hierarchy *tail) {
+    int kind = OMG_NULLSPACE_NONE;
+    if (tail && omg_hierarchy_nullspace(tail, &kind) == OMG_OK && kind != OMG_NULLSPACE_NONE)
+        throw Error(OMG_ERR_UNSUPPORTED, "a tail hierarchy with a null space: the multi-GPU runners do not project the right-hand side "
+                                         "and the iterate (single-GPU entries only)");
+}
+
 // OMG_SETUP_TIMING=1: phases of the hierarchy setup, with their wall time, on stderr
 struct SetupTimer {
     const char *what;
@@ -678,6 +687,12 @@ void fill_augmented_from_csr(const int32_t *indptr, const int32_t *indices, cons
 template <typename V>
 struct CoarseSolver {
     int64_t n = 0;
+    // OMG_NULLSPACE_CONSTANT (set before build(), kept across rebuilds): the operator is singular with the constant null
+    // space — zero row and column sums, checked on the host —; build() then inverts A + gamma 1 1^T, gamma = (mean diagonal)
+    // / n, as ONE explicit inverse (P = 1, n <= 16384: no sine solve, no substructuring, no chain).  That matrix is
+    // non-singular, its new eigenvalue the mean diagonal (inside the spectrum), and (A + gamma 1 1^T)^-1 b = pinv(A) b +
+    // mean(b) / (gamma n) 1: the minimum-norm solution of a right-hand side free of constants.  solve() does not change.
+    int nullspace = OMG_NULLSPACE_NONE;
     int P = 1;                        // interior blocks; 1 = explicit inverse; 0 = sine transforms, -1 = block chain (below)
     DevBuf<V> inv;                    // P == 1: n x n
     int64_t n_int = 0, g = 0, w = 0;  // interior / separator unknowns, half-bandwidth
@@ -720,6 +735,17 @@ struct CoarseSolver {
     void solve(const V *b, V *x, hipStream_t s) const;     // original numbering, device pointers
     bool cube16() const;                                   // solve() is one launch of sine_cube16_kernel
 };
+
+// ---- mean projection (nullspace.hip) ---------------------------------------------------------
+// x <- x - mean(x) over the n values of V at x (not a value beyond them: the slack of a DevBuf is neither read nor
+// counted), enqueued on s, no host round trip: a grid-stride launch of at most PROJECT_MAX_WG workgroups leaves one
+// double partial sum per workgroup in a fixed slot of `scratch`, one workgroup folds the slots in a fixed order into
+// scratch[PROJECT_MAX_WG] (the sum: the same bits from run to run — pcg.hip's reduction scheme), a second streaming launch
+// forms mean = sum / n in double and writes V(double(x_i) - mean).  scratch: PROJECT_SCRATCH doubles.
+constexpr int PROJECT_MAX_WG = 2048;
+constexpr int PROJECT_SCRATCH = PROJECT_MAX_WG + 1;
+template <typename V>
+void launch_project_mean(V *x, int64_t n, double *scratch, hipStream_t s);
 
 // ---- lexicographic Gauss-Seidel of grid stencils (march.hip) ---------------------------------
 // The reference's own smoother (openmg/solvers.py:56-68) relaxes the rows in their natural order.

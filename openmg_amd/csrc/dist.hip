@@ -1624,6 +1624,7 @@ int omg_dist_set_stream(omg_dist *d, void *hip_stream) {
 
 int omg_dist_set_tail(omg_dist *d, omg_hierarchy *tail) {
     return guarded([&] {
+        refuse_nullspace_tail(tail);
         with(d, [&](auto *dd) {
             if (tail) {
                 int64_t n = 0;
@@ -1917,6 +1918,7 @@ int omg_pdist_destroy(omg_pdist *d) {
 
 int omg_pdist_set_tail(omg_pdist *d, omg_hierarchy *tail) {
     return guarded([&] {
+        refuse_nullspace_tail(tail);
         OMG_REQUIRE(d && d->d && tail, "null argument");
         int64_t n = 0;
         OMG_REQUIRE(omg_hierarchy_level_rows(tail, 0, &n) == OMG_OK &&

@@ -202,6 +202,8 @@ struct Hier {
     // the scalars (PCG_NSC, then PCG_NSC zeros: beta = 0, not done), the workgroup partials, one norm per iteration
     DevBuf<V> pcg_b, pcg_x, pcg_p, pcg_p2, pcg_q;
     DevBuf<double> pcg_sc, pcg_part, pcg_norms;
+    // mean projection (nullspace.hip; project_vec below): the workgroup partials and, behind them, the folded sum
+    DevBuf<double> proj_scratch;
     // OMG_DTYPE_MIXED (a float hierarchy): the levels as for OMG_DTYPE_F32, and level 0's outer state in double — what the
     // resident entries iterate on (mixed_* below), in the level's numbering.  The operator: on a plane level (pcg_fused_plane)
     // its seven constants taken from the caller's double CSR; otherwise the caller's CSR renumbered into the level's ordering,
@@ -1253,6 +1255,17 @@ void check_level(const Hier<V> *h, int level) {
     OMG_REQUIRE(level >= 0 && level < (int)h->lv.size(), "level out of range");
 }
 
+// A hierarchy made with OMG_NULLSPACE_CONSTANT: the resident right-hand side is projected when it is loaded, the resident
+// iterate when it is fetched (include/openmg_hip.h); the cycle entries in between do not project.
+template <typename V>
+bool has_nullspace(const Hier<V> *h) { return h->coarse.nullspace == OMG_NULLSPACE_CONSTANT; }
+// x <- x - mean(x) over n values of T on the hierarchy's stream; the sum that was removed stays in proj_scratch[PROJECT_MAX_WG]
+template <typename V, typename T>
+void project_vec(Hier<V> *h, T *x, int64_t n) {
+    if (h->proj_scratch.n < size_t(PROJECT_SCRATCH)) h->proj_scratch.alloc(size_t(PROJECT_SCRATCH));
+    launch_project_mean<T>(x, n, h->proj_scratch.p, h->stream);
+}
+
 
 // The row-kernel side of a smoothed level: A and R (and P where the prolongation cannot scatter over R) in
 // the device format of common.h, the residual vector, the block partials, the sweep plan.  A, R: natural
@@ -1339,7 +1352,7 @@ void ensure_format(const Hier<V> *h, int l) { ensure_format(const_cast<Hier<V> *
 
 template <typename V>
 std::unique_ptr<Hier<V>> create(int n_levels, const omg_csr *A, const omg_csr *R, int smoother,
-                                double omega) {
+                                double omega, int nullspace = OMG_NULLSPACE_NONE) {
     using H = Hier<V>;
     using Lv = Level<V>;
     OMG_REQUIRE(n_levels >= 1, "n_levels must be >= 1");
@@ -1359,6 +1372,7 @@ std::unique_ptr<Hier<V>> create(int n_levels, const omg_csr *A, const omg_csr *R
     std::unique_ptr<H> h(new H);
     h->smoother = smoother;
     h->omega = omega;
+    h->coarse.nullspace = nullspace;       // (every build() of this hierarchy's coarse solver honours it: here and in update_fine)
     OMG_HIP(hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking));
     h->stream = h->own;
     h->lv.resize(n_levels);
@@ -1512,7 +1526,8 @@ std::unique_ptr<Hier<V>> create(int n_levels, const omg_csr *A, const omg_csr *R
 // back to the host: the coarsest operator (a few thousand entries) for its factorisation.  A hierarchy with a level
 // that does not qualify takes the ordinary route (its operators are fetched once): the result is the same object.
 template <typename V>
-std::unique_ptr<Hier<V>> create_from_fine(const omg_csr &A0, int dim, const int64_t *shape, int n_restrictions, int smoother, double omega) {
+std::unique_ptr<Hier<V>> create_from_fine(const omg_csr &A0, int dim, const int64_t *shape, int n_restrictions, int smoother, double omega,
+                                          int nullspace = OMG_NULLSPACE_NONE) {
     using H = Hier<V>;
     using Lv = Level<V>;
     OMG_REQUIRE(dim >= 2 && dim <= 3 && shape && n_restrictions >= 1, "device setup: 2-D / 3-D grids, at least one restriction");
@@ -1526,6 +1541,7 @@ std::unique_ptr<Hier<V>> create_from_fine(const omg_csr &A0, int dim, const int6
     std::unique_ptr<H> h(new H);
     h->smoother = smoother;
     h->omega = omega;
+    h->coarse.nullspace = nullspace;
     OMG_HIP(hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking));
     h->stream = h->own;
     h->norm_dev.alloc(1);
@@ -1596,7 +1612,7 @@ std::unique_ptr<Hier<V>> create_from_fine(const omg_csr &A0, int dim, const int6
         for (auto &M : hA) vA.push_back(view(M));
         for (auto &M : hR) vR.push_back(view(M));
         h.reset();
-        return create<V>(n_levels, vA.data(), vR.data(), smoother, omega);
+        return create<V>(n_levels, vA.data(), vR.data(), smoother, omega, nullspace);
     }
     // the coarsest operator: to the host for its factorisation (helper thread, as in create())
     int device = 0;
@@ -2266,6 +2282,7 @@ void mixed_load(Hier<V> *h, const double *b, const double *x0, bool dev) {
         launch_gather<double, double>(src, perm, dst, L.n, h->stream);
     };
     put(b, m.b.p);
+    if (has_nullspace(h)) project_vec(h, m.b.p, L.n);              // (the fp64 outer b; the initial iterate stays)
     if (x0) put(x0, m.x.p);
     else OMG_HIP(hipMemsetAsync(m.x.p, 0, size_t(L.n) * sizeof(double), h->stream));
     OMG_HIP(hipStreamSynchronize(h->stream));
@@ -2275,6 +2292,7 @@ template <typename V>
 void mixed_fetch(Hier<V> *h, double *x, bool dev) {
     Level<V> &L = h->lv[0];
     const int32_t *perm = L.ord.identity ? nullptr : L.perm.p;
+    if (has_nullspace(h)) project_vec(h, h->mx.x.p, L.n);          // (the fp64 outer x, in place)
     if (dev) {
         launch_scatter<double, double>(h->mx.x.p, perm, x, L.n, h->stream);
         OMG_HIP(hipStreamSynchronize(h->stream));
@@ -2334,18 +2352,26 @@ int omg_device_synchronize(void) {
     return guarded([&] { require_device(); OMG_HIP(hipDeviceSynchronize()); });
 }
 
-int omg_hierarchy_create_ex(int n_levels, const omg_csr *A, const omg_csr *R, int smoother,
-                            double omega, int dtype, omg_hierarchy **out) {
+int omg_hierarchy_create_opt(int n_levels, const omg_csr *A, const omg_csr *R, const omg_hierarchy_options *opt, omg_hierarchy **out) {
     return guarded([&] {
         OMG_REQUIRE(out, "out is null");
         *out = nullptr;
+        OMG_REQUIRE(opt, "options are null");
+        const int dtype = opt->dtype;
         OMG_REQUIRE(dtype == OMG_DTYPE_F64 || dtype == OMG_DTYPE_F32 || dtype == OMG_DTYPE_MIXED, "unknown dtype");
+        OMG_REQUIRE(opt->nullspace == OMG_NULLSPACE_NONE || opt->nullspace == OMG_NULLSPACE_CONSTANT, "unknown nullspace kind");
         std::unique_ptr<omg_hierarchy> h(new omg_hierarchy);
-        if (dtype != OMG_DTYPE_F64) h->f = create<float>(n_levels, A, R, smoother, omega);
-        else h->d = create<double>(n_levels, A, R, smoother, omega);
+        if (dtype != OMG_DTYPE_F64) h->f = create<float>(n_levels, A, R, opt->smoother, opt->omega, opt->nullspace);
+        else h->d = create<double>(n_levels, A, R, opt->smoother, opt->omega, opt->nullspace);
         if (dtype == OMG_DTYPE_MIXED) build_mixed(h->f.get(), A[0]);
         *out = h.release();
     });
+}
+
+int omg_hierarchy_create_ex(int n_levels, const omg_csr *A, const omg_csr *R, int smoother,
+                            double omega, int dtype, omg_hierarchy **out) {
+    const omg_hierarchy_options opt = {smoother, omega, dtype, OMG_NULLSPACE_NONE};
+    return omg_hierarchy_create_opt(n_levels, A, R, &opt, out);
 }
 
 int omg_hierarchy_create(int n_levels, const omg_csr *A, const omg_csr *R, int smoother,
@@ -2353,17 +2379,33 @@ int omg_hierarchy_create(int n_levels, const omg_csr *A, const omg_csr *R, int s
     return omg_hierarchy_create_ex(n_levels, A, R, smoother, omega, OMG_DTYPE_F64, out);
 }
 
-int omg_hierarchy_create_from_fine(const omg_csr *A_in, int dim, const int64_t *shape, int n_restrictions, int smoother, double omega,
-                                   int dtype, omg_hierarchy **out) {
+int omg_hierarchy_create_from_fine_opt(const omg_csr *A_in, int dim, const int64_t *shape, int n_restrictions,
+                                       const omg_hierarchy_options *opt, omg_hierarchy **out) {
     return guarded([&] {
         OMG_REQUIRE(out && A_in, "null argument");
         *out = nullptr;
+        OMG_REQUIRE(opt, "options are null");
+        const int dtype = opt->dtype;
         OMG_REQUIRE(dtype == OMG_DTYPE_F64 || dtype == OMG_DTYPE_F32 || dtype == OMG_DTYPE_MIXED, "unknown dtype");
+        OMG_REQUIRE(opt->nullspace == OMG_NULLSPACE_NONE || opt->nullspace == OMG_NULLSPACE_CONSTANT, "unknown nullspace kind");
         std::unique_ptr<omg_hierarchy> h(new omg_hierarchy);
-        if (dtype != OMG_DTYPE_F64) h->f = create_from_fine<float>(*A_in, dim, shape, n_restrictions, smoother, omega);
-        else h->d = create_from_fine<double>(*A_in, dim, shape, n_restrictions, smoother, omega);
+        if (dtype != OMG_DTYPE_F64) h->f = create_from_fine<float>(*A_in, dim, shape, n_restrictions, opt->smoother, opt->omega, opt->nullspace);
+        else h->d = create_from_fine<double>(*A_in, dim, shape, n_restrictions, opt->smoother, opt->omega, opt->nullspace);
         if (dtype == OMG_DTYPE_MIXED) build_mixed(h->f.get(), *A_in);
         *out = h.release();
+    });
+}
+
+int omg_hierarchy_create_from_fine(const omg_csr *A_in, int dim, const int64_t *shape, int n_restrictions, int smoother, double omega,
+                                   int dtype, omg_hierarchy **out) {
+    const omg_hierarchy_options opt = {smoother, omega, dtype, OMG_NULLSPACE_NONE};
+    return omg_hierarchy_create_from_fine_opt(A_in, dim, shape, n_restrictions, &opt, out);
+}
+
+int omg_hierarchy_nullspace(const omg_hierarchy *h, int *kind) {
+    return guarded([&] {
+        OMG_REQUIRE(kind, "null argument");
+        with(h, [&](auto *hh) { *kind = hh->coarse.nullspace; });
     });
 }
 
@@ -2687,6 +2729,7 @@ int omg_resident_load_dev(omg_hierarchy *h, const double *b_dev, const double *x
             }
             auto &L = hh->lv[0];
             load_vec_dev(hh, 0, b_dev, L.b.p);
+            if (has_nullspace(hh)) project_vec(hh, L.b.p, L.n);
             if (x0_dev) load_vec_dev(hh, 0, x0_dev, L.xp);
             else OMG_HIP(hipMemsetAsync(L.xp, 0, L.n * sizeof(V), hh->stream));
             OMG_HIP(hipStreamSynchronize(hh->stream));
@@ -2705,6 +2748,7 @@ int omg_resident_fetch_dev(omg_hierarchy *h, double *x_dev) {
                 mixed_fetch(hh, x_dev, true);
                 return;
             }
+            if (has_nullspace(hh)) project_vec(hh, hh->lv[0].xp, hh->lv[0].n);
             fetch_vec_dev<V>(hh, 0, hh->lv[0].xp, x_dev);
             OMG_HIP(hipStreamSynchronize(hh->stream));
             check_march(hh);
@@ -2757,6 +2801,7 @@ int omg_resident_load(omg_hierarchy *h, const double *b, const double *x0) {
             }
             auto &L = hh->lv[0];
             load_vec(hh, 0, b, L.b.p);
+            if (has_nullspace(hh)) project_vec(hh, L.b.p, L.n);
             if (x0) load_vec(hh, 0, x0, L.xp);
             else OMG_HIP(hipMemsetAsync(L.xp, 0, L.n * sizeof(V), hh->stream));
             OMG_HIP(hipStreamSynchronize(hh->stream));
@@ -2953,6 +2998,7 @@ int omg_resident_fetch(omg_hierarchy *h, double *x) {
                 mixed_fetch(hh, x, false);
                 return;
             }
+            if (has_nullspace(hh)) project_vec(hh, hh->lv[0].xp, hh->lv[0].n);
             fetch_vec<V>(hh, 0, hh->lv[0].xp, x);
         });
     });
@@ -2994,6 +3040,7 @@ int omg_solve(omg_hierarchy *h, const double *b, double *x, int pre, int post, i
                         "Either threshold or cycles must be > 0");   // openmg/__init__.py:118-119
             auto &L = hh->lv[0];
             load_vec(hh, 0, b, L.b.p);
+            if (has_nullspace(hh)) project_vec(hh, L.b.p, L.n);       // (load, cycles, fetch: as the resident entries)
             load_vec(hh, 0, x, L.xp);
             hh->resident = true;
             int cycle = 0;
@@ -3006,6 +3053,7 @@ int omg_solve(omg_hierarchy *h, const double *b, double *x, int pre, int post, i
                 const bool by_norm = threshold > 0.0 && nv < threshold;
                 if (by_cycles || by_norm) break;
             }
+            if (has_nullspace(hh)) project_vec(hh, L.xp, L.n);
             fetch_vec<V>(hh, 0, L.xp, x);
             if (cycles_done) *cycles_done = cycle;
             if (norm) *norm = nv;
@@ -3059,6 +3107,24 @@ int omg_level_smooth(omg_hierarchy *h, int level, const double *b, double *x, in
             load_vec(hh, level, x, L.xp);
             smooth_level(hh, level, iterations);
             fetch_vec<V>(hh, level, L.xp, x);
+        });
+    });
+}
+
+int omg_level_project(omg_hierarchy *h, int level, double *x_inout, double *mean) {
+    return guarded([&] {
+        with(h, [&](auto *hh) {
+            using V = value_of<decltype(hh)>;
+            check_level(hh, level);
+            OMG_REQUIRE(x_inout, "x is null");
+            auto &L = hh->lv[level];
+            hh->resident = false;
+            load_vec(hh, level, x_inout, L.xp);
+            project_vec(hh, L.xp, L.n);
+            double sum = 0.0;
+            OMG_HIP(hipMemcpyAsync(&sum, hh->proj_scratch.p + PROJECT_MAX_WG, sizeof(double), hipMemcpyDeviceToHost, hh->stream));
+            fetch_vec<V>(hh, level, L.xp, x_inout);                   // (synchronises)
+            if (mean) *mean = L.n > 0 ? sum / double(L.n) : 0.0;
         });
     });
 }
