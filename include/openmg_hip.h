@@ -156,6 +156,9 @@ int omg_level_project(omg_hierarchy *h, int level, double *x_inout, double *mean
  * or one of the small host-coded levels below them: the products are re-formed the same way, the host-coded levels
  * rebuilt from theirs.  Any other hierarchy: OMG_ERR_INVALID. */
 int omg_hierarchy_update_fine(omg_hierarchy *h, const double *data, int64_t nnz, int on_device);
+/* *yes = 1 exactly when omg_hierarchy_update_fine takes this hierarchy (the two kinds named above), else 0: a caller
+ * that holds one hierarchy for many solves asks before it decides between an update and a new setup. */
+int omg_hierarchy_can_update_fine(const omg_hierarchy *h, int *yes);
 int omg_hierarchy_dtype(const omg_hierarchy *h, int *dtype);
 int omg_hierarchy_destroy(omg_hierarchy *h);
 /* Run on a caller-owned hipStream_t instead of the hierarchy's own stream (NULL = own). */
@@ -300,6 +303,15 @@ int omg_resident_spmv_time(omg_hierarchy *h, int reps, double *avg_ms);
  * the reductions are deterministic (same bits from run to run, with or without omg_resident_use_graph). */
 int omg_resident_pcg(omg_hierarchy *h, int pre, int post, int max_iter, double threshold, int *iterations,
                      double *norms /* nullable */, double *true_norm, int *breakdown);
+/* Norms of the resident state without running a cycle (either pointer may be NULL): *rhs_norm = ||b||_2 of the resident
+ * right-hand side as it is held — after the null-space projection of omg_resident_load[_dev]; the fp64 outer b of an
+ * OMG_DTYPE_MIXED hierarchy —, *residual_norm = ||b - A x||_2 of the resident iterate, A level 0's operator (the fp64
+ * outer operator of a mixed hierarchy).  The residual is formed in the level's precision (double on a mixed hierarchy),
+ * every sum in double: fixed partial slots and a one-workgroup fold, the same bits from run to run.  Works on every kind
+ * of level 0 (a residual needs at least two levels: OMG_ERR_INVALID on a single-level hierarchy) and leaves b, x and the
+ * levels' vectors untouched: a cycle, an omg_resident_pcg run or a replayed graph after it has the bits it would have
+ * had without it.  A relative stop rule, or "the warm start is already good enough", is decided from these two. */
+int omg_resident_norms(omg_hierarchy *h, double *rhs_norm, double *residual_norm);
 /* Capture one resident cycle into a hipGraph and replay it on later omg_resident_cycle
  * calls with the same (pre, post).  enable = 0 drops the graph.                          */
 int omg_resident_use_graph(omg_hierarchy *h, int enable);

@@ -47,6 +47,12 @@ Extra keys understood in the `parameters` dict (ignored by the reference):
 
 `b` and `initial` may be DEVICE arrays (objects with `__cuda_array_interface__`, e.g. PyTorch-ROCm tensors: contiguous
 float64): mgCycle / mgSolve then return a device array of the same kind and only the norm crosses PCIe.
+
+Many right-hand sides with one operator (a time-stepping loop's pressure solves): `Solver(A_in, parameters)` runs
+mgSolve's whole setup once; `solve(b, initial=None, out=None, **overrides)` then costs the solve alone, may start from
+the previous step's u, stops below max('threshold', 'rtol' * ||b||) or after 'cycles' and returns (u, info) — from zero,
+the bits of mgSolve; `apply(r)` is one zero-start cycle (a preconditioner), `update(A_new)` takes new values in the same
+pattern, `close()` frees the device (openmg_amd/_solver.py).
 """
 import weakref
 
@@ -58,7 +64,7 @@ from . import operators, solvers, tools
 from .solvers import coarseSolve, smooth, smoothToThreshold
 
 __all__ = ["mgSolve", "mgCycle", "mg_cycle", "defaults", "smooth", "smoothToThreshold",
-           "coarseSolve", "tools", "operators", "solvers", "clear_cache"]
+           "coarseSolve", "tools", "operators", "solvers", "clear_cache", "Solver"]
 
 # Same keys and values as the reference (openmg/__init__.py:16-27).  Like there, this dict
 # is module-global and mgSolve writes 'coarsestLevel' into it on every call.
@@ -204,38 +210,9 @@ def mgSolve(A_in, b, parameters):
     Returns u, or (u, infoDict) when parameters['giveInfo'] is true; infoDict holds
     'cycle', 'norm', and the hierarchies 'R' and 'A' as SciPy CSR lists.
     """
-    accel = parameters.get("accel")
-    if accel not in (None, "cg"):
-        raise ValueError("parameters['accel'] must be None or 'cg', not %r" % (accel,))
-    shape, alpha = _cycle_of(parameters)
-    nullspace = _nullspace_of(parameters)
-    problemShape = parameters["problemShape"]
-    gridLevels = parameters["gridLevels"]
-    defaults["coarsestLevel"] = gridLevels - 1
-    tools.dictUpdateNoClobber(defaults, parameters)
+    hierarchy, R, A, accel, shape, alpha = _setup(A_in, parameters, defaults)
     verbose = parameters["verbose"]
-    dense = parameters["dense"]
-    code, omega = _smoother_of(parameters)
-
     pre, post = parameters["preIterations"], parameters["postIterations"]
-    # (the device route qualifies levels for the FUSED paths, which exist for the colour orderings and 2-D weighted Jacobi; with
-    # the reference's own lexicographic smoother it would build the Galerkin chain in HBM only to fetch it again for the host's
-    # orderings and codings: 1.14 s of setup at 256^3 where the lists route below takes 0.7)
-    fused_smoother = code == _hip.SMOOTH_GS_COLOUR or (code == _hip.SMOOTH_JACOBI and len(tuple(problemShape)) == 2)
-    n_fused = _device_setup_depth(A_in, problemShape, parameters) if fused_smoother else 0
-    if n_fused:
-        # nobody asked for the operator lists (giveInfo off): restrictions, Galerkin products and the levels' qualification
-        # for the fused paths stay in HBM (omg_hierarchy_create_from_fine); same hierarchy, same results
-        R = A = None
-        parameters["coarsestLevel"] = n_fused
-        hierarchy = _hip.Hierarchy.from_fine(A_in, problemShape, n_fused, smoother=code, omega=omega, dtype=_dtype_of(parameters),
-                                             nullspace=nullspace)
-    else:
-        R = operators.restrictionList(problemShape, parameters["coarsestLevel"], parameters["minSize"],
-                                      dense=dense, verbose=verbose)
-        parameters["coarsestLevel"] = len(R)
-        A = operators.coeffecientList(A_in, R, dense=dense, verbose=verbose)
-        hierarchy = _hip.Hierarchy(A, R, smoother=code, omega=omega, dtype=_dtype_of(parameters), nullspace=nullspace)
     depth = parameters["coarsestLevel"]
     b_on_device = _devarray.is_device_array(b)
     try:
@@ -265,18 +242,66 @@ def mgSolve(A_in, b, parameters):
     return result
 
 
+def _accel_of(parameters):
+    accel = parameters.get("accel")
+    if accel not in (None, "cg"):
+        raise ValueError("parameters['accel'] must be None or 'cg', not %r" % (accel,))
+    return accel
+
+
+def _setup(A_in, parameters, completed_from):
+    """mgSolve's whole setup, shared with Solver: checks the keys, completes `parameters` in place from `completed_from`
+    (mgSolve: the module-global `defaults`, which gets its 'coarsestLevel' written as in the reference; Solver: a copy),
+    writes the depth actually built into parameters['coarsestLevel'] and builds the device hierarchy.  Returns
+    (hierarchy, R, A, accel, cycle shape, over-correction factor); R = A = None on the device route (giveInfo off)."""
+    accel = _accel_of(parameters)
+    shape, alpha = _cycle_of(parameters)
+    nullspace = _nullspace_of(parameters)
+    problemShape = parameters["problemShape"]
+    gridLevels = parameters["gridLevels"]
+    completed_from["coarsestLevel"] = gridLevels - 1
+    tools.dictUpdateNoClobber(completed_from, parameters)
+    verbose = parameters["verbose"]
+    dense = parameters["dense"]
+    code, omega = _smoother_of(parameters)
+
+    # (the device route qualifies levels for the FUSED paths, which exist for the colour orderings and 2-D weighted Jacobi; with
+    # the reference's own lexicographic smoother it would build the Galerkin chain in HBM only to fetch it again for the host's
+    # orderings and codings: 1.14 s of setup at 256^3 where the lists route below takes 0.7)
+    fused_smoother = code == _hip.SMOOTH_GS_COLOUR or (code == _hip.SMOOTH_JACOBI and len(tuple(problemShape)) == 2)
+    n_fused = _device_setup_depth(A_in, problemShape, parameters) if fused_smoother else 0
+    if n_fused:
+        # nobody asked for the operator lists (giveInfo off): restrictions, Galerkin products and the levels' qualification
+        # for the fused paths stay in HBM (omg_hierarchy_create_from_fine); same hierarchy, same results
+        R = A = None
+        parameters["coarsestLevel"] = n_fused
+        hierarchy = _hip.Hierarchy.from_fine(A_in, problemShape, n_fused, smoother=code, omega=omega, dtype=_dtype_of(parameters),
+                                             nullspace=nullspace)
+    else:
+        R = operators.restrictionList(problemShape, parameters["coarsestLevel"], parameters["minSize"],
+                                      dense=dense, verbose=verbose)
+        parameters["coarsestLevel"] = len(R)
+        A = operators.coeffecientList(A_in, R, dense=dense, verbose=verbose)
+        hierarchy = _hip.Hierarchy(A, R, smoother=code, omega=omega, dtype=_dtype_of(parameters), nullspace=nullspace)
+    return hierarchy, R, A, accel, shape, alpha
+
+
 # CG iterations per omg_resident_pcg call when only 'threshold' stops the solve (the next call restarts from the iterate)
 _CG_CHUNK = 10000
 
 
-def _solve_cg(hierarchy, parameters, pre, post, depth, verbose, shape="V"):
-    """mgSolve's loop with parameters['accel'] == 'cg': FCG on the resident iterate; returns (iterations, true norm)."""
+def _solve_cg(hierarchy, parameters, pre, post, depth, verbose, shape="V", observe=None):
+    """mgSolve's loop with parameters['accel'] == 'cg': FCG on the resident iterate; returns (iterations, true norm).
+    observe (Solver): called with (iteration, recurrence norm) for every iteration, before a breakdown is reported."""
     cycles, threshold = parameters["cycles"], parameters["threshold"]
     both_off = threshold <= 0 and cycles <= 0
     done = 0
     while True:
         max_iter = 1 if both_off else (cycles - done if cycles > 0 else _CG_CHUNK)
         its, norms, norm, breakdown = hierarchy.resident_pcg(pre, post, max_iter, threshold if threshold > 0 else 0.0)
+        if observe is not None:
+            for k, nk in enumerate(norms):
+                observe(done + k + 1, float(nk))
         if verbose:
             for k, nk in enumerate(norms):
                 _announce_descent(depth, shape)
@@ -291,12 +316,15 @@ def _solve_cg(hierarchy, parameters, pre, post, depth, verbose, shape="V"):
             return done, norm
 
 
-def _solve_cycles(hierarchy, parameters, pre, post, depth, verbose, shape="V"):
-    """mgSolve's loop of plain V-cycles (openmg/__init__.py:112-138); returns (cycles, norm)."""
+def _solve_cycles(hierarchy, parameters, pre, post, depth, verbose, shape="V", observe=None):
+    """mgSolve's loop of plain V-cycles (openmg/__init__.py:112-138); returns (cycles, norm).
+    observe (Solver): called with (cycle, norm) for every cycle as soon as its norm is on the host."""
     if verbose:
         _announce_descent(depth, shape)
     norm = hierarchy.resident_cycle(pre, post)
     cycle = 1
+    if observe is not None:
+        observe(cycle, norm)
     if verbose:
         print("Residual norm from cycle %d is %f." % (cycle, norm))
     if parameters["threshold"] <= 0 and parameters["cycles"] <= 0:
@@ -310,7 +338,11 @@ def _solve_cycles(hierarchy, parameters, pre, post, depth, verbose, shape="V"):
     if (not verbose and parameters.get("cycles", 0) > cycle and not parameters.get("threshold", 0) > 0):
         # stop rule = cycle count only: the remaining cycles go to the device in one call (every
         # cycle's norm is still computed; only the last one is observable here)
-        norm = hierarchy.resident_cycles(pre, post, parameters["cycles"] - cycle)[-1]
+        batch = hierarchy.resident_cycles(pre, post, parameters["cycles"] - cycle)
+        norm = batch[-1]
+        if observe is not None:
+            for k, nk in enumerate(batch):
+                observe(cycle + k + 1, nk)
         cycle = parameters["cycles"]
     while not finished():
         if verbose:
@@ -318,6 +350,8 @@ def _solve_cycles(hierarchy, parameters, pre, post, depth, verbose, shape="V"):
             _announce_descent(depth, shape)
         cycle += 1
         norm = hierarchy.resident_cycle(pre, post)
+        if observe is not None:
+            observe(cycle, norm)
         if verbose:
             print("Residual norm from cycle %d is %f." % (cycle, norm))
     return cycle, norm
@@ -437,3 +471,5 @@ def mgCycle(A, b, level, R, parameters, initial=None):
 
 
 mg_cycle = mgCycle   # BASELINE.json's spelling
+
+from ._solver import Solver  # noqa: E402  (it shares the setup and the loops above)

@@ -70,6 +70,8 @@ SIGNATURES = {
     "omg_level_project": (_I, [_P, _I, _P, _DP]),
     "omg_hierarchy_dtype": (_I, [_P, _IP]),
     "omg_hierarchy_update_fine": (_I, [_P, _P, ctypes.c_int64, _I]),
+    "omg_hierarchy_can_update_fine": (_I, [_P, _IP]),
+    "omg_resident_norms": (_I, [_P, _DP, _DP]),
     "omg_hierarchy_destroy": (_I, [_P]),
     "omg_hierarchy_set_stream": (_I, [_P, _P]),
     "omg_hierarchy_sync": (_I, [_P]),
@@ -409,6 +411,12 @@ class Hierarchy:
             d = np.ascontiguousarray(data, dtype=np.float64)
             check(lib().omg_hierarchy_update_fine(self._h, d.ctypes.data, d.size, 0))
 
+    def can_update_fine(self):
+        """Whether update_fine takes this hierarchy (omg_hierarchy_can_update_fine)."""
+        yes = ctypes.c_int(0)
+        check(lib().omg_hierarchy_can_update_fine(self._h, ctypes.byref(yes)))
+        return bool(yes.value)
+
     def close(self):
         if getattr(self, "_h", None):
             lib().omg_hierarchy_destroy(self._h)
@@ -499,8 +507,15 @@ class Hierarchy:
         check(lib().omg_resident_cycles(self._h, int(pre), int(post), int(n_cycles), norms))
         return [float(norms[k]) for k in range(int(n_cycles))]
 
-    def resident_fetch(self):
-        x = np.empty(self.sizes[0], dtype=np.float64)
+    def resident_fetch(self, out=None):
+        """The resident iterate as a new array, or written into `out` (contiguous float64 of level 0's size)."""
+        if out is None:
+            x = np.empty(self.sizes[0], dtype=np.float64)
+        else:
+            x = out
+            if not (isinstance(x, np.ndarray) and x.dtype == np.float64 and x.flags.c_contiguous and x.flags.writeable
+                    and x.size == self.sizes[0]):
+                raise ValueError("out must be a writeable contiguous float64 array of %d entries" % self.sizes[0])
         check(lib().omg_resident_fetch(self._h, x.ctypes.data))
         return x
 
@@ -516,6 +531,13 @@ class Hierarchy:
         check(lib().omg_resident_pcg(self._h, int(pre), int(post), max_iter, float(threshold), ctypes.byref(it),
                                      norms.ctypes.data_as(_DP), ctypes.byref(tn), ctypes.byref(bd)))
         return int(it.value), norms[:it.value].copy(), float(tn.value), bool(bd.value)
+
+    def resident_norms(self, rhs=True, residual=True):
+        """(||b||, ||b - A x||) of the resident state without a cycle (omg_resident_norms); None for the one not asked
+        for.  The state is untouched: what runs afterwards has the bits it would have had."""
+        nb, nr = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        check(lib().omg_resident_norms(self._h, ctypes.byref(nb) if rhs else None, ctypes.byref(nr) if residual else None))
+        return (nb.value if rhs else None), (nr.value if residual else None)
 
     def spmv_time(self, reps=20):
         """Average milliseconds of one fine-grid y = A[0] x launch on the resident operator."""

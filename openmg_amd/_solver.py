@@ -1,0 +1,234 @@
+"""openmg_amd.Solver: mgSolve's setup once, then many right-hand sides on the hierarchy it built.
+
+    s = openmg_amd.Solver(A_in, parameters)     # restrictions, Galerkin products, upload, qualification: once
+    u, info = s.solve(b, initial=None, out=None, **overrides)
+    z = s.apply(r, out=None)                    # one zero-start cycle, z = M r (a preconditioner for the caller's own iteration)
+    s.update(A_new)                             # new values in the same pattern
+    s.close()                                   # also a context manager
+
+The setup and the two loops are mgSolve's own (openmg_amd._setup, _solve_cycles, _solve_cg): a solve from zero has the
+bits of mgSolve(A_in, b, parameters).  What a solve leaves on the device is the resident b and x, the cycle setting and
+the FCG vectors; the next solve loads b and x again, sets the cycle again and FCG starts from its own set-up, so that no
+solve sees anything of an earlier one.  Not thread safe; one GPU; b is one vector.
+"""
+import math
+
+import numpy as np
+
+from . import _devarray, _hip
+
+# the keys a solve may override: those that do not define the hierarchy
+SOLVE_KEYS = ("cycles", "threshold", "rtol", "preIterations", "postIterations", "accel", "cycle", "overCorrection")
+
+
+def stop_target(cycles, threshold, rtol, rhs_norm=None):
+    """The residual norm a solve stops below: max(threshold, rtol * rhs_norm), 0.0 when neither rule is on (then only
+    `cycles` stops it).  ValueError when all three rules are off or rtol is not a finite number >= 0.  rhs_norm None:
+    the check alone (before any device work).  A right-hand side whose norm is not finite leaves the threshold alone:
+    the first cycle's norm then reports it."""
+    try:
+        rtol = float(rtol)
+    except (TypeError, ValueError):
+        raise ValueError("rtol must be a finite number >= 0, not %r" % (rtol,))
+    if not math.isfinite(rtol) or rtol < 0.0:
+        raise ValueError("rtol must be a finite number >= 0, not %r" % (rtol,))
+    if not (threshold > 0 or rtol > 0.0 or cycles > 0):
+        raise ValueError("Either 'threshold', 'rtol' or 'cycles' must be > 0.")
+    if rhs_norm is None:
+        return None
+    target = float(threshold) if threshold > 0 else 0.0
+    relative = rtol * rhs_norm
+    return relative if relative > target else target
+
+
+def _host_out(out, n):
+    """A new result array, or the caller's `out` checked: writeable contiguous float64 of n entries."""
+    if out is None:
+        return np.empty(n)
+    if not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous and out.flags.writeable and out.size == n):
+        raise ValueError("out must be a writeable contiguous float64 array of %d entries" % n)
+    return out
+
+
+def _check_keys(parameters):
+    """ValueError for a value mgSolve would refuse — before any device work, GPU or not."""
+    from . import _accel_of, _cycle_of, _dtype_of, _nullspace_of, _smoother_of
+    _accel_of(parameters)
+    _cycle_of(parameters)
+    _nullspace_of(parameters)
+    _smoother_of(parameters)
+    try:
+        _dtype_of(parameters)
+    except TypeError:
+        raise ValueError("parameters['dtype'] must be 'float64', 'float32' or 'mixed', not %r" % (parameters.get("dtype"),))
+
+
+class Solver:
+    """A hierarchy set up once for A_in and `parameters` (every key mgSolve understands, and 'rtol'), solving many
+    right-hand sides.  .parameters: the solver's own completed copy (the caller's dict and openmg_amd.defaults are not
+    touched); .hierarchy: the _hip.Hierarchy; .A / .R: the operator lists when parameters['giveInfo'] asked for the
+    lists route, else None."""
+
+    def __init__(self, A_in, parameters):
+        from . import _setup, defaults
+        self._hierarchy = None
+        given = dict(parameters)
+        _check_keys(given)
+        stop_target(1, 0.0, given.get("rtol", 0.0))                 # (rtol alone: the stop rules are checked per solve)
+        self._given = given
+        completed = dict(given)
+        self._hierarchy, self.R, self.A = _setup(A_in, completed, dict(defaults))[:3]
+        completed.setdefault("rtol", 0.0)
+        self.parameters = completed
+        self._pattern_of(A_in)
+
+    def _pattern_of(self, A_in):
+        A0 = _hip.as_csr(A_in)
+        self._shape, self._indptr, self._indices = A0.shape, A0.indptr, A0.indices
+
+    # ---- life cycle -------------------------------------------------------------------------------------------------
+    @property
+    def hierarchy(self):
+        """The _hip.Hierarchy the solver runs on (level_flags and the other probes)."""
+        return self._open()
+
+    def _open(self):
+        if self._hierarchy is None:
+            raise RuntimeError("this Solver has been closed")
+        return self._hierarchy
+
+    def close(self):
+        """Free the device hierarchy; a second call does nothing, any other call afterwards raises RuntimeError."""
+        h, self._hierarchy = getattr(self, "_hierarchy", None), None
+        if h is not None:
+            h.close()
+
+    def __enter__(self):
+        self._open()
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- solve --------------------------------------------------------------------------------------------------------
+    def solve(self, b, initial=None, out=None, **overrides):
+        """Solve A u = b from `initial` (None: zero).  Stops below max(threshold, rtol * ||b||) or after `cycles` (> 0)
+        cycles / FCG iterations; a start that is already below the target returns at once with info['cycle'] == 0.
+        overrides: SOLVE_KEYS, for this call only.  b, initial, out: host arrays, or contiguous float64 device arrays
+        (then u is a device array: `out`, or a new one of b's kind).  With a null space b is projected on the device
+        (rhs_norm and every norm are the projected system's), `initial` is taken as it is and u has mean 0.
+
+        Returns (u, info): info['cycle'], ['norm'] (mgSolve's meaning: the true fp64 norm for 'cg' and 'mixed'),
+        ['norms'] (one per cycle or iteration), ['rhs_norm'], ['initial_norm'].  A norm that is not finite raises
+        RuntimeError naming the cycle; the solver stays usable."""
+        from . import _accel_of, _cycle_of, _solve_cg, _solve_cycles
+        h = self._open()
+        for key in overrides:
+            if key not in SOLVE_KEYS:
+                raise ValueError("solve() cannot override %r (it defines the hierarchy); allowed: %s" % (key, ", ".join(SOLVE_KEYS)))
+        p = dict(self.parameters, **overrides)
+        accel = _accel_of(p)
+        shape, alpha = _cycle_of(p)
+        pre, post = int(p["preIterations"]), int(p["postIterations"])
+        if pre < 0 or post < 0:
+            raise ValueError("preIterations and postIterations must be >= 0")
+        cycles, threshold, rtol = p["cycles"], p["threshold"], p["rtol"]
+        stop_target(cycles, threshold, rtol)
+        n = h.sizes[0]
+        on_device = _devarray.is_device_array(b)
+        if _devarray.is_device_array(initial) != (on_device and initial is not None):
+            raise TypeError("Solver.solve: `b` and `initial` must both be device arrays or both be host arrays")
+        if out is not None and _devarray.is_device_array(out) != on_device:
+            raise TypeError("Solver.solve: `out` must be a device array exactly when `b` is one")
+        verbose = p["verbose"]
+
+        h.set_cycle(shape, alpha)
+        if on_device:
+            if out is not None:
+                _devarray.address(out, n, "out")                    # (a wrong `out` is refused before the solve, not after)
+            _devarray.synchronize()
+            h.resident_load_dev(_devarray.address(b, n, "b"), None if initial is None else _devarray.address(initial, n, "initial"))
+        else:
+            out = _host_out(out, n)
+            h.resident_load(np.asarray(b, dtype=np.float64).reshape(-1), initial)
+        # ||b|| as it is held, and the start's residual: without `initial` that is ||b|| itself (no SpMV)
+        rhs_norm, initial_norm = h.resident_norms(rhs=True, residual=initial is not None)
+        if initial is None:
+            initial_norm = rhs_norm
+        target = stop_target(cycles, threshold, rtol, rhs_norm)
+        norms = []
+
+        def observe(k, value):
+            norms.append(float(value))
+            if not math.isfinite(value):
+                raise RuntimeError("Solver.solve: the residual norm of cycle %d is not finite (%r)" % (k, value))
+
+        if target > 0.0 and (initial_norm < target or initial_norm == 0.0):
+            cycle, norm = 0, initial_norm
+        else:
+            loop = dict(p, cycles=cycles, threshold=target)
+            run = _solve_cg if accel == "cg" else _solve_cycles
+            cycle, norm = run(h, loop, pre, post, self.parameters["coarsestLevel"], verbose, shape, observe)
+            if not math.isfinite(norm):
+                raise RuntimeError("Solver.solve: the residual norm after cycle %d is not finite (%r)" % (cycle, norm))
+        if on_device:
+            u = _devarray.empty_like(b, n) if out is None else out
+            h.resident_fetch_dev(_devarray.address(u, n, "out"))
+        else:
+            u = h.resident_fetch(out)
+        return u, {"cycle": cycle, "norm": norm, "norms": norms, "rhs_norm": rhs_norm, "initial_norm": initial_norm}
+
+    # ---- apply --------------------------------------------------------------------------------------------------------
+    def apply(self, r, out=None):
+        """z = M r: one cycle from zero with the construction's sweep counts, cycle shape and over-correction factor —
+        mgCycle(A, r, 0, R, ...)[0] without its checksum of the lists.  Nothing is projected.  r, out: host arrays, or
+        device arrays (then z is a device array).  ValueError on a mixed hierarchy."""
+        from . import _cycle_of
+        h = self._open()
+        if h.dtype == _hip.DTYPE_MIXED:
+            raise ValueError("parameters['dtype'] = 'mixed' is for solve() (fp64 iterations around fp32 cycles); "
+                             "apply runs one cycle: use 'float32' or 'float64'")
+        p = self.parameters
+        shape, alpha = _cycle_of(p)
+        pre, post = int(p["preIterations"]), int(p["postIterations"])
+        n = h.sizes[0]
+        on_device = _devarray.is_device_array(r)
+        if out is not None and _devarray.is_device_array(out) != on_device:
+            raise TypeError("Solver.apply: `out` must be a device array exactly when `r` is one")
+        h.set_cycle(shape, alpha)
+        if on_device:
+            z = _devarray.empty_like(r, n) if out is None else out
+            r_ptr, z_ptr = _devarray.address(r, n, "r"), _devarray.address(z, n, "out")
+            _devarray.synchronize()
+            h.cycle_dev(r_ptr, z_ptr, pre, post)
+            h.sync()
+            return z
+        z = _host_out(out, n)
+        h.vcycle_ex(np.asarray(r, dtype=np.float64).reshape(-1), None, z, None, pre, post, level=0)
+        return z
+
+    # ---- update -------------------------------------------------------------------------------------------------------
+    def update(self, A_new):
+        """New values in A_in's pattern (the same indptr and indices; anything else: ValueError, and the solver keeps
+        the old operator).  Where the hierarchy takes new coefficients in place (_hip.Hierarchy.can_update_fine) that
+        is update_fine; otherwise a new hierarchy is built first and the old one closed after that succeeded.  Either
+        way later solves have the bits of a fresh Solver(A_new, parameters)."""
+        from . import _setup, defaults
+        h = self._open()
+        A1 = _hip.as_csr(A_new)
+        if (A1.shape != self._shape or A1.indptr.size != self._indptr.size or A1.indices.size != self._indices.size
+                or not np.array_equal(A1.indptr, self._indptr) or not np.array_equal(A1.indices, self._indices)):
+            raise ValueError("Solver.update: A_new must have the pattern (indptr and indices) the solver was set up with")
+        if h.can_update_fine():
+            h.update_fine(A1.data)
+            return
+        fresh, R, A = _setup(A_new, dict(self._given), dict(defaults))[:3]
+        self._hierarchy, self.R, self.A = fresh, R, A
+        self._pattern_of(A1)
+        h.close()

@@ -202,6 +202,7 @@ struct Hier {
     // the scalars (PCG_NSC, then PCG_NSC zeros: beta = 0, not done), the workgroup partials, one norm per iteration
     DevBuf<V> pcg_b, pcg_x, pcg_p, pcg_p2, pcg_q;
     DevBuf<double> pcg_sc, pcg_part, pcg_norms;
+    DevBuf<double> norms2;         // omg_resident_norms: ||b||, ||b - A x|| (resident_norms; made on first use)
     // mean projection (nullspace.hip; project_vec below): the workgroup partials and, behind them, the folded sum
     DevBuf<double> proj_scratch;
     // OMG_DTYPE_MIXED (a float hierarchy): the levels as for OMG_DTYPE_F32, and level 0's outer state in double — what the
@@ -2314,6 +2315,57 @@ void mixed_update_values(Hier<V> *h, const double *vals_dev, int64_t nnz) {
     OMG_HIP(hipStreamSynchronize(h->stream));
 }
 
+// ---- omg_resident_norms: ||b|| and ||b - A x|| of the resident state without a cycle --------------------------------------
+// The launches are FCG's own: (b, b) by pcg_dot, q = A x by the level's SpMV (pcg_apply / mixed_apply: one fused launch on
+// a plane level, the row kernels anywhere else), ||b - q||^2 by pcg_residual with no r to write, each folded by one
+// workgroup (pcg_fold_sqrt).  They write q, p2, the partials and norms2 — scratch that every resident entry fills again
+// before it reads it — and nothing of b, x, the levels' vectors or their pointer state: a cycle, an FCG run or a replayed
+// graph afterwards has the bits it would have had.
+template <typename V>
+void resident_norms(Hier<V> *hh, double *rhs_norm, double *residual_norm) {
+    Level<V> &L = hh->lv[0];
+    const int64_t n = L.n;
+    hipStream_t s = hh->stream;
+    if (hh->pcg_sc.n < size_t(2 * PCG_NSC)) hh->pcg_sc.alloc(2 * PCG_NSC);
+    if (hh->pcg_part.n < size_t(2 * PCG_MAX_WG)) hh->pcg_part.alloc(2 * PCG_MAX_WG);
+    if (hh->norms2.n < 2) hh->norms2.alloc(2);
+    double *sc0 = hh->pcg_sc.p + PCG_NSC, *part = hh->pcg_part.p, *out = hh->norms2.p;
+    OMG_HIP(hipMemsetAsync(sc0, 0, PCG_NSC * sizeof(double), s));       // (beta = 0, nothing done)
+    if (hh->mixed) {
+        auto &m = hh->mx;
+        const int nwg = pcg_wgs<double>(n);
+        if (rhs_norm) {
+            pcg_dot<double>(m.b.p, m.b.p, n, part, sc0, s);
+            pcg_fold_sqrt(part, nwg, out, s);
+        }
+        if (residual_norm) {
+            mixed_apply(hh, m.x.p, m.q.p, m.p2.p, sc0);
+            pcg_residual<double, V>(m.b.p, m.q.p, static_cast<double *>(nullptr), static_cast<V *>(nullptr), n, part, s);
+            pcg_fold_sqrt(part, nwg, out + 1, s);
+        }
+    } else {
+        const int nwg = pcg_wgs<V>(n);
+        if (rhs_norm) {
+            pcg_dot<V>(L.b.p, L.b.p, n, part, sc0, s);
+            pcg_fold_sqrt(part, nwg, out, s);
+        }
+        if (residual_norm) {
+            OMG_REQUIRE(hh->lv.size() > 1, "omg_resident_norms: a single-level hierarchy has no smoothed operator to form a residual with");
+            const size_t vn = size_t(std::max<int64_t>(n, 1));
+            for (DevBuf<V> *b : {&hh->pcg_p2, &hh->pcg_q})
+                if (b->n < vn) b->alloc(vn);
+            pcg_apply(hh, L.xp, hh->pcg_q.p, hh->pcg_p2.p, sc0);
+            pcg_residual<V, V>(L.b.p, hh->pcg_q.p, static_cast<V *>(nullptr), static_cast<V *>(nullptr), n, part, s);
+            pcg_fold_sqrt(part, nwg, out + 1, s);
+        }
+    }
+    double host[2] = {0.0, 0.0};
+    OMG_HIP(hipMemcpyAsync(host, out, sizeof(host), hipMemcpyDeviceToHost, s));
+    OMG_HIP(hipStreamSynchronize(s));
+    if (rhs_norm) *rhs_norm = host[0];
+    if (residual_norm) *residual_norm = host[1];
+}
+
 }  // namespace
 }  // namespace omg
 
@@ -2427,6 +2479,13 @@ int omg_hierarchy_update_fine(omg_hierarchy *h, const double *data, int64_t nnz,
             update_fine(hh, dev, nnz, true);
             mixed_update_values(hh, dev, nnz);
         });
+    });
+}
+
+int omg_hierarchy_can_update_fine(const omg_hierarchy *h, int *yes) {
+    return guarded([&] {
+        OMG_REQUIRE(yes, "null argument");
+        with(h, [&](auto *hh) { *yes = (hh->upd7 || hh->indptr0.p) ? 1 : 0; });      // (update_fine's own test)
     });
 }
 
@@ -3014,6 +3073,16 @@ int omg_resident_pcg(omg_hierarchy *h, int pre, int post, int max_iter, double t
             OMG_REQUIRE(hh->lv.size() > 1, "a single-level hierarchy solves directly: nothing to accelerate");
             if (hh->mixed) mixed_pcg(hh, pre, post, max_iter, threshold, iterations, norms, true_norm, breakdown);
             else resident_pcg(hh, pre, post, max_iter, threshold, iterations, norms, true_norm, breakdown);
+        });
+    });
+}
+
+int omg_resident_norms(omg_hierarchy *h, double *rhs_norm, double *residual_norm) {
+    return guarded([&] {
+        with(h, [&](auto *hh) {
+            check_level(hh, 0);
+            OMG_REQUIRE(hh->resident, "omg_resident_load has not been called");
+            if (rhs_norm || residual_norm) resident_norms(hh, rhs_norm, residual_norm);
         });
     });
 }
