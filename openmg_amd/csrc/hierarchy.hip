@@ -807,8 +807,7 @@ bool use_var7(const Hier<V> *h, const Level<V> &L) {
 // pre = 0 or post = 0 — the reference's default is V(1,0), openmg/__init__.py:22-23 — the pass runs
 // without its relaxation.)
 template <typename V>
-bool use_plane(const Hier<V> *h, const Level<V> &L, int pre, int post) {
-    (void)pre; (void)post;
+bool use_plane(const Hier<V> *h, const Level<V> &L) {
     return L.plane && !h->no_plane;
 }
 
@@ -844,14 +843,14 @@ void cycle_children(Hier<V> *h, int l, int pre, int post, int shape, bool first_
 // child level (the up pass takes the same).  Returns what the child's own cycle may rely on.
 struct PlaneDown { bool child_first, child_zero; };
 template <typename V>
-PlaneDown plane_down_half(Hier<V> *h, int l, int pre, int post, bool x_zero, bool first_done, int halves, typename PlanePlan<V>::Coarse &c) {
+PlaneDown plane_down_half(Hier<V> *h, int l, int pre, int post, bool x_zero, bool first_done, typename PlanePlan<V>::Coarse &c) {
     const int last = (int)h->lv.size() - 1;
     Level<V> &L = h->lv[l];
     Level<V> &C = h->lv[l + 1];
     // :201 all but the last pre-smoothing sweep set by set (in place); the last one inside the down pass
     if (pre > 1) smooth_level(h, l, pre - 1, FUSE_NONE, nullptr, first_done);
-    const bool child_plane = l + 1 < last && use_plane(h, C, pre, post);
-    const bool child_zero = child_plane && pre <= 1 && halves == 3;       // the child's down pass never reads its zero iterate
+    const bool child_plane = l + 1 < last && use_plane(h, C);
+    const bool child_zero = child_plane && pre <= 1;       // the child's down pass never reads its zero iterate
     if (l + 1 < last && !child_zero) ensure_format(h, l + 1);
     const bool child_first = l + 1 < last && !child_zero && !use_s27(h, C) && !L.plane->g.dim2 && first_sweep_in_restrict(h, C, pre);
     c.map = L.r_out.p;
@@ -884,10 +883,10 @@ int tail_fuse_depth(const Hier<V> *h, int l, int post, int shape) {
     if (h->tail_fuse <= 0 || shape != OMG_CYCLE_V || h->cycle_shape != OMG_CYCLE_V || post > 1 || l < 0 || l >= last || !h->coarse.cube16()) return 0;
     auto fits = [&](int k) {
         const Level<V> &K = h->lv[k];
-        if (!use_plane(h, K, 1, post)) return false;
+        if (!use_plane(h, K)) return false;
         const Level<V> &D = h->lv[k + 1];
         if (k + 1 == last) return tail_up_level(K.plane->g, 16, 16, 16);
-        return use_plane(h, D, 1, post) && tail_up_level(K.plane->g, D.plane->g.nx, D.plane->g.ny, D.plane->g.nz);
+        return use_plane(h, D) && tail_up_level(K.plane->g, D.plane->g.nx, D.plane->g.ny, D.plane->g.nz);
     };
     if (l == last - 1) return fits(l) ? 1 : 0;
     if (l == last - 2 && h->tail_fuse >= 2) return fits(l) && fits(l + 1) ? 2 : 0;
@@ -911,7 +910,7 @@ int cycle_body(Hier<V> *h, int l, int pre, int post, bool want_norm, double *pre
         Stencil27Plan<V> &P = *L.s27;
         // (a 27-point child's first sweep never reads its zero iterate; a plane child's down pass only when it IS the
         // cycle's one pre-smoothing sweep — with more, smooth_level runs before it on the iterate as stored)
-        const bool child_zero = l + 1 < last && ((use_s27(h, C) && pre >= 1) || (use_plane(h, C, pre, post) && pre == 1));
+        const bool child_zero = l + 1 < last && ((use_s27(h, C) && pre >= 1) || (use_plane(h, C) && pre == 1));
         bool zero_now = x_zero;
         if (x_zero && pre == 0) {
             OMG_HIP(hipMemsetAsync(L.xp, 0, size_t(L.n) * sizeof(V), h->stream));
@@ -943,46 +942,11 @@ int cycle_body(Hier<V> *h, int l, int pre, int post, bool want_norm, double *pre
         }
         return want_norm ? NORM_S27 : NORM_NONE;
     }
-    // OMG_PLANE_HALVES=1|2 (debugging, not under hipGraph): only the down / only the up pass plane-pipelined
-    static const int halves = [] { const char *e = experiment_env("OMG_PLANE_HALVES"); return (e && (e[0] == '1' || e[0] == '2')) ? e[0] - '0' : 3; }();
-    if (use_plane(h, L, pre, post) && halves == 2 && !x_zero && pre >= 1 && post >= 1) {
-        const bool res_done = smooth_level(h, l, pre, FUSE_RESIDUAL, nullptr, first_done);
-        residual_level(h, l, L.r.p, res_done);
-        if (l + 1 < last) ensure_format(h, l + 1);
-        const bool child_first = l + 1 < last && first_sweep_in_restrict(h, C, pre);
-        restrict_level<V>(h, l, L.r.p, C.b.p, l + 1 < last ? C.xp : nullptr, child_first);
-        cycle_children(h, l, pre, post, shape, child_first, false);
+    if (use_plane(h, L)) {
         typename PlanePlan<V>::Coarse c;
-        c.map = L.r_out.p;
-        c.e = C.xp;
-        double *out = (want_norm && post == 1) ? (post_slot ? post_slot : L.plane->partials.p) : nullptr;
-        L.plane->up(L.xp, L.tp, L.b.p, c, out, h->stream);
-        std::swap(L.xp, L.tp);
-        if (post > 1)
-            return smooth_level(h, l, post - 1, want_norm ? FUSE_NORM : FUSE_NONE, nullptr, false, post_slot) ? NORM_LAST_SET : NORM_NONE;
-        return out ? NORM_PLANE : NORM_NONE;
-    }
-    if (use_plane(h, L, pre, post) && halves == 1 && pre >= 1 && post >= 1) {
-        if (pre > 1) smooth_level(h, l, pre - 1, FUSE_NONE, nullptr, first_done);
-        if (l + 1 < last) ensure_format(h, l + 1);
-        const bool child_first = l + 1 < last && first_sweep_in_restrict(h, C, pre);
-        typename PlanePlan<V>::Coarse c;
-        c.map = L.r_out.p;
-        c.b = C.b.p;
-        c.x = l + 1 < last ? C.xp : nullptr;
-        c.diag = child_first ? C.diag.p : nullptr;
-        c.first_end = child_first ? int(C.A.sets[1]) : 0;
-        L.plane->down(L.xp, L.tp, L.b.p, x_zero, c, h->stream);
-        std::swap(L.xp, L.tp);
-        cycle_children(h, l, pre, post, shape, child_first, false);
-        prolong_add_level<V>(h, l, C.xp, L.xp, h->over);
-        return smooth_level(h, l, post, want_norm ? FUSE_NORM : FUSE_NONE, nullptr, false, post_slot) ? NORM_LAST_SET : NORM_NONE;
-    }
-    if (use_plane(h, L, pre, post)) {
-        typename PlanePlan<V>::Coarse c;
-        const PlaneDown d = plane_down_half(h, l, pre, post, x_zero, first_done, halves, c);
+        const PlaneDown d = plane_down_half(h, l, pre, post, x_zero, first_done, c);
         double *out = (want_norm && post <= 1) ? (post_slot ? post_slot : L.plane->partials.p) : nullptr;
-        const int fuse = halves == 3 && !out ? tail_fuse_depth(h, l, post, shape) : 0;
+        const int fuse = !out ? tail_fuse_depth(h, l, post, shape) : 0;
         if (fuse) {
             // the rest of the cycle below this level in one launch: (depth 2: the child's down pass as ever, then) the coarsest
             // solve and the up passes of the levels above it (plane.hip tail_up_kernel)
@@ -991,7 +955,7 @@ int cycle_body(Hier<V> *h, int l, int pre, int post, bool want_norm, double *pre
             u.cmap = L.r_out.p;
             if (fuse == 2) {
                 typename PlanePlan<V>::Coarse cc;
-                plane_down_half(h, l + 1, pre, post, d.child_zero, d.child_first, halves, cc);
+                plane_down_half(h, l + 1, pre, post, d.child_zero, d.child_first, cc);
                 u.mid = &C.plane->g; u.mid_x_old = C.xp; u.mid_x_new = C.tp; u.mid_b = C.b.p;
                 u.cmap = C.r_out.p;
             }
@@ -1023,7 +987,7 @@ int cycle_body(Hier<V> *h, int l, int pre, int post, bool want_norm, double *pre
         // one inside the down pass; the up pass holds the first post-smoothing sweep and the norm's squares
         Var7Plan<V> &P = *L.var7;
         if (pre > 1) smooth_level(h, l, pre - 1, FUSE_NONE, nullptr, first_done);
-        const bool child_zero = l + 1 < last && ((use_var7(h, C) && pre == 1) || (use_plane(h, C, pre, post) && pre == 1) || (use_s27(h, C) && pre >= 1));
+        const bool child_zero = l + 1 < last && ((use_var7(h, C) && pre == 1) || (use_plane(h, C) && pre == 1) || (use_s27(h, C) && pre >= 1));
         if (l + 1 < last && !child_zero) {
             if (!use_s27(h, C)) ensure_format(h, l + 1);
             OMG_HIP(hipMemsetAsync(C.xp, 0, size_t(C.n) * sizeof(V), h->stream));      // :191-192
@@ -1055,7 +1019,7 @@ int cycle_body(Hier<V> *h, int l, int pre, int post, bool want_norm, double *pre
     residual_level(h, l, L.r.p, res_done);                          // :209
     // :210, and the coarse cycle's initial=None -> zeros (:191-192) cleared by the same launch —
     // or already relaxed once (first_sweep_in_restrict)
-    const bool child_zero = l + 1 < last && ((use_plane(h, C, pre, post) && pre == 1 && halves == 3) || (use_s27(h, C) && pre >= 1));
+    const bool child_zero = l + 1 < last && ((use_plane(h, C) && pre == 1) || (use_s27(h, C) && pre >= 1));
     if (l + 1 < last && !child_zero && !use_s27(h, C)) ensure_format(h, l + 1);
     // (a var7 child's down pass holds its whole first sweep: it cannot skip a launch already applied)
     const bool child_first = l + 1 < last && !child_zero && !use_s27(h, C) && !use_var7(h, C) && first_sweep_in_restrict(h, C, pre);
@@ -1254,6 +1218,53 @@ void run_cycle0(Hier<V> *h, int pre, int post) {
 template <typename V>
 void check_level(const Hier<V> *h, int level) {
     OMG_REQUIRE(level >= 0 && level < (int)h->lv.size(), "level out of range");
+}
+
+// omg_vcycle, omg_vcycle_ex, omg_vcycle_dev: one cycle entered at `level` from x_in (null: zeros) into x_out; x_pre (nullable,
+// may be x_in) receives the iterate after the pre-smoothing — the input's copy, or zeros, where none ran.  Returns the
+// residual norm (0 at the coarsest level, whose solve is direct).  The vectors are double in natural numbering: host
+// arrays, read back once the norm is (fetch_vec synchronises), or — dev — arrays in HBM, everything enqueued and the
+// norm's read-back the one synchronisation at the end: the outputs are complete on return either way.
+template <typename V>
+double level_cycle(Hier<V> *hh, bool dev, int level, const double *b, const double *x_in, double *x_out, double *x_pre, int pre, int post) {
+    Level<V> &L = hh->lv[level];
+    const int last = (int)hh->lv.size() - 1;
+    const size_t bytes = size_t(L.n) * sizeof(double);
+    auto load = [&](const double *src, V *dst) { dev ? load_vec_dev(hh, level, src, dst) : load_vec(hh, level, src, dst); };
+    auto fetch = [&](const V *src, double *dst) { dev ? fetch_vec_dev<V>(hh, level, src, dst) : fetch_vec<V>(hh, level, src, dst); };
+    hh->resident = false;
+    load(b, L.b.p);
+    if (x_in) load(x_in, L.xp);
+    else OMG_HIP(hipMemsetAsync(L.xp, 0, size_t(L.n) * sizeof(V), hh->stream));
+    const bool want_pre = x_pre && level < last && pre > 0;
+    int part = NORM_NONE;
+    {
+        struct Reset { int &v; ~Reset() { v = -1; } } reset{hh->pre_level};      // (cycle_body copies to pre_buf at pre_level)
+        if (want_pre) {
+            if (hh->pre_buf.n < size_t(L.n)) hh->pre_buf.alloc(size_t(L.n));
+            hh->pre_level = level;
+        }
+        part = cycle_body(hh, level, pre, post, level < last);
+    }
+    double nv = 0.0;
+    if (level < last) {
+        finish_norm(hh, level, part);
+        if (!dev) nv = read_norm(hh);
+    }
+    fetch(L.xp, x_out);
+    if (want_pre) fetch(hh->pre_buf.p, x_pre);
+    else if (x_pre && x_in && x_pre != x_in) {
+        if (dev) OMG_HIP(hipMemcpyAsync(x_pre, x_in, bytes, hipMemcpyDeviceToDevice, hh->stream));
+        else std::memcpy(x_pre, x_in, bytes);
+    } else if (x_pre && !x_in) {
+        if (dev) OMG_HIP(hipMemsetAsync(x_pre, 0, bytes, hh->stream));
+        else std::memset(x_pre, 0, bytes);
+    }
+    if (dev) {
+        if (level < last) nv = read_norm(hh);
+        else { OMG_HIP(hipStreamSynchronize(hh->stream)); check_march(hh); }
+    }
+    return nv;
 }
 
 // A hierarchy made with OMG_NULLSPACE_CONSTANT: the resident right-hand side is projected when it is loaded, the resident
@@ -1966,7 +1977,7 @@ void zero_start_cycle(Hier<V> *hh, int pre, int post) {
     Level<V> &L = hh->lv[0];
     bool first = false, zero_in = false;
     if (hh->lv.size() > 1) {
-        zero_in = (use_plane(hh, L, pre, post) && pre == 1) || (use_s27(hh, L) && pre >= 1) || (use_var7(hh, L) && pre == 1);   // the down pass / first sweep does not read a zero iterate
+        zero_in = (use_plane(hh, L) && pre == 1) || (use_s27(hh, L) && pre >= 1) || (use_var7(hh, L) && pre == 1);   // the down pass / first sweep does not read a zero iterate
         if (!zero_in) {
             // x starts from zero: the first relaxation launch is a pointwise b / diag (restrict_level).  The
             // diagonal comes from the row-kernel format, which a plane level builds on first use: BEFORE it
@@ -1996,7 +2007,7 @@ void zero_start_cycle(Hier<V> *hh, int pre, int post) {
 // launch; any other level updates p, runs the level's SpMV and the dot as three.
 template <typename V>
 bool pcg_fused_plane(const Hier<V> *hh, const Level<V> &L) {
-    return hh->lv.size() > 1 && use_plane(hh, L, 1, 1) && !L.plane->g.jacobi && L.plane->g.z_base == 0 && L.plane->g.z_end == L.plane->g.nz;
+    return hh->lv.size() > 1 && use_plane(hh, L) && !L.plane->g.jacobi && L.plane->g.z_base == 0 && L.plane->g.z_end == L.plane->g.nz;
 }
 
 template <typename V>
@@ -2009,70 +2020,86 @@ PcgPlane pcg_plane_of(const Level<V> &L) {
     return pg;
 }
 
-// q = A v on level 0 (v in its numbering); sc0: the zero scalars (the fused launch with beta = 0 and nothing done; p2 scratch)
+// FCG's outer state on level 0, in the level's numbering, in T: V itself, or double around the fp32 cycle of a mixed
+// hierarchy.  q = A v is one fused launch on a plane level (pg) and the row kernels over A anywhere else; rlo (nullable):
+// where pcg_update and pcg_residual also leave fl32(r) — the cycle's right-hand side when r itself is not
+template <typename T, typename V>
+struct Outer {
+    T *b, *x, *r, *p, *p2, *q;
+    bool plane;
+    PcgPlane pg;
+    const DevCsrT<T> *A;
+    V *rlo;
+};
+
+// the hierarchy's own copies of b and x (the cycle overwrites the level's), p, p2, q; r is the cycle's right-hand side itself
 template <typename V>
-void pcg_apply(Hier<V> *hh, const V *v, V *q, V *scratch, const double *sc0) {
+Outer<V, V> plain_outer(Hier<V> *hh) {
     Level<V> &L = hh->lv[0];
-    if (pcg_fused_plane(hh, L)) {
-        pcg_plane_step<V, V>(pcg_plane_of(L), v, v, scratch, q, hh->pcg_part.p, sc0, hh->stream);
-        return;
-    }
-    ensure_format(hh, 0);
-    RowArgsT<V> a;
-    a.x = const_cast<V *>(v);
-    a.y = q;
-    launch_rows(L.A, ROW_SPMV, -1, a, hh->stream);
+    const bool plane = pcg_fused_plane(hh, L);
+    return {hh->pcg_b.p, hh->pcg_x.p, L.b.p, hh->pcg_p.p, hh->pcg_p2.p, hh->pcg_q.p, plane, plane ? pcg_plane_of(L) : PcgPlane{}, &L.A, nullptr};
+}
+// OMG_DTYPE_MIXED (below): the resident fp64 b and x, the operator in double
+template <typename V>
+Outer<double, V> mixed_outer(Hier<V> *hh) {
+    auto &m = hh->mx;
+    return {m.b.p, m.x.p, m.r.p, m.p.p, m.p2.p, m.q.p, m.plane, m.pg, &m.A, hh->lv[0].b.p};
 }
 
-template <typename V>
-void resident_pcg(Hier<V> *hh, int pre, int post, int max_iter, double threshold, int *iterations, double *norms, double *true_norm,
-                  int *breakdown) {
+// q = A v; sc0: the zero scalars (the fused launch with beta = 0 and nothing done; scratch: its p2)
+template <typename T, typename V>
+void outer_apply(Hier<V> *hh, const Outer<T, V> &w, const T *v, T *q, T *scratch, const double *sc0) {
+    if (w.plane) {
+        pcg_plane_step<T, T>(w.pg, v, v, scratch, q, hh->pcg_part.p, sc0, hh->stream);
+        return;
+    }
+    RowArgsT<T> a;
+    a.x = const_cast<T *>(v);
+    a.y = q;
+    launch_rows(*w.A, ROW_SPMV, -1, a, hh->stream);
+}
+
+// r = b - A x (r nullable) and fl32(r) into rlo; ||r||^2 partials (pcg_wgs<T>(n) of them).  Uses q and p2.
+template <typename T, typename V>
+void outer_residual(Hier<V> *hh, const Outer<T, V> &w, T *r) {
+    outer_apply(hh, w, w.x, w.q, w.p2, hh->pcg_sc.p + PCG_NSC);
+    pcg_residual<T, V>(w.b, w.q, r, w.rlo, hh->lv[0].n, hh->pcg_part.p, hh->stream);
+}
+
+// The iterations from r = b - A x0 (in w.r, and in the cycle's right-hand side) and p = 0, then the true residual of the
+// x they leave.  restore: what puts the resident state back before that (a plain hierarchy's cycle has overwritten it).
+template <typename T, typename V, typename Restore>
+void fcg(Hier<V> *hh, Outer<T, V> w, int pre, int post, int max_iter, double threshold, int *iterations, double *norms, double *true_norm,
+         int *breakdown, Restore &&restore) {
     Level<V> &L = hh->lv[0];
     const int64_t n = L.n;
     hipStream_t s = hh->stream;
-    const size_t vn = size_t(std::max<int64_t>(n, 1));
-    for (DevBuf<V> *b : {&hh->pcg_b, &hh->pcg_x, &hh->pcg_p, &hh->pcg_p2, &hh->pcg_q})
-        if (b->n < vn) b->alloc(vn);
-    if (hh->pcg_sc.n < size_t(2 * PCG_NSC)) hh->pcg_sc.alloc(2 * PCG_NSC);
-    if (hh->pcg_part.n < size_t(2 * PCG_MAX_WG)) hh->pcg_part.alloc(2 * PCG_MAX_WG);
-    if (hh->pcg_norms.n < size_t(max_iter)) hh->pcg_norms.alloc(size_t(max_iter));
     double *sc = hh->pcg_sc.p, *sc0 = hh->pcg_sc.p + PCG_NSC, *part = hh->pcg_part.p;
-    V *B = hh->pcg_b.p, *X = hh->pcg_x.p, *Q = hh->pcg_q.p;
-    V *P = hh->pcg_p.p, *P2 = hh->pcg_p2.p;
-    const bool fused = pcg_fused_plane(hh, L);
-    const PcgPlane pg = fused ? pcg_plane_of(L) : PcgPlane{};
-    if (!fused) ensure_format(hh, 0);
-    const int nwg = pcg_wgs<V>(n);
-    OMG_HIP(hipMemsetAsync(sc, 0, 2 * PCG_NSC * sizeof(double), s));
-    OMG_HIP(hipMemcpyAsync(B, L.b.p, size_t(n) * sizeof(V), hipMemcpyDeviceToDevice, s));
-    OMG_HIP(hipMemcpyAsync(X, L.xp, size_t(n) * sizeof(V), hipMemcpyDeviceToDevice, s));
-    OMG_HIP(hipMemsetAsync(P, 0, size_t(n) * sizeof(V), s));       // (beta = 0 in the first iteration multiplies it)
-    pcg_apply(hh, X, Q, P2, sc0);
-    pcg_residual<V, V>(B, Q, L.b.p, static_cast<V *>(nullptr), n, part, s);                      // r = b - A x0
+    const int nwg = pcg_wgs<T>(n);
     constexpr int BATCH = 16;
     double hs[PCG_NSC] = {0};
     int k = 0;
     while (k < max_iter) {
         const int cnt = std::min(BATCH, max_iter - k);
         for (int j = 0; j < cnt; ++j, ++k) {
-            zero_start_cycle(hh, pre, post);                       // z = M(r)
-            V *Z = L.xp, *R = L.b.p;
-            pcg_dots<V, V>(R, Z, Q, n, part, sc, s);
+            zero_start_cycle(hh, pre, post);                       // z = M(r), of a mixed hierarchy M(fl32(r)), in L.xp
+            const V *Z = L.xp;
+            pcg_dots<T, V>(w.r, Z, w.q, n, part, sc, s);
             pcg_fold_beta(part, nwg, sc, k == 0, s);
             int nwg2 = nwg;
-            if (fused) {
-                nwg2 = pcg_plane_step<V, V>(pg, Z, P, P2, Q, part, sc, s);
+            if (w.plane) {
+                nwg2 = pcg_plane_step<T, V>(w.pg, Z, w.p, w.p2, w.q, part, sc, s);
             } else {
-                pcg_pupdate<V, V>(Z, P, P2, n, sc, s);
-                RowArgsT<V> a;
-                a.x = P2;
-                a.y = Q;
-                launch_rows(L.A, ROW_SPMV, -1, a, s);
-                pcg_dot<V>(P2, Q, n, part, sc, s);
+                pcg_pupdate<T, V>(Z, w.p, w.p2, n, sc, s);
+                RowArgsT<T> a;
+                a.x = w.p2;
+                a.y = w.q;
+                launch_rows(*w.A, ROW_SPMV, -1, a, s);
+                pcg_dot<T>(w.p2, w.q, n, part, sc, s);
             }
-            std::swap(P, P2);
+            std::swap(w.p, w.p2);
             pcg_fold_alpha(part, nwg2, sc, s);
-            pcg_update<V, V>(X, P, R, Q, static_cast<V *>(nullptr), n, part, sc, s);
+            pcg_update<T, V>(w.x, w.p, w.r, w.q, w.rlo, n, part, sc, s);
             pcg_fold_norm(part, nwg, sc, hh->pcg_norms.p, k, threshold, s);
         }
         OMG_HIP(hipMemcpyAsync(hs, sc, sizeof(hs), hipMemcpyDeviceToHost, s));
@@ -2082,11 +2109,8 @@ void resident_pcg(Hier<V> *hh, int pre, int post, int max_iter, double threshold
     }
     const int iters = int(hs[PCG_ITERS]);
     if (norms && iters > 0) OMG_HIP(hipMemcpyAsync(norms, hh->pcg_norms.p, size_t(iters) * sizeof(double), hipMemcpyDeviceToHost, s));
-    // the resident state: x as the iterate, b as the right-hand side; the true residual once
-    OMG_HIP(hipMemcpyAsync(L.xp, X, size_t(n) * sizeof(V), hipMemcpyDeviceToDevice, s));
-    OMG_HIP(hipMemcpyAsync(L.b.p, B, size_t(n) * sizeof(V), hipMemcpyDeviceToDevice, s));
-    pcg_apply(hh, X, Q, P2, sc0);
-    pcg_residual<V, V>(B, Q, static_cast<V *>(nullptr), static_cast<V *>(nullptr), n, part, s);
+    restore();
+    outer_residual(hh, w, static_cast<T *>(nullptr));              // the true residual once
     pcg_fold_sqrt(part, nwg, sc0 + PCG_ITERS, s);
     double tn = 0.0;
     OMG_HIP(hipMemcpyAsync(&tn, sc0 + PCG_ITERS, sizeof(double), hipMemcpyDeviceToHost, s));
@@ -2095,6 +2119,41 @@ void resident_pcg(Hier<V> *hh, int pre, int post, int max_iter, double threshold
     if (iterations) *iterations = iters;
     if (true_norm) *true_norm = tn;
     if (breakdown) *breakdown = hs[PCG_BREAK] != 0.0 ? 1 : 0;
+}
+
+template <typename V>
+void resident_pcg(Hier<V> *hh, int pre, int post, int max_iter, double threshold, int *iterations, double *norms, double *true_norm,
+                  int *breakdown) {
+    Level<V> &L = hh->lv[0];
+    const int64_t n = L.n;
+    hipStream_t s = hh->stream;
+    if (hh->pcg_sc.n < size_t(2 * PCG_NSC)) hh->pcg_sc.alloc(2 * PCG_NSC);
+    if (hh->pcg_part.n < size_t(2 * PCG_MAX_WG)) hh->pcg_part.alloc(2 * PCG_MAX_WG);
+    if (hh->pcg_norms.n < size_t(max_iter)) hh->pcg_norms.alloc(size_t(max_iter));
+    if (hh->mixed) {
+        // x, r, p, p2, q, b in double and z = M(fl32(r)) in float (OMG_DTYPE_MIXED below): the resident state is FCG's own
+        const Outer<double, V> w = mixed_outer(hh);
+        OMG_HIP(hipMemsetAsync(hh->pcg_sc.p, 0, 2 * PCG_NSC * sizeof(double), s));
+        outer_residual(hh, w, w.r);                                // r = b - A x0, fl32(r) -> L.b
+        OMG_HIP(hipMemsetAsync(w.p, 0, size_t(n) * sizeof(double), s));      // (beta = 0 in the first iteration multiplies it)
+        fcg(hh, w, pre, post, max_iter, threshold, iterations, norms, true_norm, breakdown, [] {});
+        return;
+    }
+    const size_t vn = size_t(std::max<int64_t>(n, 1));
+    for (DevBuf<V> *b : {&hh->pcg_b, &hh->pcg_x, &hh->pcg_p, &hh->pcg_p2, &hh->pcg_q})
+        if (b->n < vn) b->alloc(vn);
+    const Outer<V, V> w = plain_outer(hh);
+    if (!w.plane) ensure_format(hh, 0);
+    OMG_HIP(hipMemsetAsync(hh->pcg_sc.p, 0, 2 * PCG_NSC * sizeof(double), s));
+    OMG_HIP(hipMemcpyAsync(w.b, L.b.p, size_t(n) * sizeof(V), hipMemcpyDeviceToDevice, s));
+    OMG_HIP(hipMemcpyAsync(w.x, L.xp, size_t(n) * sizeof(V), hipMemcpyDeviceToDevice, s));
+    OMG_HIP(hipMemsetAsync(w.p, 0, size_t(n) * sizeof(V), s));     // (beta = 0 in the first iteration multiplies it)
+    outer_residual(hh, w, w.r);                                    // r = b - A x0
+    fcg(hh, w, pre, post, max_iter, threshold, iterations, norms, true_norm, breakdown, [&] {
+        // the resident state: x as the iterate, b as the right-hand side
+        OMG_HIP(hipMemcpyAsync(L.xp, w.x, size_t(n) * sizeof(V), hipMemcpyDeviceToDevice, s));
+        OMG_HIP(hipMemcpyAsync(L.b.p, w.b, size_t(n) * sizeof(V), hipMemcpyDeviceToDevice, s));
+    });
 }
 
 // ---- OMG_DTYPE_MIXED: fp64 iterations around the fp32 zero-start V-cycle (pcg.hip kernels with Z = float) --------------
@@ -2156,30 +2215,6 @@ void refuse_mixed(const Hier<V> *h, const char *entry) {
                                          "(omg_resident_load[_dev], omg_resident_cycle[s], omg_resident_pcg, omg_resident_fetch[_dev])");
 }
 
-// q = A v in double (sc0: zero scalars for the plane launch, scratch: its p2)
-template <typename V>
-void mixed_apply(Hier<V> *h, const double *v, double *q, double *scratch, const double *sc0) {
-    auto &m = h->mx;
-    if (m.plane) {
-        pcg_plane_step<double, double>(m.pg, v, v, scratch, q, h->pcg_part.p, sc0, h->stream);
-        return;
-    }
-    RowArgsT<double> a;
-    a.x = const_cast<double *>(v);
-    a.y = q;
-    launch_rows(m.A, ROW_SPMV, -1, a, h->stream);
-}
-
-// r = b - A x (r64 nullable) and fl32(r) into the cycle's right-hand side L.b; ||r||^2 partials (pcg_wgs<double>(n) of them).
-// Uses q and p2.
-template <typename V>
-void mixed_residual(Hier<V> *h, double *r64) {
-    auto &m = h->mx;
-    Level<V> &L = h->lv[0];
-    mixed_apply(h, m.x.p, m.q.p, m.p2.p, h->pcg_sc.p + PCG_NSC);
-    pcg_residual<double, V>(m.b.p, m.q.p, r64, L.b.p, L.n, h->pcg_part.p, h->stream);
-}
-
 // n_cycles defect-correction cycles; the norm of cycle k to out[k] (device)
 template <typename V>
 void mixed_cycles(Hier<V> *h, int pre, int post, int n_cycles, double *out) {
@@ -2189,7 +2224,7 @@ void mixed_cycles(Hier<V> *h, int pre, int post, int n_cycles, double *out) {
     hipStream_t s = h->stream;
     double *part = h->pcg_part.p;
     OMG_HIP(hipMemsetAsync(h->pcg_sc.p, 0, 2 * PCG_NSC * sizeof(double), s));
-    mixed_residual(h, static_cast<double *>(nullptr));
+    outer_residual(h, mixed_outer(h), static_cast<double *>(nullptr));      // fl32(b - A x) -> L.b
     for (int k = 0; k < n_cycles; ++k) {
         zero_start_cycle(h, pre, post);                            // z = M(fl32(r)) in L.xp
         int nwg;
@@ -2209,100 +2244,53 @@ void mixed_cycles(Hier<V> *h, int pre, int post, int n_cycles, double *out) {
     }
 }
 
-// resident_pcg with x, r, p, p2, q, b in double and z = M(fl32(r)) in float
+// omg_resident_load[_dev], omg_solve: the resident right-hand side and iterate (x0 null: zeros) from double arrays in natural
+// numbering, on the host or — dev — in HBM; b minus its mean where the hierarchy has the constant null space (the initial
+// iterate stays).  A mixed hierarchy's resident state is its fp64 outer b and x, always through the gather kernel.
+// Enqueued only: the load entries synchronise.
 template <typename V>
-void mixed_pcg(Hier<V> *hh, int pre, int post, int max_iter, double threshold, int *iterations, double *norms, double *true_norm,
-               int *breakdown) {
-    auto &m = hh->mx;
-    Level<V> &L = hh->lv[0];
-    const int64_t n = L.n;
-    hipStream_t s = hh->stream;
-    if (hh->pcg_norms.n < size_t(max_iter)) hh->pcg_norms.alloc(size_t(max_iter));
-    double *sc = hh->pcg_sc.p, *sc0 = hh->pcg_sc.p + PCG_NSC, *part = hh->pcg_part.p;
-    double *X = m.x.p, *R = m.r.p, *Q = m.q.p, *P = m.p.p, *P2 = m.p2.p;
-    const int nwg = pcg_wgs<double>(n);
-    OMG_HIP(hipMemsetAsync(sc, 0, 2 * PCG_NSC * sizeof(double), s));
-    mixed_residual(hh, R);                                          // r = b - A x0, fl32(r) -> L.b
-    OMG_HIP(hipMemsetAsync(P, 0, size_t(n) * sizeof(double), s));  // (beta = 0 in the first iteration multiplies it)
-    constexpr int BATCH = 16;
-    double hs[PCG_NSC] = {0};
-    int k = 0;
-    while (k < max_iter) {
-        const int cnt = std::min(BATCH, max_iter - k);
-        for (int j = 0; j < cnt; ++j, ++k) {
-            zero_start_cycle(hh, pre, post);                       // z = M(fl32(r))
-            const V *Z = L.xp;
-            pcg_dots<double, V>(R, Z, Q, n, part, sc, s);
-            pcg_fold_beta(part, nwg, sc, k == 0, s);
-            int nwg2 = nwg;
-            if (m.plane) {
-                nwg2 = pcg_plane_step<double, V>(m.pg, Z, P, P2, Q, part, sc, s);
-            } else {
-                pcg_pupdate<double, V>(Z, P, P2, n, sc, s);
-                RowArgsT<double> a;
-                a.x = P2;
-                a.y = Q;
-                launch_rows(m.A, ROW_SPMV, -1, a, s);
-                pcg_dot<double>(P2, Q, n, part, sc, s);
-            }
-            std::swap(P, P2);
-            pcg_fold_alpha(part, nwg2, sc, s);
-            pcg_update<double, V>(X, P, R, Q, L.b.p, n, part, sc, s);
-            pcg_fold_norm(part, nwg, sc, hh->pcg_norms.p, k, threshold, s);
-        }
-        OMG_HIP(hipMemcpyAsync(hs, sc, sizeof(hs), hipMemcpyDeviceToHost, s));
-        OMG_HIP(hipStreamSynchronize(s));
-        check_march(hh);
-        if (hs[PCG_DONE] != 0.0) break;
-    }
-    const int iters = int(hs[PCG_ITERS]);
-    if (norms && iters > 0) OMG_HIP(hipMemcpyAsync(norms, hh->pcg_norms.p, size_t(iters) * sizeof(double), hipMemcpyDeviceToHost, s));
-    mixed_residual(hh, static_cast<double *>(nullptr));            // the true residual once
-    pcg_fold_sqrt(part, nwg, sc0 + PCG_ITERS, s);
-    double tn = 0.0;
-    OMG_HIP(hipMemcpyAsync(&tn, sc0 + PCG_ITERS, sizeof(double), hipMemcpyDeviceToHost, s));
-    OMG_HIP(hipStreamSynchronize(s));
-    check_march(hh);
-    if (iterations) *iterations = iters;
-    if (true_norm) *true_norm = tn;
-    if (breakdown) *breakdown = hs[PCG_BREAK] != 0.0 ? 1 : 0;
-}
-
-// the fp64 resident vectors from / to natural numbering (host or device double arrays)
-template <typename V>
-void mixed_load(Hier<V> *h, const double *b, const double *x0, bool dev) {
-    auto &m = h->mx;
+void resident_load(Hier<V> *h, const double *b, const double *x0, bool dev) {
     Level<V> &L = h->lv[0];
-    const int32_t *perm = L.ord.identity ? nullptr : L.perm.p;
-    auto put = [&](const double *src, double *dst) {
-        if (!dev) {
-            ensure_nat(h, 0);
-            L.nat.upload(src, L.n, h->stream);
-            src = L.nat.p;
-        }
-        launch_gather<double, double>(src, perm, dst, L.n, h->stream);
+    auto load = [&](auto *b_dst, auto *x_dst, auto &&put) {
+        put(b, b_dst);
+        if (has_nullspace(h)) project_vec(h, b_dst, L.n);
+        if (x0) put(x0, x_dst);
+        else OMG_HIP(hipMemsetAsync(x_dst, 0, size_t(L.n) * sizeof(*x_dst), h->stream));
     };
-    put(b, m.b.p);
-    if (has_nullspace(h)) project_vec(h, m.b.p, L.n);              // (the fp64 outer b; the initial iterate stays)
-    if (x0) put(x0, m.x.p);
-    else OMG_HIP(hipMemsetAsync(m.x.p, 0, size_t(L.n) * sizeof(double), h->stream));
-    OMG_HIP(hipStreamSynchronize(h->stream));
+    if (h->mixed)
+        load(h->mx.b.p, h->mx.x.p, [&](const double *src, double *dst) {
+            if (!dev) {
+                ensure_nat(h, 0);
+                L.nat.upload(src, L.n, h->stream);
+                src = L.nat.p;
+            }
+            launch_gather<double, double>(src, L.ord.identity ? nullptr : L.perm.p, dst, L.n, h->stream);
+        });
+    else
+        load(L.b.p, L.xp, [&](const double *src, V *dst) { dev ? load_vec_dev(h, 0, src, dst) : load_vec(h, 0, src, dst); });
 }
 
+// omg_resident_fetch[_dev], omg_solve: the resident iterate — minus its mean, in place, where the hierarchy has the constant
+// null space — to a double array in natural numbering; complete on return
 template <typename V>
-void mixed_fetch(Hier<V> *h, double *x, bool dev) {
+void resident_fetch(Hier<V> *h, double *x, bool dev) {
     Level<V> &L = h->lv[0];
-    const int32_t *perm = L.ord.identity ? nullptr : L.perm.p;
-    if (has_nullspace(h)) project_vec(h, h->mx.x.p, L.n);          // (the fp64 outer x, in place)
-    if (dev) {
-        launch_scatter<double, double>(h->mx.x.p, perm, x, L.n, h->stream);
-        OMG_HIP(hipStreamSynchronize(h->stream));
+    auto fetch = [&](auto *src, auto &&get) {
+        if (has_nullspace(h)) project_vec(h, src, L.n);
+        get(src);
+        if (dev) OMG_HIP(hipStreamSynchronize(h->stream));
+    };
+    if (h->mixed) {
+        fetch(h->mx.x.p, [&](const double *src) {
+            if (!dev) ensure_nat(h, 0);
+            launch_scatter<double, double>(src, L.ord.identity ? nullptr : L.perm.p, dev ? x : L.nat.p, L.n, h->stream);
+            if (!dev) download_staged(x, L.nat.p, size_t(L.n) * sizeof(double), h->stream);
+        });
+        check_march(h);
     } else {
-        ensure_nat(h, 0);
-        launch_scatter<double, double>(h->mx.x.p, perm, L.nat.p, L.n, h->stream);
-        download_staged(x, L.nat.p, size_t(L.n) * sizeof(double), h->stream);
+        fetch(L.xp, [&](const V *src) { dev ? fetch_vec_dev<V>(h, 0, src, x) : fetch_vec<V>(h, 0, src, x); });
+        if (dev) check_march(h);                                    // (fetch_vec has asked already)
     }
-    check_march(h);
 }
 
 // omg_hierarchy_update_fine on a mixed hierarchy, after the fp32 levels: the outer operator's values gathered from the new
@@ -2315,49 +2303,117 @@ void mixed_update_values(Hier<V> *h, const double *vals_dev, int64_t nnz) {
     OMG_HIP(hipStreamSynchronize(h->stream));
 }
 
+// ---- omg_resident_cycles: n cycles back to back, the norm of cycle k to out[k] (device) -------------------------------------
+template <typename V>
+void batched_cycles(Hier<V> *hh, int pre, int post, int n_cycles, double *out) {
+    auto &L0 = hh->lv[0];
+    const bool single = hh->lv.size() == 1;
+    // What a cycle leaves of its norm goes to a slot of nb partials in the batch buffer, and one launch per chunk adds
+    // the slots up (the additions of launch_sum_sqrt: the same bits as omg_resident_cycle).  Level 0 decides nb, what
+    // a cycle does with its slots, and how many slots of a chunk of cnt that launch adds:
+    //  plane (post <= 1): the up pass leaves its workgroup partials in the cycle's slot; cnt
+    //  s27: with pre >= 1 the first sweep of cycle j + 1 also squares the residuals with respect to the iterate it starts
+    //    from — cycle j's norm (openmg/__init__.py:227) without another pass over the operator; the last cycle of a
+    //    chunk (and every cycle when pre = 0) runs the norm kernel; cnt
+    //  rows, where can_prenorm() holds: the last set's block partials by the cycle's fused post-smoothing launch, the
+    //    first set's by cycle j + 1's first launch; the last cycle of a chunk has no successor in it and takes the
+    //    usual norm launch; cnt - 1
+    //  anything else (nb = 0): every cycle the usual norm launch — of a single level, whose solve is direct, a zero; none
+    enum { PLANE, S27, ROWS } kind = ROWS;
+    int64_t nb = 0;
+    if (!single && use_plane(hh, L0) && post <= 1) {
+        kind = PLANE;
+        nb = L0.plane->g.n_wg;
+    } else if (!single && use_s27(hh, L0)) {
+        kind = S27;
+        nb = int64_t(4) * L0.s27->g.n_wg;
+    } else if (!single && !use_var7(hh, L0)) {                 // (a var7 cycle never touches the row-kernel format)
+        ensure_format(hh, 0);
+        // (a plane-pipelined cycle with post > 1 ends set by set: its first launch is no PRENORM launch)
+        if (!getenv_flag("OMG_NO_PRENORM") && can_prenorm(hh, L0, pre, post) && !use_plane(hh, L0)) nb = L0.A.n_blocks();
+    }
+    constexpr int CHUNK = 64;
+    if (hh->batch_partials.n < size_t(CHUNK) * size_t(nb)) hh->batch_partials.alloc(size_t(CHUNK) * size_t(nb));
+    auto slot = [&](int j) { return hh->batch_partials.p + size_t(j) * size_t(nb); };
+    for (int k0 = 0; k0 < n_cycles; k0 += CHUNK) {
+        const int cnt = std::min(CHUNK, n_cycles - k0);
+        for (int j = 0; j < cnt; ++j) {
+            const bool last_of_chunk = j + 1 == cnt;
+            if (single) {
+                cycle_body(hh, 0, pre, post);
+                OMG_HIP(hipMemsetAsync(out + k0 + j, 0, sizeof(double), hh->stream));   // :232
+            } else if (kind == PLANE) {
+                const int st = cycle_body(hh, 0, pre, post, true, nullptr, false, slot(j));
+                OMG_REQUIRE(st == NORM_PLANE, "internal: plane-pipelined cycle without its norm partials");
+            } else if (kind == S27) {
+                const bool own_norm = last_of_chunk || pre == 0;
+                cycle_body(hh, 0, pre, post, own_norm, (pre >= 1 && j > 0) ? slot(j - 1) : nullptr, false, own_norm ? slot(j) : nullptr);
+                if (own_norm) {
+                    Prof<V> p(hh, 0, 4);
+                    L0.s27->norm(L0.xp, L0.b.p, L0.s27->have67, slot(j), hh->stream);
+                }
+            } else {
+                const bool defer = nb > 0;
+                const int part = cycle_body(hh, 0, pre, post, true, (defer && j > 0) ? slot(j - 1) : nullptr, false,
+                                            (defer && !last_of_chunk) ? slot(j) : nullptr);
+                if (!defer || last_of_chunk) {
+                    finish_norm(hh, 0, part, out + k0 + j);                            // :227
+                } else {
+                    OMG_REQUIRE(part || hh->smoother == OMG_SMOOTH_JACOBI, "internal: deferred norm without the fused post-smoothing launch");
+                }
+            }
+        }
+        const int sums = kind == ROWS ? (nb > 0 ? cnt - 1 : 0) : cnt;
+        if (sums > 0) launch_sum_batch(hh->batch_partials.p, nb, nb, sums, out + k0, true, hh->stream);
+    }
+}
+
 // ---- omg_resident_norms: ||b|| and ||b - A x|| of the resident state without a cycle --------------------------------------
-// The launches are FCG's own: (b, b) by pcg_dot, q = A x by the level's SpMV (pcg_apply / mixed_apply: one fused launch on
+// The launches are FCG's own: (b, b) by pcg_dot, q = A x by the level's SpMV (outer_apply: one fused launch on
 // a plane level, the row kernels anywhere else), ||b - q||^2 by pcg_residual with no r to write, each folded by one
 // workgroup (pcg_fold_sqrt).  They write q, p2, the partials and norms2 — scratch that every resident entry fills again
 // before it reads it — and nothing of b, x, the levels' vectors or their pointer state: a cycle, an FCG run or a replayed
 // graph afterwards has the bits it would have had.
+template <typename T, typename V>
+void outer_norms(Hier<V> *hh, const Outer<T, V> &w, bool rhs, bool residual, double *out) {
+    const int64_t n = hh->lv[0].n;
+    double *sc0 = hh->pcg_sc.p + PCG_NSC, *part = hh->pcg_part.p;
+    const int nwg = pcg_wgs<T>(n);
+    if (rhs) {
+        pcg_dot<T>(w.b, w.b, n, part, sc0, hh->stream);
+        pcg_fold_sqrt(part, nwg, out, hh->stream);
+    }
+    if (residual) {
+        outer_residual(hh, w, static_cast<T *>(nullptr));
+        pcg_fold_sqrt(part, nwg, out + 1, hh->stream);
+    }
+}
+
 template <typename V>
 void resident_norms(Hier<V> *hh, double *rhs_norm, double *residual_norm) {
     Level<V> &L = hh->lv[0];
-    const int64_t n = L.n;
     hipStream_t s = hh->stream;
     if (hh->pcg_sc.n < size_t(2 * PCG_NSC)) hh->pcg_sc.alloc(2 * PCG_NSC);
     if (hh->pcg_part.n < size_t(2 * PCG_MAX_WG)) hh->pcg_part.alloc(2 * PCG_MAX_WG);
     if (hh->norms2.n < 2) hh->norms2.alloc(2);
-    double *sc0 = hh->pcg_sc.p + PCG_NSC, *part = hh->pcg_part.p, *out = hh->norms2.p;
-    OMG_HIP(hipMemsetAsync(sc0, 0, PCG_NSC * sizeof(double), s));       // (beta = 0, nothing done)
+    double *out = hh->norms2.p;
+    OMG_HIP(hipMemsetAsync(hh->pcg_sc.p + PCG_NSC, 0, PCG_NSC * sizeof(double), s));       // (beta = 0, nothing done)
     if (hh->mixed) {
-        auto &m = hh->mx;
-        const int nwg = pcg_wgs<double>(n);
-        if (rhs_norm) {
-            pcg_dot<double>(m.b.p, m.b.p, n, part, sc0, s);
-            pcg_fold_sqrt(part, nwg, out, s);
-        }
-        if (residual_norm) {
-            mixed_apply(hh, m.x.p, m.q.p, m.p2.p, sc0);
-            pcg_residual<double, V>(m.b.p, m.q.p, static_cast<double *>(nullptr), static_cast<V *>(nullptr), n, part, s);
-            pcg_fold_sqrt(part, nwg, out + 1, s);
-        }
+        Outer<double, V> w = mixed_outer(hh);
+        w.rlo = nullptr;                                           // (the cycle's right-hand side stays as it is)
+        outer_norms(hh, w, rhs_norm != nullptr, residual_norm != nullptr, out);
     } else {
-        const int nwg = pcg_wgs<V>(n);
-        if (rhs_norm) {
-            pcg_dot<V>(L.b.p, L.b.p, n, part, sc0, s);
-            pcg_fold_sqrt(part, nwg, out, s);
-        }
         if (residual_norm) {
             OMG_REQUIRE(hh->lv.size() > 1, "omg_resident_norms: a single-level hierarchy has no smoothed operator to form a residual with");
-            const size_t vn = size_t(std::max<int64_t>(n, 1));
+            const size_t vn = size_t(std::max<int64_t>(L.n, 1));
             for (DevBuf<V> *b : {&hh->pcg_p2, &hh->pcg_q})
                 if (b->n < vn) b->alloc(vn);
-            pcg_apply(hh, L.xp, hh->pcg_q.p, hh->pcg_p2.p, sc0);
-            pcg_residual<V, V>(L.b.p, hh->pcg_q.p, static_cast<V *>(nullptr), static_cast<V *>(nullptr), n, part, s);
-            pcg_fold_sqrt(part, nwg, out + 1, s);
         }
+        Outer<V, V> w = plain_outer(hh);
+        w.b = L.b.p;                                               // (the resident b and x themselves, not FCG's copies)
+        w.x = L.xp;
+        if (residual_norm && !w.plane) ensure_format(hh, 0);
+        outer_norms(hh, w, rhs_norm != nullptr, residual_norm != nullptr, out);
     }
     double host[2] = {0.0, 0.0};
     OMG_HIP(hipMemcpyAsync(host, out, sizeof(host), hipMemcpyDeviceToHost, s));
@@ -2668,22 +2724,10 @@ int omg_vcycle(omg_hierarchy *h, int level, const double *b, double *x, int pre,
     return guarded([&] {
         with(h, [&](auto *hh) {
             refuse_mixed(hh, "omg_vcycle");
-            using V = value_of<decltype(hh)>;
             check_level(hh, level);
             OMG_REQUIRE(b && x, "b / x is null");
             OMG_REQUIRE(pre >= 0 && post >= 0, "negative sweep count");
-            auto &L = hh->lv[level];
-            hh->resident = false;
-            load_vec(hh, level, b, L.b.p);
-            load_vec(hh, level, x, L.xp);
-            const int last = (int)hh->lv.size() - 1;
-            const int part = cycle_body(hh, level, pre, post, level < last);
-            double nv = 0.0;
-            if (level < last) {
-                finish_norm(hh, level, part);
-                nv = read_norm(hh);
-            }
-            fetch_vec<V>(hh, level, L.xp, x);
+            const double nv = level_cycle(hh, false, level, b, x, x, nullptr, pre, post);
             if (norm) *norm = nv;
         });
     });
@@ -2694,38 +2738,10 @@ int omg_vcycle_ex(omg_hierarchy *h, int level, const double *b, const double *x_
     return guarded([&] {
         with(h, [&](auto *hh) {
             refuse_mixed(hh, "omg_vcycle_ex");
-            using V = value_of<decltype(hh)>;
             check_level(hh, level);
             OMG_REQUIRE(b && x_out, "b / x_out is null");
             OMG_REQUIRE(pre >= 0 && post >= 0, "negative sweep count");
-            auto &L = hh->lv[level];
-            const int last = (int)hh->lv.size() - 1;
-            hh->resident = false;
-            load_vec(hh, level, b, L.b.p);
-            if (x_in) load_vec(hh, level, x_in, L.xp);
-            else OMG_HIP(hipMemsetAsync(L.xp, 0, size_t(L.n) * sizeof(V), hh->stream));
-            const bool want_pre = x_pre && level < last && pre > 0;
-            if (want_pre) {
-                if (hh->pre_buf.n < size_t(L.n)) hh->pre_buf.alloc(size_t(L.n));
-                hh->pre_level = level;
-            }
-            int part = NORM_NONE;
-            try {
-                part = cycle_body(hh, level, pre, post, level < last);
-            } catch (...) {
-                hh->pre_level = -1;
-                throw;
-            }
-            hh->pre_level = -1;
-            double nv = 0.0;
-            if (level < last) {
-                finish_norm(hh, level, part);
-                nv = read_norm(hh);
-            }
-            fetch_vec<V>(hh, level, L.xp, x_out);
-            if (want_pre) fetch_vec<V>(hh, level, hh->pre_buf.p, x_pre);
-            else if (x_pre && x_in) { if (x_pre != x_in) std::memcpy(x_pre, x_in, size_t(L.n) * sizeof(double)); }
-            else if (x_pre) std::memset(x_pre, 0, size_t(L.n) * sizeof(double));
+            const double nv = level_cycle(hh, false, level, b, x_in, x_out, x_pre, pre, post);
             if (norm) *norm = nv;
         });
     });
@@ -2739,36 +2755,10 @@ int omg_vcycle_dev(omg_hierarchy *h, int level, const double *b_dev, const doubl
     return guarded([&] {
         with(h, [&](auto *hh) {
             refuse_mixed(hh, "omg_vcycle_dev");
-            using V = value_of<decltype(hh)>;
             check_level(hh, level);
             OMG_REQUIRE(b_dev && x_out_dev, "b / x_out is null");
             OMG_REQUIRE(pre >= 0 && post >= 0, "negative sweep count");
-            auto &L = hh->lv[level];
-            const int last = (int)hh->lv.size() - 1;
-            hh->resident = false;
-            load_vec_dev(hh, level, b_dev, L.b.p);
-            if (x_in_dev) load_vec_dev(hh, level, x_in_dev, L.xp);
-            else OMG_HIP(hipMemsetAsync(L.xp, 0, size_t(L.n) * sizeof(V), hh->stream));
-            const bool want_pre = x_pre_dev && level < last && pre > 0;
-            if (want_pre) {
-                if (hh->pre_buf.n < size_t(L.n)) hh->pre_buf.alloc(size_t(L.n));
-                hh->pre_level = level;
-            }
-            int part = NORM_NONE;
-            try {
-                part = cycle_body(hh, level, pre, post, level < last);
-            } catch (...) {
-                hh->pre_level = -1;
-                throw;
-            }
-            hh->pre_level = -1;
-            if (level < last) finish_norm(hh, level, part);
-            fetch_vec_dev<V>(hh, level, L.xp, x_out_dev);
-            if (want_pre) fetch_vec_dev<V>(hh, level, hh->pre_buf.p, x_pre_dev);
-            else if (x_pre_dev && x_in_dev) { if (x_pre_dev != x_in_dev) OMG_HIP(hipMemcpyAsync(x_pre_dev, x_in_dev, size_t(L.n) * sizeof(double), hipMemcpyDeviceToDevice, hh->stream)); }
-            else if (x_pre_dev) OMG_HIP(hipMemsetAsync(x_pre_dev, 0, size_t(L.n) * sizeof(double), hh->stream));
-            const double nv = level < last ? read_norm(hh) : 0.0;     // (synchronises the stream: the outputs are complete on return)
-            if (level >= last) { OMG_HIP(hipStreamSynchronize(hh->stream)); check_march(hh); }
+            const double nv = level_cycle(hh, true, level, b_dev, x_in_dev, x_out_dev, x_pre_dev, pre, post);
             if (norm) *norm = nv;
         });
     });
@@ -2778,19 +2768,9 @@ int omg_vcycle_dev(omg_hierarchy *h, int level, const double *b_dev, const doubl
 int omg_resident_load_dev(omg_hierarchy *h, const double *b_dev, const double *x0_dev) {
     return guarded([&] {
         with(h, [&](auto *hh) {
-            using V = value_of<decltype(hh)>;
             check_level(hh, 0);
             OMG_REQUIRE(b_dev, "b is null");
-            if (hh->mixed) {
-                mixed_load(hh, b_dev, x0_dev, true);
-                hh->resident = true;
-                return;
-            }
-            auto &L = hh->lv[0];
-            load_vec_dev(hh, 0, b_dev, L.b.p);
-            if (has_nullspace(hh)) project_vec(hh, L.b.p, L.n);
-            if (x0_dev) load_vec_dev(hh, 0, x0_dev, L.xp);
-            else OMG_HIP(hipMemsetAsync(L.xp, 0, L.n * sizeof(V), hh->stream));
+            resident_load(hh, b_dev, x0_dev, true);
             OMG_HIP(hipStreamSynchronize(hh->stream));
             hh->resident = true;
         });
@@ -2800,17 +2780,9 @@ int omg_resident_load_dev(omg_hierarchy *h, const double *b_dev, const double *x
 int omg_resident_fetch_dev(omg_hierarchy *h, double *x_dev) {
     return guarded([&] {
         with(h, [&](auto *hh) {
-            using V = value_of<decltype(hh)>;
             check_level(hh, 0);
             OMG_REQUIRE(hh->resident && x_dev, "nothing resident / x is null");
-            if (hh->mixed) {
-                mixed_fetch(hh, x_dev, true);
-                return;
-            }
-            if (has_nullspace(hh)) project_vec(hh, hh->lv[0].xp, hh->lv[0].n);
-            fetch_vec_dev<V>(hh, 0, hh->lv[0].xp, x_dev);
-            OMG_HIP(hipStreamSynchronize(hh->stream));
-            check_march(hh);
+            resident_fetch(hh, x_dev, true);
         });
     });
 }
@@ -2850,19 +2822,9 @@ int omg_hierarchy_cycle_dev(omg_hierarchy *h, const double *b_dev, double *x_dev
 int omg_resident_load(omg_hierarchy *h, const double *b, const double *x0) {
     return guarded([&] {
         with(h, [&](auto *hh) {
-            using V = value_of<decltype(hh)>;
             check_level(hh, 0);
             OMG_REQUIRE(b, "b is null");
-            if (hh->mixed) {
-                mixed_load(hh, b, x0, false);
-                hh->resident = true;
-                return;
-            }
-            auto &L = hh->lv[0];
-            load_vec(hh, 0, b, L.b.p);
-            if (has_nullspace(hh)) project_vec(hh, L.b.p, L.n);
-            if (x0) load_vec(hh, 0, x0, L.xp);
-            else OMG_HIP(hipMemsetAsync(L.xp, 0, L.n * sizeof(V), hh->stream));
+            resident_load(hh, b, x0, false);
             OMG_HIP(hipStreamSynchronize(hh->stream));
             hh->resident = true;
         });
@@ -2899,98 +2861,8 @@ int omg_resident_cycles(omg_hierarchy *h, int pre, int post, int n_cycles, doubl
             OMG_REQUIRE(pre >= 0 && post >= 0 && n_cycles >= 0, "negative argument");
             if (n_cycles == 0) return;
             if (hh->norms_dev.n < size_t(n_cycles)) hh->norms_dev.alloc(size_t(n_cycles));
-            if (hh->mixed) {
-                mixed_cycles(hh, pre, post, n_cycles, hh->norms_dev.p);
-                if (norms) OMG_HIP(hipMemcpyAsync(norms, hh->norms_dev.p, size_t(n_cycles) * sizeof(double), hipMemcpyDeviceToHost, hh->stream));
-                OMG_HIP(hipStreamSynchronize(hh->stream));
-                check_march(hh);
-                return;
-            }
-            const bool single = hh->lv.size() == 1;
-            if (!single && use_plane(hh, hh->lv[0], pre, post) && post <= 1) {
-                // every cycle's up pass leaves its workgroup partials in a slot of the batch buffer; one
-                // launch per chunk adds the slots up (the additions of launch_sum_sqrt: same bits as
-                // omg_resident_cycle)
-                constexpr int CHUNK = 64;
-                const int64_t nb = hh->lv[0].plane->g.n_wg;
-                if (hh->batch_partials.n < size_t(CHUNK) * size_t(nb)) hh->batch_partials.alloc(size_t(CHUNK) * size_t(nb));
-                for (int k0 = 0; k0 < n_cycles; k0 += CHUNK) {
-                    const int cnt = std::min(CHUNK, n_cycles - k0);
-                    for (int j = 0; j < cnt; ++j) {
-                        const int st = cycle_body(hh, 0, pre, post, true, nullptr, false, hh->batch_partials.p + size_t(j) * size_t(nb));
-                        OMG_REQUIRE(st == NORM_PLANE, "internal: plane-pipelined cycle without its norm partials");
-                    }
-                    launch_sum_batch(hh->batch_partials.p, nb, nb, cnt, hh->norms_dev.p + k0, true, hh->stream);
-                }
-                if (norms) OMG_HIP(hipMemcpyAsync(norms, hh->norms_dev.p, size_t(n_cycles) * sizeof(double), hipMemcpyDeviceToHost, hh->stream));
-                OMG_HIP(hipStreamSynchronize(hh->stream));
-                check_march(hh);
-                return;
-            }
-            if (!single && use_s27(hh, hh->lv[0])) {
-                // 27-point level: with pre >= 1 the first sweep of cycle j + 1 also squares the residuals with respect
-                // to the iterate it starts from — cycle j's norm (openmg/__init__.py:227) without another pass over
-                // the operator; the last cycle of a chunk (and every cycle when pre = 0) runs the norm kernel
-                constexpr int CHUNK = 64;
-                using V = value_of<decltype(hh)>;
-                auto &L0 = hh->lv[0];
-                Stencil27Plan<V> &P = *L0.s27;
-                const int64_t nb = int64_t(4) * P.g.n_wg;
-                if (hh->batch_partials.n < size_t(CHUNK) * size_t(nb)) hh->batch_partials.alloc(size_t(CHUNK) * size_t(nb));
-                for (int k0 = 0; k0 < n_cycles; k0 += CHUNK) {
-                    const int cnt = std::min(CHUNK, n_cycles - k0);
-                    for (int j = 0; j < cnt; ++j) {
-                        double *slot_prev = (pre >= 1 && j > 0) ? hh->batch_partials.p + size_t(j - 1) * size_t(nb) : nullptr;
-                        double *slot_this = hh->batch_partials.p + size_t(j) * size_t(nb);
-                        const bool own_norm = j + 1 == cnt || pre == 0;
-                        cycle_body(hh, 0, pre, post, own_norm, slot_prev, false, own_norm ? slot_this : nullptr);
-                        if (own_norm) {
-                            Prof<V> p(hh, 0, 4);
-                            P.norm(L0.xp, L0.b.p, P.have67, slot_this, hh->stream);
-                        }
-                    }
-                    launch_sum_batch(hh->batch_partials.p, nb, nb, cnt, hh->norms_dev.p + k0, true, hh->stream);
-                }
-                if (norms) OMG_HIP(hipMemcpyAsync(norms, hh->norms_dev.p, size_t(n_cycles) * sizeof(double), hipMemcpyDeviceToHost, hh->stream));
-                OMG_HIP(hipStreamSynchronize(hh->stream));
-                check_march(hh);
-                return;
-            }
-            const bool v7 = !single && use_var7(hh, hh->lv[0]);       // (its cycle never touches the row-kernel format)
-            if (!single && !v7) ensure_format(hh, 0);
-            // (a plane-pipelined cycle with post > 1 ends set by set: its first launch is no PRENORM launch)
-            const bool defer = !single && !v7 && !getenv_flag("OMG_NO_PRENORM") && can_prenorm(hh, hh->lv[0], pre, post) &&
-                               !use_plane(hh, hh->lv[0], pre, post);
-            // Deferred norms: cycle k's block partials are collected in slot k of a batch buffer — the
-            // last set's by its fused post-smoothing launch, the first set's by cycle k + 1's first
-            // launch — and ALL slots of a chunk are added up by one launch at the chunk's end (the
-            // additions of launch_sum_sqrt, same bits).  The last cycle of a chunk has no successor
-            // in it: the usual norm launch.
-            constexpr int CHUNK = 64;
-            const int64_t nb = (single || v7) ? 0 : hh->lv[0].A.n_blocks();
-            if (defer && hh->batch_partials.n < size_t(CHUNK) * size_t(nb)) hh->batch_partials.alloc(size_t(CHUNK) * size_t(nb));
-            for (int k0 = 0; k0 < n_cycles; k0 += CHUNK) {
-                const int cnt = std::min(CHUNK, n_cycles - k0);
-                for (int j = 0; j < cnt; ++j) {
-                    const int k = k0 + j;
-                    if (single) {
-                        cycle_body(hh, 0, pre, post);
-                        OMG_HIP(hipMemsetAsync(hh->norms_dev.p + k, 0, sizeof(double), hh->stream));   // :232
-                        continue;
-                    }
-                    const bool last_of_chunk = j + 1 == cnt;
-                    double *slot_prev = (defer && j > 0) ? hh->batch_partials.p + size_t(j - 1) * size_t(nb) : nullptr;
-                    double *slot_this = (defer && !last_of_chunk) ? hh->batch_partials.p + size_t(j) * size_t(nb) : nullptr;
-                    const int part = cycle_body(hh, 0, pre, post, true, slot_prev, false, slot_this);
-                    if (!defer || last_of_chunk) {
-                        finish_norm(hh, 0, part, hh->norms_dev.p + k);                                 // :227
-                    } else {
-                        OMG_REQUIRE(part || hh->smoother == OMG_SMOOTH_JACOBI, "internal: deferred norm without the fused post-smoothing launch");
-                    }
-                }
-                if (defer && cnt > 1)
-                    launch_sum_batch(hh->batch_partials.p, nb, nb, cnt - 1, hh->norms_dev.p + k0, true, hh->stream);
-            }
+            if (hh->mixed) mixed_cycles(hh, pre, post, n_cycles, hh->norms_dev.p);
+            else batched_cycles(hh, pre, post, n_cycles, hh->norms_dev.p);
             if (norms) OMG_HIP(hipMemcpyAsync(norms, hh->norms_dev.p, size_t(n_cycles) * sizeof(double), hipMemcpyDeviceToHost, hh->stream));
             OMG_HIP(hipStreamSynchronize(hh->stream));
             check_march(hh);       // (the batched entry returned norms of a sweep that had given up)
@@ -3012,7 +2884,7 @@ int omg_resident_spmv_time(omg_hierarchy *h, int reps, double *avg_ms) {
             auto &L = hh->lv[0];
             // a plane level (red-black ordered constant-coefficient stencil): matrix-free, like its cycle; y = the level's
             // scratch vector.  Anything else: the row kernels on the operator as it sits in HBM.
-            const bool mf = use_plane(hh, L, 1, 1) && !L.plane->g.jacobi;
+            const bool mf = use_plane(hh, L) && !L.plane->g.jacobi;
             if (!mf) ensure_format(hh, 0);
             RowArgsT<V> a;
             a.x = L.xp; a.y = mf ? L.tp : L.r.p;
@@ -3050,15 +2922,9 @@ int omg_resident_spmv_time(omg_hierarchy *h, int reps, double *avg_ms) {
 int omg_resident_fetch(omg_hierarchy *h, double *x) {
     return guarded([&] {
         with(h, [&](auto *hh) {
-            using V = value_of<decltype(hh)>;
             check_level(hh, 0);
             OMG_REQUIRE(hh->resident && x, "nothing resident / x is null");
-            if (hh->mixed) {
-                mixed_fetch(hh, x, false);
-                return;
-            }
-            if (has_nullspace(hh)) project_vec(hh, hh->lv[0].xp, hh->lv[0].n);
-            fetch_vec<V>(hh, 0, hh->lv[0].xp, x);
+            resident_fetch(hh, x, false);
         });
     });
 }
@@ -3071,8 +2937,7 @@ int omg_resident_pcg(omg_hierarchy *h, int pre, int post, int max_iter, double t
             OMG_REQUIRE(hh->resident, "omg_resident_load has not been called");
             OMG_REQUIRE(pre >= 0 && post >= 0 && max_iter >= 1, "negative sweep count / max_iter < 1");
             OMG_REQUIRE(hh->lv.size() > 1, "a single-level hierarchy solves directly: nothing to accelerate");
-            if (hh->mixed) mixed_pcg(hh, pre, post, max_iter, threshold, iterations, norms, true_norm, breakdown);
-            else resident_pcg(hh, pre, post, max_iter, threshold, iterations, norms, true_norm, breakdown);
+            resident_pcg(hh, pre, post, max_iter, threshold, iterations, norms, true_norm, breakdown);
         });
     });
 }
@@ -3102,15 +2967,11 @@ int omg_solve(omg_hierarchy *h, const double *b, double *x, int pre, int post, i
     return guarded([&] {
         with(h, [&](auto *hh) {
             refuse_mixed(hh, "omg_solve");
-            using V = value_of<decltype(hh)>;
             check_level(hh, 0);
             OMG_REQUIRE(b && x, "b / x is null");
             OMG_REQUIRE(max_cycles > 0 || threshold > 0.0,
                         "Either threshold or cycles must be > 0");   // openmg/__init__.py:118-119
-            auto &L = hh->lv[0];
-            load_vec(hh, 0, b, L.b.p);
-            if (has_nullspace(hh)) project_vec(hh, L.b.p, L.n);       // (load, cycles, fetch: as the resident entries)
-            load_vec(hh, 0, x, L.xp);
+            resident_load(hh, b, x, false);                           // (load, cycles, fetch: as the resident entries)
             hh->resident = true;
             int cycle = 0;
             double nv = 0.0;
@@ -3122,8 +2983,7 @@ int omg_solve(omg_hierarchy *h, const double *b, double *x, int pre, int post, i
                 const bool by_norm = threshold > 0.0 && nv < threshold;
                 if (by_cycles || by_norm) break;
             }
-            if (has_nullspace(hh)) project_vec(hh, L.xp, L.n);
-            fetch_vec<V>(hh, 0, L.xp, x);
+            resident_fetch(hh, x, false);
             if (cycles_done) *cycles_done = cycle;
             if (norm) *norm = nv;
         });
@@ -3231,7 +3091,7 @@ int omg_level_spmv(omg_hierarchy *h, int level, const double *x, double *y) {
             auto &L = hh->lv[level];
             hh->resident = false;
             load_vec(hh, level, x, L.xp);
-            const bool mf = use_plane(hh, L, 1, 1) && !L.plane->g.jacobi;
+            const bool mf = use_plane(hh, L) && !L.plane->g.jacobi;
             if (mf) {
                 ensure_spmv_y(hh, L);
                 L.plane->spmv(L.xp, L.spmv_y.p, hh->stream);
