@@ -1133,7 +1133,10 @@ struct Stencil27Plan {
 // ---- flexible preconditioned CG on a hierarchy's finest level (pcg.hip; driven by hierarchy.hip omg_resident_pcg) -----
 // The iteration's scalars: one device array of PCG_NSC doubles.  PCG_DONE set (converged, breakdown) turns every
 // pcg_* launch after it into a no-op.
-enum { PCG_RHO = 0, PCG_ALPHA = 1, PCG_BETA = 2, PCG_DONE = 3, PCG_BREAK = 4, PCG_ITERS = 5, PCG_NSC = 8 };
+// PCG_E_USED / PCG_E_NEXT: the exponents e of a mixed iteration's power-of-two factors (pcg.hip; 0 = none); PCG_RELOWER:
+// the first residual has to go to the cycle once more, with another exponent
+enum { PCG_RHO = 0, PCG_ALPHA = 1, PCG_BETA = 2, PCG_DONE = 3, PCG_BREAK = 4, PCG_ITERS = 5, PCG_E_USED = 6, PCG_E_NEXT = 7,
+       PCG_RELOWER = 8, PCG_NSC = 12 };
 constexpr int PCG_MAX_WG = 2048;      // workgroups of a pcg launch at most (grid stride beyond): partials per reduction
 // a plane level's operator (PlanePlan: red-black layout, nr = n / 2 red slots first, hx = nx / 2 cells per colour and line)
 struct PcgPlane {
@@ -1144,7 +1147,8 @@ struct PcgPlane {
 template <typename V>
 int pcg_wgs(int64_t n);               // workgroups (= partials) of the streaming launches over n values
 // Z: the element type of z = M(r) and of the cycle's right-hand side — V itself, or float under an fp64 outer iteration
-// (OMG_DTYPE_MIXED); rlo (Z != V only, otherwise ignored): fl32(r) goes there as well
+// (OMG_DTYPE_MIXED); rlo (Z != V only, otherwise ignored): fl32(2^-e r) goes there as well, e = sc[PCG_E_NEXT], and a z
+// of type Z counts as 2^e z, e = sc[PCG_E_USED]
 // (r, z) -> part[0, nwg), (z, q) -> part[nwg, 2 nwg)
 template <typename V, typename Z>
 void pcg_dots(const V *r, const Z *z, const V *q, int64_t n, double *part, const double *sc, hipStream_t s);
@@ -1156,21 +1160,31 @@ void pcg_pupdate(const Z *z, const V *p, V *p2, int64_t n, const double *sc, hip
 // x += alpha p ; r -= alpha q ; ||r||^2 partials ; rlo = fl32(r)
 template <typename V, typename Z>
 void pcg_update(V *x, const V *p, V *r, const V *q, Z *rlo, int64_t n, double *part, const double *sc, hipStream_t s);
-// r = b - q (r nullable) and ||b - q||^2 partials ; rlo = fl32(b - q) (nullable); runs whatever PCG_DONE says
+// r = b - q (r nullable) and ||b - q||^2 partials ; rlo = fl32(2^-e (b - q)) (nullable; sc is read for it alone); runs
+// whatever PCG_DONE says
 template <typename V, typename Z>
-void pcg_residual(const V *b, const V *q, V *r, Z *rlo, int64_t n, double *part, hipStream_t s);
+void pcg_residual(const V *b, const V *q, V *r, Z *rlo, int64_t n, double *part, const double *sc, hipStream_t s);
+// the start of a mixed iteration, after the first pcg_residual: the exponents stay those of ||b|| unless ||b - q|| is
+// more than 2^60 away; then they become its own, and pcg_lower writes rlo = fl32(2^-e (b - q)) again (else it does nothing)
+void pcg_fold_start(const double *part, int nwg, double *sc, hipStream_t s);
+template <typename V, typename Z>
+void pcg_lower(const V *b, const V *q, Z *rlo, int64_t n, const double *sc, hipStream_t s);
 // p2 = z + beta p ; q = A p2 ; (p2, q) partials, matrix-free on a plane level; returns the partials' count
 template <typename V, typename Z>
 int pcg_plane_step(const PcgPlane &g, const Z *z, const V *p, V *p2, V *q, double *part, const double *sc, hipStream_t s);
-// the mixed plain cycle's defect correction (not gated by PCG_DONE): x += z ...
+// the mixed plain cycle's defect correction (not gated by PCG_DONE): x += 2^e z ...
 template <typename V, typename Z>
-void pcg_defect_add(V *x, const Z *z, int64_t n, hipStream_t s);
-// ... or on a plane level in one launch: x2 = x + z ; rlo = fl32(b - A x2) ; ||b - A x2||^2 partials (returns their count)
+void pcg_defect_add(V *x, const Z *z, int64_t n, const double *sc, hipStream_t s);
+// ... or on a plane level in one launch: x2 = x + 2^e z ; rlo = fl32(2^-e' (b - A x2)) ; ||b - A x2||^2 partials (returns
+// their count)
 template <typename V, typename Z>
-int pcg_defect_plane(const PcgPlane &g, const V *x, const Z *z, V *x2, const V *b, Z *rlo, double *part, hipStream_t s);
+int pcg_defect_plane(const PcgPlane &g, const V *x, const Z *z, V *x2, const V *b, Z *rlo, double *part, const double *sc,
+                     hipStream_t s);
 void pcg_fold_beta(const double *part, int nwg, double *sc, bool first, hipStream_t s);
 void pcg_fold_alpha(const double *part, int nwg, double *sc, hipStream_t s);
 void pcg_fold_norm(const double *part, int nwg, double *sc, double *norms, int k, double threshold, hipStream_t s);
-void pcg_fold_sqrt(const double *part, int nwg, double *out, hipStream_t s);
+// sqrt of the folded sum -> *out (nullable); sc (nullable): and its exponent into PCG_E_NEXT, the old one (first: the same)
+// into PCG_E_USED
+void pcg_fold_sqrt(const double *part, int nwg, double *out, hipStream_t s, double *sc = nullptr, bool first = false);
 
 }  // namespace omg

@@ -217,6 +217,7 @@ struct Hier {
         DevCsrT<double> A;
         DevBuf<int32_t> src;
         DevBuf<double> b, x, x2, r, p, p2, q;
+        DevBuf<double> load_sc;          // PCG_NSC scalars: the exponent of ||b|| in PCG_E_USED and PCG_E_NEXT, since resident_load
     } mx;
     int smoother = OMG_SMOOTH_GS_LEX;
     double omega = 1.0;
@@ -2022,7 +2023,7 @@ PcgPlane pcg_plane_of(const Level<V> &L) {
 
 // FCG's outer state on level 0, in the level's numbering, in T: V itself, or double around the fp32 cycle of a mixed
 // hierarchy.  q = A v is one fused launch on a plane level (pg) and the row kernels over A anywhere else; rlo (nullable):
-// where pcg_update and pcg_residual also leave fl32(r) — the cycle's right-hand side when r itself is not
+// where pcg_update and pcg_residual also leave fl32(2^-e r) — the cycle's right-hand side when r itself is not
 template <typename T, typename V>
 struct Outer {
     T *b, *x, *r, *p, *p2, *q;
@@ -2059,11 +2060,26 @@ void outer_apply(Hier<V> *hh, const Outer<T, V> &w, const T *v, T *q, T *scratch
     launch_rows(*w.A, ROW_SPMV, -1, a, hh->stream);
 }
 
-// r = b - A x (r nullable) and fl32(r) into rlo; ||r||^2 partials (pcg_wgs<T>(n) of them).  Uses q and p2.
+// r = b - A x (r nullable); ||r||^2 partials (pcg_wgs<T>(n) of them).  Uses q and p2.  start (a mixed hierarchy): the
+// iteration begins here (the scalars are zero) — the exponent of ||b|| from the load becomes both of the scalars'
+// exponents (pcg.hip), fl32(2^-e r) goes to the cycle's right-hand side in the same pass, and only a start whose norm is
+// far from ||b|| makes pcg_lower write it again.
 template <typename T, typename V>
-void outer_residual(Hier<V> *hh, const Outer<T, V> &w, T *r) {
-    outer_apply(hh, w, w.x, w.q, w.p2, hh->pcg_sc.p + PCG_NSC);
-    pcg_residual<T, V>(w.b, w.q, r, w.rlo, hh->lv[0].n, hh->pcg_part.p, hh->stream);
+void outer_residual(Hier<V> *hh, const Outer<T, V> &w, T *r, bool start = false) {
+    const int64_t n = hh->lv[0].n;
+    double *sc = hh->pcg_sc.p;
+    if constexpr (!std::is_same<T, V>::value) {
+        if (start && w.rlo) {
+            OMG_HIP(hipMemcpyAsync(sc + PCG_E_USED, hh->mx.load_sc.p + PCG_E_USED, 2 * sizeof(double), hipMemcpyDeviceToDevice, hh->stream));
+            outer_apply(hh, w, w.x, w.q, w.p2, sc + PCG_NSC);
+            pcg_residual<T, V>(w.b, w.q, r, w.rlo, n, hh->pcg_part.p, sc, hh->stream);
+            pcg_fold_start(hh->pcg_part.p, pcg_wgs<T>(n), sc, hh->stream);
+            pcg_lower<T, V>(w.b, w.q, w.rlo, n, sc, hh->stream);
+            return;
+        }
+    }
+    outer_apply(hh, w, w.x, w.q, w.p2, sc + PCG_NSC);
+    pcg_residual<T, V>(w.b, w.q, r, static_cast<V *>(nullptr), n, hh->pcg_part.p, nullptr, hh->stream);
 }
 
 // The iterations from r = b - A x0 (in w.r, and in the cycle's right-hand side) and p = 0, then the true residual of the
@@ -2134,7 +2150,7 @@ void resident_pcg(Hier<V> *hh, int pre, int post, int max_iter, double threshold
         // x, r, p, p2, q, b in double and z = M(fl32(r)) in float (OMG_DTYPE_MIXED below): the resident state is FCG's own
         const Outer<double, V> w = mixed_outer(hh);
         OMG_HIP(hipMemsetAsync(hh->pcg_sc.p, 0, 2 * PCG_NSC * sizeof(double), s));
-        outer_residual(hh, w, w.r);                                // r = b - A x0, fl32(r) -> L.b
+        outer_residual(hh, w, w.r, true);                          // r = b - A x0, fl32(2^-e r) -> L.b
         OMG_HIP(hipMemsetAsync(w.p, 0, size_t(n) * sizeof(double), s));      // (beta = 0 in the first iteration multiplies it)
         fcg(hh, w, pre, post, max_iter, threshold, iterations, norms, true_norm, breakdown, [] {});
         return;
@@ -2201,6 +2217,8 @@ void build_mixed(Hier<V> *h, const omg_csr &A0) {
     const size_t vn = size_t(std::max<int64_t>(L.n, 1));
     for (DevBuf<double> *b : {&m.b, &m.x, &m.r, &m.p, &m.p2, &m.q}) { b->alloc(vn); b->zero(h->stream); }
     if (m.plane) { m.x2.alloc(vn); m.x2.zero(h->stream); }
+    m.load_sc.alloc(PCG_NSC);
+    m.load_sc.zero(h->stream);
     if (h->pcg_sc.n < size_t(2 * PCG_NSC)) h->pcg_sc.alloc(2 * PCG_NSC);
     if (h->pcg_part.n < size_t(2 * PCG_MAX_WG)) h->pcg_part.alloc(2 * PCG_MAX_WG);
     OMG_HIP(hipStreamSynchronize(h->stream));
@@ -2224,23 +2242,23 @@ void mixed_cycles(Hier<V> *h, int pre, int post, int n_cycles, double *out) {
     hipStream_t s = h->stream;
     double *part = h->pcg_part.p;
     OMG_HIP(hipMemsetAsync(h->pcg_sc.p, 0, 2 * PCG_NSC * sizeof(double), s));
-    outer_residual(h, mixed_outer(h), static_cast<double *>(nullptr));      // fl32(b - A x) -> L.b
+    outer_residual(h, mixed_outer(h), static_cast<double *>(nullptr), true);        // fl32(2^-e (b - A x)) -> L.b
     for (int k = 0; k < n_cycles; ++k) {
         zero_start_cycle(h, pre, post);                            // z = M(fl32(r)) in L.xp
         int nwg;
         if (m.plane) {
-            nwg = pcg_defect_plane<double, V>(m.pg, m.x.p, L.xp, m.x2.p, m.b.p, L.b.p, part, s);
+            nwg = pcg_defect_plane<double, V>(m.pg, m.x.p, L.xp, m.x2.p, m.b.p, L.b.p, part, h->pcg_sc.p, s);
             std::swap(m.x, m.x2);
         } else {
-            pcg_defect_add<double, V>(m.x.p, L.xp, n, s);
+            pcg_defect_add<double, V>(m.x.p, L.xp, n, h->pcg_sc.p, s);
             RowArgsT<double> a;
             a.x = m.x.p;
             a.y = m.q.p;
             launch_rows(m.A, ROW_SPMV, -1, a, s);
-            pcg_residual<double, V>(m.b.p, m.q.p, static_cast<double *>(nullptr), L.b.p, n, part, s);
+            pcg_residual<double, V>(m.b.p, m.q.p, static_cast<double *>(nullptr), L.b.p, n, part, h->pcg_sc.p, s);
             nwg = pcg_wgs<double>(n);
         }
-        pcg_fold_sqrt(part, nwg, out + k, s);
+        pcg_fold_sqrt(part, nwg, out + k, s, h->pcg_sc.p);
     }
 }
 
@@ -2257,7 +2275,7 @@ void resident_load(Hier<V> *h, const double *b, const double *x0, bool dev) {
         if (x0) put(x0, x_dst);
         else OMG_HIP(hipMemsetAsync(x_dst, 0, size_t(L.n) * sizeof(*x_dst), h->stream));
     };
-    if (h->mixed)
+    if (h->mixed) {
         load(h->mx.b.p, h->mx.x.p, [&](const double *src, double *dst) {
             if (!dev) {
                 ensure_nat(h, 0);
@@ -2266,7 +2284,12 @@ void resident_load(Hier<V> *h, const double *b, const double *x0, bool dev) {
             }
             launch_gather<double, double>(src, L.ord.identity ? nullptr : L.perm.p, dst, L.n, h->stream);
         });
-    else
+        // ||b||'s exponent, once per load: what the first residual of every iteration on this b is scaled by (pcg.hip)
+        double *sc0 = h->pcg_sc.p + PCG_NSC;
+        OMG_HIP(hipMemsetAsync(sc0, 0, PCG_NSC * sizeof(double), h->stream));
+        pcg_dot<double>(h->mx.b.p, h->mx.b.p, L.n, h->pcg_part.p, sc0, h->stream);
+        pcg_fold_sqrt(h->pcg_part.p, pcg_wgs<double>(L.n), nullptr, h->stream, h->mx.load_sc.p, true);
+    } else
         load(L.b.p, L.xp, [&](const double *src, V *dst) { dev ? load_vec_dev(h, 0, src, dst) : load_vec(h, 0, src, dst); });
 }
 

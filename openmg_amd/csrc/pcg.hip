@@ -16,6 +16,13 @@
 // — z = M(r) arrives as float, and the update / residual kernels also leave fl32(r) in the cycle's right-hand side —
 // while x, r, p, q, b and every scalar stay double.  With Z = V (the fp64 and fp32 hierarchies) they compute what they
 // always computed.  The defect-correction kernels at the end (x += z, r = b - A x) serve the mixed plain cycle.
+//
+// The range of float is not the range of double, so the cycle never sees r itself: it gets fl32(2^-e r) and its z counts
+// as 2^e z, with e the exponent of a norm the iteration already has — ||b|| (folded when b was loaded) for the first
+// residual, the last residual norm after that (PCG_E_NEXT: what the kernels that write the cycle's right-hand side
+// read; PCG_E_USED: the one the right-hand side the cycle last ran on was written with, what the kernels that read z
+// use).  No pass over the vectors is added for it, and no host round trip.  Both factors are powers of two, so the bits are those of
+// the unscaled iteration wherever no component of fl32(r) was subnormal, and a solve of 2^k b is 2^k times the solve of b.
 #include <algorithm>
 #include <type_traits>
 #include <cmath>
@@ -56,12 +63,26 @@ __device__ __forceinline__ void st(V *p, int64_t c, const Chunk<V, VW> &v) {
 
 __device__ __forceinline__ bool pcg_done(const double *sc) { return sc[PCG_DONE] != 0.0; }
 
+// the mixed iteration's power-of-two factors (Z != V only; 1 otherwise, and the compiler drops the product)
+template <bool LO>
+__device__ __forceinline__ double scale_up(const double *sc) { return LO ? ldexp(1.0, int(sc[PCG_E_USED])) : 1.0; }
+template <bool LO>
+__device__ __forceinline__ double scale_down(const double *sc) { return LO ? ldexp(1.0, -int(sc[PCG_E_NEXT])) : 1.0; }
+// the exponent a residual norm gives (0 for a norm that is zero or not finite); within +-1000 so that 2^-e is normal
+__device__ __forceinline__ double scale_exponent(double norm) {
+    if (!(norm > 0.0) || !std::isfinite(norm)) return 0.0;
+    return double(min(1000, max(-1000, ilogb(norm))));
+}
+
 // (r, z) -> part[wg], (z, q) -> part[nwg + wg]
 template <typename V, typename Z, int VW>
 __global__ __launch_bounds__(PCG_WG) void dots_kernel(const V *__restrict__ r, const Z *__restrict__ z, const V *__restrict__ q,
                                                       int64_t n, double *__restrict__ part, const double *__restrict__ sc) {
+    constexpr bool LO = !std::is_same<V, Z>::value;
     __shared__ double sh[PCG_WG];
     if (pcg_done(sc)) return;
+    const double up = scale_up<LO>(sc);
+    auto zv = [&](Z v) -> double { return LO ? double(v) * up : double(v); };
     const int64_t nc = n / VW, stride = int64_t(gridDim.x) * PCG_WG;
     double rz = 0.0, zq = 0.0;
     for (int64_t c = int64_t(blockIdx.x) * PCG_WG + threadIdx.x; c < nc; c += stride) {
@@ -69,14 +90,14 @@ __global__ __launch_bounds__(PCG_WG) void dots_kernel(const V *__restrict__ r, c
         const Chunk<Z, VW> b = ld<Z, VW>(z, c);
 #pragma unroll
         for (int e = 0; e < VW; ++e) {
-            rz = fma(double(a.v[e]), double(b.v[e]), rz);
-            zq = fma(double(b.v[e]), double(d.v[e]), zq);
+            rz = fma(double(a.v[e]), zv(b.v[e]), rz);
+            zq = fma(zv(b.v[e]), double(d.v[e]), zq);
         }
     }
     if (blockIdx.x == 0)
         for (int64_t i = nc * VW + threadIdx.x; i < n; i += PCG_WG) {
-            rz = fma(double(r[i]), double(z[i]), rz);
-            zq = fma(double(z[i]), double(q[i]), zq);
+            rz = fma(double(r[i]), zv(z[i]), rz);
+            zq = fma(zv(z[i]), double(q[i]), zq);
         }
     rz = block_sum(rz, sh);
     if (threadIdx.x == 0) part[blockIdx.x] = rz;
@@ -108,22 +129,25 @@ __global__ __launch_bounds__(PCG_WG) void dot_kernel(const V *__restrict__ a, co
 template <typename V, typename Z, int VW>
 __global__ __launch_bounds__(PCG_WG) void pupdate_kernel(const Z *__restrict__ z, const V *__restrict__ p, V *__restrict__ p2,
                                                          int64_t n, const double *__restrict__ sc) {
+    constexpr bool LO = !std::is_same<V, Z>::value;
     if (pcg_done(sc)) return;
     const double beta = sc[PCG_BETA];
+    const double up = scale_up<LO>(sc);
+    auto zv = [&](Z v) -> double { return LO ? double(v) * up : double(v); };
     const int64_t nc = n / VW, stride = int64_t(gridDim.x) * PCG_WG;
     for (int64_t c = int64_t(blockIdx.x) * PCG_WG + threadIdx.x; c < nc; c += stride) {
         const Chunk<Z, VW> u = ld<Z, VW>(z, c);
         const Chunk<V, VW> w = ld<V, VW>(p, c);
         Chunk<V, VW> o;
 #pragma unroll
-        for (int e = 0; e < VW; ++e) o.v[e] = V(fma(beta, double(w.v[e]), double(u.v[e])));
+        for (int e = 0; e < VW; ++e) o.v[e] = V(fma(beta, double(w.v[e]), zv(u.v[e])));
         st<V, VW>(p2, c, o);
     }
     if (blockIdx.x == 0)
-        for (int64_t i = nc * VW + threadIdx.x; i < n; i += PCG_WG) p2[i] = V(fma(beta, double(p[i]), double(z[i])));
+        for (int64_t i = nc * VW + threadIdx.x; i < n; i += PCG_WG) p2[i] = V(fma(beta, double(p[i]), zv(z[i])));
 }
 
-// x += alpha p ; r -= alpha q ; ||r||^2 -> part[wg]; Z != V: also rlo = fl32(r), the cycle's right-hand side
+// x += alpha p ; r -= alpha q ; ||r||^2 -> part[wg]; Z != V: also rlo = fl32(2^-e r), the cycle's right-hand side
 template <typename V, typename Z, int VW>
 __global__ __launch_bounds__(PCG_WG) void update_kernel(V *__restrict__ x, const V *__restrict__ p, V *__restrict__ r,
                                                         const V *__restrict__ q, Z *__restrict__ rlo, int64_t n,
@@ -132,6 +156,7 @@ __global__ __launch_bounds__(PCG_WG) void update_kernel(V *__restrict__ x, const
     __shared__ double sh[PCG_WG];
     if (pcg_done(sc)) return;
     const double alpha = sc[PCG_ALPHA];
+    const double down = scale_down<LO>(sc);
     const int64_t nc = n / VW, stride = int64_t(gridDim.x) * PCG_WG;
     double rr = 0.0;
     for (int64_t c = int64_t(blockIdx.x) * PCG_WG + threadIdx.x; c < nc; c += stride) {
@@ -148,7 +173,7 @@ __global__ __launch_bounds__(PCG_WG) void update_kernel(V *__restrict__ x, const
         if constexpr (LO) {
             Chunk<Z, VW> lo;
 #pragma unroll
-            for (int e = 0; e < VW; ++e) lo.v[e] = Z(rv.v[e]);
+            for (int e = 0; e < VW; ++e) lo.v[e] = Z(double(rv.v[e]) * down);
             st<Z, VW>(rlo, c, lo);
         }
     }
@@ -157,19 +182,22 @@ __global__ __launch_bounds__(PCG_WG) void update_kernel(V *__restrict__ x, const
             x[i] = V(fma(alpha, double(p[i]), double(x[i])));
             r[i] = V(fma(-alpha, double(q[i]), double(r[i])));
             rr = fma(double(r[i]), double(r[i]), rr);
-            if constexpr (LO) rlo[i] = Z(r[i]);
+            if constexpr (LO) rlo[i] = Z(double(r[i]) * down);
         }
     rr = block_sum(rr, sh);
     if (threadIdx.x == 0) part[blockIdx.x] = rr;
 }
 
 // r = b - q (r nullable) ; ||b - q||^2 -> part[wg].  Not gated by PCG_DONE (the set-up and the final true residual).
-// Z != V: also rlo = fl32(b - q) (nullable)
+// Z != V: also rlo = fl32(2^-e (b - q)) (nullable; sc is read only then)
 template <typename V, typename Z, int VW>
 __global__ __launch_bounds__(PCG_WG) void residual_kernel(const V *__restrict__ b, const V *__restrict__ q, V *__restrict__ r,
-                                                          Z *__restrict__ rlo, int64_t n, double *__restrict__ part) {
+                                                          Z *__restrict__ rlo, int64_t n, double *__restrict__ part,
+                                                          const double *__restrict__ sc) {
     constexpr bool LO = !std::is_same<V, Z>::value;
     __shared__ double sh[PCG_WG];
+    double down = 1.0;
+    if constexpr (LO) { if (rlo) down = scale_down<LO>(sc); }
     const int64_t nc = n / VW, stride = int64_t(gridDim.x) * PCG_WG;
     double rr = 0.0;
     for (int64_t c = int64_t(blockIdx.x) * PCG_WG + threadIdx.x; c < nc; c += stride) {
@@ -185,7 +213,7 @@ __global__ __launch_bounds__(PCG_WG) void residual_kernel(const V *__restrict__ 
             if (rlo) {
                 Chunk<Z, VW> lo;
 #pragma unroll
-                for (int e = 0; e < VW; ++e) lo.v[e] = Z(o.v[e]);
+                for (int e = 0; e < VW; ++e) lo.v[e] = Z(double(o.v[e]) * down);
                 st<Z, VW>(rlo, c, lo);
             }
         }
@@ -194,7 +222,7 @@ __global__ __launch_bounds__(PCG_WG) void residual_kernel(const V *__restrict__ 
         for (int64_t i = nc * VW + threadIdx.x; i < n; i += PCG_WG) {
             const V o = b[i] - q[i];
             if (r) r[i] = o;
-            if constexpr (LO) { if (rlo) rlo[i] = Z(o); }
+            if constexpr (LO) { if (rlo) rlo[i] = Z(double(o) * down); }
             rr = fma(double(o), double(o), rr);
         }
     rr = block_sum(rr, sh);
@@ -215,7 +243,9 @@ __global__ __launch_bounds__(PCG_WG) void plane_step_kernel(const Z *__restrict_
     const V beta = V(sc[PCG_BETA]);
     const V c0 = V(g.c[0]), c1 = V(g.c[1]), c2 = V(g.c[2]), c3 = V(g.c[3]), c4 = V(g.c[4]), c5 = V(g.c[5]), c6 = V(g.c[6]);
     const int64_t ps = int64_t(g.ny) * g.hx, n = 2 * g.nr, stride = int64_t(gridDim.x) * PCG_WG;
-    auto pv = [&](int64_t s) -> V { return V(fma(double(beta), double(p[s]), double(z[s]))); };
+    constexpr bool LO = !std::is_same<V, Z>::value;
+    const double up = scale_up<LO>(sc);
+    auto pv = [&](int64_t s) -> V { return V(fma(double(beta), double(p[s]), LO ? double(z[s]) * up : double(z[s]))); };
     double pq = 0.0;
     for (int64_t s = int64_t(blockIdx.x) * PCG_WG + threadIdx.x; s < n; s += stride) {
         const int colour = s >= g.nr ? 1 : 0;
@@ -251,31 +281,37 @@ __global__ __launch_bounds__(PCG_WG) void plane_step_kernel(const Z *__restrict_
 
 // ---- defect correction of the mixed plain cycle: x' = x + z, r = b - A x', fl32(r) for the next cycle, ||r||^2 ----------
 
-// x += z (any level); the fp64 SpMV and residual_kernel follow
+// x += 2^e z (any level); the fp64 SpMV and residual_kernel follow
 template <typename V, typename Z, int VW>
-__global__ __launch_bounds__(PCG_WG) void defect_add_kernel(V *__restrict__ x, const Z *__restrict__ z, int64_t n) {
+__global__ __launch_bounds__(PCG_WG) void defect_add_kernel(V *__restrict__ x, const Z *__restrict__ z, int64_t n,
+                                                            const double *__restrict__ sc) {
+    constexpr bool LO = !std::is_same<V, Z>::value;
+    const V up = V(scale_up<LO>(sc));
     const int64_t nc = n / VW, stride = int64_t(gridDim.x) * PCG_WG;
     for (int64_t c = int64_t(blockIdx.x) * PCG_WG + threadIdx.x; c < nc; c += stride) {
         Chunk<V, VW> xv = ld<V, VW>(x, c);
         const Chunk<Z, VW> zv = ld<Z, VW>(z, c);
 #pragma unroll
-        for (int e = 0; e < VW; ++e) xv.v[e] = xv.v[e] + V(zv.v[e]);
+        for (int e = 0; e < VW; ++e) xv.v[e] = xv.v[e] + (LO ? V(zv.v[e]) * up : V(zv.v[e]));
         st<V, VW>(x, c, xv);
     }
     if (blockIdx.x == 0)
-        for (int64_t i = nc * VW + threadIdx.x; i < n; i += PCG_WG) x[i] = x[i] + V(z[i]);
+        for (int64_t i = nc * VW + threadIdx.x; i < n; i += PCG_WG) x[i] = x[i] + (LO ? V(z[i]) * up : V(z[i]));
 }
 
 // On a plane level (the layout of plane_step_kernel): x2 = x + z, r = b - A x2 with the neighbours' x2 formed again from their
-// x and z (so x2 is a buffer of its own), rlo = fl32(r), ||r||^2 -> part[wg].  A x2 is plane_step_kernel's fma chain.
+// x and 2^e z (so x2 is a buffer of its own), rlo = fl32(2^-e' r), ||r||^2 -> part[wg].  A x2 is plane_step_kernel's fma chain.
 template <typename V, typename Z>
 __global__ __launch_bounds__(PCG_WG) void defect_plane_kernel(const V *__restrict__ x, const Z *__restrict__ z, V *__restrict__ x2,
                                                               const V *__restrict__ b, Z *__restrict__ rlo, PcgPlane g,
-                                                              double *__restrict__ part) {
+                                                              double *__restrict__ part, const double *__restrict__ sc) {
+    constexpr bool LO = !std::is_same<V, Z>::value;
     __shared__ double sh[PCG_WG];
+    const V up = V(scale_up<LO>(sc));
+    const double down = scale_down<LO>(sc);
     const V c0 = V(g.c[0]), c1 = V(g.c[1]), c2 = V(g.c[2]), c3 = V(g.c[3]), c4 = V(g.c[4]), c5 = V(g.c[5]), c6 = V(g.c[6]);
     const int64_t ps = int64_t(g.ny) * g.hx, n = 2 * g.nr, stride = int64_t(gridDim.x) * PCG_WG;
-    auto xv = [&](int64_t s) -> V { return x[s] + V(z[s]); };
+    auto xv = [&](int64_t s) -> V { return x[s] + (LO ? V(z[s]) * up : V(z[s])); };
     double rr = 0.0;
     for (int64_t s = int64_t(blockIdx.x) * PCG_WG + threadIdx.x; s < n; s += stride) {
         const int colour = s >= g.nr ? 1 : 0;
@@ -303,7 +339,7 @@ __global__ __launch_bounds__(PCG_WG) void defect_plane_kernel(const V *__restric
         a = fma(c6, kp, a);
         const V r = b[s] - a;
         x2[s] = d;
-        rlo[s] = Z(r);
+        rlo[s] = Z(LO ? double(r) * down : double(r));
         rr = fma(double(r), double(r), rr);
     }
     rr = block_sum(rr, sh);
@@ -356,14 +392,59 @@ __global__ __launch_bounds__(PCG_WG) void fold_norm_kernel(const double *__restr
     if (threadIdx.x != 0) return;
     norms[k] = nr;
     sc[PCG_ITERS] = double(k + 1);
+    sc[PCG_E_USED] = sc[PCG_E_NEXT];       // (the update that just ran wrote the cycle's right-hand side with it)
+    sc[PCG_E_NEXT] = scale_exponent(nr);
     if (!std::isfinite(nr)) pcg_break(sc);
     else if (threshold > 0.0 && nr < threshold) sc[PCG_DONE] = 1.0;
 }
 
-__global__ __launch_bounds__(PCG_WG) void fold_sqrt_kernel(const double *__restrict__ part, int nwg, double *__restrict__ out) {
+// sc (nullable): the mixed iteration's exponents move on as in fold_norm_kernel; first: both are this norm's
+__global__ __launch_bounds__(PCG_WG) void fold_sqrt_kernel(const double *__restrict__ part, int nwg, double *__restrict__ out,
+                                                           double *__restrict__ sc, int first) {
     __shared__ double sh[PCG_WG];
     const double s = fold(part, nwg, sh);
-    if (threadIdx.x == 0) *out = sqrt(s);
+    if (threadIdx.x != 0) return;
+    const double nr = sqrt(s);
+    if (out) *out = nr;
+    if (sc) {
+        const double e = scale_exponent(nr);
+        sc[PCG_E_USED] = first ? e : sc[PCG_E_NEXT];
+        sc[PCG_E_NEXT] = e;
+    }
+}
+
+// The start of a mixed iteration.  The first residual went to the cycle's right-hand side with the exponent of ||b||
+// (known since the load), in the pass that formed it.  That is the right size for a start from zero and for any start
+// within 2^60 of it either way; only for another one (a warm start far off, b = 0) do both exponents become that of
+// ||r0|| itself, and PCG_RELOWER makes lower_kernel write fl32(2^-e (b - q)) once more.
+constexpr double PCG_E_WINDOW = 60.0;
+__global__ __launch_bounds__(PCG_WG) void fold_start_kernel(const double *__restrict__ part, int nwg, double *__restrict__ sc) {
+    __shared__ double sh[PCG_WG];
+    const double s = fold(part, nwg, sh);
+    if (threadIdx.x != 0) return;
+    const double e = scale_exponent(sqrt(s));
+    if (fabs(e - sc[PCG_E_NEXT]) > PCG_E_WINDOW) {
+        sc[PCG_E_USED] = e;
+        sc[PCG_E_NEXT] = e;
+        sc[PCG_RELOWER] = 1.0;
+    }
+}
+
+template <typename V, typename Z, int VW>
+__global__ __launch_bounds__(PCG_WG) void lower_kernel(const V *__restrict__ b, const V *__restrict__ q, Z *__restrict__ rlo,
+                                                       int64_t n, const double *__restrict__ sc) {
+    if (sc[PCG_RELOWER] == 0.0) return;
+    const double down = scale_down<true>(sc);
+    const int64_t nc = n / VW, stride = int64_t(gridDim.x) * PCG_WG;
+    for (int64_t c = int64_t(blockIdx.x) * PCG_WG + threadIdx.x; c < nc; c += stride) {
+        const Chunk<V, VW> bv = ld<V, VW>(b, c), qv = ld<V, VW>(q, c);
+        Chunk<Z, VW> lo;
+#pragma unroll
+        for (int e = 0; e < VW; ++e) lo.v[e] = Z(double(bv.v[e] - qv.v[e]) * down);
+        st<Z, VW>(rlo, c, lo);
+    }
+    if (blockIdx.x == 0)
+        for (int64_t i = nc * VW + threadIdx.x; i < n; i += PCG_WG) rlo[i] = Z(double(b[i] - q[i]) * down);
 }
 
 template <typename V>
@@ -409,12 +490,16 @@ void pcg_update(V *x, const V *p, V *r, const V *q, Z *rlo, int64_t n, double *p
     PCG_LAUNCH(update_kernel, aligned16(x) && aligned16(p) && aligned16(r) && aligned16(q) && aligned16(rlo), x, p, r, q, rlo, n, part, sc);
 }
 template <typename V, typename Z>
-void pcg_residual(const V *b, const V *q, V *r, Z *rlo, int64_t n, double *part, hipStream_t s) {
-    PCG_LAUNCH(residual_kernel, aligned16(b) && aligned16(q) && aligned16(r) && aligned16(rlo), b, q, r, rlo, n, part);
+void pcg_residual(const V *b, const V *q, V *r, Z *rlo, int64_t n, double *part, const double *sc, hipStream_t s) {
+    PCG_LAUNCH(residual_kernel, aligned16(b) && aligned16(q) && aligned16(r) && aligned16(rlo), b, q, r, rlo, n, part, sc);
 }
 template <typename V, typename Z>
-void pcg_defect_add(V *x, const Z *z, int64_t n, hipStream_t s) {
-    PCG_LAUNCH(defect_add_kernel, aligned16(x) && aligned16(z), x, z, n);
+void pcg_defect_add(V *x, const Z *z, int64_t n, const double *sc, hipStream_t s) {
+    PCG_LAUNCH(defect_add_kernel, aligned16(x) && aligned16(z), x, z, n, sc);
+}
+template <typename V, typename Z>
+void pcg_lower(const V *b, const V *q, Z *rlo, int64_t n, const double *sc, hipStream_t s) {
+    PCG_LAUNCH(lower_kernel, aligned16(b) && aligned16(q) && aligned16(rlo), b, q, rlo, n, sc);
 }
 #undef PCG_LAUNCH
 
@@ -428,10 +513,11 @@ int pcg_plane_step(const PcgPlane &g, const Z *z, const V *p, V *p2, V *q, doubl
 }
 
 template <typename V, typename Z>
-int pcg_defect_plane(const PcgPlane &g, const V *x, const Z *z, V *x2, const V *b, Z *rlo, double *part, hipStream_t s) {
+int pcg_defect_plane(const PcgPlane &g, const V *x, const Z *z, V *x2, const V *b, Z *rlo, double *part, const double *sc,
+                     hipStream_t s) {
     const int64_t n = 2 * g.nr;
     const int nwg = int(std::max<int64_t>(1, std::min<int64_t>(PCG_MAX_WG, (n + PCG_WG - 1) / PCG_WG)));
-    hipLaunchKernelGGL((defect_plane_kernel<V, Z>), dim3(unsigned(nwg)), dim3(PCG_WG), 0, s, x, z, x2, b, rlo, g, part);
+    hipLaunchKernelGGL((defect_plane_kernel<V, Z>), dim3(unsigned(nwg)), dim3(PCG_WG), 0, s, x, z, x2, b, rlo, g, part, sc);
     OMG_HIP(hipGetLastError());
     return nwg;
 }
@@ -448,8 +534,12 @@ void pcg_fold_norm(const double *part, int nwg, double *sc, double *norms, int k
     hipLaunchKernelGGL(fold_norm_kernel, dim3(1), dim3(PCG_WG), 0, s, part, nwg, sc, norms, k, threshold);
     OMG_HIP(hipGetLastError());
 }
-void pcg_fold_sqrt(const double *part, int nwg, double *out, hipStream_t s) {
-    hipLaunchKernelGGL(fold_sqrt_kernel, dim3(1), dim3(PCG_WG), 0, s, part, nwg, out);
+void pcg_fold_start(const double *part, int nwg, double *sc, hipStream_t s) {
+    hipLaunchKernelGGL(fold_start_kernel, dim3(1), dim3(PCG_WG), 0, s, part, nwg, sc);
+    OMG_HIP(hipGetLastError());
+}
+void pcg_fold_sqrt(const double *part, int nwg, double *out, hipStream_t s, double *sc, bool first) {
+    hipLaunchKernelGGL(fold_sqrt_kernel, dim3(1), dim3(PCG_WG), 0, s, part, nwg, out, sc, first ? 1 : 0);
     OMG_HIP(hipGetLastError());
 }
 
@@ -457,14 +547,15 @@ void pcg_fold_sqrt(const double *part, int nwg, double *out, hipStream_t s) {
     template void pcg_dots<V, Z>(const V *, const Z *, const V *, int64_t, double *, const double *, hipStream_t);       \
     template void pcg_pupdate<V, Z>(const Z *, const V *, V *, int64_t, const double *, hipStream_t);                    \
     template void pcg_update<V, Z>(V *, const V *, V *, const V *, Z *, int64_t, double *, const double *, hipStream_t); \
-    template void pcg_residual<V, Z>(const V *, const V *, V *, Z *, int64_t, double *, hipStream_t);                    \
+    template void pcg_residual<V, Z>(const V *, const V *, V *, Z *, int64_t, double *, const double *, hipStream_t);    \
     template int pcg_plane_step<V, Z>(const PcgPlane &, const Z *, const V *, V *, V *, double *, const double *, hipStream_t);   \
-    template void pcg_defect_add<V, Z>(V *, const Z *, int64_t, hipStream_t);                                            \
-    template int pcg_defect_plane<V, Z>(const PcgPlane &, const V *, const Z *, V *, const V *, Z *, double *, hipStream_t);
+    template void pcg_defect_add<V, Z>(V *, const Z *, int64_t, const double *, hipStream_t);                            \
+    template int pcg_defect_plane<V, Z>(const PcgPlane &, const V *, const Z *, V *, const V *, Z *, double *, const double *, hipStream_t);
 PCG_INST(double, double)
 PCG_INST(float, float)
 PCG_INST(double, float)
 #undef PCG_INST
+template void pcg_lower<double, float>(const double *, const double *, float *, int64_t, const double *, hipStream_t);
 template int pcg_wgs<double>(int64_t);
 template int pcg_wgs<float>(int64_t);
 template void pcg_dot<double>(const double *, const double *, int64_t, double *, const double *, hipStream_t);

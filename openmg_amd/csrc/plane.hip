@@ -241,7 +241,9 @@ __device__ __forceinline__ V chain_tail(const PlaneKArgs<V> &a, V s, V d, V ip, 
 // denominator, the sequence reduces to q0 = n r, q = fma(fma(-c, q0, n), r, q0) with r = the refined
 // reciprocal: the same instructions on the same operands, hence the same bits (march.hip does the same;
 // tests/test_gpu_plane.py compares with the row kernels, which divide).  A wave that meets any other
-// numerator redoes its four quotients with the division itself.
+// numerator redoes its four quotients with the division itself.  One case differs in one bit: from a numerator of
+// -0.0 (which plain_numerator takes) the sequence gives +0.0 where the division gives -0.0: fma(-c, -0, -0) = +0.
+// The relaxation ADDS the quotient to x, so only an x of -0.0 could show it (tests/test_gpu_scaling.py).
 __device__ __forceinline__ double refined_rcp(double d) {
     double r = __builtin_amdgcn_rcp(d);
     double e = fma(-d, r, 1.0);
