@@ -8,6 +8,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <array>
 #include <map>
@@ -1363,6 +1364,164 @@ template <typename V>
 void ensure_format(const Hier<V> *h, int l) { ensure_format(const_cast<Hier<V> *>(h), l); }
 
 
+// ---- The steps of setup that create() and create_from_fine() share, in the order both take them ----
+
+// A new handle: its stream and the norm's slot.
+template <typename V>
+std::unique_ptr<Hier<V>> new_handle(int smoother, double omega, int nullspace) {
+    std::unique_ptr<Hier<V>> h(new Hier<V>);
+    h->smoother = smoother;
+    h->omega = omega;
+    h->coarse.nullspace = nullspace;       // (every build() of this hierarchy's coarse solver honours it: at setup and in update_fine)
+    OMG_HIP(hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking));
+    h->stream = h->own;
+    h->norm_dev.alloc(1);
+    return h;
+}
+
+// The coarsest level: n rows in their natural order, one set.
+template <typename V>
+void coarsest_level(Level<V> &L, int64_t n) {
+    L.n = n;
+    L.ord.identity = true;
+    L.ord.sets = {0, L.n};
+}
+
+// The coarsest operator on the device and its factorisation (at setup: on the helper thread's stream; in an update: on the handle's)
+template <typename V>
+void factorise_coarsest(Hier<V> *h, const HostCsr &Ac, hipStream_t s) {
+    Level<V> &L = h->lv.back();
+    L.A.upload(Ac, L.ord.sets, s);
+    h->coarse.build(Ac, s);                // factors in double, stored in V
+}
+
+// The coarsest operator is factored once (reference: SuperLU factorisation on every
+// cycle; here: explicit inverse or substructuring along the band, common.h CoarseSolver).
+// That is thousands of tiny dependent launches, so it runs on a helper thread with its own
+// stream while the calling thread does the index work of the smoothed levels.  The factors are
+// always computed in double; a float hierarchy stores their rounding.
+// An error of the work is kept until rethrow().  Declared AFTER the handle and whatever else the work reads: the destructor
+// joins, so an exception on the calling thread ends the helper before any of that dies.
+struct CoarseThread {
+    int code = OMG_OK;
+    std::string msg;
+    std::thread t;                         // (last: code and msg exist when it starts)
+    static int current_device() { int device = 0; OMG_HIP(hipGetDevice(&device)); return device; }
+    void run(int device, const std::function<void(hipStream_t)> &work) {
+        hipStream_t s = nullptr;
+        SetupTimer tm("coarse factorisation (helper thread)");
+        try {
+            OMG_HIP(hipSetDevice(device));
+            OMG_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+            work(s);
+        } catch (const Error &e) {
+            code = e.code;
+            msg = e.what();
+        } catch (const std::exception &e) {
+            code = OMG_ERR_HIP;
+            msg = e.what();
+        }
+        if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
+    }
+    explicit CoarseThread(std::function<void(hipStream_t)> work) : t(&CoarseThread::run, this, current_device(), std::move(work)) {}
+    CoarseThread(const CoarseThread &) = delete;
+    CoarseThread &operator=(const CoarseThread &) = delete;
+    ~CoarseThread() { finish(); }
+    void finish() { if (t.joinable()) t.join(); }
+    void rethrow() const { if (code != OMG_OK) throw Error(code, msg); }        // (after finish())
+};
+
+// OMG_PLANE_CHECK_ORDER=1 (tests): a fused level's closed-form ordering is the greedy colouring's (a Jacobi plane level keeps
+// its natural ordering: nothing to compare)
+void check_closed_form(const omg_csr &A, int smoother, const Ordering &ord, const char *what) {
+    if (!getenv_flag("OMG_PLANE_CHECK_ORDER") || smoother != OMG_SMOOTH_GS_COLOUR) return;
+    const Ordering g = make_ordering(A, smoother);
+    OMG_REQUIRE(g.sets == ord.sets && g.perm == ord.perm && g.inv == ord.inv, what);
+}
+
+// The ordering maps of level l on the device: perm (slot -> natural row, for the gathers at the host boundary) and, for the
+// level above the coarsest, r_out — restriction rows are in NATURAL coarse order and write through this map into the coarse
+// level's ordering (build_format; the plane passes use it too).  closed_form_by_kernel: a closed-form ordering's maps are
+// written by a kernel (create_from_fine: nothing of it is on the host); otherwise, and for every other ordering, the host's
+// arrays are uploaded, each upload waited for.
+template <typename V>
+void level_maps(Hier<V> *h, int l, bool closed_form_by_kernel) {
+    Level<V> &L = h->lv[size_t(l)];
+    if (!L.ord.identity) {
+        L.perm.alloc(L.n);
+        if (closed_form_by_kernel && L.ord.closed_form) {
+            fill_ordering_device(L.ord.closed_form, L.ord.cf_nx, L.ord.cf_ny, L.ord.cf_nz, L.perm.p, nullptr, h->stream);
+        } else {
+            L.perm.upload(L.ord.perm.data(), L.n, h->stream);
+            OMG_HIP(hipStreamSynchronize(h->stream));
+        }
+    }
+    if (size_t(l) + 1 >= h->lv.size()) return;
+    const Level<V> &C = h->lv[size_t(l) + 1];
+    const Ordering &co = C.ord;
+    if (co.identity) return;
+    L.r_out.alloc(size_t(C.n));
+    if (closed_form_by_kernel && co.closed_form) {
+        fill_ordering_device(co.closed_form, co.cf_nx, co.cf_ny, co.cf_nz, nullptr, L.r_out.p, h->stream);
+    } else {
+        L.r_out.upload(co.inv.data(), co.inv.size(), h->stream);
+        OMG_HIP(hipStreamSynchronize(h->stream));
+    }
+}
+
+// The scratch vector of a smoothed level that runs a fused path.  (Apart from level_vectors: the level's format is made
+// between the two, and the order of the allocations decides where the large vectors land — place_finest_pool.)
+template <typename V>
+void level_scratch(Hier<V> *h, int l) {
+    Level<V> &L = h->lv[size_t(l)];
+    if (L.plane && !pooled_vectors(L)) L.tmp.alloc(L.n, vector_stagger(1));
+    if (L.s27 && !pooled_vectors(L)) L.tmp.alloc(L.n);
+    if (L.var7 && !L.tmp.p) L.tmp.alloc(L.n);
+}
+
+// The iterate and the right-hand side of level l, and what the cycle starts from.
+template <typename V>
+void level_vectors(Hier<V> *h, int l) {
+    Level<V> &L = h->lv[size_t(l)];
+    if (!L.x.p) {
+        L.x.alloc(std::max<int64_t>(L.n, 1));
+        L.b.alloc(std::max<int64_t>(L.n, 1), L.plane ? vector_stagger(2) : 0);
+    }
+    // (finite from the start: the 27-point sweeps multiply the slot of a neighbour that does not exist — a zero
+    // coefficient — with whatever the vectors hold at the index the slot's shift lands on)
+    L.x.zero(h->stream);
+    L.tmp.zero(h->stream);
+    L.xp = L.x.p;
+    L.tp = L.tmp.p;
+    if (SetupTimer::on() && l == 0) fprintf(stderr, "[omg setup] level 0 vectors at x %p  tmp %p  b %p\n", (void *)L.x.p, (void *)L.tmp.p, (void *)L.b.p);
+}
+
+// The end of setup: the large levels' tilings, the wait for the helper thread, the placements, the helper's error.
+template <typename V>
+void finish_setup(const std::unique_ptr<Hier<V>> &h, CoarseThread &inverter) {
+    for (size_t l = 0; l + 1 < h->lv.size(); ++l) {
+        // the large levels' tilings: measured, not modelled (plane.hip choose_tiles; tune() skips the small ones)
+        if (!h->lv[l].plane || !h->lv[l].tmp.p) continue;
+        SetupTimer tm("plane tiling of a large level");
+        Level<V> &L = h->lv[l], &C = h->lv[l + 1];
+        L.x.zero(h->stream); L.tmp.zero(h->stream); L.b.zero(h->stream); C.x.zero(h->stream);
+        typename PlanePlan<V>::Coarse c;
+        c.map = L.r_out.p;
+        c.b = C.b.p;
+        c.e = C.xp;
+        L.plane->tune(L.xp, L.tp, L.b.p, c, h->stream, l == 0);
+        OMG_HIP(hipStreamSynchronize(h->stream));
+    }
+    // (first: the coarse factorisation's kernels on their own stream beside the timed passes would make a candidate look slow
+    // and the decision depend on the overlap)
+    { SetupTimer tm("wait for the coarse factorisation"); inverter.finish(); }
+    place_finest_pool(h.get());
+    place_s27_tiles(h.get());
+    inverter.rethrow();                    // (an error of the calling thread has propagated before this one)
+    OMG_HIP(hipStreamSynchronize(h->stream));
+}
+
+
 template <typename V>
 std::unique_ptr<Hier<V>> create(int n_levels, const omg_csr *A, const omg_csr *R, int smoother,
                                 double omega, int nullspace = OMG_NULLSPACE_NONE) {
@@ -1382,53 +1541,16 @@ std::unique_ptr<Hier<V>> create(int n_levels, const omg_csr *A, const omg_csr *R
         }
     }
     require_device();
-    std::unique_ptr<H> h(new H);
-    h->smoother = smoother;
-    h->omega = omega;
-    h->coarse.nullspace = nullspace;       // (every build() of this hierarchy's coarse solver honours it: here and in update_fine)
-    OMG_HIP(hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking));
-    h->stream = h->own;
+    std::unique_ptr<H> h = new_handle<V>(smoother, omega, nullspace);
     h->lv.resize(n_levels);
-    h->norm_dev.alloc(1);
-    // The coarsest operator is factored once (reference: SuperLU factorisation on every
-    // cycle; here: explicit inverse or substructuring along the band, common.h CoarseSolver).
-    // That is thousands of tiny dependent launches, so it runs on a helper thread with its own
-    // stream while this thread does the index work of the smoothed levels.  The factors are
-    // always computed in double; a float hierarchy stores their rounding.
-    int device = 0;
-    OMG_HIP(hipGetDevice(&device));
-    {
-        Lv &L = h->lv.back();
-        L.n = A[n_levels - 1].n_rows;
-        L.ord.identity = true;
-        L.ord.sets = {0, L.n};
-    }
-    int inv_code = OMG_OK;
-    std::string inv_msg;
-    std::thread inverter([&] {
-        hipStream_t s = nullptr;
-        SetupTimer tm("coarse factorisation (helper thread)");
-        try {
-            OMG_HIP(hipSetDevice(device));
-            OMG_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-            Lv &L = h->lv.back();
-            HostCsr Ap = permute_csr(A[n_levels - 1], nullptr, nullptr);
-            L.A.upload(Ap, L.ord.sets, s);
-            h->coarse.build(Ap, s);               // factors in double, stored in V
-        } catch (const Error &e) {
-            inv_code = e.code;
-            inv_msg = e.what();
-        } catch (const std::exception &e) {
-            inv_code = OMG_ERR_HIP;
-            inv_msg = e.what();
-        }
-        if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
-    });
-    struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{inverter};
+    coarsest_level(h->lv.back(), A[n_levels - 1].n_rows);
+    // (the copy of the caller's coarsest operator is made on the helper thread too)
+    CoarseThread inverter([&](hipStream_t s) { factorise_coarsest(h.get(), permute_csr(A[n_levels - 1], nullptr, nullptr), s); });
     // orderings first (restrictions need both neighbours')
     for (int l = 0; l + 1 < n_levels; ++l) {
         Lv &L = h->lv[l];
         L.n = A[l].n_rows;
+        auto check_parity = [&] { check_closed_form(A[l], smoother, L.ord, "internal: the parity ordering differs from the greedy colouring"); };
         if (smoother == OMG_SMOOTH_GS_COLOUR || smoother == OMG_SMOOTH_JACOBI) {
             SetupTimer tp("plane-pipelined passes: does the level qualify (+ its parity ordering)");
             std::unique_ptr<PlanePlan<V>> plan(new PlanePlan<V>);
@@ -1438,22 +1560,13 @@ std::unique_ptr<Hier<V>> create(int n_levels, const omg_csr *A, const omg_csr *R
                 if (!h->plane_status.p) { h->plane_status.alloc(1); h->plane_status.zero(h->stream); }
                 plan->status = h->plane_status.p;
                 L.plane = std::move(plan);
-                // OMG_PLANE_CHECK_ORDER=1 (tests): the closed-form ordering is the greedy colouring's
-                if (getenv_flag("OMG_PLANE_CHECK_ORDER") && smoother == OMG_SMOOTH_GS_COLOUR) {
-                    const Ordering g = make_ordering(A[l], smoother);
-                    OMG_REQUIRE(g.sets == L.ord.sets && g.perm == L.ord.perm && g.inv == L.ord.inv,
-                                "internal: the parity ordering differs from the greedy colouring");
-                }
+                check_parity();
                 continue;
             }
             std::unique_ptr<Stencil27Plan<V>> s27(new Stencil27Plan<V>);
             if (smoother == OMG_SMOOTH_GS_COLOUR && s27->build(A[l], R[l], L.ord, h->stream)) {
                 L.s27 = std::move(s27);
-                if (getenv_flag("OMG_PLANE_CHECK_ORDER")) {
-                    const Ordering g = make_ordering(A[l], smoother);
-                    OMG_REQUIRE(g.sets == L.ord.sets && g.perm == L.ord.perm && g.inv == L.ord.inv,
-                                "internal: the octant ordering differs from the greedy colouring");
-                }
+                check_closed_form(A[l], smoother, L.ord, "internal: the octant ordering differs from the greedy colouring");
                 continue;
             }
         }
@@ -1463,11 +1576,7 @@ std::unique_ptr<Hier<V>> create(int n_levels, const omg_csr *A, const omg_csr *R
             std::unique_ptr<Var7Plan<V>> v7(new Var7Plan<V>);
             if (v7->build(A[l], R[l], L.ord, h->stream)) {
                 L.var7 = std::move(v7);
-                if (getenv_flag("OMG_PLANE_CHECK_ORDER")) {
-                    const Ordering g = make_ordering(A[l], smoother);
-                    OMG_REQUIRE(g.sets == L.ord.sets && g.perm == L.ord.perm && g.inv == L.ord.inv,
-                                "internal: the parity ordering differs from the greedy colouring");
-                }
+                check_parity();
                 continue;
             }
         }
@@ -1476,60 +1585,18 @@ std::unique_ptr<Hier<V>> create(int n_levels, const omg_csr *A, const omg_csr *R
     }
     for (int l = 0; l < n_levels; ++l) {
         Lv &L = h->lv[l];
-        const bool id = L.ord.identity;
-        if (!id) {
-            L.perm.alloc(L.n);
-            L.perm.upload(L.ord.perm.data(), L.n, h->stream);
-            OMG_HIP(hipStreamSynchronize(h->stream));
-        }
+        // (every ordering is on the host here, a closed-form one too — the host builds write it out —, and is uploaded)
+        level_maps(h.get(), l, false);
         if (l + 1 < n_levels) {
-            const Ordering &co = h->lv[l + 1].ord;
-            if (!co.identity) {
-                // restriction rows are in NATURAL coarse order and write through this map into the coarse
-                // level's ordering (build_format; the plane passes use it too)
-                L.r_out.alloc(co.inv.size());
-                L.r_out.upload(co.inv.data(), co.inv.size(), h->stream);
-                OMG_HIP(hipStreamSynchronize(h->stream));
-            }
-            if (L.plane && !pooled_vectors(L)) L.tmp.alloc(L.n, vector_stagger(1));
-            if (L.s27 && !pooled_vectors(L)) L.tmp.alloc(L.n);
-            if (L.var7 && !L.tmp.p) L.tmp.alloc(L.n);
+            level_scratch(h.get(), l);
+            // (OMG_PLANE_LAZY=0, the format at creation, is this route's switch alone: the device route always leaves a fused level's to its first use)
             if ((L.plane || L.s27 || L.var7) && !experiment_flag0("OMG_PLANE_LAZY")) L.format_pending = true;
             else if (L.s27) { L.format_pending = true; ensure_format(h.get(), l); }      // (from the padded operator)
             else build_format(h.get(), l, A[l], R[l]);
         }
-        if (!L.x.p) {
-            L.x.alloc(std::max<int64_t>(L.n, 1));
-            L.b.alloc(std::max<int64_t>(L.n, 1), L.plane ? vector_stagger(2) : 0);
-        }
-        // (finite from the start: the 27-point sweeps multiply the slot of a neighbour that does not exist — a zero
-        // coefficient — with whatever the vectors hold at the index the slot's shift lands on)
-        L.x.zero(h->stream);
-        L.tmp.zero(h->stream);
-        L.xp = L.x.p;
-        L.tp = L.tmp.p;
-        if (SetupTimer::on() && l == 0) fprintf(stderr, "[omg setup] level 0 vectors at x %p  tmp %p  b %p\n", (void *)L.x.p, (void *)L.tmp.p, (void *)L.b.p);
+        level_vectors(h.get(), l);
     }
-    for (int l = 0; l + 1 < n_levels; ++l) {
-        // the large levels' tilings: measured, not modelled (plane.hip choose_tiles; tune() skips the small ones)
-        if (!h->lv[l].plane || !h->lv[l].tmp.p) continue;
-        SetupTimer tm("plane tiling of a large level");
-        Level<V> &L = h->lv[l], &C = h->lv[l + 1];
-        L.x.zero(h->stream); L.tmp.zero(h->stream); L.b.zero(h->stream); C.x.zero(h->stream);
-        typename PlanePlan<V>::Coarse c;
-        c.map = L.r_out.p;
-        c.b = C.b.p;
-        c.e = C.xp;
-        L.plane->tune(L.xp, L.tp, L.b.p, c, h->stream, l == 0);
-        OMG_HIP(hipStreamSynchronize(h->stream));
-    }
-    // (first: the coarse factorisation's kernels on their own stream beside the timed passes would make a candidate look slow
-    // and the decision depend on the overlap)
-    { SetupTimer tm("wait for the coarse factorisation"); inverter.join(); }
-    place_finest_pool(h.get());
-    place_s27_tiles(h.get());
-    if (inv_code != OMG_OK) throw Error(inv_code, inv_msg);
-    OMG_HIP(hipStreamSynchronize(h->stream));
+    finish_setup(h, inverter);
     return h;
 }
 
@@ -1551,13 +1618,7 @@ std::unique_ptr<Hier<V>> create_from_fine(const omg_csr &A0, int dim, const int6
     // true one: first and last extent equal
     OMG_REQUIRE(shape[0] == shape[dim - 1], "device setup: first and last extent must be equal");
     require_device();
-    std::unique_ptr<H> h(new H);
-    h->smoother = smoother;
-    h->omega = omega;
-    h->coarse.nullspace = nullspace;
-    OMG_HIP(hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking));
-    h->stream = h->own;
-    h->norm_dev.alloc(1);
+    std::unique_ptr<H> h = new_handle<V>(smoother, omega, nullspace);
     std::vector<DevCsrPlain> dA, dR;
     galerkin_chain_device(A0, dim, shape, n_restrictions, dA, dR, h->stream);
     const int n_levels = n_restrictions + 1;
@@ -1627,38 +1688,11 @@ std::unique_ptr<Hier<V>> create_from_fine(const omg_csr &A0, int dim, const int6
         h.reset();
         return create<V>(n_levels, vA.data(), vR.data(), smoother, omega, nullspace);
     }
-    // the coarsest operator: to the host for its factorisation (helper thread, as in create())
-    int device = 0;
-    OMG_HIP(hipGetDevice(&device));
-    HostCsr Ac = download_csr(dA.back(), h->stream);
-    {
-        Lv &L = h->lv.back();
-        L.n = Ac.n_rows;
-        L.ord.identity = true;
-        L.ord.sets = {0, L.n};
-    }
+    // the coarsest operator: to the host for its factorisation
+    const HostCsr Ac = download_csr(dA.back(), h->stream);
+    coarsest_level(h->lv.back(), Ac.n_rows);
     check_diagonal(view(Ac), n_levels - 1);
-    int inv_code = OMG_OK;
-    std::string inv_msg;
-    std::thread inverter([&] {
-        hipStream_t s = nullptr;
-        SetupTimer tm("coarse factorisation (helper thread)");
-        try {
-            OMG_HIP(hipSetDevice(device));
-            OMG_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-            Lv &L = h->lv.back();
-            L.A.upload(Ac, L.ord.sets, s);
-            h->coarse.build(Ac, s);
-        } catch (const Error &e) {
-            inv_code = e.code;
-            inv_msg = e.what();
-        } catch (const std::exception &e) {
-            inv_code = OMG_ERR_HIP;
-            inv_msg = e.what();
-        }
-        if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
-    });
-    struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{inverter};
+    CoarseThread inverter([&](hipStream_t s) { factorise_coarsest(h.get(), Ac, s); });
     {
         // (new coefficients later: omg_hierarchy_update_fine needs the fine pattern's row pointers, nothing else of the operators;
         // 27-point levels throughout, or 7-point var7 levels with host-coded levels below them)
@@ -1679,97 +1713,91 @@ std::unique_ptr<Hier<V>> create_from_fine(const omg_csr &A0, int dim, const int6
     dR.clear();
     for (int l = 0; l < n_levels; ++l) {
         Lv &L = h->lv[size_t(l)];
-        if (!L.ord.identity) {
-            L.perm.alloc(L.n);
-            if (L.ord.closed_form) {
-                // slot -> natural row, for the gathers at the host boundary: written by a kernel
-                fill_ordering_device(L.ord.closed_form, L.ord.cf_nx, L.ord.cf_ny, L.ord.cf_nz, L.perm.p, nullptr, h->stream);
-            } else {
-                L.perm.upload(L.ord.perm.data(), L.n, h->stream);         // (a level the host ordered)
-                OMG_HIP(hipStreamSynchronize(h->stream));
-            }
-        }
+        // (a closed-form ordering exists on the device only: a kernel writes its maps; a level the host ordered is uploaded)
+        level_maps(h.get(), l, true);
         if (l + 1 < n_levels) {
-            Ordering &co = h->lv[size_t(l) + 1].ord;
-            if (!co.identity) {
-                L.r_out.alloc(size_t(h->lv[size_t(l) + 1].n));
-                if (co.closed_form) {
-                    fill_ordering_device(co.closed_form, co.cf_nx, co.cf_ny, co.cf_nz, nullptr, L.r_out.p, h->stream);
-                } else {
-                    L.r_out.upload(co.inv.data(), co.inv.size(), h->stream);
-                    OMG_HIP(hipStreamSynchronize(h->stream));
-                }
-            }
-            if (L.plane && !pooled_vectors(L)) L.tmp.alloc(L.n, vector_stagger(1));
-            if (L.s27 && !pooled_vectors(L)) L.tmp.alloc(L.n);
-            if (L.var7 && !L.tmp.p) L.tmp.alloc(L.n);
+            level_scratch(h.get(), l);
             if (host_level[size_t(l)]) {
                 // (the restriction's rows land in the coarse level's ordering: a closed-form one is written out for that)
-                materialise_ordering(co);
+                materialise_ordering(h->lv[size_t(l) + 1].ord);
                 build_format(h.get(), l, view(hostA[size_t(l)]), view(hostR[size_t(l)]));
             } else {
                 L.format_pending = true;
             }
         }
-        if (!L.x.p) {
-            L.x.alloc(std::max<int64_t>(L.n, 1));
-            L.b.alloc(std::max<int64_t>(L.n, 1), L.plane ? vector_stagger(2) : 0);
-        }
-        // (finite from the start: the 27-point sweeps multiply the slot of a neighbour that does not exist — a zero
-        // coefficient — with whatever the vectors hold at the index the slot's shift lands on)
-        L.x.zero(h->stream);
-        L.tmp.zero(h->stream);
-        L.xp = L.x.p;
-        L.tp = L.tmp.p;
-        if (SetupTimer::on() && l == 0) fprintf(stderr, "[omg setup] level 0 vectors at x %p  tmp %p  b %p\n", (void *)L.x.p, (void *)L.tmp.p, (void *)L.b.p);
+        level_vectors(h.get(), l);
     }
+    // (this route's alone: create() has never waited here.  No result can depend on it, the stream orders the work; what the
+    // tuning passes of finish_setup measure might, so each route keeps what it had)
     OMG_HIP(hipStreamSynchronize(h->stream));
-    for (int l = 0; l + 1 < n_levels; ++l) {
-        if (!h->lv[size_t(l)].plane || !h->lv[size_t(l)].tmp.p) continue;
-        SetupTimer tm("plane tiling of a large level");
-        Level<V> &L = h->lv[size_t(l)], &C = h->lv[size_t(l) + 1];
-        L.x.zero(h->stream); L.tmp.zero(h->stream); L.b.zero(h->stream); C.x.zero(h->stream);
-        typename PlanePlan<V>::Coarse c;
-        c.map = L.r_out.p;
-        c.b = C.b.p;
-        c.e = C.xp;
-        L.plane->tune(L.xp, L.tp, L.b.p, c, h->stream, l == 0);
-        OMG_HIP(hipStreamSynchronize(h->stream));
-    }
-    // (first: the coarse factorisation's kernels on their own stream beside the timed passes would make a candidate look slow
-    // and the decision depend on the overlap)
-    { SetupTimer tm("wait for the coarse factorisation"); inverter.join(); }
-    place_finest_pool(h.get());
-    place_s27_tiles(h.get());
-    if (inv_code != OMG_OK) throw Error(inv_code, inv_msg);
-    OMG_HIP(hipStreamSynchronize(h->stream));
+    finish_setup(h, inverter);
     return h;
 }
 
-// A 7-point level's operator from its dense [row][7] form (slots -K, -J, -I, D, +I, +J, +K): the in-grid neighbours whose value
-// is not exactly zero, columns ascending — what the Galerkin chain hands create_from_fine (SciPy drops exact zeros).
-HostCsr csr_from_dense7(const std::vector<double> &d, int nx, int ny, int nz) {
-    const int64_t n = int64_t(nx) * ny * nz, sj = nx, sk = int64_t(nx) * ny;
+// A grid level's operator from its dense [row][S] form on the device, slot e the neighbour at offset slots[e] (ascending in
+// column): the in-grid neighbours whose value is not exactly zero, columns ascending — what the Galerkin chain hands
+// create_from_fine (SciPy's csr_matmat drops exact zeros).
+struct SlotOffset { int dx, dy, dz; };
+// 7-point levels: -K, -J, -I, D, +I, +J, +K
+std::vector<SlotOffset> slots7() { return {{0, 0, -1}, {0, -1, 0}, {-1, 0, 0}, {0, 0, 0}, {1, 0, 0}, {0, 1, 0}, {0, 0, 1}}; }
+// 27-point levels: x fastest
+std::vector<SlotOffset> slots27() {
+    std::vector<SlotOffset> s;
+    for (int sl = 0; sl < 27; ++sl) s.push_back({sl % 3 - 1, (sl / 3) % 3 - 1, sl / 9 - 1});
+    return s;
+}
+template <typename V>
+HostCsr csr_from_dense(Hier<V> *h, const DevBuf<double> &dense, const std::vector<SlotOffset> &slots, int nx, int ny, int nz) {
+    const int64_t n = int64_t(nx) * ny * nz;
+    const size_t S = slots.size();
+    std::vector<double> d(size_t(n) * S);
+    OMG_HIP(hipMemcpyAsync(d.data(), dense.p, d.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    OMG_HIP(hipStreamSynchronize(h->stream));
     HostCsr A;
     A.n_rows = A.n_cols = n;
     A.indptr.resize(size_t(n) + 1);
-    A.indices.reserve(size_t(n) * 7);
-    A.data.reserve(size_t(n) * 7);
+    A.indices.reserve(d.size());
+    A.data.reserve(d.size());
     for (int64_t r = 0; r < n; ++r) {
         A.indptr[size_t(r)] = int32_t(A.indices.size());
-        const int64_t i = r % nx, j = (r / nx) % ny, k = r / sk;
-        const int64_t col[7] = {r - sk, r - sj, r - 1, r, r + 1, r + sj, r + sk};
-        const bool in[7] = {k > 0, j > 0, i > 0, true, i + 1 < nx, j + 1 < ny, k + 1 < nz};
-        for (int e = 0; e < 7; ++e) {
-            const double v = d[size_t(r) * 7 + size_t(e)];
-            if (!in[e] || v == 0.0) continue;
-            A.indices.push_back(int32_t(col[e]));
+        const int64_t i = r % nx, j = (r / nx) % ny, k = r / (int64_t(nx) * ny);
+        for (size_t e = 0; e < S; ++e) {
+            const SlotOffset &o = slots[e];
+            const bool present = i + o.dx >= 0 && i + o.dx < nx && j + o.dy >= 0 && j + o.dy < ny && k + o.dz >= 0 && k + o.dz < nz;
+            const double v = d[size_t(r) * S + e];
+            if (!present || v == 0.0) continue;
+            A.indices.push_back(int32_t(r + (int64_t(o.dz) * ny + o.dy) * nx + o.dx));
             A.data.push_back(v);
         }
     }
     A.indptr[size_t(n)] = int32_t(A.indices.size());
     A.nnz = int64_t(A.indices.size());
     return A;
+}
+
+// The opening of an update: the value array checked, the handle idle, no captured cycle of the old operator, the new values
+// on the device (up: the owner of a host array's copy).  Returns the device array.
+template <typename V>
+const double *update_values(Hier<V> *h, const double *vals, int64_t nnz, bool on_device, DevBuf<double> &up) {
+    OMG_REQUIRE(vals && nnz == h->nnz0, "omg_hierarchy_update_fine: the value array must have the fine operator's number of entries");
+    OMG_HIP(hipStreamSynchronize(h->stream));
+    drop_graph(h);
+    if (on_device) return vals;
+    SetupTimer tm("update: upload the new values");
+    up.alloc(size_t(nnz));
+    OMG_HIP(hipMemcpyAsync(up.p, vals, size_t(nnz) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    return up.p;
+}
+
+// The close of an update: the coarsest operator factorised anew.
+template <typename V>
+void refactorise_coarsest(Hier<V> *h, const HostCsr &Ac) {
+    {
+        SetupTimer tm("update: coarse factorisation");
+        h->coarse.retain_workspace = true;                          // (a hierarchy that is updated once is updated again)
+        factorise_coarsest(h, Ac, h->stream);
+    }
+    OMG_HIP(hipStreamSynchronize(h->stream));
 }
 
 // The plain 2 x 2 x 2 aggregation of an nx x ny x nz grid, weight 1/8, columns ascending (setup_device.hip restriction_kernel
@@ -1804,17 +1832,9 @@ HostCsr aggregation_csr(int nx, int ny, int nz) {
 // operator gives, bit for bit.
 template <typename V>
 void update_fine_var7(Hier<V> *h, const double *vals, int64_t nnz, bool on_device) {
-    OMG_REQUIRE(vals && nnz == h->nnz0, "omg_hierarchy_update_fine: the value array must have the fine operator's number of entries");
     const int last = (int)h->lv.size() - 1;
-    OMG_HIP(hipStreamSynchronize(h->stream));
-    drop_graph(h);
     DevBuf<double> up;
-    if (!on_device) {
-        SetupTimer tm("update: upload the new values");
-        up.alloc(size_t(nnz));
-        OMG_HIP(hipMemcpyAsync(up.p, vals, size_t(nnz) * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        vals = up.p;
-    }
+    vals = update_values(h, vals, nnz, on_device, up);
     if (h->dense7.size() != h->lv.size()) h->dense7.resize(h->lv.size());
     DevBuf<unsigned long long> d_err(size_t(2 * last));
     std::vector<unsigned long long> err(size_t(2 * last));
@@ -1852,10 +1872,7 @@ void update_fine_var7(Hier<V> *h, const double *vals, int64_t nnz, bool on_devic
         SetupTimer tm("update: host-coded levels' and the coarsest operators, from their products");
         for (int l = 1; l <= last; ++l) {
             if (l < last && h->lv[size_t(l)].var7) continue;
-            std::vector<double> d(size_t(h->lv[size_t(l)].n) * 7);
-            OMG_HIP(hipMemcpyAsync(d.data(), h->dense7[size_t(l)].p, d.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            OMG_HIP(hipStreamSynchronize(h->stream));
-            hA[size_t(l)] = csr_from_dense7(d, h->g7[0] >> l, h->g7[1] >> l, h->g7[2] >> l);
+            hA[size_t(l)] = csr_from_dense(h, h->dense7[size_t(l)], slots7(), h->g7[0] >> l, h->g7[1] >> l, h->g7[2] >> l);
             check_diagonal(view(hA[size_t(l)]), l);
         }
     }
@@ -1882,14 +1899,7 @@ void update_fine_var7(Hier<V> *h, const double *vals, int64_t nnz, bool on_devic
         materialise_ordering(h->lv[size_t(l) + 1].ord);
         build_format(h, l, view(hA[size_t(l)]), view(R));
     }
-    Level<V> &Lc = h->lv.back();
-    {
-        SetupTimer tm("update: coarse factorisation");
-        Lc.A.upload(hA[size_t(last)], Lc.ord.sets, h->stream);
-        h->coarse.retain_workspace = true;                          // (a hierarchy that is updated once is updated again)
-        h->coarse.build(hA[size_t(last)], h->stream);
-    }
-    OMG_HIP(hipStreamSynchronize(h->stream));
+    refactorise_coarsest(h, hA[size_t(last)]);
 }
 
 // New coefficients for the fine operator of a hierarchy that create_from_fine set up with 27-point levels throughout (same
@@ -1900,17 +1910,9 @@ template <typename V>
 void update_fine(Hier<V> *h, const double *vals, int64_t nnz, bool on_device) {
     if (h->upd7) { update_fine_var7(h, vals, nnz, on_device); return; }
     OMG_REQUIRE(h->indptr0.p, "omg_hierarchy_update_fine: needs a hierarchy made by omg_hierarchy_create_from_fine whose smoothed levels all run the 27-point kernels, or whose level 0 runs the 7-point var7 passes and whose smoothed levels are var7 or host-coded");
-    OMG_REQUIRE(vals && nnz == h->nnz0, "omg_hierarchy_update_fine: the value array must have the fine operator's number of entries");
     const int last = (int)h->lv.size() - 1;
-    OMG_HIP(hipStreamSynchronize(h->stream));
-    drop_graph(h);
     DevBuf<double> up;
-    if (!on_device) {
-        SetupTimer tm("update: upload the new values");
-        up.alloc(size_t(nnz));
-        OMG_HIP(hipMemcpyAsync(up.p, vals, size_t(nnz) * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        vals = up.p;
-    }
+    vals = update_values(h, vals, nnz, on_device, up);
     if (h->dense27.size() != h->lv.size()) h->dense27.resize(h->lv.size());
     for (int l = 0; l < last; ++l) {
         SetupTimer tm("update: tiles + Galerkin product of a level (one pass)");
@@ -1924,39 +1926,10 @@ void update_fine(Hier<V> *h, const double *vals, int64_t nnz, bool on_device) {
         L.format_pending = true;                                   // (its row-kernel side, if it was ever built, is of the old operator)
     }
     // the coarsest operator: its present, nonzero entries as CSR (what the Galerkin chain hands create_from_fine), factorised anew
-    Level<V> &Lc = h->lv.back();
     const Stencil27Plan<V> &P = *h->lv[size_t(last) - 1].s27;
-    const int cx = P.g.hx, cy = P.g.hy, cz = P.g.hz;
-    std::vector<double> host(size_t(Lc.n) * 27);
-    OMG_HIP(hipMemcpyAsync(host.data(), h->dense27[size_t(last)].p, host.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    OMG_HIP(hipStreamSynchronize(h->stream));
-    HostCsr Ac;
-    Ac.n_rows = Ac.n_cols = Lc.n;
-    Ac.indptr.resize(size_t(Lc.n) + 1);
-    Ac.indices.reserve(host.size());
-    Ac.data.reserve(host.size());
-    for (int64_t r = 0; r < Lc.n; ++r) {
-        Ac.indptr[size_t(r)] = int32_t(Ac.indices.size());
-        const int i = int(r % cx), j = int((r / cx) % cy), k = int(r / (int64_t(cx) * cy));
-        for (int sl = 0; sl < 27; ++sl) {
-            const int dx = sl % 3 - 1, dy = (sl / 3) % 3 - 1, dz = sl / 9 - 1;
-            const bool present = i + dx >= 0 && i + dx < cx && j + dy >= 0 && j + dy < cy && k + dz >= 0 && k + dz < cz;
-            const double v = host[size_t(r) * 27 + size_t(sl)];
-            if (!present || v == 0.0) continue;                       // (exact zeros are not stored: csr_matmat drops them)
-            Ac.indices.push_back(int32_t(r + (int64_t(dz) * cy + dy) * cx + dx));
-            Ac.data.push_back(v);
-        }
-    }
-    Ac.indptr[size_t(Lc.n)] = int32_t(Ac.indices.size());
-    Ac.nnz = int64_t(Ac.indices.size());
+    const HostCsr Ac = csr_from_dense(h, h->dense27[size_t(last)], slots27(), P.g.hx, P.g.hy, P.g.hz);
     check_diagonal(view(Ac), last);
-    {
-        SetupTimer tm("update: coarse factorisation");
-        Lc.A.upload(Ac, Lc.ord.sets, h->stream);
-        h->coarse.retain_workspace = true;                          // (a hierarchy that is updated once is updated again)
-        h->coarse.build(Ac, h->stream);
-    }
-    OMG_HIP(hipStreamSynchronize(h->stream));
+    refactorise_coarsest(h, Ac);
 }
 
 // A throw-away single operator for the standalone entry points.
