@@ -51,6 +51,24 @@ extern "C" {
 #define OMG_SMOOTH_GS_LEX     0
 #define OMG_SMOOTH_GS_COLOUR  1
 #define OMG_SMOOTH_JACOBI     2
+/*   LINE      zebra line Gauss-Seidel for anisotropic grid operators (csrc/line.hip; no reference counterpart): the grid
+ *             lines along one axis, coloured by the parity of the sum of their other two indices (2-D: of the other
+ *             index), are solved exactly — x_line <- T^-1 (b_line - cross couplings * x of the neighbouring lines), T the
+ *             line's tridiagonal block of A — colour 0 first, then colour 1, in place.  Axes are named by stride: X is the
+ *             unit-stride axis, Z the slowest.  OMG_SMOOTH_LINE takes the axis whose couplings of A[0] have the largest
+ *             sum of |a_ij| (ties: the smaller stride); the same axis on every level.  Every smoothed level must be a 3-D
+ *             7-point or 2-D 5-point stencil on a lexicographically numbered grid, every row holding exactly its in-grid
+ *             neighbours in ascending column order with any coefficients (extents even or odd): otherwise hierarchy
+ *             creation returns OMG_ERR_UNSUPPORTED and names the level (27-point, periodic wrap, 1-D, unsorted columns);
+ *             OMG_SMOOTH_LINE_Z on a 2-D grid, or a zero / non-finite pivot of a line: OMG_ERR_INVALID.  omega is ignored.
+ *             Taken by omg_hierarchy_create, _create_ex and _create_opt.  omg_hierarchy_create_from_fine[_opt],
+ *             omg_gauss_seidel, omg_dist_create[_ex] and the omg_*dist_set_tail entries (for a tail made with it)
+ *             return OMG_ERR_UNSUPPORTED.  The cycle over such a level runs set by set: two launches per sweep, the full
+ *             residual / norm launches, no fused passes.                                                            */
+#define OMG_SMOOTH_LINE       3
+#define OMG_SMOOTH_LINE_X     4
+#define OMG_SMOOTH_LINE_Y     5
+#define OMG_SMOOTH_LINE_Z     6
 
 typedef struct {
     int64_t n_rows, n_cols, nnz;
@@ -191,7 +209,11 @@ int omg_hierarchy_level_fused(const omg_hierarchy *h, int level, int *fused);
 #define OMG_LEVEL_TAIL_FUSED       1024 /* a V(1,1) cycle of the hierarchy's shape runs this level's up pass inside the fused
                                         * tail launch: the 16 x 16 x 16 sine solve + the up passes of the block levels above it
                                         * (OMG_TAIL_FUSE=0|1|2 when the hierarchy is made; plane.hip tail_up_kernel) */
+#define OMG_LEVEL_LINE             2048 /* zebra line smoother (OMG_SMOOTH_LINE*; line.hip): two launches per sweep */
 int omg_hierarchy_level_flags(const omg_hierarchy *h, int level, int *flags);
+/* The axis a hierarchy made with OMG_SMOOTH_LINE* smooths along, by stride (0 = X, the unit-stride axis, 1 = Y, 2 = Z),
+ * and the dimension of its grid (2 or 3); *axis = -1 and *dim = 0 for every other hierarchy (and one of a single level). */
+int omg_hierarchy_line_axis(const omg_hierarchy *h, int *axis, int *dim);
 /* The fused tail launch (OMG_LEVEL_TAIL_FUSED) as it actually ran: out[0] = launches of it put on the hierarchy's stream
  * since the hierarchy was made, by any entry; out[1] = how many of those came from replaying a captured graph.         */
 int omg_hierarchy_tail_info(const omg_hierarchy *h, int64_t *out2);

@@ -10,6 +10,20 @@ CPU fallback: without the library or without a GPU the calls raise.
 Extra keys understood in the `parameters` dict (ignored by the reference):
     'smoother'  'gs' (default: the reference's lexicographic Gauss-Seidel iterate),
                 'colour' (multi-colour GS; red-black on 5/7-point stencils) or 'jacobi'
+                or 'line' (alias 'line-gs'): zebra line Gauss-Seidel for ANISOTROPIC grid operators — a stretched grid, thin
+                boundary-layer cells — where every point smoother stalls whatever the 'cycle' and 'accel'.  The grid lines
+                along one axis, coloured by the parity of the sum of their other two indices, are solved exactly (a
+                tridiagonal solve each), colour 0 then colour 1.  Every smoothed level must be a 5-point (2-D) or 7-point
+                (3-D) stencil on the lexicographically numbered grid, any coefficients, extents even or odd; a 27-point,
+                periodic or 1-D operator raises HipError (ERR_UNSUPPORTED) naming the level.  It repairs ONE strong axis
+                (couplings 100 : 1 : 1: 9 V-cycles where 'colour' needs hundreds); with two strong axes (one weak one) it
+                is no better than 'colour' — that needs plane smoothing or semicoarsening, which this package lacks.
+                Works with every 'accel', 'dtype', 'cycle', 'overCorrection', 'nullspace', device arrays and Solver;
+                single GPU, the lists setup route, set-by-set launches (no fused passes)
+    'lineAxis'  with 'line': None or 'auto' (default: the axis whose couplings of A_in have the largest sum of |a_ij|, ties
+                to the unit-stride axis), or an index into 'problemShape' (C order: the last entry is the unit-stride
+                axis).  The same axis on every level.  Anything else raises ValueError before any device work; mgSolve's
+                infoDict['lineAxis'] (and Solver's info) reports the axis used
     'omega'     relaxation weight for 'jacobi' (default 2/3)
     'accel'     mgSolve only: None (default: plain V-cycles, the reference's loop) or 'cg': flexible preconditioned
                 conjugate gradients (FCG(1)) on the finest level with one zero-start V-cycle as the preconditioner per
@@ -87,6 +101,13 @@ _DEFAULT_OMEGA = 2.0 / 3.0
 def _smoother_of(parameters):
     kind = parameters.get("smoother", "gs")
     code = _hip.smoother_code(kind)
+    if code == _hip.SMOOTH_LINE:
+        # 'line': parameters['lineAxis'] picks the code (None / 'auto': the library scans level 0)
+        axis = parameters.get("lineAxis")
+        shape = parameters.get("problemShape")
+        if shape is None and not (axis is None or (isinstance(axis, str) and axis == "auto")):
+            raise ValueError("parameters['lineAxis'] = %r is an index into parameters['problemShape'], which is missing" % (axis,))
+        code = _hip.line_smoother_code(axis, () if shape is None else shape)
     omega = float(parameters.get("omega", _DEFAULT_OMEGA if code == _hip.SMOOTH_JACOBI else 1.0))
     return code, omega
 
@@ -231,10 +252,13 @@ def mgSolve(A_in, b, parameters):
             hierarchy.resident_fetch_dev(_devarray.address(result, hierarchy.sizes[0], "result"))
         else:
             result = hierarchy.resident_fetch()
+        line_axis = hierarchy.line_axis
     finally:
         hierarchy.close()
 
     infoDict = {"norm": norm, "cycle": cycle, "R": R, "A": A}
+    if line_axis is not None:
+        infoDict["lineAxis"] = line_axis           # ('line': the axis the lines ran along, an index into problemShape)
     if verbose:
         print("Returning mgSolve after %i cycle(s) with norm %f" % (cycle, norm))
     if parameters["giveInfo"]:

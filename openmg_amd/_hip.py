@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get("OMG_LIB_PATH") or os.path.join(_HERE, "lib", "libopen
 OMG_OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_SINGULAR, ERR_NO_DIAGONAL, ERR_ALLOC, ERR_UNSUPPORTED = range(1, 8)
 SMOOTH_GS_LEX, SMOOTH_GS_COLOUR, SMOOTH_JACOBI = 0, 1, 2
+# zebra line smoother: the strongest axis of level 0 (LINE), or lines along the axis named by stride — X unit stride, Z slowest
+SMOOTH_LINE, SMOOTH_LINE_X, SMOOTH_LINE_Y, SMOOTH_LINE_Z = 3, 4, 5, 6
 PROFILE_CLASSES = 7
 PROFILE_NAMES = ("smoother_set_sweep", "residual", "restrict", "prolong_add", "residual_norm", "plane_down", "plane_up")
 
@@ -23,6 +25,7 @@ SMOOTHERS = {
     "colour": SMOOTH_GS_COLOUR, "color": SMOOTH_GS_COLOUR, "rbgs": SMOOTH_GS_COLOUR,
     "red-black": SMOOTH_GS_COLOUR, "multicolour": SMOOTH_GS_COLOUR,
     "jacobi": SMOOTH_JACOBI, "weighted-jacobi": SMOOTH_JACOBI,
+    "line": SMOOTH_LINE, "line-gs": SMOOTH_LINE,
 }
 
 
@@ -80,6 +83,7 @@ SIGNATURES = {
     "omg_hierarchy_set_info": (_I, [_P, _I, _I, _I64P, _I64P]),
     "omg_hierarchy_level_fused": (_I, [_P, _I, _IP]),
     "omg_hierarchy_level_flags": (_I, [_P, _I, _IP]),
+    "omg_hierarchy_line_axis": (_I, [_P, _IP, _IP]),
     "omg_hierarchy_tail_info": (_I, [_P, _I64P]),
     "omg_hierarchy_use_plane": (_I, [_P, _I]),
     "omg_hierarchy_set_cycle": (_I, [_P, _I, _D]),
@@ -253,6 +257,21 @@ def smoother_code(kind):
         return SMOOTHERS[kind]
     except KeyError:
         raise ValueError("unknown smoother %r (choose from %s)" % (kind, sorted(set(SMOOTHERS))))
+
+
+def is_line_smoother(code):
+    return isinstance(code, int) and SMOOTH_LINE <= code <= SMOOTH_LINE_Z
+
+
+def line_smoother_code(line_axis, shape):
+    """The OMG_SMOOTH_LINE* code for parameters['lineAxis']: None / 'auto' (the strongest axis of level 0), or an index into
+    problemShape = shape (C order: the last entry is the unit-stride axis X).  ValueError for anything else."""
+    if line_axis is None or (isinstance(line_axis, str) and line_axis == "auto"):
+        return SMOOTH_LINE
+    dim = len(tuple(shape))
+    if isinstance(line_axis, bool) or not isinstance(line_axis, (int, np.integer)) or not 0 <= int(line_axis) < dim or dim > 3:
+        raise ValueError("lineAxis must be None, 'auto' or an index into problemShape (0 .. %d), not %r" % (dim - 1, line_axis))
+    return SMOOTH_LINE_X + (dim - 1 - int(line_axis))
 
 
 CYCLE_V, CYCLE_F, CYCLE_W = 0, 1, 2
@@ -587,13 +606,21 @@ class Hierarchy:
 
     def level_flags(self, level):
         """dict(fused_last_set=bool, scatter_prolong=bool, union_walk=bool, march=bool, plane=bool, stencil27=bool, var7=bool,
-        march_scan=bool, tail_fused=bool) of a smoothed level.  tail_fused: a V(1,1) cycle of the hierarchy's shape runs this
-        level's up pass inside the fused tail launch (OMG_TAIL_FUSE)."""
+        march_scan=bool, tail_fused=bool, line=bool) of a smoothed level.  tail_fused: a V(1,1) cycle of the hierarchy's shape runs
+        this level's up pass inside the fused tail launch (OMG_TAIL_FUSE).  line: the zebra line smoother (OMG_SMOOTH_LINE*)."""
         f = ctypes.c_int(0)
         check(lib().omg_hierarchy_level_flags(self._h, int(level), ctypes.byref(f)))
         return {"fused_last_set": bool(f.value & 1), "scatter_prolong": bool(f.value & 2), "union_walk": bool(f.value & 16),
                 "march": bool(f.value & 32), "plane": bool(f.value & 64), "stencil27": bool(f.value & 128), "var7": bool(f.value & 256),
-                "march_scan": bool(f.value & 512), "tail_fused": bool(f.value & 1024)}
+                "march_scan": bool(f.value & 512), "tail_fused": bool(f.value & 1024), "line": bool(f.value & 2048)}
+
+    @property
+    def line_axis(self):
+        """The axis the line smoother's lines follow, as an index into the grid's shape in C order (the last axis is the
+        unit-stride one), or None for a hierarchy made with another smoother (omg_hierarchy_line_axis)."""
+        axis, dim = ctypes.c_int(-1), ctypes.c_int(0)
+        check(lib().omg_hierarchy_line_axis(self._h, ctypes.byref(axis), ctypes.byref(dim)))
+        return None if axis.value < 0 else dim.value - 1 - axis.value
 
     def tail_info(self):
         """(fused tail launches put on the stream so far, how many of them by replaying a graph): omg_hierarchy_tail_info"""

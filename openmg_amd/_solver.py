@@ -17,7 +17,8 @@ import numpy as np
 
 from . import _devarray, _hip
 
-# the keys a solve may override: those that do not define the hierarchy
+# the keys a solve may override: those that do not define the hierarchy ('smoother', 'lineAxis', 'dtype', 'nullspace',
+# the grids do, and are refused)
 SOLVE_KEYS = ("cycles", "threshold", "rtol", "preIterations", "postIterations", "accel", "cycle", "overCorrection")
 
 
@@ -182,7 +183,10 @@ class Solver:
             h.resident_fetch_dev(_devarray.address(u, n, "out"))
         else:
             u = h.resident_fetch(out)
-        return u, {"cycle": cycle, "norm": norm, "norms": norms, "rhs_norm": rhs_norm, "initial_norm": initial_norm}
+        info = {"cycle": cycle, "norm": norm, "norms": norms, "rhs_norm": rhs_norm, "initial_norm": initial_norm}
+        if _hip.is_line_smoother(h.smoother):
+            info["lineAxis"] = h.line_axis          # ('smoother': 'line': the axis of the lines, an index into problemShape)
+        return u, info
 
     # ---- apply --------------------------------------------------------------------------------------------------------
     def apply(self, r, out=None):

@@ -110,6 +110,17 @@ inline void refuse_nullspace_tail(const omg_hierarchy *tail) {
         throw Error(OMG_ERR_UNSUPPORTED, "a tail hierarchy with a null space: the multi-GPU runners do not project the right-hand side "
                                          "and the iterate (single-GPU entries only)");
 }
+// ... and know nothing of the line smoother: a smoother code of theirs, or a tail hierarchy, that names it is refused
+inline bool is_line_smoother(int smoother) { return smoother >= OMG_SMOOTH_LINE && smoother <= OMG_SMOOTH_LINE_Z; }
+inline void refuse_line_smoother(int smoother, const char *entry) {
+    if (is_line_smoother(smoother))
+        throw Error(OMG_ERR_UNSUPPORTED, std::string(entry) + ": the line smoother (OMG_SMOOTH_LINE*) runs in hierarchies made by omg_hierarchy_create* only");
+}
+inline void refuse_line_tail(const omg_hierarchy *tail) {
+    int axis = -1, dim = 0;
+    if (tail && omg_hierarchy_line_axis(tail, &axis, &dim) == OMG_OK && axis >= 0)
+        throw Error(OMG_ERR_UNSUPPORTED, "a tail hierarchy with the line smoother: the multi-GPU runners do not run it (single-GPU entries only)");
+}
 
 // OMG_SETUP_TIMING=1: phases of the hierarchy setup, with their wall time, on stderr
 struct SetupTimer {
@@ -1045,6 +1056,35 @@ struct Var7Plan {
 template <typename V>
 void var7_rap(const int32_t *indptr, const double *vals, int nx, int ny, int nz, double w, Var7Plan<V> *fine, Var7Plan<V> *coarse,
               double *coarse_dense, unsigned long long *err, hipStream_t s);
+
+// ---- zebra line smoother of 5- / 7-point grid stencils with any coefficients (line.hip) -------------------
+// The lines of the grid along one axis, coloured by the parity of the sum of their other two indices; a sweep solves the
+// lines of colour 0, then those of colour 1, exactly (their tridiagonal blocks factorised once at setup).  The plan writes
+// the level's ordering: two sets, the lines of a colour in bundles of 64, cell i of the k-th line in slot
+// base[c] + (k / 64) * 64 * len + i * w + k % 64 (w = 64; the last bundle: the lines left), so that one thread per line
+// walks with unit stride across the wave, and the wave through one contiguous stream, whichever axis the lines follow.
+// The row kernels (residual, restriction, prolongation, norm) run on that ordering as on any other.
+struct LineGeom {
+    int nx = 0, ny = 0, nz = 0;       // the grid (nz = 1: 2-D)
+    int axis = 0;                     // 0 = unit stride (X), 1 = Y, 2 = Z
+    int len = 0;                      // cells per line
+    int ncross = 0;                   // neighbouring lines of a line: 4 (3-D) or 2 (2-D)
+    int64_t nl[2] = {0, 0};           // lines per colour
+    int64_t base[2] = {0, 0};         // first slot of each colour
+};
+template <typename V>
+struct LinePlan {
+    LineGeom g;
+    DevBuf<V> cross;                  // [ncross][slot]: couplings to the lines q - 1, q + 1, p - 1, p + 1 (q the faster other axis)
+    DevBuf<V> upper, inv_pivot, factor;   // [slot]: the line's super-diagonal, 1 / p_i, f_i = l_i / p_{i-1}
+    DevBuf<int32_t> nbr;              // [colour][ncross][line]: the neighbouring line's rank among the other colour's lines
+    // A: the level's operator in natural numbering; axis as LineGeom::axis.  Writes ord.  Throws OMG_ERR_UNSUPPORTED when A is
+    // not such a stencil, OMG_ERR_INVALID for a zero or non-finite pivot or an axis the grid does not have.
+    void build(const omg_csr &A, int axis, Ordering &ord, hipStream_t s);
+    void sweep(V *x, const V *b, hipStream_t s) const;   // one in-place zebra sweep: two launches
+};
+// the axis (as LineGeom::axis) whose couplings have the largest sum of |a_ij|; ties go to the smaller stride
+int line_auto_axis(const omg_csr &A);
 
 // ---- 27-point grid stencils with per-row coefficients: BASELINE configs[4] (stencil27.hip) ----------------
 // A level whose operator holds, in every row, exactly the in-grid neighbours of a 27-point stencil on a

@@ -1591,6 +1591,7 @@ int omg_dist_create_ex(int rank, int n_ranks, int n_levels, const omg_dist_level
         OMG_REQUIRE(out, "out is null");
         *out = nullptr;
         OMG_REQUIRE(dtype == OMG_DTYPE_F64 || dtype == OMG_DTYPE_F32, "unknown dtype");
+        refuse_line_smoother(smoother, "omg_dist_create");
         std::unique_ptr<omg_dist> h(new omg_dist);
         if (dtype == OMG_DTYPE_F32) h->f = create<float>(rank, n_ranks, n_levels, levels, coarse_global, coarse_counts, smoother, omega);
         else h->d = create<double>(rank, n_ranks, n_levels, levels, coarse_global, coarse_counts, smoother, omega);
@@ -1625,6 +1626,7 @@ int omg_dist_set_stream(omg_dist *d, void *hip_stream) {
 int omg_dist_set_tail(omg_dist *d, omg_hierarchy *tail) {
     return guarded([&] {
         refuse_nullspace_tail(tail);
+        refuse_line_tail(tail);
         with(d, [&](auto *dd) {
             if (tail) {
                 int64_t n = 0;
@@ -1919,6 +1921,7 @@ int omg_pdist_destroy(omg_pdist *d) {
 int omg_pdist_set_tail(omg_pdist *d, omg_hierarchy *tail) {
     return guarded([&] {
         refuse_nullspace_tail(tail);
+        refuse_line_tail(tail);
         OMG_REQUIRE(d && d->d && tail, "null argument");
         int64_t n = 0;
         OMG_REQUIRE(omg_hierarchy_level_rows(tail, 0, &n) == OMG_OK &&

@@ -742,6 +742,7 @@ int omg_sdist_coarse_fetch(omg_sdist *d, int32_t *indptr, int32_t *indices, doub
 int omg_sdist_set_tail(omg_sdist *d, omg_hierarchy *tail) {
     return guarded([&] {
         refuse_nullspace_tail(tail);
+        refuse_line_tail(tail);
         OMG_REQUIRE(tail, "null argument");
         with(d, [&](auto *dd) {
             int64_t n = 0;

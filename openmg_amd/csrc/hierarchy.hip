@@ -169,6 +169,9 @@ struct Level {
     // 7-point grid stencil with per-row coefficients, red-black (the ordinary variable-coefficient input): each half of the
     // cycle over this level is one launch of var7.hip (common.h Var7Plan); the row-kernel format exists beside it
     std::unique_ptr<Var7Plan<V>> var7;
+    // zebra line smoother (OMG_SMOOTH_LINE*; common.h LinePlan): the level's ordering is the plan's, a sweep is its two
+    // launches; everything else of the cycle runs the row kernels, set by set, with nothing fused into the sweeps
+    std::unique_ptr<LinePlan<V>> line;
     DevBuf<char> pool;               // OMG_VEC_POOL=1: x, tmp, b of a large plane level as three views into ONE allocation
     size_t pool_span = 0, pool_off1 = 0, pool_off2 = 0;      // ... its layout (pool_views)
     // where the matrix-free SpMV of a plane level leaves its product: an allocation of its OWN, made on first use.  Written
@@ -222,6 +225,8 @@ struct Hier {
     } mx;
     int smoother = OMG_SMOOTH_GS_LEX;
     double omega = 1.0;
+    // OMG_SMOOTH_LINE*: the axis every smoothed level's lines follow (LineGeom::axis; -1: no line smoother) and the grid's dimension
+    int line_axis = -1, line_dim = 0;
     // omg_hierarchy_set_cycle: the shape of every cycle run on this hierarchy (cycle_body) and the over-correction factor —
     // the prolongation's weight is over * (the restriction's weight), rounded once to V; the restriction keeps its own
     int cycle_shape = OMG_CYCLE_V;
@@ -377,7 +382,7 @@ enum Fuse { FUSE_NONE = 0, FUSE_RESIDUAL = 1, FUSE_NORM = 2 };
 // Fusion needs a Gauss-Seidel ordering whose final step is an ordinary set launch.
 template <typename V>
 bool can_fuse(const Hier<V> *h, const Level<V> &L) {
-    if (h->smoother == OMG_SMOOTH_JACOBI || L.plan.empty() || h->no_fuse || L.march) return false;
+    if (h->smoother == OMG_SMOOTH_JACOBI || L.plan.empty() || h->no_fuse || L.march || L.line) return false;
     return !L.plan.back().serial;
 }
 
@@ -388,7 +393,7 @@ bool can_fuse(const Hier<V> *h, const Level<V> &L) {
 // post-smoothing launch (ROW_GS_NORM).
 template <typename V>
 bool can_prenorm(const Hier<V> *h, const Level<V> &L, int pre, int post) {
-    if (pre <= 0 || L.plan.empty() || L.march) return false;
+    if (pre <= 0 || L.plan.empty() || L.march || L.line) return false;
     if (h->smoother == OMG_SMOOTH_JACOBI) return true;
     return L.A.n_sets() == 2 && post > 0 && can_fuse(h, L) && !L.plan.front().serial && L.plan.size() == 2;
 }
@@ -422,6 +427,11 @@ bool smooth_level(Hier<V> *h, int l, int iterations, Fuse fuse = FUSE_NONE, doub
         } else if (L.march) {
             Prof<V> p(h, l, 0);
             L.march->sweep(L.xp, L.b.p, h->stream);
+        } else if (L.line) {
+            // (a line solve reads nothing of its own line's iterate: no first launch to skip, nothing to fuse — the callers
+            // ask can_fuse / can_prenorm / first_sweep_in_restrict, all false for such a level)
+            Prof<V> p(h, l, 0);
+            L.line->sweep(L.xp, L.b.p, h->stream);
         } else {
             RowArgsT<V> a;
             a.x = L.xp; a.b = L.b.p; a.y = L.xp;
@@ -486,7 +496,7 @@ void norm_level(Hier<V> *h, int l, V *r_out, bool last_set_done = false, double 
 // the restriction's thread holds b_i (RowArgsT::first_diag).  OMG_NO_FIRST_SWEEP=1 switches it off.
 template <typename V>
 bool first_sweep_in_restrict(const Hier<V> *h, const Level<V> &C, int pre) {
-    if (pre <= 0 || !C.diag.p || C.plan.empty() || C.march || getenv_flag("OMG_NO_FIRST_SWEEP")) return false;
+    if (pre <= 0 || !C.diag.p || C.plan.empty() || C.march || C.line || getenv_flag("OMG_NO_FIRST_SWEEP")) return false;
     // (a captured graph bakes the Jacobi ping-pong pointers in: keep two swaps per V(1,1) level there)
     if (h->smoother == OMG_SMOOTH_JACOBI) return !h->want_graph;
     const SweepStep &st = C.plan.front();
@@ -1529,7 +1539,7 @@ std::unique_ptr<Hier<V>> create(int n_levels, const omg_csr *A, const omg_csr *R
     using Lv = Level<V>;
     OMG_REQUIRE(n_levels >= 1, "n_levels must be >= 1");
     OMG_REQUIRE(A != nullptr && (n_levels == 1 || R != nullptr), "A / R array is null");
-    OMG_REQUIRE(smoother >= OMG_SMOOTH_GS_LEX && smoother <= OMG_SMOOTH_JACOBI, "unknown smoother");
+    OMG_REQUIRE(smoother >= OMG_SMOOTH_GS_LEX && smoother <= OMG_SMOOTH_LINE_Z, "unknown smoother");
     for (int l = 0; l < n_levels; ++l) {
         validate_csr(A[l], ("A[" + std::to_string(l) + "]").c_str());
         OMG_REQUIRE(A[l].n_rows == A[l].n_cols, "A[l] must be square");
@@ -1543,6 +1553,14 @@ std::unique_ptr<Hier<V>> create(int n_levels, const omg_csr *A, const omg_csr *R
     require_device();
     std::unique_ptr<H> h = new_handle<V>(smoother, omega, nullspace);
     h->lv.resize(n_levels);
+    // (the line smoother's axis: the caller's, or the strongest of level 0 — before the helper thread starts: a refusal costs nothing)
+    if (is_line_smoother(smoother) && n_levels > 1) {
+        try {
+            h->line_axis = smoother == OMG_SMOOTH_LINE ? line_auto_axis(A[0]) : smoother - OMG_SMOOTH_LINE_X;
+        } catch (const Error &e) {
+            throw Error(e.code, std::string("level 0: ") + e.what());
+        }
+    }
     coarsest_level(h->lv.back(), A[n_levels - 1].n_rows);
     // (the copy of the caller's coarsest operator is made on the helper thread too)
     CoarseThread inverter([&](hipStream_t s) { factorise_coarsest(h.get(), permute_csr(A[n_levels - 1], nullptr, nullptr), s); });
@@ -1551,6 +1569,21 @@ std::unique_ptr<Hier<V>> create(int n_levels, const omg_csr *A, const omg_csr *R
         Lv &L = h->lv[l];
         L.n = A[l].n_rows;
         auto check_parity = [&] { check_closed_form(A[l], smoother, L.ord, "internal: the parity ordering differs from the greedy colouring"); };
+        if (is_line_smoother(smoother)) {
+            SetupTimer tl("line smoother: the level's grid, its ordering, the lines' factorisations");
+            std::unique_ptr<LinePlan<V>> plan(new LinePlan<V>);
+            try {
+                plan->build(A[l], h->line_axis, L.ord, h->stream);
+            } catch (const Error &e) {
+                throw Error(e.code, "level " + std::to_string(l) + ": " + e.what());
+            }
+            const int dim = plan->g.nz > 1 ? 3 : 2;
+            if (l == 0) h->line_dim = dim;
+            else if (dim != h->line_dim)
+                throw Error(OMG_ERR_UNSUPPORTED, "level " + std::to_string(l) + ": the line smoother needs a grid of the dimension of level 0's on every smoothed level");
+            L.line = std::move(plan);
+            continue;
+        }
         if (smoother == OMG_SMOOTH_GS_COLOUR || smoother == OMG_SMOOTH_JACOBI) {
             SetupTimer tp("plane-pipelined passes: does the level qualify (+ its parity ordering)");
             std::unique_ptr<PlanePlan<V>> plan(new PlanePlan<V>);
@@ -1610,6 +1643,7 @@ std::unique_ptr<Hier<V>> create_from_fine(const omg_csr &A0, int dim, const int6
                                           int nullspace = OMG_NULLSPACE_NONE) {
     using H = Hier<V>;
     using Lv = Level<V>;
+    refuse_line_smoother(smoother, "omg_hierarchy_create_from_fine");
     OMG_REQUIRE(dim >= 2 && dim <= 3 && shape && n_restrictions >= 1, "device setup: 2-D / 3-D grids, at least one restriction");
     OMG_REQUIRE(smoother >= OMG_SMOOTH_GS_LEX && smoother <= OMG_SMOOTH_JACOBI, "unknown smoother");
     validate_csr(A0, "A_in");
@@ -2612,9 +2646,17 @@ int omg_hierarchy_level_flags(const omg_hierarchy *h, int level, int *flags) {
                      ((smoothed && hh->lv[level].plane && !hh->no_plane) ? OMG_LEVEL_PLANE : 0) |
                      ((smoothed && hh->lv[level].s27 && !hh->no_plane) ? OMG_LEVEL_STENCIL27 : 0) |
                      ((smoothed && hh->lv[level].var7 && !hh->no_plane) ? OMG_LEVEL_VAR7 : 0) |
+                     ((smoothed && hh->lv[level].line) ? OMG_LEVEL_LINE : 0) |
                      ((tail_fuse_depth(hh, level, 1, hh->cycle_shape) || tail_fuse_depth(hh, level - 1, 1, hh->cycle_shape) == 2)
                           ? OMG_LEVEL_TAIL_FUSED : 0);
         });
+    });
+}
+
+int omg_hierarchy_line_axis(const omg_hierarchy *h, int *axis, int *dim) {
+    return guarded([&] {
+        OMG_REQUIRE(axis && dim, "null argument");
+        with(h, [&](auto *hh) { *axis = hh->line_axis; *dim = hh->line_dim; });
     });
 }
 
@@ -3205,6 +3247,7 @@ int omg_gauss_seidel(const omg_csr *A, const double *b, double *x, int smoother,
     return guarded([&] {
         using H = Hier<double>;
         OMG_REQUIRE(A && b && x, "null argument");
+        refuse_line_smoother(smoother, "omg_gauss_seidel");
         OMG_REQUIRE(A->n_rows == A->n_cols, "smoother needs a square operator");
         validate_csr(*A, "A");
         check_diagonal(*A, 0);
