@@ -567,7 +567,7 @@ void coarse_solve_level(Hier<V> *h) {
 }
 
 // What a cycle leaves of the entry level's residual norm (openmg/__init__.py:227)
-enum NormState { NORM_NONE = 0, NORM_LAST_SET = 1, NORM_PLANE = 2, NORM_S27 = 3, NORM_VAR7 = 4 };
+enum NormState { NORM_NONE = 0, NORM_LAST_SET = 1, NORM_PASS = 2, NORM_S27 = 3 };
 
 // Does the cycle over this level run the 27-point kernels of stencil27.hip?  (Switched with the plane passes.)
 // The three vectors a large fused level's passes stream side by side (x, its out-of-place twin, b) come out of ONE
@@ -823,17 +823,51 @@ bool use_plane(const Hier<V> *h, const Level<V> &L) {
     return L.plane && !h->no_plane;
 }
 
+// The arm of cycle_body a level takes; PLANE and VAR7 are the "pass" kinds: each half of the cycle is one launch
+enum LevelKind { KIND_ROWS, KIND_PLANE, KIND_VAR7, KIND_S27 };
+template <typename V>
+LevelKind level_kind(const Hier<V> *h, const Level<V> &L) {
+    return use_s27(h, L) ? KIND_S27 : use_plane(h, L) ? KIND_PLANE : use_var7(h, L) ? KIND_VAR7 : KIND_ROWS;
+}
+
+// The two columns of the table above cycle_body.  x_zero: does the level's first launch NOT read the iterate?  A pass
+// level's down pass when it IS the one pre-smoothing sweep (with more, smooth_level runs before it on the iterate as
+// stored; with none it forms the iterate's residual), a 27-point level's first sweep, the row kernels never.
+template <typename V>
+bool enters_without_iterate(const Hier<V> *h, const Level<V> &L, int pre) {
+    const LevelKind k = level_kind(h, L);
+    return k == KIND_S27 ? pre >= 1 : k != KIND_ROWS && pre == 1;
+}
+// first_done: does the arm skip (or harmlessly repeat) the first relaxation launch of a zero iterate?
+template <typename V>
+bool honours_first_done(const Hier<V> *h, const Level<V> &L, int pre) {
+    const LevelKind k = level_kind(h, L);
+    return k == KIND_ROWS || k == KIND_PLANE || (k == KIND_VAR7 && pre > 1);
+}
+
 // openmg/__init__.py:199-234 with the dead work removed: R[l]*b (:205-206) is computed by the
 // reference only for its length, and the norm at levels > entry (:227) is discarded by the
 // caller (:213 takes [0]); neither changes any returned value.
 //
 // want_norm: the caller will ask for ||b - A x|| of THIS level right after the cycle.  Returns what
 // is already there of it: NORM_LAST_SET — the post-smoother's last set launch has left that set's
-// share in the block partials (norm_level(..., last_set_done = true) finishes it); NORM_PLANE — the
-// plane-pipelined up pass has left ALL of it in its workgroup partials (post_slot, or the plan's own
-// array: finish_plane_norm).
-// x_zero: the level's iterate is zero and has not been written (plane levels only).
+// share in the block partials (norm_level(..., last_set_done = true) finishes it); NORM_PASS — the
+// up pass of a plane or var7 level has left ALL of it in its workgroup partials (post_slot, or the plan's own
+// array); NORM_S27 — the last sweep has left the share of the rows it made final (finish_norm).
 // shape: OMG_CYCLE_V / F / W from this level downward (-1, what every entry passes: the hierarchy's setting).
+//
+// x_zero, first_done: what the caller has made of a zero iterate — enter_child() for the level below, zero_start_cycle()
+// for level 0.  One table says when each may arrive, and cycle_body refuses them anywhere else (an internal error):
+//
+//   level's kind | x_zero: the iterate is zero and has NOT been written | first_done: the first relaxation launch of the
+//                | (enters_without_iterate)                             | zero iterate is applied (honours_first_done)
+//   -------------+------------------------------------------------------+------------------------------------------------
+//   plane        | pre = 1 (pre = 0 from a plane parent, which then     | pre >= 1: smooth_level skips the launch; with
+//                | writes the zeros itself: the up pass reads them)     | pre = 1 the down pass relaxes on what it finds
+//   var7         | pre = 1                                              | pre > 1 only (smooth_level): the down pass is a
+//                |                                                      | whole sweep and cannot skip a launch
+//   27-point     | pre >= 1                                             | never
+//   row kernels  | never                                                | pre >= 1 (smooth_level)
 template <typename V>
 int cycle_body(Hier<V> *h, int l, int pre, int post, bool want_norm = false, double *pre_slot = nullptr,
                bool first_done = false, double *post_slot = nullptr, bool x_zero = false, int shape = -1);
@@ -850,35 +884,70 @@ void cycle_children(Hier<V> *h, int l, int pre, int post, int shape, bool first_
         cycle_body(h, l + 1, pre, post, false, nullptr, false, nullptr, false, shape == OMG_CYCLE_F ? OMG_CYCLE_V : OMG_CYCLE_W);
 }
 
-// The way down over a plane level (cycle_body): all but the last pre-smoothing sweep set by set, then the down pass — the
-// last sweep, the residual and the restriction (openmg/__init__.py:201, :209, :210).  c: what the pass was given of the
-// child level (the up pass takes the same).  Returns what the child's own cycle may rely on.
-struct PlaneDown { bool child_first, child_zero; };
+// How the first visit of a cycle over level l enters level l + 1 (openmg/__init__.py:191-192: from zeros), for every kind
+// of parent.  zero / first: what the child is told (x_zero / first_done).  write: the child's iterate, for the parent's
+// restricting launch to clear or, with `first`, to set to the first relaxation of zeros (first_sweep_in_restrict); null:
+// nothing to write — the child does not read it, or is the coarsest level (the solve reads b only), or the zeros were
+// written by a memset here.  Builds the child's row-kernel format where the child or `first` uses it: a pending format
+// launches its build kernels, so WHERE this is called is part of the cycle's dispatch sequence.
 template <typename V>
-PlaneDown plane_down_half(Hier<V> *h, int l, int pre, int post, bool x_zero, bool first_done, typename PlanePlan<V>::Coarse &c) {
-    const int last = (int)h->lv.size() - 1;
-    Level<V> &L = h->lv[l];
-    Level<V> &C = h->lv[l + 1];
-    // :201 all but the last pre-smoothing sweep set by set (in place); the last one inside the down pass
-    if (pre > 1) smooth_level(h, l, pre - 1, FUSE_NONE, nullptr, first_done);
-    const bool child_plane = l + 1 < last && use_plane(h, C);
-    const bool child_zero = child_plane && pre <= 1;       // the child's down pass never reads its zero iterate
-    if (l + 1 < last && !child_zero) ensure_format(h, l + 1);
-    const bool child_first = l + 1 < last && !child_zero && !use_s27(h, C) && !L.plane->g.dim2 && first_sweep_in_restrict(h, C, pre);
+struct ChildEntry { bool zero = false, first = false; V *write = nullptr; };
+template <typename V>
+ChildEntry<V> enter_child(Hier<V> *h, int l, int pre) {
+    ChildEntry<V> e;
+    if (l + 1 >= (int)h->lv.size() - 1) return e;
+    Level<V> &L = h->lv[l], &C = h->lv[l + 1];
+    const LevelKind pk = level_kind(h, L), ck = level_kind(h, C);
+    // what the parent's restricting launch can do: rows — clear or first-relax (restrict_level); plane — the same through
+    // Coarse::x / diag, no first relaxation out of a 2-D level; var7 and 27-point — neither
+    const bool in_launch = pk == KIND_ROWS || pk == KIND_PLANE, may_first = pk == KIND_ROWS || (pk == KIND_PLANE && !L.plane->g.dim2);
+    e.zero = enters_without_iterate(h, C, pre);
+    // Where a parent knows less or more than that rule (each line is the behaviour as it was, kept launch for launch):
+    // a plane parent skips the clear for a plane child only — at pre = 0 too, where the child's down pass does not write
+    // the iterate either and its up pass reads it: zeros by a memset
+    if (pk == KIND_PLANE) e.zero = ck == KIND_PLANE && pre <= 1;
+    // a rows parent clears a var7 child in its restriction launch, a 27-point parent by a memset
+    if (ck == KIND_VAR7 && (pk == KIND_ROWS || pk == KIND_S27)) e.zero = false;
+    // (a 27-point child runs no row kernel and a 27-point parent builds for no child; a plane parent builds for any)
+    if (!e.zero && (pk == KIND_PLANE || (pk != KIND_S27 && ck != KIND_S27))) ensure_format(h, l + 1);
+    if (e.zero ? pre == 0 : !in_launch) OMG_HIP(hipMemsetAsync(C.xp, 0, size_t(C.n) * sizeof(V), h->stream));
+    if (e.zero || !in_launch) return e;
+    e.write = C.xp;
+    // (only for a child that skips the launch again; a rows parent never for a var7 child)
+    e.first = may_first && honours_first_done(h, C, pre) && !(ck == KIND_VAR7 && pk == KIND_ROWS) && first_sweep_in_restrict(h, C, pre);
+    return e;
+}
+
+// A pass level's plan: plane (plane.hip) or var7 (var7.hip)
+template <typename V, typename Plan>
+constexpr bool is_plane_plan = std::is_same<Plan, PlanePlan<V>>::value;
+template <typename V, typename Plan>
+Plan &pass_plan(Level<V> &L) { if constexpr (is_plane_plan<V, Plan>) return *L.plane; else return *L.var7; }
+
+// The way down over a pass level: all but the last pre-smoothing sweep set by set (in place), then the down pass — the
+// last sweep, the residual and the restriction (openmg/__init__.py:201, :209, :210).  c: what the pass was given of the
+// child level (the up pass takes the same).  Returns how the child is entered.
+template <typename V, typename Plan>
+ChildEntry<V> pass_down(Hier<V> *h, int l, int pre, bool x_zero, bool first_done, typename Plan::Coarse &c) {
+    Level<V> &L = h->lv[l], &C = h->lv[l + 1];
+    Plan &P = pass_plan<V, Plan>(L);
+    if (pre > 1) smooth_level(h, l, pre - 1, FUSE_NONE, nullptr, first_done);          // :201
+    const ChildEntry<V> e = enter_child(h, l, pre);
     c.map = L.r_out.p;
     c.b = C.b.p;
-    c.x = (l + 1 < last && !child_zero) ? C.xp : nullptr;
-    c.diag = child_first ? C.diag.p : nullptr;
-    c.first_end = child_first ? int(C.A.sets[1]) : 0;
-    // (pre = 0: the child's down pass does not write its iterate either, and its up pass reads it)
-    if (child_zero && pre == 0) OMG_HIP(hipMemsetAsync(C.xp, 0, size_t(C.n) * sizeof(V), h->stream));
+    if constexpr (is_plane_plan<V, Plan>) {
+        c.x = e.write;
+        c.diag = e.first ? C.diag.p : nullptr;
+        c.first_end = e.first ? int(C.A.sets[1]) : 0;
+    }
     {
-        Prof<V> p(h, l, 5);
-        L.plane->down(L.xp, L.tp, L.b.p, x_zero, c, h->stream, nullptr, pre >= 1);      // :201 (last sweep), :209, :210
+        Prof<V> p(h, l, 5);                                                             // :201 (last sweep), :209, :210
+        if constexpr (is_plane_plan<V, Plan>) P.down(L.xp, L.tp, L.b.p, x_zero, c, h->stream, nullptr, pre >= 1);
+        else P.down(L.xp, L.tp, L.b.p, x_zero, c, h->stream, pre >= 1);
     }
     if (pre >= 1) std::swap(L.xp, L.tp);
     if (l == h->pre_level) OMG_HIP(hipMemcpyAsync(h->pre_buf.p, L.xp, size_t(L.n) * sizeof(V), hipMemcpyDeviceToDevice, h->stream));
-    return {child_first, child_zero};
+    return e;
 }
 
 // Does the cycle from plane level l downward end in the fused tail launch (plane.hip tail_up_kernel), and with how many
@@ -905,6 +974,53 @@ int tail_fuse_depth(const Hier<V> *h, int l, int post, int shape) {
     return 0;
 }
 
+// The cycle over a pass level: the down half, the levels below, then the up pass — the prolongation, the first
+// post-smoothing sweep and, where asked for and post <= 1, the norm's squares (:214, :220/:224, :216-222, :227) — and the
+// further post-smoothing sweeps set by set.
+template <typename V, typename Plan>
+int pass_cycle(Hier<V> *h, int l, int pre, int post, bool want_norm, bool first_done, double *post_slot, bool x_zero, int shape) {
+    Level<V> &L = h->lv[l], &C = h->lv[l + 1];
+    Plan &P = pass_plan<V, Plan>(L);
+    typename Plan::Coarse c;
+    const ChildEntry<V> e = pass_down<V, Plan>(h, l, pre, x_zero, first_done, c);
+    double *out = (want_norm && post <= 1) ? (post_slot ? post_slot : P.partials.p) : nullptr;
+    if constexpr (is_plane_plan<V, Plan>) if (const int fuse = !out ? tail_fuse_depth(h, l, post, shape) : 0) {
+        // plane levels only: the rest of the cycle below this level in one launch — (depth 2: the child's down pass as ever,
+        // then) the coarsest solve and the up passes of the levels above it (plane.hip tail_up_kernel)
+        TailUp<V> u;
+        u.top = &P.g; u.x_old = L.xp; u.x_new = L.tp; u.b = L.b.p;
+        u.cmap = L.r_out.p;
+        if (fuse == 2) {
+            typename Plan::Coarse cc;
+            pass_down<V, Plan>(h, l + 1, pre, e.zero, e.first, cc);
+            u.mid = &C.plane->g; u.mid_x_old = C.xp; u.mid_x_new = C.tp; u.mid_b = C.b.p;
+            u.cmap = C.r_out.p;
+        }
+        Level<V> &Z = h->lv.back();
+        u.cb = Z.b.p; u.cx = Z.xp; u.tables = h->coarse.sine.p; u.lambda = h->coarse.lambda.p;
+        u.sweep = post >= 1;
+        {
+            Prof<V> p(h, l, 6);
+            launch_tail_up<V>(u, h->stream);
+            ++h->tail_launches;
+        }
+        if (fuse == 2) std::swap(C.xp, C.tp);
+        std::swap(L.xp, L.tp);
+        return NORM_NONE;
+    }
+    cycle_children(h, l, pre, post, shape, e.first, e.zero);                              // :213
+    c.e = C.xp;
+    {
+        Prof<V> p(h, l, 6);
+        if constexpr (is_plane_plan<V, Plan>) P.up(L.xp, L.tp, L.b.p, c, out, h->stream, nullptr, post >= 1);
+        else P.up(L.xp, L.tp, L.b.p, c, out, h->stream, post >= 1);
+    }
+    std::swap(L.xp, L.tp);
+    if (post > 1)
+        return smooth_level(h, l, post - 1, want_norm ? FUSE_NORM : FUSE_NONE, nullptr, false, post_slot) ? NORM_LAST_SET : NORM_NONE;
+    return out ? NORM_PASS : NORM_NONE;
+}
+
 template <typename V>
 int cycle_body(Hier<V> *h, int l, int pre, int post, bool want_norm, double *pre_slot, bool first_done, double *post_slot, bool x_zero,
                int shape) {
@@ -916,18 +1032,18 @@ int cycle_body(Hier<V> *h, int l, int pre, int post, bool want_norm, double *pre
     }
     Level<V> &L = h->lv[l];
     Level<V> &C = h->lv[l + 1];
-    if (use_s27(h, L)) {
+    const LevelKind kind = level_kind(h, L);
+    // (a plane level also takes x_zero at pre = 0, from a plane parent that has written the zeros)
+    OMG_REQUIRE(!x_zero || enters_without_iterate(h, L, pre) || (kind == KIND_PLANE && pre == 0),
+                "internal: x_zero for a level whose first launch reads the iterate");
+    OMG_REQUIRE(!first_done || honours_first_done(h, L, pre), "internal: first_done for a level that cannot skip its first relaxation");
+    if (kind == KIND_PLANE) return pass_cycle<V, PlanePlan<V>>(h, l, pre, post, want_norm, first_done, post_slot, x_zero, shape);
+    if (kind == KIND_VAR7) return pass_cycle<V, Var7Plan<V>>(h, l, pre, post, want_norm, first_done, post_slot, x_zero, shape);
+    if (kind == KIND_S27) {
         // 27-point per-row-coefficient level (stencil27.hip): sweeps as four pair launches, out of place; the last
         // pre-smoothing sweep leaves the residuals of its final rows, the others' are formed inside the restriction
         Stencil27Plan<V> &P = *L.s27;
-        // (a 27-point child's first sweep never reads its zero iterate; a plane child's down pass only when it IS the
-        // cycle's one pre-smoothing sweep — with more, smooth_level runs before it on the iterate as stored)
-        const bool child_zero = l + 1 < last && ((use_s27(h, C) && pre >= 1) || (use_plane(h, C) && pre == 1));
         bool zero_now = x_zero;
-        if (x_zero && pre == 0) {
-            OMG_HIP(hipMemsetAsync(L.xp, 0, size_t(L.n) * sizeof(V), h->stream));
-            zero_now = false;
-        }
         for (int it = 0; it < pre; ++it) {                      // :201
             Prof<V> p(h, l, 0);
             P.sweep(L.xp, L.tp, L.b.p, zero_now, (it == 0 && !zero_now) ? pre_slot : nullptr, it + 1 == pre, nullptr, h->stream);
@@ -935,12 +1051,12 @@ int cycle_body(Hier<V> *h, int l, int pre, int post, bool want_norm, double *pre
             zero_now = false;
         }
         if (l == h->pre_level) OMG_HIP(hipMemcpyAsync(h->pre_buf.p, L.xp, size_t(L.n) * sizeof(V), hipMemcpyDeviceToDevice, h->stream));
-        if (l + 1 < last && !child_zero) OMG_HIP(hipMemsetAsync(C.xp, 0, size_t(C.n) * sizeof(V), h->stream));   // :191-192
+        const ChildEntry<V> e = enter_child(h, l, pre);                                // :191-192
         {
             Prof<V> p(h, l, 1);
             P.residual_restrict(L.xp, L.b.p, pre >= 1, L.r_out.p, C.b.p, h->stream);                  // :209, :210
         }
-        cycle_children(h, l, pre, post, shape, false, child_zero);                                     // :213
+        cycle_children(h, l, pre, post, shape, false, e.zero);                                         // :213
         {
             Prof<V> p(h, l, 3);
             P.prolong(L.xp, C.xp, L.r_out.p, h->stream);                                               // :214, :220 / :224
@@ -954,89 +1070,14 @@ int cycle_body(Hier<V> *h, int l, int pre, int post, bool want_norm, double *pre
         }
         return want_norm ? NORM_S27 : NORM_NONE;
     }
-    if (use_plane(h, L)) {
-        typename PlanePlan<V>::Coarse c;
-        const PlaneDown d = plane_down_half(h, l, pre, post, x_zero, first_done, c);
-        double *out = (want_norm && post <= 1) ? (post_slot ? post_slot : L.plane->partials.p) : nullptr;
-        const int fuse = !out ? tail_fuse_depth(h, l, post, shape) : 0;
-        if (fuse) {
-            // the rest of the cycle below this level in one launch: (depth 2: the child's down pass as ever, then) the coarsest
-            // solve and the up passes of the levels above it (plane.hip tail_up_kernel)
-            TailUp<V> u;
-            u.top = &L.plane->g; u.x_old = L.xp; u.x_new = L.tp; u.b = L.b.p;
-            u.cmap = L.r_out.p;
-            if (fuse == 2) {
-                typename PlanePlan<V>::Coarse cc;
-                plane_down_half(h, l + 1, pre, post, d.child_zero, d.child_first, cc);
-                u.mid = &C.plane->g; u.mid_x_old = C.xp; u.mid_x_new = C.tp; u.mid_b = C.b.p;
-                u.cmap = C.r_out.p;
-            }
-            Level<V> &Z = h->lv[last];
-            u.cb = Z.b.p; u.cx = Z.xp; u.tables = h->coarse.sine.p; u.lambda = h->coarse.lambda.p;
-            u.sweep = post >= 1;
-            {
-                Prof<V> p(h, l, 6);
-                launch_tail_up<V>(u, h->stream);
-                ++h->tail_launches;
-            }
-            if (fuse == 2) std::swap(C.xp, C.tp);
-            std::swap(L.xp, L.tp);
-            return NORM_NONE;
-        }
-        cycle_children(h, l, pre, post, shape, d.child_first, d.child_zero);                 // :213
-        c.e = C.xp;
-        {
-            Prof<V> p(h, l, 6);
-            L.plane->up(L.xp, L.tp, L.b.p, c, out, h->stream, nullptr, post >= 1);           // :214, :220/:224, first sweep of :216-222 (, :227)
-        }
-        std::swap(L.xp, L.tp);
-        if (post > 1)
-            return smooth_level(h, l, post - 1, want_norm ? FUSE_NORM : FUSE_NONE, nullptr, false, post_slot) ? NORM_LAST_SET : NORM_NONE;
-        return out ? NORM_PLANE : NORM_NONE;
-    }
-    if (use_var7(h, L)) {
-        // 7-point per-row-coefficient level (var7.hip): all but the last pre-smoothing sweep set by set (in place), the last
-        // one inside the down pass; the up pass holds the first post-smoothing sweep and the norm's squares
-        Var7Plan<V> &P = *L.var7;
-        if (pre > 1) smooth_level(h, l, pre - 1, FUSE_NONE, nullptr, first_done);
-        const bool child_zero = l + 1 < last && ((use_var7(h, C) && pre == 1) || (use_plane(h, C) && pre == 1) || (use_s27(h, C) && pre >= 1));
-        if (l + 1 < last && !child_zero) {
-            if (!use_s27(h, C)) ensure_format(h, l + 1);
-            OMG_HIP(hipMemsetAsync(C.xp, 0, size_t(C.n) * sizeof(V), h->stream));      // :191-192
-        }
-        typename Var7Plan<V>::Coarse c;
-        c.map = L.r_out.p;
-        c.b = C.b.p;
-        {
-            Prof<V> p(h, l, 5);
-            P.down(L.xp, L.tp, L.b.p, x_zero && pre == 1, c, h->stream, pre >= 1);       // :201 (last sweep), :209, :210
-        }
-        if (pre >= 1) std::swap(L.xp, L.tp);
-        else if (x_zero) OMG_HIP(hipMemsetAsync(L.xp, 0, size_t(L.n) * sizeof(V), h->stream));
-        if (l == h->pre_level) OMG_HIP(hipMemcpyAsync(h->pre_buf.p, L.xp, size_t(L.n) * sizeof(V), hipMemcpyDeviceToDevice, h->stream));
-        cycle_children(h, l, pre, post, shape, false, child_zero);                        // :213
-        c.e = C.xp;
-        double *out = (want_norm && post <= 1) ? (post_slot ? post_slot : P.partials.p) : nullptr;
-        {
-            Prof<V> p(h, l, 6);
-            P.up(L.xp, L.tp, L.b.p, c, out, h->stream, post >= 1);                       // :214, :220/:224, first sweep of :216-222 (, :227)
-        }
-        std::swap(L.xp, L.tp);
-        if (post > 1)
-            return smooth_level(h, l, post - 1, want_norm ? FUSE_NORM : FUSE_NONE, nullptr, false, post_slot) ? NORM_LAST_SET : NORM_NONE;
-        return out ? NORM_VAR7 : NORM_NONE;
-    }
     const bool res_done = smooth_level(h, l, pre, FUSE_RESIDUAL, pre_slot, first_done);   // :201 (+ last set's share of :209)
     if (l == h->pre_level) OMG_HIP(hipMemcpyAsync(h->pre_buf.p, L.xp, size_t(L.n) * sizeof(V), hipMemcpyDeviceToDevice, h->stream));
     residual_level(h, l, L.r.p, res_done);                          // :209
     // :210, and the coarse cycle's initial=None -> zeros (:191-192) cleared by the same launch —
     // or already relaxed once (first_sweep_in_restrict)
-    const bool child_zero = l + 1 < last && ((use_plane(h, C) && pre == 1) || (use_s27(h, C) && pre >= 1));
-    if (l + 1 < last && !child_zero && !use_s27(h, C)) ensure_format(h, l + 1);
-    // (a var7 child's down pass holds its whole first sweep: it cannot skip a launch already applied)
-    const bool child_first = l + 1 < last && !child_zero && !use_s27(h, C) && !use_var7(h, C) && first_sweep_in_restrict(h, C, pre);
-    restrict_level<V>(h, l, L.r.p, C.b.p, (l + 1 < last && !child_zero) ? C.xp : nullptr, child_first);
-    cycle_children(h, l, pre, post, shape, child_first, child_zero);                     // :213
+    const ChildEntry<V> e = enter_child(h, l, pre);
+    restrict_level<V>(h, l, L.r.p, C.b.p, e.write, e.first);
+    cycle_children(h, l, pre, post, shape, e.first, e.zero);                             // :213
     prolong_add_level<V>(h, l, C.xp, L.xp, h->over);                // :214, :220/:224
     if (post > 0)
         return smooth_level(h, l, post, want_norm ? FUSE_NORM : FUSE_NONE, nullptr, false, post_slot) ? NORM_LAST_SET : NORM_NONE;   // :216-222
@@ -1046,12 +1087,11 @@ int cycle_body(Hier<V> *h, int l, int pre, int post, bool want_norm, double *pre
 // ||b - A x|| of level l into out (device scalar; null: h->norm_dev) after a cycle that returned `state`
 template <typename V>
 void finish_norm(Hier<V> *h, int l, int state, double *out = nullptr) {
-    if (state == NORM_PLANE) {
+    if (state == NORM_PASS) {
         Level<V> &L = h->lv[l];
-        launch_sum_sqrt(L.plane->partials.p, L.plane->g.n_wg, out ? out : h->norm_dev.p, h->stream);
-    } else if (state == NORM_VAR7) {
-        Level<V> &L = h->lv[l];
-        launch_sum_sqrt(L.var7->partials.p, L.var7->n_wg, out ? out : h->norm_dev.p, h->stream);
+        const bool plane = level_kind(h, L) == KIND_PLANE;
+        launch_sum_sqrt(plane ? L.plane->partials.p : L.var7->partials.p, plane ? L.plane->g.n_wg : L.var7->n_wg,
+                        out ? out : h->norm_dev.p, h->stream);
     } else if (state == NORM_S27) {
         // the rows the last post-smoothing launch made final have left their squares (segment 3); the others' now
         Level<V> &L = h->lv[l];
@@ -1985,7 +2025,7 @@ void zero_start_cycle(Hier<V> *hh, int pre, int post) {
     Level<V> &L = hh->lv[0];
     bool first = false, zero_in = false;
     if (hh->lv.size() > 1) {
-        zero_in = (use_plane(hh, L) && pre == 1) || (use_s27(hh, L) && pre >= 1) || (use_var7(hh, L) && pre == 1);   // the down pass / first sweep does not read a zero iterate
+        zero_in = enters_without_iterate(hh, L, pre);
         if (!zero_in) {
             // x starts from zero: the first relaxation launch is a pointwise b / diag (restrict_level).  The
             // diagonal comes from the row-kernel format, which a plane level builds on first use: BEFORE it
@@ -2374,7 +2414,7 @@ void batched_cycles(Hier<V> *hh, int pre, int post, int n_cycles, double *out) {
                 OMG_HIP(hipMemsetAsync(out + k0 + j, 0, sizeof(double), hh->stream));   // :232
             } else if (kind == PLANE) {
                 const int st = cycle_body(hh, 0, pre, post, true, nullptr, false, slot(j));
-                OMG_REQUIRE(st == NORM_PLANE, "internal: plane-pipelined cycle without its norm partials");
+                OMG_REQUIRE(st == NORM_PASS, "internal: plane-pipelined cycle without its norm partials");
             } else if (kind == S27) {
                 const bool own_norm = last_of_chunk || pre == 0;
                 cycle_body(hh, 0, pre, post, own_norm, (pre >= 1 && j > 0) ? slot(j - 1) : nullptr, false, own_norm ? slot(j) : nullptr);
