@@ -8,7 +8,8 @@ The operator is the 7-point finite-volume Laplacian on N^3 cells whose couplings
 times those along the other two (Dirichlet walls).  Point smoothing only damps the error along the strong axis, so the
 cycles crawl whatever their shape; 'line' solves every grid line along that axis exactly ('lineAxis': 'auto' finds it) and
 converges like multigrid on an isotropic problem.  With TWO strong axes (try ratio < 1: the unit-stride axis becomes the
-one weak axis) lines along one axis are not enough — that needs plane smoothing or semicoarsening, which is not here.
+one weak axis) lines along one axis are not enough — that is what 'coarsening': 'auto' (semicoarsening) repairs:
+examples/semicoarsen3d_solve.py.
 """
 import os
 import sys

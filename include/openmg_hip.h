@@ -407,6 +407,42 @@ int omg_csr_result_free(omg_csr_result *res);
 int omg_restriction(int dim, const int64_t *shape, int32_t *indptr, int32_t *indices,
                     double *data, int64_t *n_rows, int64_t *nnz);
 
+/* ---- Semicoarsening: a coarsening factor of 1 or 2 per axis and restriction (no reference counterpart) ----
+ * On a grid-aligned anisotropic operator only the strongly coupled axes are coarsened; plain aggregation halves the
+ * coupling of a coarsened axis relative to the others, so a few levels down the operator is isotropic and coarsening is
+ * full again.  Every shape and factor tuple is in the grid's C order: the LAST axis has unit stride; dim is 2 or 3.
+ *
+ * omg_restriction_ex: the plain C-order aggregation of the grid `shape` by factors[0..dim-1], weight 1 / prod(factors),
+ * ascending columns.  Caller-allocated indptr[n / prod(factors) + 1], indices[n], data[n], n = prod(shape).  A factor other
+ * than 1 or 2, factors all 1, or a 2 on an extent that is odd or below 4: OMG_ERR_INVALID.  With all factors 2 on a shape
+ * whose first and last extent are equal it is omg_restriction's matrix, bit for bit. */
+int omg_restriction_ex(int dim, const int64_t *shape, const int *factors, int32_t *indptr, int32_t *indices, double *data);
+/* Per-axis couplings of a grid operator held as CSR: sums3[a] = sum |a_ij| and counts4[a] = the number of the STORED
+ * entries whose column offset is +- the stride of axis a of `shape`, counts4[3] = the stored entries at any other non-zero
+ * offset (27-point, periodic wrap); a 2-D grid leaves sums3[2] = counts4[2] = 0.  A reduction on the device over fixed
+ * slots in a fixed order: two calls give the same bits. */
+int omg_axis_couplings(const omg_csr *A, int dim, const int64_t *shape, double *sums3, int64_t *counts4);
+/* The rule that picks one level's factors from its couplings — a pure host function, no device: both setup routes call
+ * this one statement of it.  An axis is eligible when its extent is even and >= 4; m is the eligible axis with the largest
+ * mean sums3 / counts4; every eligible axis a with 2 S_a N_m >= S_m N_a (in double, no division: theta = 1/2, ties
+ * coarsen) gets factor 2.  line_axis (an index into shape, or -1): the axis of a line smoother is left out of the maximum
+ * whenever another axis is eligible, and is always coarsened when eligible.  factors3 all 1: no axis is eligible, the
+ * hierarchy ends at this level.  counts4[3] != 0: OMG_ERR_UNSUPPORTED, `level` in the text. */
+int omg_semicoarsen_rule(int dim, const int64_t *shape, const double *sums3, const int64_t *counts4, int line_axis, int level,
+                         int *factors3);
+/* omg_hierarchy_create_from_fine_opt with factors: n_restrictions * dim entries, restriction after restriction, or NULL =
+ * 'auto' (couplings kernel, rule, restriction kernel, Galerkin product per level, all in HBM).  Under 'auto' the hierarchy
+ * ends where no axis is eligible, and after the first restriction where the coarse level would have <= min_size rows
+ * (min_size <= 0: no such rule) — it may have fewer than n_restrictions + 1 levels; named factors are all used.  The
+ * operators are then fetched once and the levels made as omg_hierarchy_create_opt makes them from the same lists (same
+ * object, same bits): a level whose restriction is not the full 2^dim aggregation runs the set-by-set row kernels.  The
+ * line smoothers: OMG_ERR_UNSUPPORTED (omg_hierarchy_create_opt takes them).  omg_hierarchy_can_update_fine is false. */
+int omg_hierarchy_create_from_fine_semi(const omg_csr *A_in, int dim, const int64_t *shape, int n_restrictions, const int *factors,
+                                        int64_t min_size, const omg_hierarchy_options *opt, omg_hierarchy **out);
+/* factors3[0..dim-1] of restriction `level` of a hierarchy made by omg_hierarchy_create_from_fine_semi (the rest 1); any
+ * other hierarchy, or no such restriction: OMG_ERR_INVALID. */
+int omg_hierarchy_coarsening(const omg_hierarchy *h, int level, int *factors3);
+
 /* Host-side helper of the mgCycle binding (no reference counterpart, no device involved): mgCycle(A, b, level, R,
  * parameters, initial) — openmg/__init__.py:151 — is handed the operator lists on EVERY call; the binding keeps the
  * device hierarchy between calls and recognises the lists by a checksum of every byte (an operator edited in place

@@ -17,13 +17,34 @@ Extra keys understood in the `parameters` dict (ignored by the reference):
                 (3-D) stencil on the lexicographically numbered grid, any coefficients, extents even or odd; a 27-point,
                 periodic or 1-D operator raises HipError (ERR_UNSUPPORTED) naming the level.  It repairs ONE strong axis
                 (couplings 100 : 1 : 1: 9 V-cycles where 'colour' needs hundreds); with two strong axes (one weak one) it
-                is no better than 'colour' — that needs plane smoothing or semicoarsening, which this package lacks.
-                Works with every 'accel', 'dtype', 'cycle', 'overCorrection', 'nullspace', device arrays and Solver;
-                single GPU, the lists setup route, set-by-set launches (no fused passes)
+                is no better than 'colour' — that is what 'coarsening' (semicoarsening, below) repairs, with 'line' or
+                with any point smoother; plane smoothing is not here.
+                Works with every 'accel', 'dtype', 'cycle', 'overCorrection', 'nullspace', 'coarsening', device arrays
+                and Solver; single GPU, the lists setup route, set-by-set launches (no fused passes)
     'lineAxis'  with 'line': None or 'auto' (default: the axis whose couplings of A_in have the largest sum of |a_ij|, ties
                 to the unit-stride axis), or an index into 'problemShape' (C order: the last entry is the unit-stride
                 axis).  The same axis on every level.  Anything else raises ValueError before any device work; mgSolve's
                 infoDict['lineAxis'] (and Solver's info) reports the axis used
+    'coarsening'  None or 'full' (default: every restriction halves every axis, the reference's hierarchy, bit for bit),
+                'auto', or a sequence with one tuple per restriction holding a factor of 1 or 2 for each axis of
+                'problemShape' (2-D / 3-D): SEMICOARSENING for grid-aligned anisotropic operators — only the strongly
+                coupled axes are coarsened, which halves their coupling relative to the others, until the operator is
+                isotropic and coarsening is full again.  It repairs what 'line' cannot (two strong axes, three different
+                strengths) with any smoother, and composes with 'line'.  'auto' picks the factors level by level from
+                the operator's couplings (an axis is coarsened when its mean |a_ij| is at least half the strongest
+                axis's; it needs a 5- / 7-point stencil: a 27-point or periodic operator raises HipError
+                (ERR_UNSUPPORTED) naming the level — name the factors for those).  A named sequence is consumed entry by
+                entry; the depth rule is unchanged ('gridLevels', then 'minSize' after the first restriction).  An
+                entry of all ones, a factor of 2 on an extent that is odd or below 4, or a sequence shorter than the
+                depth reached raises ValueError before any device work.  No axis ever collapses to 1.  Works with every
+                'smoother', 'accel', 'dtype', 'cycle', 'overCorrection', 'nullspace' and device arrays; single GPU.
+                Semicoarsened levels run the set-by-set row kernels (no fused passes) and a V-cycle does about twice
+                the finest level's work instead of 8/7 of it: a cycle costs more, the gain is in their number.
+                'overCorrection' > 1 is the repair for the 2**dim aggregation and CAN DIVERGE on a hierarchy that
+                coarsens one axis per level (measured: 'colour', F, 1.8 at 100 : 10 : 1); with ONE strong
+                axis use 'line' (a point smoother then leaves a large coarsest level to the direct solve).
+                infoDict['coarsening'] (and Solver's info) lists the factor tuples used, infoDict['levelShapes'] every
+                level's grid.  Solver.update keeps the factors chosen at construction and builds a new hierarchy
     'omega'     relaxation weight for 'jacobi' (default 2/3)
     'accel'     mgSolve only: None (default: plain V-cycles, the reference's loop) or 'cg': flexible preconditioned
                 conjugate gradients (FCG(1)) on the finest level with one zero-start V-cycle as the preconditioner per
@@ -259,6 +280,10 @@ def mgSolve(A_in, b, parameters):
     infoDict = {"norm": norm, "cycle": cycle, "R": R, "A": A}
     if line_axis is not None:
         infoDict["lineAxis"] = line_axis           # ('line': the axis the lines ran along, an index into problemShape)
+    if hierarchy.coarsening is not None:
+        # ('coarsening' 'auto' or named: the factors of every restriction built, and every level's grid)
+        infoDict["coarsening"] = list(hierarchy.coarsening)
+        infoDict["levelShapes"] = list(hierarchy.level_shapes)
     if verbose:
         print("Returning mgSolve after %i cycle(s) with norm %f" % (cycle, norm))
     if parameters["giveInfo"]:
@@ -288,6 +313,9 @@ def _setup(A_in, parameters, completed_from):
     verbose = parameters["verbose"]
     dense = parameters["dense"]
     code, omega = _smoother_of(parameters)
+    coarsening = _coarsening_of(parameters)
+    if coarsening is not None:
+        return _setup_semicoarsened(A_in, parameters, coarsening, code, omega, nullspace) + (accel, shape, alpha)
 
     # (the device route qualifies levels for the FUSED paths, which exist for the colour orderings and 2-D weighted Jacobi; with
     # the reference's own lexicographic smoother it would build the Galerkin chain in HBM only to fetch it again for the host's
@@ -308,6 +336,59 @@ def _setup(A_in, parameters, completed_from):
         A = operators.coeffecientList(A_in, R, dense=dense, verbose=verbose)
         hierarchy = _hip.Hierarchy(A, R, smoother=code, omega=omega, dtype=_dtype_of(parameters), nullspace=nullspace)
     return hierarchy, R, A, accel, shape, alpha
+
+
+def _coarsening_of(parameters):
+    """parameters['coarsening'] checked (operators.coarseningOf): None for full coarsening, 'auto', or the list of factor
+    tuples the depth rule will use; ValueError for anything else — before any device work."""
+    value = parameters.get("coarsening")
+    if value is None or (isinstance(value, str) and value == "full"):
+        return None
+    levels = parameters.get("coarsestLevel", parameters.get("gridLevels", defaults["gridLevels"]) - 1)
+    return operators.coarseningOf(value, parameters.get("problemShape"), levels, parameters.get("minSize", defaults["minSize"]))
+
+
+def _setup_semicoarsened(A_in, parameters, coarsening, code, omega, nullspace):
+    """_setup with parameters['coarsening'] = 'auto' or factor tuples: (hierarchy, R, A).  The device route
+    (omg_hierarchy_create_from_fine_semi) when nobody asked for the lists and the smoother is one the device route takes
+    today, else operators.semicoarsenedLists; either way the same hierarchy."""
+    problemShape = tuple(int(s) for s in parameters["problemShape"])
+    dim = len(problemShape)
+    if parameters["dense"]:
+        raise ValueError("parameters['coarsening'] works on sparse operators: parameters['dense'] must be false")
+    if not sp.issparse(A_in):
+        A_in = sp.csr_matrix(A_in)
+    if A_in.shape != (tools.product(problemShape),) * 2:
+        raise ValueError("parameters['problemShape'] %s does not match the operator's shape %s" % (problemShape, A_in.shape))
+    levels = parameters["coarsestLevel"] + 1
+    line_axis = None
+    if _hip.is_line_smoother(code) and coarsening == "auto":
+        # the rule treats the line axis apart, so it must know it before the hierarchy exists: 'lineAxis' None / 'auto' is
+        # resolved here as the library resolves it (the largest sum of |a_ij|, ties to the unit-stride axis) and then NAMED
+        # to the library, so that both use the same axis
+        if code == _hip.SMOOTH_LINE:
+            sums = _hip.axis_couplings(A_in, problemShape)[0]
+            line_axis = dim - 1
+            for axis in range(dim - 2, -1, -1):
+                if sums[axis] > sums[line_axis]:
+                    line_axis = axis
+            code = _hip.line_smoother_code(line_axis, problemShape)
+        else:
+            line_axis = dim - 1 - (code - _hip.SMOOTH_LINE_X)
+    fused_smoother = code == _hip.SMOOTH_GS_COLOUR or (code == _hip.SMOOTH_JACOBI and dim == 2)
+    if fused_smoother and not (parameters["giveInfo"] or parameters["verbose"]):
+        R = A = None
+        named = None if coarsening == "auto" else coarsening
+        hierarchy = _hip.Hierarchy.from_fine_semi(A_in, problemShape, levels if named is None else len(named), named,
+                                                  min_size=parameters["minSize"], smoother=code, omega=omega, dtype=_dtype_of(parameters),
+                                                  nullspace=nullspace)
+    else:
+        R, A, factors = operators.semicoarsenedLists(A_in, problemShape, coarsening, parameters["coarsestLevel"], parameters["minSize"],
+                                                     lineAxis=line_axis)
+        hierarchy = _hip.Hierarchy(A, R, smoother=code, omega=omega, dtype=_dtype_of(parameters), nullspace=nullspace)
+        hierarchy._set_coarsening(problemShape, factors)
+    parameters["coarsestLevel"] = len(hierarchy.coarsening)
+    return hierarchy, R, A
 
 
 # CG iterations per omg_resident_pcg call when only 'threshold' stops the solve (the next call restarts from the iterate)

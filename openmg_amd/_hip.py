@@ -124,6 +124,11 @@ SIGNATURES = {
     "omg_csr_result_fetch": (_I, [_P, _P, _P, _P]),
     "omg_csr_result_free": (_I, [_P]),
     "omg_restriction": (_I, [_I, _I64P, _P, _P, _P, _I64P, _I64P]),
+    "omg_restriction_ex": (_I, [_I, _I64P, _IP, _P, _P, _P]),
+    "omg_axis_couplings": (_I, [_CSR, _I, _I64P, _DP, _I64P]),
+    "omg_semicoarsen_rule": (_I, [_I, _I64P, _DP, _I64P, _I, _I, _IP]),
+    "omg_hierarchy_create_from_fine_semi": (_I, [_CSR, _I, _I64P, _I, _IP, ctypes.c_int64, _OPT, _PP]),
+    "omg_hierarchy_coarsening": (_I, [_P, _I, _IP]),
     "omg_host_checksum": (_I, [_P, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint64)]),
     "omg_dist_create": (_I, [_I, _I, _I, _P, _CSR, _I64P, _I, _D, _PP]),
     "omg_dist_create_ex": (_I, [_I, _I, _I, _P, _CSR, _I64P, _I, _D, _I, _PP]),
@@ -417,6 +422,60 @@ class Hierarchy:
         self._h = h
         self._A = self._R = None
         return self
+
+    @classmethod
+    def from_fine_semi(cls, A_in, shape, n_restrictions, factors=None, min_size=0, smoother="gs", omega=1.0, dtype="float64",
+                       nullspace=None):
+        """mgSolve's setup with semicoarsening on the device (omg_hierarchy_create_from_fine_semi).  factors: one tuple of 1 or 2
+        per axis of `shape` for each of the n_restrictions restrictions, or None = 'auto': the rule picks them level by level, at
+        most n_restrictions of them, ending early where no axis can be coarsened or (after the first restriction) the coarse level
+        would have <= min_size rows.  .coarsening lists what was built, .level_shapes every level's grid."""
+        self = cls.__new__(cls)
+        self._h = None
+        self.nullspace_kind = nullspace_code(nullspace)
+        A0 = as_csr(A_in)
+        shape = tuple(int(s) for s in shape)
+        dim = len(shape)
+        arr = (ctypes.c_int64 * dim)(*shape)
+        n_restrictions = int(n_restrictions)
+        flat = None
+        if factors is not None:
+            factors = [tuple(int(f) for f in entry) for entry in factors]
+            if len(factors) != n_restrictions or any(len(entry) != dim for entry in factors):
+                raise ValueError("factors needs n_restrictions entries of one factor per axis of the shape")
+            flat = (ctypes.c_int * max(n_restrictions * dim, 1))(*[f for entry in factors for f in entry])
+        self.smoother = smoother_code(smoother)
+        self.omega = float(omega)
+        self.dtype = dtype_code(dtype)
+        h = ctypes.c_void_p()
+        v = csr_view(A0)
+        opt = HierarchyOptions(self.smoother, self.omega, self.dtype, self.nullspace_kind)
+        check(lib().omg_hierarchy_create_from_fine_semi(ctypes.byref(v), dim, arr, n_restrictions, flat, int(min_size), ctypes.byref(opt),
+                                                        ctypes.byref(h)))
+        self._h = h
+        self._A = self._R = None
+        used = []
+        f3 = (ctypes.c_int * 3)()
+        for level in range(n_restrictions):
+            if lib().omg_hierarchy_coarsening(h, level, f3) != OMG_OK:      # (past the last restriction built)
+                break
+            used.append(tuple(int(f3[d]) for d in range(dim)))
+        self._set_coarsening(shape, used)
+        self.n_levels = len(used) + 1
+        self.sizes = [int(np.prod(s)) for s in self.level_shapes]
+        return self
+
+    def _set_coarsening(self, shape, factors):
+        """Records the factors of every restriction and the grid of every level (None: not a semicoarsened hierarchy)."""
+        self.coarsening = None if factors is None else [tuple(int(f) for f in entry) for entry in factors]
+        self.level_shapes = None
+        if factors is not None:
+            self.level_shapes = [tuple(int(s) for s in shape)]
+            for entry in self.coarsening:
+                self.level_shapes.append(tuple(s // f for s, f in zip(self.level_shapes[-1], entry)))
+
+    coarsening = None          # [(factor per axis), ...] per restriction of a semicoarsened hierarchy, else None
+    level_shapes = None        # [(extent per axis), ...] per level of a semicoarsened hierarchy, else None
 
     def update_fine(self, data, on_device=False):
         """New values for the fine operator, same pattern (omg_hierarchy_update_fine).  data: the CSR's value array as a
@@ -833,3 +892,48 @@ def restriction(shape):
         # the reference's LIL assignment raises the same for shapes its offsets overrun
         raise IndexError("column index (%d) out of range" % int(indices[:k].max()))
     return sp.csr_matrix((data[:k], indices[:k], indptr[:nr.value + 1]), shape=(nr.value, N))
+
+
+def restriction_ex(shape, factors):
+    """The plain C-order aggregation of the grid `shape` by `factors` (1 or 2 per axis) built on the device -> scipy CSR
+    (omg_restriction_ex); HipError (ERR_INVALID) for factors it does not take."""
+    shape = tuple(int(s) for s in shape)
+    factors = tuple(int(f) for f in factors)
+    dim = len(shape)
+    if len(factors) != dim:
+        raise ValueError("need one factor per axis of the shape %s, not %r" % (shape, factors))
+    N = int(np.prod(shape))
+    n = N // max(int(np.prod(factors)), 1) if all(f > 0 for f in factors) else 0
+    indptr = np.empty(n + 1, dtype=np.int32)
+    indices = np.empty(max(N, 1), dtype=np.int32)
+    data = np.empty(max(N, 1), dtype=np.float64)
+    check(lib().omg_restriction_ex(dim, (ctypes.c_int64 * dim)(*shape), (ctypes.c_int * dim)(*factors), indptr.ctypes.data,
+                                   indices.ctypes.data, data.ctypes.data))
+    R = sp.csr_matrix((data[:N], indices[:N], indptr), shape=(n, N))
+    R.has_sorted_indices = True
+    return R
+
+
+def axis_couplings(A, shape):
+    """(sums, counts, off_axis) of a grid operator (omg_axis_couplings): per axis of `shape` the sum of |a_ij| and the number
+    of the stored entries at column offset +- the axis's stride, and the number of stored entries at any other non-zero offset."""
+    A = as_csr(A)
+    shape = tuple(int(s) for s in shape)
+    dim = len(shape)
+    sums = (ctypes.c_double * 3)()
+    counts = (ctypes.c_int64 * 4)()
+    v = csr_view(A)
+    check(lib().omg_axis_couplings(ctypes.byref(v), dim, (ctypes.c_int64 * dim)(*shape), sums, counts))
+    return tuple(float(sums[a]) for a in range(dim)), tuple(int(counts[a]) for a in range(dim)), int(counts[3])
+
+
+def semicoarsen_rule(shape, sums, counts, off_axis=0, line_axis=None, level=0):
+    """The factors (1 or 2 per axis of `shape`) the 'auto' rule picks for one level from its couplings (omg_semicoarsen_rule, a
+    host function: no device).  All ones: no axis can be coarsened.  HipError (ERR_UNSUPPORTED) when off_axis != 0."""
+    shape = tuple(int(s) for s in shape)
+    dim = len(shape)
+    s3 = (ctypes.c_double * 3)(*([float(x) for x in sums] + [0.0] * (3 - dim)))
+    c4 = (ctypes.c_int64 * 4)(*([int(x) for x in counts] + [0] * (3 - dim) + [int(off_axis)]))
+    f3 = (ctypes.c_int * 3)()
+    check(lib().omg_semicoarsen_rule(dim, (ctypes.c_int64 * dim)(*shape), s3, c4, -1 if line_axis is None else int(line_axis), int(level), f3))
+    return tuple(int(f3[d]) for d in range(dim))

@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _devarray, _hip
 
-# the keys a solve may override: those that do not define the hierarchy ('smoother', 'lineAxis', 'dtype', 'nullspace',
+# the keys a solve may override: those that do not define the hierarchy ('smoother', 'lineAxis', 'coarsening', 'dtype', 'nullspace',
 # the grids do, and are refused)
 SOLVE_KEYS = ("cycles", "threshold", "rtol", "preIterations", "postIterations", "accel", "cycle", "overCorrection")
 
@@ -53,8 +53,9 @@ def _host_out(out, n):
 
 def _check_keys(parameters):
     """ValueError for a value mgSolve would refuse — before any device work, GPU or not."""
-    from . import _accel_of, _cycle_of, _dtype_of, _nullspace_of, _smoother_of
+    from . import _accel_of, _coarsening_of, _cycle_of, _dtype_of, _nullspace_of, _smoother_of
     _accel_of(parameters)
+    _coarsening_of(parameters)
     _cycle_of(parameters)
     _nullspace_of(parameters)
     _smoother_of(parameters)
@@ -186,6 +187,9 @@ class Solver:
         info = {"cycle": cycle, "norm": norm, "norms": norms, "rhs_norm": rhs_norm, "initial_norm": initial_norm}
         if _hip.is_line_smoother(h.smoother):
             info["lineAxis"] = h.line_axis          # ('smoother': 'line': the axis of the lines, an index into problemShape)
+        if h.coarsening is not None:
+            info["coarsening"] = list(h.coarsening)   # ('coarsening': the factors of every restriction, every level's grid)
+            info["levelShapes"] = list(h.level_shapes)
         return u, info
 
     # ---- apply --------------------------------------------------------------------------------------------------------
@@ -222,7 +226,9 @@ class Solver:
         """New values in A_in's pattern (the same indptr and indices; anything else: ValueError, and the solver keeps
         the old operator).  Where the hierarchy takes new coefficients in place (_hip.Hierarchy.can_update_fine) that
         is update_fine; otherwise a new hierarchy is built first and the old one closed after that succeeded.  Either
-        way later solves have the bits of a fresh Solver(A_new, parameters)."""
+        way later solves have the bits of a fresh Solver(A_new, parameters).  With parameters['coarsening'] the new
+        hierarchy is built with the FACTORS CHOSEN AT CONSTRUCTION ('auto' is not asked again: sizes and patterns cannot
+        change under the caller), always as a new hierarchy: a semicoarsened one takes no update in place."""
         from . import _setup, defaults
         h = self._open()
         A1 = _hip.as_csr(A_new)
@@ -232,7 +238,12 @@ class Solver:
         if h.can_update_fine():
             h.update_fine(A1.data)
             return
-        fresh, R, A = _setup(A_new, dict(self._given), dict(defaults))[:3]
+        given = dict(self._given)
+        if h.coarsening is not None:
+            given["coarsening"] = list(h.coarsening)
+            given["gridLevels"] = len(h.coarsening)  # (the depth built: the list is consumed exactly)
+            given.pop("coarsestLevel", None)
+        fresh, R, A = _setup(A_new, given, dict(defaults))[:3]
         self._hierarchy, self.R, self.A = fresh, R, A
         self._pattern_of(A1)
         h.close()

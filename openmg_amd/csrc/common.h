@@ -826,6 +826,18 @@ struct DevCsrPlain {
 // reference's depth rule).  (setup_device.hip)
 void galerkin_chain_device(const omg_csr &A0, int dim, const int64_t *shape, int n_restrictions, std::vector<DevCsrPlain> &A,
                            std::vector<DevCsrPlain> &R, hipStream_t s);
+// The same chain with a factor (1 or 2) per axis and restriction instead of 2 everywhere (semicoarsening).
+// shape and every factor tuple are in the grid's C order (the last axis has unit stride).  factors: n_restrictions * dim
+// entries, or null = 'auto': per level the couplings kernel, semicoarsen_rule, the restriction kernel, the product.  Auto
+// ends the chain where no axis can be coarsened, and after the first restriction where the coarse level would have
+// <= min_size rows (min_size <= 0: no such rule); named factors are all used.  used: what was built, dim entries per
+// restriction; A.size() == R.size() + 1 == used.size() / dim + 1.  (setup_device.hip)
+void galerkin_chain_semi_device(const omg_csr &A0, int dim, const int64_t *shape, int n_restrictions, const int *factors, int64_t min_size,
+                                std::vector<DevCsrPlain> &A, std::vector<DevCsrPlain> &R, std::vector<int> &used, hipStream_t s);
+// (setup_host.cpp) the rule of one level; factors all 1: no axis can be coarsened
+void semicoarsen_rule(int dim, const int64_t *shape, const double *sums, const int64_t *counts, int line_axis, int level, int *factors);
+// a factor tuple of one restriction against the extents it is applied to: 1 or 2 per axis, not all 1, 2 only on an even extent >= 4
+void check_factors(int dim, const int64_t *ext, const int *f, int level);
 HostCsr download_csr(const DevCsrPlain &M, hipStream_t s);
 // C = (R A) R^T for an aggregation R (every column of R owned by exactly one row) by the fused kernel, SciPy's
 // accumulation order, ascending columns; false: the operands do not qualify (setup_device.hip)

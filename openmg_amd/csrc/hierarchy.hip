@@ -293,6 +293,9 @@ struct Hier {
 struct omg_hierarchy {
     std::unique_ptr<omg::Hier<double>> d;
     std::unique_ptr<omg::Hier<float>> f;
+    // omg_hierarchy_create_from_fine_semi: the factors of every restriction it built, semi_dim per restriction in the grid's C order
+    std::vector<int> semi_factors;
+    int semi_dim = 0;
 };
 
 namespace omg {
@@ -1808,6 +1811,45 @@ std::unique_ptr<Hier<V>> create_from_fine(const omg_csr &A0, int dim, const int6
     return h;
 }
 
+// mgSolve's setup with a coarsening factor of 1 or 2 per axis and restriction: the chain of restrictions and
+// Galerkin products — under 'auto' with the couplings kernel and the rule between them — is made in HBM
+// (galerkin_chain_semi_device), fetched once and handed to create(): a level whose restriction is not the full 2^dim
+// aggregation runs the set-by-set row kernels (the fused passes bake that aggregate into their LDS images), a level further
+// down whose restriction is full again qualifies for them there as in every hierarchy made from lists.  The result is the
+// object create() makes from the same lists.
+template <typename V>
+std::unique_ptr<Hier<V>> create_from_fine_semi(const omg_csr &A0, int dim, const int64_t *shape, int n_restrictions, const int *factors,
+                                               int64_t min_size, int smoother, double omega, int nullspace, std::vector<int> &used) {
+    refuse_line_smoother(smoother, "omg_hierarchy_create_from_fine_semi");
+    OMG_REQUIRE(smoother >= OMG_SMOOTH_GS_LEX && smoother <= OMG_SMOOTH_JACOBI, "unknown smoother");
+    validate_csr(A0, "A_in");
+    OMG_REQUIRE(A0.n_rows == A0.n_cols, "A_in must be square");
+    require_device();
+    std::vector<HostCsr> hA, hR;
+    {
+        hipStream_t s = nullptr;
+        OMG_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        try {
+            std::vector<DevCsrPlain> dA, dR;
+            galerkin_chain_semi_device(A0, dim, shape, n_restrictions, factors, min_size, dA, dR, used, s);
+            SetupTimer tm("device setup: semicoarsened operators fetched, ordinary route");
+            // (level 0 is the caller's own operator: not fetched)
+            for (size_t l = 1; l < dA.size(); ++l) hA.push_back(download_csr(dA[l], s));
+            for (auto &M : dR) hR.push_back(download_csr(M, s));
+        } catch (...) {
+            (void)hipStreamSynchronize(s);
+            (void)hipStreamDestroy(s);
+            throw;
+        }
+        OMG_HIP(hipStreamSynchronize(s));
+        OMG_HIP(hipStreamDestroy(s));
+    }
+    std::vector<omg_csr> vA = {A0}, vR;
+    for (auto &M : hA) vA.push_back(view(M));
+    for (auto &M : hR) vR.push_back(view(M));
+    return create<V>(int(vA.size()), vA.data(), vR.data(), smoother, omega, nullspace);
+}
+
 // A grid level's operator from its dense [row][S] form on the device, slot e the neighbour at offset slots[e] (ascending in
 // column): the in-grid neighbours whose value is not exactly zero, columns ascending — what the Galerkin chain hands
 // create_from_fine (SciPy's csr_matmat drops exact zeros).
@@ -2578,6 +2620,36 @@ int omg_hierarchy_create_from_fine(const omg_csr *A_in, int dim, const int64_t *
                                    int dtype, omg_hierarchy **out) {
     const omg_hierarchy_options opt = {smoother, omega, dtype, OMG_NULLSPACE_NONE};
     return omg_hierarchy_create_from_fine_opt(A_in, dim, shape, n_restrictions, &opt, out);
+}
+
+int omg_hierarchy_create_from_fine_semi(const omg_csr *A_in, int dim, const int64_t *shape, int n_restrictions, const int *factors,
+                                        int64_t min_size, const omg_hierarchy_options *opt, omg_hierarchy **out) {
+    return guarded([&] {
+        OMG_REQUIRE(out && A_in, "null argument");
+        *out = nullptr;
+        OMG_REQUIRE(opt, "options are null");
+        const int dtype = opt->dtype;
+        OMG_REQUIRE(dtype == OMG_DTYPE_F64 || dtype == OMG_DTYPE_F32 || dtype == OMG_DTYPE_MIXED, "unknown dtype");
+        OMG_REQUIRE(opt->nullspace == OMG_NULLSPACE_NONE || opt->nullspace == OMG_NULLSPACE_CONSTANT, "unknown nullspace kind");
+        std::unique_ptr<omg_hierarchy> h(new omg_hierarchy);
+        h->semi_dim = dim;
+        if (dtype != OMG_DTYPE_F64)
+            h->f = create_from_fine_semi<float>(*A_in, dim, shape, n_restrictions, factors, min_size, opt->smoother, opt->omega, opt->nullspace, h->semi_factors);
+        else
+            h->d = create_from_fine_semi<double>(*A_in, dim, shape, n_restrictions, factors, min_size, opt->smoother, opt->omega, opt->nullspace, h->semi_factors);
+        if (dtype == OMG_DTYPE_MIXED) build_mixed(h->f.get(), *A_in);
+        *out = h.release();
+    });
+}
+
+int omg_hierarchy_coarsening(const omg_hierarchy *h, int level, int *factors3) {
+    return guarded([&] {
+        OMG_REQUIRE(h && (h->d || h->f) && factors3, "null argument");
+        OMG_REQUIRE(h->semi_dim > 0, "omg_hierarchy_coarsening: the hierarchy was not made by omg_hierarchy_create_from_fine_semi (the restrictions "
+                                     "of every other hierarchy are the caller's, or the full 2^dim aggregation)");
+        OMG_REQUIRE(level >= 0 && size_t(level + 1) * size_t(h->semi_dim) <= h->semi_factors.size(), "omg_hierarchy_coarsening: no such restriction");
+        for (int d = 0; d < 3; ++d) factors3[d] = d < h->semi_dim ? h->semi_factors[size_t(level) * size_t(h->semi_dim) + d] : 1;
+    });
 }
 
 int omg_hierarchy_nullspace(const omg_hierarchy *h, int *kind) {

@@ -546,6 +546,148 @@ __global__ void restriction_kernel(int dim, int64_t s0, int64_t s1, int64_t s2, 
     }
 }
 
+// ---- semicoarsening: a factor of 1 or 2 per axis ---------------------------------------------------------
+// The plain C-order aggregation of an e0 x e1 x e2 grid (axis 2 has unit stride; a 2-D grid has e0 = 1) by factors f0, f1,
+// f2: row r <-> the r-th coarse cell in C order over e / f, its f0 f1 f2 members in (d0, d1, d2) order — ascending
+// columns —, one weight 1 / (f0 f1 f2).  A thread per coarse row; rows * per = e0 e1 e2 entries.
+__global__ void restriction_ex_kernel(int64_t e1, int64_t e2, int f0, int f1, int f2, int64_t c1, int64_t c2, int64_t rows,
+                                      int32_t *indptr, int32_t *indices, double *data) {
+    const int per = f0 * f1 * f2;
+    const double w = 1.0 / double(per);
+    for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r <= rows; r += (int64_t)gridDim.x * blockDim.x) {
+        indptr[r] = (int32_t)(r * per);
+        if (r == rows) break;
+        const int64_t i0 = r / (c1 * c2), rem = r % (c1 * c2), i1 = rem / c2, i2 = rem % c2;
+        const int64_t first = ((f0 * i0) * e1 + f1 * i1) * e2 + f2 * i2;
+        int m = 0;
+        for (int d0 = 0; d0 < f0; ++d0)
+            for (int d1 = 0; d1 < f1; ++d1)
+                for (int d2 = 0; d2 < f2; ++d2, ++m) {
+                    indices[r * per + m] = (int32_t)(first + (int64_t(d0) * e1 + d1) * e2 + d2);
+                    data[r * per + m] = w;
+                }
+    }
+}
+
+// Per-axis couplings of a grid operator: S_a = sum |a_ij| and N_a = the number of the stored entries at column offset
+// +- stride(a), and the number of stored entries at any other non-zero offset.  The sums follow nullspace.hip: a thread adds
+// its rows of a grid-stride launch in order, a workgroup folds its 256 threads by a fixed tree into its own slot, one
+// workgroup folds the slots in a fixed order — no atomics; the launch geometry depends on n alone: the same bits every run.
+constexpr int CPL_WG = 256, CPL_MAX_WG = 256;
+template <typename T>
+__device__ __forceinline__ T couplings_block_sum(T v, T *sh) {
+    const int t = int(threadIdx.x);
+    __syncthreads();                                                 // (sh is used once per quantity)
+    sh[t] = v;
+    __syncthreads();
+#pragma unroll
+    for (int s = CPL_WG / 2; s > 0; s >>= 1) {
+        if (t < s) sh[t] += sh[t + s];
+        __syncthreads();
+    }
+    return sh[0];
+}
+// part_s[wg * 3 + a], part_n[wg * 4 + a]
+__global__ __launch_bounds__(CPL_WG) void axis_couplings_kernel(int64_t n, const int32_t *ap, const int32_t *ai, const double *av,
+                                                                int64_t st0, int64_t st1, int64_t st2, double *part_s, long long *part_n) {
+    __shared__ double sh_d[CPL_WG];
+    __shared__ long long sh_n[CPL_WG];
+    double s[3] = {0.0, 0.0, 0.0};
+    long long c[4] = {0, 0, 0, 0};
+    for (int64_t i = blockIdx.x * (int64_t)CPL_WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * CPL_WG)
+        for (int32_t p = ap[i]; p < ap[i + 1]; ++p) {
+            int64_t off = int64_t(ai[p]) - i;
+            if (off == 0) continue;
+            if (off < 0) off = -off;
+            const double v = fabs(av[p]);
+            if (off == st2) { s[2] += v; ++c[2]; }                   // (a stride of 0 names an axis the grid does not have)
+            else if (off == st1) { s[1] += v; ++c[1]; }
+            else if (off == st0) { s[0] += v; ++c[0]; }
+            else ++c[3];
+        }
+    for (int a = 0; a < 3; ++a) {
+        const double t = couplings_block_sum(s[a], sh_d);
+        if (threadIdx.x == 0) part_s[blockIdx.x * 3 + a] = t;
+    }
+    for (int a = 0; a < 4; ++a) {
+        const long long t = couplings_block_sum(c[a], sh_n);
+        if (threadIdx.x == 0) part_n[blockIdx.x * 4 + a] = t;
+    }
+}
+// one workgroup: thread t takes slot t (nwg <= CPL_WG), then the fixed tree
+__global__ __launch_bounds__(CPL_WG) void axis_couplings_fold_kernel(int nwg, const double *part_s, const long long *part_n, double *out_s,
+                                                                     long long *out_n) {
+    __shared__ double sh_d[CPL_WG];
+    __shared__ long long sh_n[CPL_WG];
+    const int t = int(threadIdx.x);
+    for (int a = 0; a < 3; ++a) {
+        const double v = couplings_block_sum(t < nwg ? part_s[t * 3 + a] : 0.0, sh_d);
+        if (t == 0) out_s[a] = v;
+    }
+    for (int a = 0; a < 4; ++a) {
+        const long long v = couplings_block_sum(t < nwg ? part_n[t * 4 + a] : 0ll, sh_n);
+        if (t == 0) out_n[a] = v;
+    }
+}
+
+// sums[a], counts[a] by the axes of shape (C order), counts[3] = off-axis entries; synchronises
+void axis_couplings(const DevMat &A, int dim, const int64_t *shape, double *sums, int64_t *counts, hipStream_t s) {
+    int64_t N = 1;
+    for (int d = 0; d < dim; ++d) N *= shape[d];
+    OMG_REQUIRE(N == A.n_rows && A.n_rows == A.n_cols, "the shape does not match the operator");
+    // strides by axis; an absent third axis gets the stride 0, which no off-diagonal entry has
+    int64_t st[3] = {0, 0, 0};
+    st[dim - 1] = 1;
+    for (int d = dim - 2; d >= 0; --d) st[d] = st[d + 1] * shape[d + 1];
+    const int nwg = int(std::max<int64_t>(1, std::min<int64_t>(CPL_MAX_WG, (N + CPL_WG - 1) / CPL_WG)));
+    DevBuf<double> part_s(size_t(nwg) * 3 + 3);
+    DevBuf<long long> part_n(size_t(nwg) * 4 + 4);
+    hipLaunchKernelGGL(axis_couplings_kernel, dim3(unsigned(nwg)), dim3(CPL_WG), 0, s, N, A.indptr.p, A.indices.p, A.data.p, st[0], st[1],
+                       st[2], part_s.p, part_n.p);
+    hipLaunchKernelGGL(axis_couplings_fold_kernel, dim3(1), dim3(CPL_WG), 0, s, nwg, part_s.p, part_n.p, part_s.p + size_t(nwg) * 3,
+                       part_n.p + size_t(nwg) * 4);
+    OMG_HIP(hipGetLastError());
+    double hs[3];
+    long long hn[4];
+    OMG_HIP(hipMemcpyAsync(hs, part_s.p + size_t(nwg) * 3, sizeof(hs), hipMemcpyDeviceToHost, s));
+    OMG_HIP(hipMemcpyAsync(hn, part_n.p + size_t(nwg) * 4, sizeof(hn), hipMemcpyDeviceToHost, s));
+    OMG_HIP(hipStreamSynchronize(s));
+    for (int a = 0; a < 3; ++a) { sums[a] = hs[a]; counts[a] = int64_t(hn[a]); }
+    counts[3] = int64_t(hn[3]);
+}
+
+// R of one restriction with factors f on the extents ext (both in C order), on the device
+void restriction_ex(int dim, const int64_t *ext, const int *f, DevMat &Rl, hipStream_t s) {
+    int64_t e[3] = {1, 1, 1};
+    int g[3] = {1, 1, 1};
+    for (int d = 0; d < dim; ++d) { e[3 - dim + d] = ext[d]; g[3 - dim + d] = f[d]; }
+    const int64_t N = e[0] * e[1] * e[2];
+    const int per = g[0] * g[1] * g[2];
+    const int64_t rows = N / per;
+    Rl.n_rows = rows; Rl.n_cols = N; Rl.nnz = N;
+    Rl.indptr.alloc(size_t(rows) + 1);
+    Rl.indices.alloc(size_t(N));
+    Rl.data.alloc(size_t(N));
+    hipLaunchKernelGGL(restriction_ex_kernel, dim3(grid1d(rows + 1)), dim3(256), 0, s, e[1], e[2], g[0], g[1], g[2], e[1] / g[1],
+                       e[2] / g[2], rows, Rl.indptr.p, Rl.indices.p, Rl.data.p);
+    OMG_HIP(hipGetLastError());
+}
+
+// A_next = (R A) R^T: the fused aggregation kernel, or the two sparse products where the operands do not qualify for it
+void galerkin_product(const DevMat &Rl, const DevMat &Al, DevMat &next, hipStream_t s) {
+    SetupTimer tm("device setup: Galerkin product of a level");
+    omg_csr_result C;
+    if (!rap_aggregation(Rl, Al, C, s)) {
+        DevMat Rt, RA;
+        device_transpose(Rl, Rt, s);
+        omg_csr_result T;
+        spgemm(Rl, Al, T, s);
+        as_devmat(std::move(T), RA);
+        spgemm(RA, Rt, C, s);
+    }
+    as_devmat(std::move(C), next);
+}
+
 // perm[slot] = natural row, inv[row] = slot of a closed-form ordering (either pointer may be null)
 __global__ void ordering_fill_kernel(int kind, int nx, int ny, int nz, int32_t *perm, int32_t *inv) {
     const int64_t n = int64_t(nx) * ny * nz;
@@ -619,18 +761,60 @@ void galerkin_chain_device(const omg_csr &A0, int dim, const int64_t *shape, int
         hipLaunchKernelGGL(restriction_kernel, dim3(grid1d(rows + 1)), dim3(256), 0, s, dim, ext[0], dim >= 2 ? ext[1] : 1, dim >= 3 ? ext[2] : 1,
                            rows, Rl.indptr.p, Rl.indices.p, Rl.data.p);
         OMG_HIP(hipGetLastError());
-        SetupTimer tm("device setup: Galerkin product of a level");
-        omg_csr_result C;
-        if (!rap_aggregation(Rl, A[size_t(l)], C, s)) {
-            DevMat Rt, RA;
-            device_transpose(Rl, Rt, s);
-            omg_csr_result T;
-            spgemm(Rl, A[size_t(l)], T, s);
-            as_devmat(std::move(T), RA);
-            spgemm(RA, Rt, C, s);
-        }
-        as_devmat(std::move(C), A[size_t(l) + 1]);
+        galerkin_product(Rl, A[size_t(l)], A[size_t(l) + 1], s);
         for (int d = 0; d < dim; ++d) ext[d] /= 2;
+    }
+}
+
+void check_factors(int dim, const int64_t *ext, const int *f, int level) {
+    bool any = false;
+    for (int d = 0; d < dim; ++d) {
+        OMG_REQUIRE(f[d] == 1 || f[d] == 2, "restriction " + std::to_string(level) + ": a coarsening factor must be 1 or 2");
+        OMG_REQUIRE(f[d] == 1 || (ext[d] >= 4 && !(ext[d] & 1)),
+                    "restriction " + std::to_string(level) + ": a factor of 2 needs an even extent >= 4, axis " + std::to_string(d) + " has " +
+                        std::to_string(ext[d]));
+        any = any || f[d] == 2;
+    }
+    OMG_REQUIRE(any, "restriction " + std::to_string(level) + ": the factors are all 1");
+}
+
+void galerkin_chain_semi_device(const omg_csr &A0, int dim, const int64_t *shape, int n_restrictions, const int *factors, int64_t min_size,
+                                std::vector<DevCsrPlain> &A, std::vector<DevCsrPlain> &R, std::vector<int> &used, hipStream_t s) {
+    OMG_REQUIRE(dim >= 2 && dim <= 3 && shape && n_restrictions >= 1, "semicoarsening: 2-D / 3-D grids, at least one restriction");
+    A.clear();
+    R.clear();
+    used.clear();
+    A.resize(1);
+    int64_t ext[3] = {1, 1, 1}, N = 1;
+    for (int d = 0; d < dim; ++d) {
+        OMG_REQUIRE(shape[d] >= 2, "semicoarsening: every extent must be >= 2");
+        ext[d] = shape[d];
+        N *= ext[d];
+    }
+    OMG_REQUIRE(N == A0.n_rows && N < INT32_MAX, "problemShape does not match the operator");
+    { SetupTimer tm("device setup: upload the fine operator"); upload(A[0], A0, s); OMG_HIP(hipStreamSynchronize(s)); }
+    for (int l = 0; l < n_restrictions; ++l) {
+        int f[3] = {1, 1, 1};
+        if (factors) {
+            for (int d = 0; d < dim; ++d) f[d] = factors[size_t(l) * dim + d];
+        } else {
+            SetupTimer tm("device setup: per-axis couplings and the coarsening rule of a level");
+            double sums[3];
+            int64_t counts[4];
+            axis_couplings(A.back(), dim, ext, sums, counts, s);
+            semicoarsen_rule(dim, ext, sums, counts, -1, l, f);
+            if (f[0] * f[1] * f[2] == 1) {
+                OMG_REQUIRE(l > 0, "semicoarsening: no axis of problemShape can be coarsened (it needs an even extent >= 4)");
+                break;
+            }
+            if (l > 0 && min_size > 0 && N / (f[0] * f[1] * f[2]) <= min_size) break;
+        }
+        check_factors(dim, ext, f, l);
+        R.emplace_back();
+        restriction_ex(dim, ext, f, R.back(), s);
+        A.emplace_back();
+        galerkin_product(R.back(), A[A.size() - 2], A.back(), s);
+        for (int d = 0; d < dim; ++d) { used.push_back(f[d]); ext[d] /= f[d]; N /= f[d]; }
     }
 }
 
@@ -740,6 +924,46 @@ int omg_restriction(int dim, const int64_t *shape, int32_t *indptr, int32_t *ind
         for (int64_t r = rows + 1; r <= n; ++r) indptr[r] = (int32_t)(rows * per);   // trailing empty rows
         *n_rows = n;
         *nnz = rows * per;
+    });
+}
+
+int omg_restriction_ex(int dim, const int64_t *shape, const int *factors, int32_t *indptr, int32_t *indices, double *data) {
+    return guarded([&] {
+        OMG_REQUIRE(shape && factors && indptr && indices && data, "null argument");
+        OMG_REQUIRE(dim >= 2 && dim <= 3, "omg_restriction_ex: 2-D / 3-D grids");
+        int64_t N = 1;
+        int per = 1;
+        for (int d = 0; d < dim; ++d) {
+            OMG_REQUIRE(shape[d] >= 2 && shape[d] < INT32_MAX, "omg_restriction_ex: every extent must be >= 2");
+            N *= shape[d];
+            OMG_REQUIRE(N < INT32_MAX, "int32 index range exceeded");
+        }
+        check_factors(dim, shape, factors, 0);
+        for (int d = 0; d < dim; ++d) per *= factors[d];
+        Stream st;
+        DevMat Rl;
+        restriction_ex(dim, shape, factors, Rl, st.s);
+        download_staged(indptr, Rl.indptr.p, size_t(N / per + 1) * sizeof(int32_t), st.s);
+        download_staged(indices, Rl.indices.p, size_t(N) * sizeof(int32_t), st.s);
+        download_staged(data, Rl.data.p, size_t(N) * sizeof(double), st.s);
+    });
+}
+
+int omg_axis_couplings(const omg_csr *A, int dim, const int64_t *shape, double *sums3, int64_t *counts4) {
+    return guarded([&] {
+        OMG_REQUIRE(A && shape && sums3 && counts4, "null argument");
+        OMG_REQUIRE(dim >= 2 && dim <= 3, "omg_axis_couplings: 2-D / 3-D grids");
+        validate_csr(*A, "A");
+        int64_t N = 1;
+        for (int d = 0; d < dim; ++d) {
+            OMG_REQUIRE(shape[d] >= 2 && shape[d] < INT32_MAX, "omg_axis_couplings: every extent must be >= 2");
+            N *= shape[d];
+            OMG_REQUIRE(N < INT32_MAX, "int32 index range exceeded");
+        }
+        Stream st;
+        DevMat dA;
+        upload(dA, *A, st.s);
+        axis_couplings(dA, dim, shape, sums3, counts4, st.s);
     });
 }
 

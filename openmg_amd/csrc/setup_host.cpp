@@ -1063,3 +1063,51 @@ extern "C" int omg_host_checksum(const void *buf, int64_t bytes, uint64_t *out) 
     return OMG_OK;
 }
 
+
+namespace omg {
+
+// The semicoarsening rule of one level, the one statement of it: the lists route (Python, through
+// omg_semicoarsen_rule) and the device route (galerkin_chain_semi_device) both call this.  shape, sums, counts and factors
+// are indexed like the grid's shape in C order (the last axis has unit stride); sums[a] = sum |a_ij| and counts[a] = number
+// of the stored entries at column offset +- stride(a), counts[3] = stored entries at any other non-zero offset.  line_axis:
+// the line smoother's axis as an index into shape, or -1.  factors all 1: no axis can be coarsened, the hierarchy ends here.
+void semicoarsen_rule(int dim, const int64_t *shape, const double *sums, const int64_t *counts, int line_axis, int level, int *factors) {
+    OMG_REQUIRE(dim >= 2 && dim <= 3 && shape && sums && counts && factors, "semicoarsening: 2-D / 3-D grids");
+    OMG_REQUIRE(line_axis >= -1 && line_axis < dim, "semicoarsening: the line axis is not an axis of the grid");
+    if (counts[3] != 0)
+        throw Error(OMG_ERR_UNSUPPORTED, "level " + std::to_string(level) + ": coarsening 'auto' needs a star stencil (5-point / 7-point) on the "
+                                         "lexicographically numbered grid, and " + std::to_string(counts[3]) + " stored entries couple a row to a "
+                                         "column off the axes (a 27-point or periodic operator): name the factors instead");
+    bool eligible[3] = {false, false, false};
+    int n_eligible = 0, n_other = 0;
+    for (int a = 0; a < dim; ++a) {
+        factors[a] = 1;
+        OMG_REQUIRE(shape[a] >= 1 && counts[a] >= 0, "semicoarsening: negative extent or count");
+        eligible[a] = shape[a] >= 4 && !(shape[a] & 1);
+        n_eligible += eligible[a];
+        n_other += eligible[a] && a != line_axis;
+    }
+    if (!n_eligible) return;
+    // the reference axis m: the eligible axis with the largest mean S / N (an axis without entries has strength 0); under a
+    // line smoother the line axis stands back whenever another axis is eligible.  No division: S_a N_m against S_m N_a.
+    int m = -1;
+    for (int a = 0; a < dim; ++a) {
+        if (!eligible[a] || (a == line_axis && n_other)) continue;
+        if (m < 0) { m = a; continue; }
+        const double lhs = counts[a] ? sums[a] * double(counts[m]) : 0.0, rhs = counts[m] ? sums[m] * double(counts[a]) : 0.0;
+        if (counts[a] && (!counts[m] || lhs > rhs)) m = a;
+    }
+    for (int a = 0; a < dim; ++a) {
+        if (!eligible[a]) continue;
+        bool take = a == m || a == line_axis;          // (the smoother already deals with the line axis: always coarsened)
+        if (!take) take = counts[a] ? (counts[m] == 0 || 2.0 * sums[a] * double(counts[m]) >= sums[m] * double(counts[a])) : counts[m] == 0;
+        factors[a] = take ? 2 : 1;
+    }
+}
+
+}  // namespace omg
+
+extern "C" int omg_semicoarsen_rule(int dim, const int64_t *shape, const double *sums3, const int64_t *counts4, int line_axis, int level,
+                                    int *factors3) {
+    return omg::guarded([&] { omg::semicoarsen_rule(dim, shape, sums3, counts4, line_axis, level, factors3); });
+}

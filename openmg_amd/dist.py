@@ -239,9 +239,11 @@ class RankSetup:
 
     `spgemm(X, Y)` does the two Galerkin products (default: the device SpGEMM)."""
 
-    def __init__(self, part, rank, A0_rows, smoother="colour", spgemm=None, overlap=True, colouring="parity"):
+    def __init__(self, part, rank, A0_rows, smoother="colour", spgemm=None, overlap=True, colouring="parity", coarsening=None):
         """colouring: 'parity' (3/5/7-point stencils) or 'octant' (9/27-point), see set_keys; it
-        must be a valid colouring of every level's operator on every rank (checked)."""
+        must be a valid colouring of every level's operator on every rank (checked).
+        coarsening: None / 'full' only (refuse_coarsening)."""
+        refuse_coarsening(coarsening)
         self.part, self.rank, self.smoother, self.overlap = part, int(rank), smoother, bool(overlap)
         self.colouring = colouring
         if spgemm is None:
@@ -351,13 +353,22 @@ class RankSetup:
                              "(colouring='parity' fits 3/5/7-point grid stencils, 'octant' 9/27-point ones)")
 
 
-def make_tail(coarse_global, shape, n_grids, smoother="colour", omega=1.0, dtype="float64"):
+def refuse_coarsening(coarsening):
+    """The multi-GPU entries coarsen every axis by two on every level (the slab partition and the restriction rows are
+    built on that): mgSolve's parameters['coarsening'] set to anything but None / 'full' raises ValueError here."""
+    if not (coarsening is None or (isinstance(coarsening, str) and coarsening == "full")):
+        raise ValueError("coarsening = %r: the multi-GPU entries take full coarsening only (None or 'full'); semicoarsening is "
+                         "single-GPU (mgSolve, Solver)" % (coarsening,))
+
+
+def make_tail(coarse_global, shape, n_grids, smoother="colour", omega=1.0, dtype="float64", coarsening=None):
     """Replicated tail: an ordinary single-GPU hierarchy over the levels BELOW the last
     distributed one.  `coarse_global` is the whole operator of that level (shape `shape`),
     `n_grids` how many grids the tail has (1 = direct solve only).  Every rank builds the same
     object; DistRank(..., coarse_global=None, tail=...) uses it as its coarse solver, so the
     small levels — pure exchange latency in a slab decomposition — need no communication."""
     from . import _hip, operators
+    refuse_coarsening(coarsening)
     shapes = [tuple(s // 2 ** l for s in shape) for l in range(n_grids)]
     R = [operators.restriction(shapes[l]) for l in range(n_grids - 1)]
     A = operators.coeffecientList(sp.csr_matrix(coarse_global), R)
@@ -370,9 +381,10 @@ def assemble_coarse(rows_per_rank):
     return G
 
 
-def build_all_ranks(part, A0_rows_of, smoother="colour", spgemm=None, overlap=True, colouring="parity"):
+def build_all_ranks(part, A0_rows_of, smoother="colour", spgemm=None, overlap=True, colouring="parity", coarsening=None):
     """In-process construction of EVERY rank (loopback groups, tests).  A0_rows_of(rank) gives
     that rank's fine rows.  Returns (levels_per_rank, coarse_global, coarse_counts)."""
+    refuse_coarsening(coarsening)
     setups = [RankSetup(part, q, A0_rows_of(q), smoother=smoother, spgemm=spgemm, overlap=overlap, colouring=colouring)
               for q in range(part.n_ranks)]
     for l in range(part.n_grids):
@@ -386,10 +398,10 @@ def build_all_ranks(part, A0_rows_of, smoother="colour", spgemm=None, overlap=Tr
 
 
 def build_this_rank(part, rank, A0_rows, all_gather, smoother="colour", spgemm=None, overlap=True,
-                    colouring="parity"):
+                    colouring="parity", coarsening=None):
     """SPMD construction: `all_gather(obj)` returns the list of every rank's obj (e.g.
     torch.distributed.all_gather_object).  Returns (levels, coarse_global, coarse_counts)."""
-    s = RankSetup(part, rank, A0_rows, smoother=smoother, spgemm=spgemm, overlap=overlap, colouring=colouring)
+    s = RankSetup(part, rank, A0_rows, smoother=smoother, spgemm=spgemm, overlap=overlap, colouring=colouring, coarsening=coarsening)
     for l in range(part.n_grids):
         halo = s.begin_level(l)
         s.finish_level(l, all_gather(halo))

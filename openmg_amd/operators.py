@@ -9,11 +9,18 @@ import scipy.sparse as sp
 from . import _hip, tools
 
 
-def restriction(shape, dense=False):
+def restriction(shape, dense=False, factors=None):
     """R of shape (N / 2**alpha, N): every coarse cell averages its 2**alpha fine cells
     (openmg/operators.py:15-89).  Index conventions follow the reference exactly, including
-    the second-axis offset shape[0] and third-axis offset shape[0]*shape[1] (Q6)."""
+    the second-axis offset shape[0] and third-axis offset shape[0]*shape[1] (Q6).
+
+    factors (not in the reference): 1 or 2 per axis of a 2-D / 3-D `shape` — the plain C-order aggregation that
+    coarsens only the axes with factor 2 (semicoarsening), weight 1 / prod(factors); ValueError for a factor other
+    than 1 or 2, all ones, or a 2 on an extent that is odd or below 4."""
     shape = tuple(int(s) for s in shape)
+    if factors is not None:
+        R = _hip.restriction_ex(shape, checkFactors(shape, factors))
+        return R.toarray() if dense else R
     alpha = len(shape)
     N = tools.product(shape)
     n = N // (2 ** alpha)
@@ -62,6 +69,100 @@ def coeffecientList(A_in, R, dense=False, verbose=False):
     if verbose:
         print("made %i A matrices" % len(levels))
     return levels
+
+
+# ---- semicoarsening (NOT in the reference): a factor of 1 or 2 per axis and restriction -------
+def checkFactors(shape, factors):
+    """One restriction's factors as a tuple of ints, checked against the extents they apply to; ValueError otherwise."""
+    shape = tuple(int(s) for s in shape)
+    try:
+        entry = tuple(factors)
+    except TypeError:
+        raise ValueError("a coarsening entry must be a tuple of one factor per axis of %s, not %r" % (shape, factors))
+    if len(entry) != len(shape) or any(isinstance(f, bool) or not isinstance(f, (int, np.integer)) or f not in (1, 2) for f in entry):
+        raise ValueError("a coarsening entry must hold a factor of 1 or 2 for each axis of %s, not %r" % (shape, factors))
+    entry = tuple(int(f) for f in entry)
+    if all(f == 1 for f in entry):
+        raise ValueError("a coarsening entry of all ones coarsens nothing: %r" % (factors,))
+    for axis, (s, f) in enumerate(zip(shape, entry)):
+        if f == 2 and (s < 4 or s % 2):
+            raise ValueError("a factor of 2 needs an even extent >= 4: axis %d of the level's grid %s has %d" % (axis, shape, s))
+    return entry
+
+
+def coarseningOf(coarsening, problemShape=None, coarsestLevel=None, minSize=None):
+    """parameters['coarsening'] checked, without any device work: None for full coarsening (None / 'full'), 'auto', or the
+    list of factor tuples that will be used — the depth rule is restrictionList's: the first restriction always, then more
+    until coarsestLevel + 1 exist or the next coarse level would have <= minSize rows; a sequence that ends before that
+    depth is reached (while an axis can still be coarsened) raises ValueError, like every other malformed value."""
+    if coarsening is None or (isinstance(coarsening, str) and coarsening == "full"):
+        return None
+    try:
+        shape = tuple(int(s) for s in problemShape)
+    except TypeError:
+        raise ValueError("parameters['coarsening'] needs a 2-D or 3-D parameters['problemShape'], not %r" % (problemShape,))
+    if len(shape) not in (2, 3) or min(shape) < 2:
+        raise ValueError("parameters['coarsening'] needs a 2-D or 3-D parameters['problemShape'] with extents >= 2, not %r" % (problemShape,))
+    if isinstance(coarsening, str):
+        if coarsening == "auto":
+            return "auto"
+        raise ValueError("parameters['coarsening'] must be None, 'full', 'auto' or a sequence of factor tuples, not %r" % (coarsening,))
+    try:
+        given = list(coarsening)
+    except TypeError:
+        raise ValueError("parameters['coarsening'] must be None, 'full', 'auto' or a sequence of factor tuples, not %r" % (coarsening,))
+    used = []
+    ext = shape
+    for k in range(int(coarsestLevel) + 1):
+        if k >= len(given):
+            if not any(s >= 4 and s % 2 == 0 for s in ext) or (k >= 1 and tools.product(ext) // 2 <= minSize):
+                break                               # (nothing left to coarsen, or whatever the factors minSize ends it here)
+            raise ValueError("parameters['coarsening'] has %d entries but restriction %d is reached (gridLevels %d, minSize %d)"
+                             % (len(given), k, int(coarsestLevel) + 1, minSize))
+        entry = checkFactors(ext, given[k])
+        coarse = tuple(s // f for s, f in zip(ext, entry))
+        if k >= 1 and tools.product(coarse) <= minSize:
+            break
+        used.append(entry)
+        ext = coarse
+    if not used:
+        raise ValueError("parameters['coarsening'] is empty")
+    return used
+
+
+def semicoarsenedLists(A_in, problemShape, coarsening, coarsestLevel, minSize, lineAxis=None):
+    """restrictionList + coeffecientList with a factor of 1 or 2 per axis and restriction: returns (R, A, factors), every
+    restriction built on the device (omg_restriction_ex), every Galerkin product too (omg_rap).  coarsening: 'auto' — per level
+    the couplings of its operator (omg_axis_couplings) go through the rule (omg_semicoarsen_rule), which ends the hierarchy
+    where no axis can be coarsened — or a sequence of factor tuples, consumed entry by entry.  The depth rule is
+    restrictionList's.  lineAxis: the line smoother's axis (an index into problemShape) for the rule, or None."""
+    shape = tuple(int(s) for s in problemShape)
+    named = coarseningOf(coarsening, shape, coarsestLevel, minSize)
+    if named is None:
+        raise ValueError("semicoarsenedLists needs coarsening 'auto' or a sequence of factor tuples; restrictionList does 'full'")
+    A = [sp.csr_matrix(A_in)]
+    if A[0].shape != (tools.product(shape),) * 2:
+        raise ValueError("problemShape %s does not match the operator's shape %s" % (shape, A[0].shape))
+    R, factors, ext = [], [], shape
+    for k in range(int(coarsestLevel) + 1):
+        if named == "auto":
+            sums, counts, off_axis = _hip.axis_couplings(A[-1], ext)
+            entry = _hip.semicoarsen_rule(ext, sums, counts, off_axis, lineAxis, level=k)
+            if all(f == 1 for f in entry):
+                if k == 0:
+                    raise ValueError("coarsening 'auto': no axis of problemShape %s can be coarsened (it needs an even extent >= 4)" % (shape,))
+                break
+            if k >= 1 and tools.product(ext) // tools.product(entry) <= minSize:
+                break
+        elif k >= len(named):
+            break
+        else:
+            entry = named[k]
+        R.append(_hip.restriction_ex(ext, entry))
+        A.append(_hip.rap(R[-1], A[-1]))
+        factors.append(entry)
+        ext = tuple(s // f for s, f in zip(ext, entry))
+    return R, A, factors
 
 
 # ---- generators (test inputs; quirks of the reference kept, SURVEY Q3) ----------------------
