@@ -443,6 +443,32 @@ int omg_hierarchy_create_from_fine_semi(const omg_csr *A_in, int dim, const int6
  * other hierarchy, or no such restriction: OMG_ERR_INVALID. */
 int omg_hierarchy_coarsening(const omg_hierarchy *h, int level, int *factors3);
 
+/* ---- Grids of any extent: an odd extent's last cell is merged (no reference counterpart) ----
+ * The entries above halve an axis only where its extent is even.  With odd = OMG_ODD_MERGE an axis of ANY extent e >= 4
+ * takes a factor 2: it gets e / 2 (rounded down) coarse cells, coarse cell i holds the fine cells 2i and 2i + 1, and the
+ * last one also holds e - 1 when e is odd (an extent of 3 would collapse to 1 and stays).  Every stored entry of R keeps
+ * the ONE weight 1 / prod(factors) — also in the rows with 3, 6, 9, 12, 18 or 27 members —, so that R^T 1 is a constant
+ * vector and a Galerkin operator keeps the constant null space of its parent (OMG_NULLSPACE_CONSTANT works unchanged).
+ * With odd = OMG_ODD_REFUSE every entry below is the entry above it is named after, bit for bit; any other value of odd:
+ * OMG_ERR_INVALID. */
+#define OMG_ODD_REFUSE 0   /* a factor 2 needs an even extent >= 4 (the entries above) */
+#define OMG_ODD_MERGE  1   /* a factor 2 needs an extent >= 4; an odd extent's last aggregate takes three cells */
+/* omg_restriction_ex with the flag.  Rows: prod(shape[d] / factors[d]) (rounded down per axis); caller-allocated
+ * indptr[rows + 1], indices[n], data[n], n = prod(shape): every fine cell is in exactly one row, members in (d0, d1, d2)
+ * order — ascending columns. */
+int omg_restriction_ragged(int dim, const int64_t *shape, const int *factors, int odd, int32_t *indptr, int32_t *indices,
+                           double *data);
+/* omg_semicoarsen_rule with the flag: under OMG_ODD_MERGE an axis is eligible when its extent is >= 4, odd or even;
+ * everything else in the rule is unchanged.  A pure host function; both setup routes call this one statement. */
+int omg_semicoarsen_rule_ragged(int dim, const int64_t *shape, const double *sums3, const int64_t *counts4, int line_axis, int level,
+                                int odd, int *factors3);
+/* omg_hierarchy_create_from_fine_semi with the flag (factors NULL = 'auto').  A level whose outgoing restriction has a
+ * three-cell aggregate runs the set-by-set row kernels, as a semicoarsened level does; the levels whose restriction is the
+ * even 2^dim aggregation qualify for the fused passes as in every hierarchy made from lists.  omg_hierarchy_coarsening
+ * reports the factors; omg_hierarchy_can_update_fine is false. */
+int omg_hierarchy_create_from_fine_ragged(const omg_csr *A_in, int dim, const int64_t *shape, int n_restrictions, const int *factors,
+                                          int64_t min_size, int odd, const omg_hierarchy_options *opt, omg_hierarchy **out);
+
 /* Host-side helper of the mgCycle binding (no reference counterpart, no device involved): mgCycle(A, b, level, R,
  * parameters, initial) — openmg/__init__.py:151 — is handed the operator lists on EVERY call; the binding keeps the
  * device hierarchy between calls and recognises the lists by a checksum of every byte (an operator edited in place

@@ -35,7 +35,7 @@ Extra keys understood in the `parameters` dict (ignored by the reference):
                 axis's; it needs a 5- / 7-point stencil: a 27-point or periodic operator raises HipError
                 (ERR_UNSUPPORTED) naming the level — name the factors for those).  A named sequence is consumed entry by
                 entry; the depth rule is unchanged ('gridLevels', then 'minSize' after the first restriction).  An
-                entry of all ones, a factor of 2 on an extent that is odd or below 4, or a sequence shorter than the
+                entry of all ones, a factor of 2 on an extent that is odd (see 'oddExtents') or below 4, or a sequence shorter than the
                 depth reached raises ValueError before any device work.  No axis ever collapses to 1.  Works with every
                 'smoother', 'accel', 'dtype', 'cycle', 'overCorrection', 'nullspace' and device arrays; single GPU.
                 Semicoarsened levels run the set-by-set row kernels (no fused passes) and a V-cycle does about twice
@@ -45,6 +45,20 @@ Extra keys understood in the `parameters` dict (ignored by the reference):
                 axis use 'line' (a point smoother then leaves a large coarsest level to the direct solve).
                 infoDict['coarsening'] (and Solver's info) lists the factor tuples used, infoDict['levelShapes'] every
                 level's grid.  Solver.update keeps the factors chosen at construction and builds a new hierarchy
+    'oddExtents'  None (default: an axis is halved only where its extent is even — the behaviour above, bit for bit) or
+                'merge': grids of ANY extent get a real hierarchy (100^3, 250^3, 300 x 150 x 75).  An axis of extent
+                e >= 4, odd or even, can take a factor 2: it gets e // 2 coarse cells, and where e is odd the last
+                aggregate along that axis holds three cells instead of two (every entry of R keeps the one weight
+                1 / prod(factors), so 'nullspace': 'constant' works unchanged).  With 'coarsening' 'auto' the rule's
+                eligibility becomes extent >= 4; named factor tuples may put a 2 on any extent >= 4 (below 4 still raises
+                ValueError); with None / 'full' every restriction takes factor 2 on each axis with extent >= 4 and 1 on
+                the others — the plain C-order aggregation, on boxes too, NOT the reference's restriction(), which is no
+                aggregation on an odd extent — to the usual depth rule, ending where no axis is eligible; on a cube
+                with extents m * 2^k these are the matrices of the default.  A level whose restriction has a merged
+                cell runs the set-by-set row kernels (no fused passes); the even levels above and below it keep theirs.
+                infoDict['coarsening'] / ['levelShapes'] report what was built.  Works with every 'smoother', 'accel',
+                'dtype', 'cycle', 'overCorrection', 'nullspace', device arrays and Solver (update keeps the factors
+                and the key); single GPU; 'dense' true or any other value raises ValueError before any device work
     'omega'     relaxation weight for 'jacobi' (default 2/3)
     'accel'     mgSolve only: None (default: plain V-cycles, the reference's loop) or 'cg': flexible preconditioned
                 conjugate gradients (FCG(1)) on the finest level with one zero-start V-cycle as the preconditioner per
@@ -338,14 +352,25 @@ def _setup(A_in, parameters, completed_from):
     return hierarchy, R, A, accel, shape, alpha
 
 
+def _odd_extents_of(parameters):
+    """parameters['oddExtents']: None or 'merge'; ValueError for anything else."""
+    value = parameters.get("oddExtents")
+    _hip.odd_code(value)
+    return value
+
+
 def _coarsening_of(parameters):
-    """parameters['coarsening'] checked (operators.coarseningOf): None for full coarsening, 'auto', or the list of factor
-    tuples the depth rule will use; ValueError for anything else — before any device work."""
+    """parameters['coarsening'] and ['oddExtents'] checked (operators.coarseningOf): None for the reference's full
+    coarsening, 'auto', or the list of factor tuples the depth rule will use (with 'oddExtents': 'merge' also for None /
+    'full'); ValueError for anything else — before any device work."""
     value = parameters.get("coarsening")
-    if value is None or (isinstance(value, str) and value == "full"):
+    odd = _odd_extents_of(parameters)
+    if odd is None and (value is None or (isinstance(value, str) and value == "full")):
         return None
+    if odd is not None and parameters.get("dense", defaults["dense"]):
+        raise ValueError("parameters['oddExtents'] works on sparse operators: parameters['dense'] must be false")
     levels = parameters.get("coarsestLevel", parameters.get("gridLevels", defaults["gridLevels"]) - 1)
-    return operators.coarseningOf(value, parameters.get("problemShape"), levels, parameters.get("minSize", defaults["minSize"]))
+    return operators.coarseningOf(value, parameters.get("problemShape"), levels, parameters.get("minSize", defaults["minSize"]), odd)
 
 
 def _setup_semicoarsened(A_in, parameters, coarsening, code, omega, nullspace):
@@ -354,8 +379,9 @@ def _setup_semicoarsened(A_in, parameters, coarsening, code, omega, nullspace):
     today, else operators.semicoarsenedLists; either way the same hierarchy."""
     problemShape = tuple(int(s) for s in parameters["problemShape"])
     dim = len(problemShape)
+    odd = _odd_extents_of(parameters)
     if parameters["dense"]:
-        raise ValueError("parameters['coarsening'] works on sparse operators: parameters['dense'] must be false")
+        raise ValueError("parameters['coarsening'] / ['oddExtents'] work on sparse operators: parameters['dense'] must be false")
     if not sp.issparse(A_in):
         A_in = sp.csr_matrix(A_in)
     if A_in.shape != (tools.product(problemShape),) * 2:
@@ -381,12 +407,12 @@ def _setup_semicoarsened(A_in, parameters, coarsening, code, omega, nullspace):
         named = None if coarsening == "auto" else coarsening
         hierarchy = _hip.Hierarchy.from_fine_semi(A_in, problemShape, levels if named is None else len(named), named,
                                                   min_size=parameters["minSize"], smoother=code, omega=omega, dtype=_dtype_of(parameters),
-                                                  nullspace=nullspace)
+                                                  nullspace=nullspace, oddExtents=odd)
     else:
         R, A, factors = operators.semicoarsenedLists(A_in, problemShape, coarsening, parameters["coarsestLevel"], parameters["minSize"],
-                                                     lineAxis=line_axis)
+                                                     lineAxis=line_axis, oddExtents=odd)
         hierarchy = _hip.Hierarchy(A, R, smoother=code, omega=omega, dtype=_dtype_of(parameters), nullspace=nullspace)
-        hierarchy._set_coarsening(problemShape, factors)
+        hierarchy._set_coarsening(problemShape, factors, odd)
     parameters["coarsestLevel"] = len(hierarchy.coarsening)
     return hierarchy, R, A
 

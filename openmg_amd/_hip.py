@@ -129,6 +129,9 @@ SIGNATURES = {
     "omg_semicoarsen_rule": (_I, [_I, _I64P, _DP, _I64P, _I, _I, _IP]),
     "omg_hierarchy_create_from_fine_semi": (_I, [_CSR, _I, _I64P, _I, _IP, ctypes.c_int64, _OPT, _PP]),
     "omg_hierarchy_coarsening": (_I, [_P, _I, _IP]),
+    "omg_restriction_ragged": (_I, [_I, _I64P, _IP, _I, _P, _P, _P]),
+    "omg_semicoarsen_rule_ragged": (_I, [_I, _I64P, _DP, _I64P, _I, _I, _I, _IP]),
+    "omg_hierarchy_create_from_fine_ragged": (_I, [_CSR, _I, _I64P, _I, _IP, ctypes.c_int64, _I, _OPT, _PP]),
     "omg_host_checksum": (_I, [_P, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint64)]),
     "omg_dist_create": (_I, [_I, _I, _I, _P, _CSR, _I64P, _I, _D, _PP]),
     "omg_dist_create_ex": (_I, [_I, _I, _I, _P, _CSR, _I64P, _I, _D, _I, _PP]),
@@ -425,11 +428,12 @@ class Hierarchy:
 
     @classmethod
     def from_fine_semi(cls, A_in, shape, n_restrictions, factors=None, min_size=0, smoother="gs", omega=1.0, dtype="float64",
-                       nullspace=None):
+                       nullspace=None, oddExtents=None):
         """mgSolve's setup with semicoarsening on the device (omg_hierarchy_create_from_fine_semi).  factors: one tuple of 1 or 2
         per axis of `shape` for each of the n_restrictions restrictions, or None = 'auto': the rule picks them level by level, at
         most n_restrictions of them, ending early where no axis can be coarsened or (after the first restriction) the coarse level
-        would have <= min_size rows.  .coarsening lists what was built, .level_shapes every level's grid."""
+        would have <= min_size rows.  .coarsening lists what was built, .level_shapes every level's grid.
+        oddExtents: None, or 'merge' — a factor 2 on any extent >= 4 (omg_hierarchy_create_from_fine_ragged)."""
         self = cls.__new__(cls)
         self._h = None
         self.nullspace_kind = nullspace_code(nullspace)
@@ -450,8 +454,8 @@ class Hierarchy:
         h = ctypes.c_void_p()
         v = csr_view(A0)
         opt = HierarchyOptions(self.smoother, self.omega, self.dtype, self.nullspace_kind)
-        check(lib().omg_hierarchy_create_from_fine_semi(ctypes.byref(v), dim, arr, n_restrictions, flat, int(min_size), ctypes.byref(opt),
-                                                        ctypes.byref(h)))
+        check(lib().omg_hierarchy_create_from_fine_ragged(ctypes.byref(v), dim, arr, n_restrictions, flat, int(min_size),
+                                                          odd_code(oddExtents), ctypes.byref(opt), ctypes.byref(h)))
         self._h = h
         self._A = self._R = None
         used = []
@@ -460,13 +464,15 @@ class Hierarchy:
             if lib().omg_hierarchy_coarsening(h, level, f3) != OMG_OK:      # (past the last restriction built)
                 break
             used.append(tuple(int(f3[d]) for d in range(dim)))
-        self._set_coarsening(shape, used)
+        self._set_coarsening(shape, used, oddExtents)
         self.n_levels = len(used) + 1
         self.sizes = [int(np.prod(s)) for s in self.level_shapes]
         return self
 
-    def _set_coarsening(self, shape, factors):
-        """Records the factors of every restriction and the grid of every level (None: not a semicoarsened hierarchy)."""
+    def _set_coarsening(self, shape, factors, oddExtents=None):
+        """Records the factors of every restriction and the grid of every level (None: not a semicoarsened hierarchy), and
+        the 'oddExtents' key they were chosen under (an odd extent halves to its floor)."""
+        self.odd_extents = None if factors is None else oddExtents
         self.coarsening = None if factors is None else [tuple(int(f) for f in entry) for entry in factors]
         self.level_shapes = None
         if factors is not None:
@@ -476,6 +482,7 @@ class Hierarchy:
 
     coarsening = None          # [(factor per axis), ...] per restriction of a semicoarsened hierarchy, else None
     level_shapes = None        # [(extent per axis), ...] per level of a semicoarsened hierarchy, else None
+    odd_extents = None         # 'merge' where the factors were chosen with parameters['oddExtents'] = 'merge', else None
 
     def update_fine(self, data, on_device=False):
         """New values for the fine operator, same pattern (omg_hierarchy_update_fine).  data: the CSR's value array as a
@@ -894,21 +901,35 @@ def restriction(shape):
     return sp.csr_matrix((data[:k], indices[:k], indptr[:nr.value + 1]), shape=(nr.value, N))
 
 
-def restriction_ex(shape, factors):
+ODD_REFUSE, ODD_MERGE = 0, 1
+
+
+def odd_code(oddExtents):
+    """OMG_ODD_* of parameters['oddExtents']: None or 'merge'; ValueError for anything else."""
+    if oddExtents is None:
+        return ODD_REFUSE
+    if isinstance(oddExtents, str) and oddExtents == "merge":
+        return ODD_MERGE
+    raise ValueError("parameters['oddExtents'] must be None or 'merge', not %r" % (oddExtents,))
+
+
+def restriction_ex(shape, factors, oddExtents=None):
     """The plain C-order aggregation of the grid `shape` by `factors` (1 or 2 per axis) built on the device -> scipy CSR
-    (omg_restriction_ex); HipError (ERR_INVALID) for factors it does not take."""
+    (omg_restriction_ragged); HipError (ERR_INVALID) for factors it does not take.  oddExtents 'merge': a 2 on any extent
+    >= 4, an odd extent's last aggregate takes three cells; every entry keeps the weight 1 / prod(factors)."""
+    odd = odd_code(oddExtents)
     shape = tuple(int(s) for s in shape)
     factors = tuple(int(f) for f in factors)
     dim = len(shape)
     if len(factors) != dim:
         raise ValueError("need one factor per axis of the shape %s, not %r" % (shape, factors))
     N = int(np.prod(shape))
-    n = N // max(int(np.prod(factors)), 1) if all(f > 0 for f in factors) else 0
+    n = int(np.prod([s // f for s, f in zip(shape, factors)])) if all(f > 0 for f in factors) else 0
     indptr = np.empty(n + 1, dtype=np.int32)
     indices = np.empty(max(N, 1), dtype=np.int32)
     data = np.empty(max(N, 1), dtype=np.float64)
-    check(lib().omg_restriction_ex(dim, (ctypes.c_int64 * dim)(*shape), (ctypes.c_int * dim)(*factors), indptr.ctypes.data,
-                                   indices.ctypes.data, data.ctypes.data))
+    check(lib().omg_restriction_ragged(dim, (ctypes.c_int64 * dim)(*shape), (ctypes.c_int * dim)(*factors), odd, indptr.ctypes.data,
+                                       indices.ctypes.data, data.ctypes.data))
     R = sp.csr_matrix((data[:N], indices[:N], indptr), shape=(n, N))
     R.has_sorted_indices = True
     return R
@@ -927,13 +948,16 @@ def axis_couplings(A, shape):
     return tuple(float(sums[a]) for a in range(dim)), tuple(int(counts[a]) for a in range(dim)), int(counts[3])
 
 
-def semicoarsen_rule(shape, sums, counts, off_axis=0, line_axis=None, level=0):
-    """The factors (1 or 2 per axis of `shape`) the 'auto' rule picks for one level from its couplings (omg_semicoarsen_rule, a
-    host function: no device).  All ones: no axis can be coarsened.  HipError (ERR_UNSUPPORTED) when off_axis != 0."""
+def semicoarsen_rule(shape, sums, counts, off_axis=0, line_axis=None, level=0, oddExtents=None):
+    """The factors (1 or 2 per axis of `shape`) the 'auto' rule picks for one level from its couplings
+    (omg_semicoarsen_rule_ragged, a host function: no device).  All ones: no axis can be coarsened.  HipError
+    (ERR_UNSUPPORTED) when off_axis != 0.  oddExtents 'merge': an axis is eligible when its extent is >= 4, odd or even."""
+    odd = odd_code(oddExtents)
     shape = tuple(int(s) for s in shape)
     dim = len(shape)
     s3 = (ctypes.c_double * 3)(*([float(x) for x in sums] + [0.0] * (3 - dim)))
     c4 = (ctypes.c_int64 * 4)(*([int(x) for x in counts] + [0] * (3 - dim) + [int(off_axis)]))
     f3 = (ctypes.c_int * 3)()
-    check(lib().omg_semicoarsen_rule(dim, (ctypes.c_int64 * dim)(*shape), s3, c4, -1 if line_axis is None else int(line_axis), int(level), f3))
+    check(lib().omg_semicoarsen_rule_ragged(dim, (ctypes.c_int64 * dim)(*shape), s3, c4, -1 if line_axis is None else int(line_axis),
+                                            int(level), odd, f3))
     return tuple(int(f3[d]) for d in range(dim))

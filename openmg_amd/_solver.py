@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _devarray, _hip
 
-# the keys a solve may override: those that do not define the hierarchy ('smoother', 'lineAxis', 'coarsening', 'dtype', 'nullspace',
+# the keys a solve may override: those that do not define the hierarchy ('smoother', 'lineAxis', 'coarsening', 'oddExtents', 'dtype', 'nullspace',
 # the grids do, and are refused)
 SOLVE_KEYS = ("cycles", "threshold", "rtol", "preIterations", "postIterations", "accel", "cycle", "overCorrection")
 
@@ -228,7 +228,8 @@ class Solver:
         is update_fine; otherwise a new hierarchy is built first and the old one closed after that succeeded.  Either
         way later solves have the bits of a fresh Solver(A_new, parameters).  With parameters['coarsening'] the new
         hierarchy is built with the FACTORS CHOSEN AT CONSTRUCTION ('auto' is not asked again: sizes and patterns cannot
-        change under the caller), always as a new hierarchy: a semicoarsened one takes no update in place."""
+        change under the caller), always as a new hierarchy: a semicoarsened one takes no update in place.  The same holds
+        with parameters['oddExtents'] = 'merge': the factors and the key are kept, the hierarchy is built anew."""
         from . import _setup, defaults
         h = self._open()
         A1 = _hip.as_csr(A_new)

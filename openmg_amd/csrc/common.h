@@ -832,12 +832,17 @@ void galerkin_chain_device(const omg_csr &A0, int dim, const int64_t *shape, int
 // ends the chain where no axis can be coarsened, and after the first restriction where the coarse level would have
 // <= min_size rows (min_size <= 0: no such rule); named factors are all used.  used: what was built, dim entries per
 // restriction; A.size() == R.size() + 1 == used.size() / dim + 1.  (setup_device.hip)
+// odd (OMG_ODD_REFUSE / OMG_ODD_MERGE): under MERGE a factor 2 is taken on any extent >= 4 and an odd
+// extent's last aggregate holds three cells along that axis; the coarse extent is e / f rounded down either way.
 void galerkin_chain_semi_device(const omg_csr &A0, int dim, const int64_t *shape, int n_restrictions, const int *factors, int64_t min_size,
-                                std::vector<DevCsrPlain> &A, std::vector<DevCsrPlain> &R, std::vector<int> &used, hipStream_t s);
+                                int odd, std::vector<DevCsrPlain> &A, std::vector<DevCsrPlain> &R, std::vector<int> &used, hipStream_t s);
 // (setup_host.cpp) the rule of one level; factors all 1: no axis can be coarsened
-void semicoarsen_rule(int dim, const int64_t *shape, const double *sums, const int64_t *counts, int line_axis, int level, int *factors);
-// a factor tuple of one restriction against the extents it is applied to: 1 or 2 per axis, not all 1, 2 only on an even extent >= 4
-void check_factors(int dim, const int64_t *ext, const int *f, int level);
+void semicoarsen_rule(int dim, const int64_t *shape, const double *sums, const int64_t *counts, int line_axis, int level, int odd,
+                      int *factors);
+// may an axis of extent e take a factor 2: e >= 4, and even unless odd extents are merged (the one statement of it)
+inline bool axis_can_halve(int64_t e, int odd) { return e >= 4 && (odd == OMG_ODD_MERGE || !(e & 1)); }
+// a factor tuple of one restriction against the extents it is applied to: 1 or 2 per axis, not all 1, 2 only where axis_can_halve
+void check_factors(int dim, const int64_t *ext, const int *f, int odd, int level);
 HostCsr download_csr(const DevCsrPlain &M, hipStream_t s);
 // C = (R A) R^T for an aggregation R (every column of R owned by exactly one row) by the fused kernel, SciPy's
 // accumulation order, ascending columns; false: the operands do not qualify (setup_device.hip)

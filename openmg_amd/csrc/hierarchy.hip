@@ -1816,10 +1816,11 @@ std::unique_ptr<Hier<V>> create_from_fine(const omg_csr &A0, int dim, const int6
 // (galerkin_chain_semi_device), fetched once and handed to create(): a level whose restriction is not the full 2^dim
 // aggregation runs the set-by-set row kernels (the fused passes bake that aggregate into their LDS images), a level further
 // down whose restriction is full again qualifies for them there as in every hierarchy made from lists.  The result is the
-// object create() makes from the same lists.
+// object create() makes from the same lists.  odd = OMG_ODD_MERGE: a restriction with a three-cell
+// aggregate is one more restriction that is not the 2^dim aggregation — its level fails every fused plan's check of R.
 template <typename V>
 std::unique_ptr<Hier<V>> create_from_fine_semi(const omg_csr &A0, int dim, const int64_t *shape, int n_restrictions, const int *factors,
-                                               int64_t min_size, int smoother, double omega, int nullspace, std::vector<int> &used) {
+                                               int64_t min_size, int odd, int smoother, double omega, int nullspace, std::vector<int> &used) {
     refuse_line_smoother(smoother, "omg_hierarchy_create_from_fine_semi");
     OMG_REQUIRE(smoother >= OMG_SMOOTH_GS_LEX && smoother <= OMG_SMOOTH_JACOBI, "unknown smoother");
     validate_csr(A0, "A_in");
@@ -1831,7 +1832,7 @@ std::unique_ptr<Hier<V>> create_from_fine_semi(const omg_csr &A0, int dim, const
         OMG_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
         try {
             std::vector<DevCsrPlain> dA, dR;
-            galerkin_chain_semi_device(A0, dim, shape, n_restrictions, factors, min_size, dA, dR, used, s);
+            galerkin_chain_semi_device(A0, dim, shape, n_restrictions, factors, min_size, odd, dA, dR, used, s);
             SetupTimer tm("device setup: semicoarsened operators fetched, ordinary route");
             // (level 0 is the caller's own operator: not fetched)
             for (size_t l = 1; l < dA.size(); ++l) hA.push_back(download_csr(dA[l], s));
@@ -2624,19 +2625,25 @@ int omg_hierarchy_create_from_fine(const omg_csr *A_in, int dim, const int64_t *
 
 int omg_hierarchy_create_from_fine_semi(const omg_csr *A_in, int dim, const int64_t *shape, int n_restrictions, const int *factors,
                                         int64_t min_size, const omg_hierarchy_options *opt, omg_hierarchy **out) {
+    return omg_hierarchy_create_from_fine_ragged(A_in, dim, shape, n_restrictions, factors, min_size, OMG_ODD_REFUSE, opt, out);
+}
+
+int omg_hierarchy_create_from_fine_ragged(const omg_csr *A_in, int dim, const int64_t *shape, int n_restrictions, const int *factors,
+                                          int64_t min_size, int odd, const omg_hierarchy_options *opt, omg_hierarchy **out) {
     return guarded([&] {
         OMG_REQUIRE(out && A_in, "null argument");
         *out = nullptr;
         OMG_REQUIRE(opt, "options are null");
+        OMG_REQUIRE(odd == OMG_ODD_REFUSE || odd == OMG_ODD_MERGE, "odd must be OMG_ODD_REFUSE or OMG_ODD_MERGE");
         const int dtype = opt->dtype;
         OMG_REQUIRE(dtype == OMG_DTYPE_F64 || dtype == OMG_DTYPE_F32 || dtype == OMG_DTYPE_MIXED, "unknown dtype");
         OMG_REQUIRE(opt->nullspace == OMG_NULLSPACE_NONE || opt->nullspace == OMG_NULLSPACE_CONSTANT, "unknown nullspace kind");
         std::unique_ptr<omg_hierarchy> h(new omg_hierarchy);
         h->semi_dim = dim;
         if (dtype != OMG_DTYPE_F64)
-            h->f = create_from_fine_semi<float>(*A_in, dim, shape, n_restrictions, factors, min_size, opt->smoother, opt->omega, opt->nullspace, h->semi_factors);
+            h->f = create_from_fine_semi<float>(*A_in, dim, shape, n_restrictions, factors, min_size, odd, opt->smoother, opt->omega, opt->nullspace, h->semi_factors);
         else
-            h->d = create_from_fine_semi<double>(*A_in, dim, shape, n_restrictions, factors, min_size, opt->smoother, opt->omega, opt->nullspace, h->semi_factors);
+            h->d = create_from_fine_semi<double>(*A_in, dim, shape, n_restrictions, factors, min_size, odd, opt->smoother, opt->omega, opt->nullspace, h->semi_factors);
         if (dtype == OMG_DTYPE_MIXED) build_mixed(h->f.get(), *A_in);
         *out = h.release();
     });

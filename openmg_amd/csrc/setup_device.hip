@@ -355,13 +355,21 @@ __global__ __launch_bounds__(RAP_WAVES * 64) void rap_aggregation_kernel(
         const int total = __shfl(inc, 63, 64);                      // <= CAP / 2 (host check)
         const int start = inc - len;
         const int rows_here = min(64, nk - done);
-        for (int e = lane; e < total; e += 64) {
+        // (the whole wave takes every round of 64 entries, the lanes past the end with the last entry and without the stores:
+        // a shuffle reads nothing from a lane that has left the loop, and lane q < rows_here holds row q — with 64 < total
+        // < 64 + rows_here, which an aggregate of 12 or 18 boundary rows has and one of 8 never had, it would have left)
+        for (int e0 = 0; e0 < total; e0 += 64) {
+            const bool live = e0 + lane < total;
+            const int e = live ? e0 + lane : total - 1;
             // the row this entry belongs to: the last one whose start is <= e
             int row = 0;
             for (int q = 1; q < rows_here; ++q) row = __shfl(start, q, 64) <= e ? q : row;
             const int32_t p = __shfl(beg, row, 64) + (e - __shfl(start, row, 64));
-            ent_j[e] = ai[p];
-            ent_p[e] = __dmul_rn(__shfl(r, row, 64), av[p]);         // no FMA contraction: SciPy's order and rounding
+            const double rq = __shfl(r, row, 64);
+            if (live) {
+                ent_j[e] = ai[p];
+                ent_p[e] = __dmul_rn(rq, av[p]);                     // no FMA contraction: SciPy's order and rounding
+            }
         }
         __builtin_amdgcn_wave_barrier();
         for (int q = 0; q < rows_here; ++q) {                        // the additions, one row of the aggregate after the other
@@ -550,6 +558,8 @@ __global__ void restriction_kernel(int dim, int64_t s0, int64_t s1, int64_t s2, 
 // The plain C-order aggregation of an e0 x e1 x e2 grid (axis 2 has unit stride; a 2-D grid has e0 = 1) by factors f0, f1,
 // f2: row r <-> the r-th coarse cell in C order over e / f, its f0 f1 f2 members in (d0, d1, d2) order — ascending
 // columns —, one weight 1 / (f0 f1 f2).  A thread per coarse row; rows * per = e0 e1 e2 entries.
+// (Every extent a multiple of its factor.  restriction_ragged_kernel below builds the same matrix on such a grid; this one
+// stays as the kernel of the entries without the odd-extent flag.)
 __global__ void restriction_ex_kernel(int64_t e1, int64_t e2, int f0, int f1, int f2, int64_t c1, int64_t c2, int64_t rows,
                                       int32_t *indptr, int32_t *indices, double *data) {
     const int per = f0 * f1 * f2;
@@ -565,6 +575,39 @@ __global__ void restriction_ex_kernel(int64_t e1, int64_t e2, int f0, int f1, in
                 for (int d2 = 0; d2 < f2; ++d2, ++m) {
                     indices[r * per + m] = (int32_t)(first + (int64_t(d0) * e1 + d1) * e2 + d2);
                     data[r * per + m] = w;
+                }
+    }
+}
+
+// ---- grids of any extent: an odd extent's last cell is merged ----------------------------------------------
+// The same aggregation on an e0 x e1 x e2 grid whose coarsened extents may be odd: c_a = e_a / f_a coarse cells along axis
+// a (rounded down), coarse index i holds the fine cells f_a i .. f_a i + m_a(i) - 1 with m_a(i) = f_a, and the LAST one
+// (i = c_a - 1) the remainder e_a - f_a c_a (0 or 1) as well: 1, 2 or 3 members along an axis, 1 .. 27 in a row, all with
+// the one weight 1 / (f0 f1 f2).  Rows are no longer equally long, but their starts are a closed form (no scan): the rows
+// before (i0, i1, i2) cover the f0 i0 fine planes below it whole, then inside its own m0 planes the f1 i1 lines below it,
+// then inside its m0 m1 lines the f2 i2 cells before it:
+//     start(i0, i1, i2) = f0 i0 e1 e2 + m0 (f1 i1 e2 + m1 f2 i2),      nnz = e0 e1 e2.
+// A thread per coarse row (thread `rows` writes the closing pointer); members in (d0, d1, d2) order — ascending columns.
+// Every index written is < e0 e1 e2 (< 2^31, host check): f_a i + d < f_a c_a + (e_a - f_a c_a) = e_a along every axis.
+__global__ void restriction_ragged_kernel(int64_t e0, int64_t e1, int64_t e2, int f0, int f1, int f2, int64_t c0, int64_t c1, int64_t c2,
+                                          int32_t *indptr, int32_t *indices, double *data) {
+    const int64_t rows = c0 * c1 * c2;
+    const double w = 1.0 / double(f0 * f1 * f2);
+    for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r <= rows; r += (int64_t)gridDim.x * blockDim.x) {
+        if (r == rows) { indptr[r] = (int32_t)(e0 * e1 * e2); break; }
+        const int64_t i0 = r / (c1 * c2), rem = r % (c1 * c2), i1 = rem / c2, i2 = rem % c2;
+        const int m0 = f0 + (i0 == c0 - 1 ? int(e0 - f0 * c0) : 0);
+        const int m1 = f1 + (i1 == c1 - 1 ? int(e1 - f1 * c1) : 0);
+        const int m2 = f2 + (i2 == c2 - 1 ? int(e2 - f2 * c2) : 0);
+        const int64_t start = f0 * i0 * e1 * e2 + m0 * (f1 * i1 * e2 + m1 * (f2 * i2));
+        const int64_t first = ((f0 * i0) * e1 + f1 * i1) * e2 + f2 * i2;
+        indptr[r] = (int32_t)start;
+        int m = 0;
+        for (int d0 = 0; d0 < m0; ++d0)
+            for (int d1 = 0; d1 < m1; ++d1)
+                for (int d2 = 0; d2 < m2; ++d2, ++m) {
+                    indices[start + m] = (int32_t)(first + (int64_t(d0) * e1 + d1) * e2 + d2);
+                    data[start + m] = w;
                 }
     }
 }
@@ -657,19 +700,24 @@ void axis_couplings(const DevMat &A, int dim, const int64_t *shape, double *sums
 }
 
 // R of one restriction with factors f on the extents ext (both in C order), on the device
-void restriction_ex(int dim, const int64_t *ext, const int *f, DevMat &Rl, hipStream_t s) {
+// (the factors have passed check_factors with the same `odd`: under OMG_ODD_REFUSE every coarsened extent is even)
+void restriction_ex(int dim, const int64_t *ext, const int *f, int odd, DevMat &Rl, hipStream_t s) {
     int64_t e[3] = {1, 1, 1};
     int g[3] = {1, 1, 1};
     for (int d = 0; d < dim; ++d) { e[3 - dim + d] = ext[d]; g[3 - dim + d] = f[d]; }
     const int64_t N = e[0] * e[1] * e[2];
-    const int per = g[0] * g[1] * g[2];
-    const int64_t rows = N / per;
+    const int64_t c[3] = {e[0] / g[0], e[1] / g[1], e[2] / g[2]};
+    const int64_t rows = c[0] * c[1] * c[2];
     Rl.n_rows = rows; Rl.n_cols = N; Rl.nnz = N;
     Rl.indptr.alloc(size_t(rows) + 1);
     Rl.indices.alloc(size_t(N));
     Rl.data.alloc(size_t(N));
-    hipLaunchKernelGGL(restriction_ex_kernel, dim3(grid1d(rows + 1)), dim3(256), 0, s, e[1], e[2], g[0], g[1], g[2], e[1] / g[1],
-                       e[2] / g[2], rows, Rl.indptr.p, Rl.indices.p, Rl.data.p);
+    if (odd == OMG_ODD_MERGE)
+        hipLaunchKernelGGL(restriction_ragged_kernel, dim3(grid1d(rows + 1)), dim3(256), 0, s, e[0], e[1], e[2], g[0], g[1], g[2], c[0], c[1],
+                           c[2], Rl.indptr.p, Rl.indices.p, Rl.data.p);
+    else
+        hipLaunchKernelGGL(restriction_ex_kernel, dim3(grid1d(rows + 1)), dim3(256), 0, s, e[1], e[2], g[0], g[1], g[2], c[1], c[2], rows,
+                           Rl.indptr.p, Rl.indices.p, Rl.data.p);
     OMG_HIP(hipGetLastError());
 }
 
@@ -766,21 +814,23 @@ void galerkin_chain_device(const omg_csr &A0, int dim, const int64_t *shape, int
     }
 }
 
-void check_factors(int dim, const int64_t *ext, const int *f, int level) {
+void check_factors(int dim, const int64_t *ext, const int *f, int odd, int level) {
+    OMG_REQUIRE(odd == OMG_ODD_REFUSE || odd == OMG_ODD_MERGE, "odd must be OMG_ODD_REFUSE or OMG_ODD_MERGE");
     bool any = false;
     for (int d = 0; d < dim; ++d) {
         OMG_REQUIRE(f[d] == 1 || f[d] == 2, "restriction " + std::to_string(level) + ": a coarsening factor must be 1 or 2");
-        OMG_REQUIRE(f[d] == 1 || (ext[d] >= 4 && !(ext[d] & 1)),
-                    "restriction " + std::to_string(level) + ": a factor of 2 needs an even extent >= 4, axis " + std::to_string(d) + " has " +
-                        std::to_string(ext[d]));
+        OMG_REQUIRE(f[d] == 1 || axis_can_halve(ext[d], odd),
+                    "restriction " + std::to_string(level) + ": a factor of 2 needs an " + (odd == OMG_ODD_MERGE ? "" : "even ") +
+                        "extent >= 4, axis " + std::to_string(d) + " has " + std::to_string(ext[d]));
         any = any || f[d] == 2;
     }
     OMG_REQUIRE(any, "restriction " + std::to_string(level) + ": the factors are all 1");
 }
 
 void galerkin_chain_semi_device(const omg_csr &A0, int dim, const int64_t *shape, int n_restrictions, const int *factors, int64_t min_size,
-                                std::vector<DevCsrPlain> &A, std::vector<DevCsrPlain> &R, std::vector<int> &used, hipStream_t s) {
+                                int odd, std::vector<DevCsrPlain> &A, std::vector<DevCsrPlain> &R, std::vector<int> &used, hipStream_t s) {
     OMG_REQUIRE(dim >= 2 && dim <= 3 && shape && n_restrictions >= 1, "semicoarsening: 2-D / 3-D grids, at least one restriction");
+    OMG_REQUIRE(odd == OMG_ODD_REFUSE || odd == OMG_ODD_MERGE, "odd must be OMG_ODD_REFUSE or OMG_ODD_MERGE");
     A.clear();
     R.clear();
     used.clear();
@@ -802,19 +852,24 @@ void galerkin_chain_semi_device(const omg_csr &A0, int dim, const int64_t *shape
             double sums[3];
             int64_t counts[4];
             axis_couplings(A.back(), dim, ext, sums, counts, s);
-            semicoarsen_rule(dim, ext, sums, counts, -1, l, f);
+            semicoarsen_rule(dim, ext, sums, counts, -1, l, odd, f);
             if (f[0] * f[1] * f[2] == 1) {
-                OMG_REQUIRE(l > 0, "semicoarsening: no axis of problemShape can be coarsened (it needs an even extent >= 4)");
+                OMG_REQUIRE(l > 0, odd == OMG_ODD_MERGE ? "semicoarsening: no axis of problemShape can be coarsened (it needs an extent >= 4)"
+                                                        : "semicoarsening: no axis of problemShape can be coarsened (it needs an even extent >= 4)");
                 break;
             }
-            if (l > 0 && min_size > 0 && N / (f[0] * f[1] * f[2]) <= min_size) break;
+            // (the coarse level's rows: the product of the coarse extents, each rounded down)
+            int64_t coarse = 1;
+            for (int d = 0; d < dim; ++d) coarse *= ext[d] / f[d];
+            if (l > 0 && min_size > 0 && coarse <= min_size) break;
         }
-        check_factors(dim, ext, f, l);
+        check_factors(dim, ext, f, odd, l);
         R.emplace_back();
-        restriction_ex(dim, ext, f, R.back(), s);
+        restriction_ex(dim, ext, f, odd, R.back(), s);
         A.emplace_back();
         galerkin_product(R.back(), A[A.size() - 2], A.back(), s);
-        for (int d = 0; d < dim; ++d) { used.push_back(f[d]); ext[d] /= f[d]; N /= f[d]; }
+        N = 1;
+        for (int d = 0; d < dim; ++d) { used.push_back(f[d]); ext[d] /= f[d]; N *= ext[d]; }
     }
 }
 
@@ -927,26 +982,28 @@ int omg_restriction(int dim, const int64_t *shape, int32_t *indptr, int32_t *ind
     });
 }
 
-int omg_restriction_ex(int dim, const int64_t *shape, const int *factors, int32_t *indptr, int32_t *indices, double *data) {
+int omg_restriction_ragged(int dim, const int64_t *shape, const int *factors, int odd, int32_t *indptr, int32_t *indices, double *data) {
     return guarded([&] {
         OMG_REQUIRE(shape && factors && indptr && indices && data, "null argument");
         OMG_REQUIRE(dim >= 2 && dim <= 3, "omg_restriction_ex: 2-D / 3-D grids");
         int64_t N = 1;
-        int per = 1;
         for (int d = 0; d < dim; ++d) {
             OMG_REQUIRE(shape[d] >= 2 && shape[d] < INT32_MAX, "omg_restriction_ex: every extent must be >= 2");
             N *= shape[d];
             OMG_REQUIRE(N < INT32_MAX, "int32 index range exceeded");
         }
-        check_factors(dim, shape, factors, 0);
-        for (int d = 0; d < dim; ++d) per *= factors[d];
+        check_factors(dim, shape, factors, odd, 0);
         Stream st;
         DevMat Rl;
-        restriction_ex(dim, shape, factors, Rl, st.s);
-        download_staged(indptr, Rl.indptr.p, size_t(N / per + 1) * sizeof(int32_t), st.s);
+        restriction_ex(dim, shape, factors, odd, Rl, st.s);
+        download_staged(indptr, Rl.indptr.p, size_t(Rl.n_rows + 1) * sizeof(int32_t), st.s);
         download_staged(indices, Rl.indices.p, size_t(N) * sizeof(int32_t), st.s);
         download_staged(data, Rl.data.p, size_t(N) * sizeof(double), st.s);
     });
+}
+
+int omg_restriction_ex(int dim, const int64_t *shape, const int *factors, int32_t *indptr, int32_t *indices, double *data) {
+    return omg_restriction_ragged(dim, shape, factors, OMG_ODD_REFUSE, indptr, indices, data);
 }
 
 int omg_axis_couplings(const omg_csr *A, int dim, const int64_t *shape, double *sums3, int64_t *counts4) {

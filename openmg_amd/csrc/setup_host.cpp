@@ -1071,7 +1071,10 @@ namespace omg {
 // are indexed like the grid's shape in C order (the last axis has unit stride); sums[a] = sum |a_ij| and counts[a] = number
 // of the stored entries at column offset +- stride(a), counts[3] = stored entries at any other non-zero offset.  line_axis:
 // the line smoother's axis as an index into shape, or -1.  factors all 1: no axis can be coarsened, the hierarchy ends here.
-void semicoarsen_rule(int dim, const int64_t *shape, const double *sums, const int64_t *counts, int line_axis, int level, int *factors) {
+// odd: OMG_ODD_REFUSE — an axis is eligible when its extent is even and >= 4 — or OMG_ODD_MERGE — when it is >= 4 (§5p).
+void semicoarsen_rule(int dim, const int64_t *shape, const double *sums, const int64_t *counts, int line_axis, int level, int odd,
+                      int *factors) {
+    OMG_REQUIRE(odd == OMG_ODD_REFUSE || odd == OMG_ODD_MERGE, "semicoarsening: odd must be OMG_ODD_REFUSE or OMG_ODD_MERGE");
     OMG_REQUIRE(dim >= 2 && dim <= 3 && shape && sums && counts && factors, "semicoarsening: 2-D / 3-D grids");
     OMG_REQUIRE(line_axis >= -1 && line_axis < dim, "semicoarsening: the line axis is not an axis of the grid");
     if (counts[3] != 0)
@@ -1083,7 +1086,7 @@ void semicoarsen_rule(int dim, const int64_t *shape, const double *sums, const i
     for (int a = 0; a < dim; ++a) {
         factors[a] = 1;
         OMG_REQUIRE(shape[a] >= 1 && counts[a] >= 0, "semicoarsening: negative extent or count");
-        eligible[a] = shape[a] >= 4 && !(shape[a] & 1);
+        eligible[a] = axis_can_halve(shape[a], odd);
         n_eligible += eligible[a];
         n_other += eligible[a] && a != line_axis;
     }
@@ -1107,7 +1110,12 @@ void semicoarsen_rule(int dim, const int64_t *shape, const double *sums, const i
 
 }  // namespace omg
 
+extern "C" int omg_semicoarsen_rule_ragged(int dim, const int64_t *shape, const double *sums3, const int64_t *counts4, int line_axis,
+                                           int level, int odd, int *factors3) {
+    return omg::guarded([&] { omg::semicoarsen_rule(dim, shape, sums3, counts4, line_axis, level, odd, factors3); });
+}
+
 extern "C" int omg_semicoarsen_rule(int dim, const int64_t *shape, const double *sums3, const int64_t *counts4, int line_axis, int level,
                                     int *factors3) {
-    return omg::guarded([&] { omg::semicoarsen_rule(dim, shape, sums3, counts4, line_axis, level, factors3); });
+    return omg_semicoarsen_rule_ragged(dim, shape, sums3, counts4, line_axis, level, OMG_ODD_REFUSE, factors3);
 }

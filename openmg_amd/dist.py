@@ -239,11 +239,13 @@ class RankSetup:
 
     `spgemm(X, Y)` does the two Galerkin products (default: the device SpGEMM)."""
 
-    def __init__(self, part, rank, A0_rows, smoother="colour", spgemm=None, overlap=True, colouring="parity", coarsening=None):
+    def __init__(self, part, rank, A0_rows, smoother="colour", spgemm=None, overlap=True, colouring="parity", coarsening=None,
+                 oddExtents=None):
         """colouring: 'parity' (3/5/7-point stencils) or 'octant' (9/27-point), see set_keys; it
         must be a valid colouring of every level's operator on every rank (checked).
-        coarsening: None / 'full' only (refuse_coarsening)."""
+        coarsening: None / 'full' only (refuse_coarsening); oddExtents: None only (refuse_odd_extents)."""
         refuse_coarsening(coarsening)
+        refuse_odd_extents(oddExtents)
         self.part, self.rank, self.smoother, self.overlap = part, int(rank), smoother, bool(overlap)
         self.colouring = colouring
         if spgemm is None:
@@ -361,7 +363,15 @@ def refuse_coarsening(coarsening):
                          "single-GPU (mgSolve, Solver)" % (coarsening,))
 
 
-def make_tail(coarse_global, shape, n_grids, smoother="colour", omega=1.0, dtype="float64", coarsening=None):
+def refuse_odd_extents(oddExtents):
+    """refuse_coarsening's sibling for parameters['oddExtents']: the slab partition cuts on two-cell aggregate boundaries,
+    so the multi-GPU entries take None only; anything else raises ValueError here."""
+    if oddExtents is not None:
+        raise ValueError("oddExtents = %r: the multi-GPU entries halve even extents only (oddExtents None); merging an odd "
+                         "extent's last cell is single-GPU (mgSolve, Solver)" % (oddExtents,))
+
+
+def make_tail(coarse_global, shape, n_grids, smoother="colour", omega=1.0, dtype="float64", coarsening=None, oddExtents=None):
     """Replicated tail: an ordinary single-GPU hierarchy over the levels BELOW the last
     distributed one.  `coarse_global` is the whole operator of that level (shape `shape`),
     `n_grids` how many grids the tail has (1 = direct solve only).  Every rank builds the same
@@ -369,6 +379,7 @@ def make_tail(coarse_global, shape, n_grids, smoother="colour", omega=1.0, dtype
     small levels — pure exchange latency in a slab decomposition — need no communication."""
     from . import _hip, operators
     refuse_coarsening(coarsening)
+    refuse_odd_extents(oddExtents)
     shapes = [tuple(s // 2 ** l for s in shape) for l in range(n_grids)]
     R = [operators.restriction(shapes[l]) for l in range(n_grids - 1)]
     A = operators.coeffecientList(sp.csr_matrix(coarse_global), R)
@@ -381,10 +392,12 @@ def assemble_coarse(rows_per_rank):
     return G
 
 
-def build_all_ranks(part, A0_rows_of, smoother="colour", spgemm=None, overlap=True, colouring="parity", coarsening=None):
+def build_all_ranks(part, A0_rows_of, smoother="colour", spgemm=None, overlap=True, colouring="parity", coarsening=None,
+                    oddExtents=None):
     """In-process construction of EVERY rank (loopback groups, tests).  A0_rows_of(rank) gives
     that rank's fine rows.  Returns (levels_per_rank, coarse_global, coarse_counts)."""
     refuse_coarsening(coarsening)
+    refuse_odd_extents(oddExtents)
     setups = [RankSetup(part, q, A0_rows_of(q), smoother=smoother, spgemm=spgemm, overlap=overlap, colouring=colouring)
               for q in range(part.n_ranks)]
     for l in range(part.n_grids):
@@ -398,10 +411,11 @@ def build_all_ranks(part, A0_rows_of, smoother="colour", spgemm=None, overlap=Tr
 
 
 def build_this_rank(part, rank, A0_rows, all_gather, smoother="colour", spgemm=None, overlap=True,
-                    colouring="parity", coarsening=None):
+                    colouring="parity", coarsening=None, oddExtents=None):
     """SPMD construction: `all_gather(obj)` returns the list of every rank's obj (e.g.
     torch.distributed.all_gather_object).  Returns (levels, coarse_global, coarse_counts)."""
-    s = RankSetup(part, rank, A0_rows, smoother=smoother, spgemm=spgemm, overlap=overlap, colouring=colouring, coarsening=coarsening)
+    s = RankSetup(part, rank, A0_rows, smoother=smoother, spgemm=spgemm, overlap=overlap, colouring=colouring, coarsening=coarsening,
+                  oddExtents=oddExtents)
     for l in range(part.n_grids):
         halo = s.begin_level(l)
         s.finish_level(l, all_gather(halo))

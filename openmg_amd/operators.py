@@ -9,18 +9,23 @@ import scipy.sparse as sp
 from . import _hip, tools
 
 
-def restriction(shape, dense=False, factors=None):
+def restriction(shape, dense=False, factors=None, oddExtents=None):
     """R of shape (N / 2**alpha, N): every coarse cell averages its 2**alpha fine cells
     (openmg/operators.py:15-89).  Index conventions follow the reference exactly, including
     the second-axis offset shape[0] and third-axis offset shape[0]*shape[1] (Q6).
 
     factors (not in the reference): 1 or 2 per axis of a 2-D / 3-D `shape` — the plain C-order aggregation that
     coarsens only the axes with factor 2 (semicoarsening), weight 1 / prod(factors); ValueError for a factor other
-    than 1 or 2, all ones, or a 2 on an extent that is odd or below 4."""
+    than 1 or 2, all ones, or a 2 on an extent that is odd or below 4.
+
+    oddExtents (with factors): None, or 'merge' — a 2 is taken on any extent e >= 4 and gives e // 2 coarse cells, the
+    last of which holds three fine cells along an odd axis; every entry keeps the weight 1 / prod(factors)."""
     shape = tuple(int(s) for s in shape)
     if factors is not None:
-        R = _hip.restriction_ex(shape, checkFactors(shape, factors))
+        R = _hip.restriction_ex(shape, checkFactors(shape, factors, oddExtents), oddExtents)
         return R.toarray() if dense else R
+    if oddExtents is not None:
+        raise ValueError("restriction(): oddExtents goes with factors (the reference's restriction knows no such key)")
     alpha = len(shape)
     N = tools.product(shape)
     n = N // (2 ** alpha)
@@ -72,8 +77,21 @@ def coeffecientList(A_in, R, dense=False, verbose=False):
 
 
 # ---- semicoarsening (NOT in the reference): a factor of 1 or 2 per axis and restriction -------
-def checkFactors(shape, factors):
-    """One restriction's factors as a tuple of ints, checked against the extents they apply to; ValueError otherwise."""
+def canHalve(extent, oddExtents=None):
+    """May an axis of this extent take a factor 2: even and >= 4, or — oddExtents 'merge' — just >= 4."""
+    return extent >= 4 and (extent % 2 == 0 or _hip.odd_code(oddExtents) == _hip.ODD_MERGE)
+
+
+def fullFactors(shape, oddExtents="merge"):
+    """The factors of 'full' coarsening with oddExtents 'merge' on a level's grid: 2 on every axis that can take it, 1 on
+    the others; all ones where no axis can."""
+    return tuple(2 if canHalve(int(s), oddExtents) else 1 for s in shape)
+
+
+def checkFactors(shape, factors, oddExtents=None):
+    """One restriction's factors as a tuple of ints, checked against the extents they apply to; ValueError otherwise.
+    oddExtents: None (a 2 needs an even extent >= 4) or 'merge' (a 2 needs an extent >= 4)."""
+    merge = _hip.odd_code(oddExtents) == _hip.ODD_MERGE
     shape = tuple(int(s) for s in shape)
     try:
         entry = tuple(factors)
@@ -85,17 +103,23 @@ def checkFactors(shape, factors):
     if all(f == 1 for f in entry):
         raise ValueError("a coarsening entry of all ones coarsens nothing: %r" % (factors,))
     for axis, (s, f) in enumerate(zip(shape, entry)):
-        if f == 2 and (s < 4 or s % 2):
-            raise ValueError("a factor of 2 needs an even extent >= 4: axis %d of the level's grid %s has %d" % (axis, shape, s))
+        if f == 2 and not canHalve(s, oddExtents):
+            raise ValueError("a factor of 2 needs an %sextent >= 4: axis %d of the level's grid %s has %d"
+                             % ("" if merge else "even ", axis, shape, s))
     return entry
 
 
-def coarseningOf(coarsening, problemShape=None, coarsestLevel=None, minSize=None):
+def coarseningOf(coarsening, problemShape=None, coarsestLevel=None, minSize=None, oddExtents=None):
     """parameters['coarsening'] checked, without any device work: None for full coarsening (None / 'full'), 'auto', or the
     list of factor tuples that will be used — the depth rule is restrictionList's: the first restriction always, then more
     until coarsestLevel + 1 exist or the next coarse level would have <= minSize rows; a sequence that ends before that
-    depth is reached (while an axis can still be coarsened) raises ValueError, like every other malformed value."""
-    if coarsening is None or (isinstance(coarsening, str) and coarsening == "full"):
+    depth is reached (while an axis can still be coarsened) raises ValueError, like every other malformed value.
+    oddExtents: None or 'merge' (anything else: ValueError).  With 'merge' a 2 is accepted on any extent >= 4, and None /
+    'full' is no longer the reference's hierarchy but a NAMED one, returned as such: every restriction takes fullFactors of
+    its level (2 on every axis with extent >= 4), to the same depth rule, ending where no axis can be coarsened."""
+    merge = _hip.odd_code(oddExtents) == _hip.ODD_MERGE
+    full = coarsening is None or (isinstance(coarsening, str) and coarsening == "full")
+    if full and not merge:
         return None
     try:
         shape = tuple(int(s) for s in problemShape)
@@ -103,6 +127,18 @@ def coarseningOf(coarsening, problemShape=None, coarsestLevel=None, minSize=None
         raise ValueError("parameters['coarsening'] needs a 2-D or 3-D parameters['problemShape'], not %r" % (problemShape,))
     if len(shape) not in (2, 3) or min(shape) < 2:
         raise ValueError("parameters['coarsening'] needs a 2-D or 3-D parameters['problemShape'] with extents >= 2, not %r" % (problemShape,))
+    if full:
+        used, ext = [], shape
+        for k in range(int(coarsestLevel) + 1):
+            entry = fullFactors(ext, oddExtents)
+            coarse = tuple(s // f for s, f in zip(ext, entry))
+            if all(f == 1 for f in entry) or (k >= 1 and tools.product(coarse) <= minSize):
+                break
+            used.append(entry)
+            ext = coarse
+        if not used:
+            raise ValueError("parameters['oddExtents'] = 'merge': no axis of problemShape %s can be coarsened (it needs an extent >= 4)" % (shape,))
+        return used
     if isinstance(coarsening, str):
         if coarsening == "auto":
             return "auto"
@@ -115,11 +151,11 @@ def coarseningOf(coarsening, problemShape=None, coarsestLevel=None, minSize=None
     ext = shape
     for k in range(int(coarsestLevel) + 1):
         if k >= len(given):
-            if not any(s >= 4 and s % 2 == 0 for s in ext) or (k >= 1 and tools.product(ext) // 2 <= minSize):
+            if not any(canHalve(s, oddExtents) for s in ext) or (k >= 1 and tools.product(ext) // 2 <= minSize):
                 break                               # (nothing left to coarsen, or whatever the factors minSize ends it here)
             raise ValueError("parameters['coarsening'] has %d entries but restriction %d is reached (gridLevels %d, minSize %d)"
                              % (len(given), k, int(coarsestLevel) + 1, minSize))
-        entry = checkFactors(ext, given[k])
+        entry = checkFactors(ext, given[k], oddExtents)
         coarse = tuple(s // f for s, f in zip(ext, entry))
         if k >= 1 and tools.product(coarse) <= minSize:
             break
@@ -130,14 +166,15 @@ def coarseningOf(coarsening, problemShape=None, coarsestLevel=None, minSize=None
     return used
 
 
-def semicoarsenedLists(A_in, problemShape, coarsening, coarsestLevel, minSize, lineAxis=None):
+def semicoarsenedLists(A_in, problemShape, coarsening, coarsestLevel, minSize, lineAxis=None, oddExtents=None):
     """restrictionList + coeffecientList with a factor of 1 or 2 per axis and restriction: returns (R, A, factors), every
     restriction built on the device (omg_restriction_ex), every Galerkin product too (omg_rap).  coarsening: 'auto' — per level
     the couplings of its operator (omg_axis_couplings) go through the rule (omg_semicoarsen_rule), which ends the hierarchy
     where no axis can be coarsened — or a sequence of factor tuples, consumed entry by entry.  The depth rule is
-    restrictionList's.  lineAxis: the line smoother's axis (an index into problemShape) for the rule, or None."""
+    restrictionList's.  lineAxis: the line smoother's axis (an index into problemShape) for the rule, or None.
+    oddExtents: None or 'merge' (coarseningOf); with 'merge' coarsening may also be None / 'full'."""
     shape = tuple(int(s) for s in problemShape)
-    named = coarseningOf(coarsening, shape, coarsestLevel, minSize)
+    named = coarseningOf(coarsening, shape, coarsestLevel, minSize, oddExtents)
     if named is None:
         raise ValueError("semicoarsenedLists needs coarsening 'auto' or a sequence of factor tuples; restrictionList does 'full'")
     A = [sp.csr_matrix(A_in)]
@@ -147,18 +184,19 @@ def semicoarsenedLists(A_in, problemShape, coarsening, coarsestLevel, minSize, l
     for k in range(int(coarsestLevel) + 1):
         if named == "auto":
             sums, counts, off_axis = _hip.axis_couplings(A[-1], ext)
-            entry = _hip.semicoarsen_rule(ext, sums, counts, off_axis, lineAxis, level=k)
+            entry = _hip.semicoarsen_rule(ext, sums, counts, off_axis, lineAxis, level=k, oddExtents=oddExtents)
             if all(f == 1 for f in entry):
                 if k == 0:
-                    raise ValueError("coarsening 'auto': no axis of problemShape %s can be coarsened (it needs an even extent >= 4)" % (shape,))
+                    raise ValueError("coarsening 'auto': no axis of problemShape %s can be coarsened (it needs an %sextent >= 4)"
+                                     % (shape, "" if oddExtents else "even "))
                 break
-            if k >= 1 and tools.product(ext) // tools.product(entry) <= minSize:
+            if k >= 1 and tools.product(s // f for s, f in zip(ext, entry)) <= minSize:
                 break
         elif k >= len(named):
             break
         else:
             entry = named[k]
-        R.append(_hip.restriction_ex(ext, entry))
+        R.append(_hip.restriction_ex(ext, entry, oddExtents))
         A.append(_hip.rap(R[-1], A[-1]))
         factors.append(entry)
         ext = tuple(s // f for s, f in zip(ext, entry))
