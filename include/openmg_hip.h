@@ -177,6 +177,47 @@ int omg_hierarchy_update_fine(omg_hierarchy *h, const double *data, int64_t nnz,
 /* *yes = 1 exactly when omg_hierarchy_update_fine takes this hierarchy (the two kinds named above), else 0: a caller
  * that holds one hierarchy for many solves asks before it decides between an update and a new setup. */
 int omg_hierarchy_can_update_fine(const omg_hierarchy *h, int *yes);
+
+/* ---- the 7-point operator of a coefficient field --------------------------------------------------------
+ * -div(kappa grad u) + sigma u by cell-centred finite volumes on a box of shape = (nz, ny, nx) cells, C-order numbering.
+ * kappa: (nz + 2)(ny + 2)(nx + 2) doubles in C order, the cells and one ghost layer; walls: six flags in the order
+ * -z, +z, -y, +y, -x, +x (NULL: all OMG_WALL_DIRICHLET); sigma: NULL (OMG_SIGMA_NONE), one double (OMG_SIGMA_SCALAR) or one per
+ * cell (OMG_SIGMA_FIELD); scale: one factor per axis z, y, x (NULL: 1).  kappa and sigma lie in host memory or — *_on_device
+ * != 0 — in HBM.  Every operation is rounded once in double, nothing is contracted:
+ *     face(a, b) = ((2 a) b) / (a + b),  c = face * scale[axis],  off-diagonal entry -c,
+ *     diagonal (((((c-K + c-J) + c-I) + c+I) + c+J) + c+K), then + sigma.
+ * The face at a Dirichlet wall takes the ghost cell's kappa and enters the diagonal only; at a Neumann wall it is +0.0.
+ * The result is operators.stencil7_kappa's matrix bit for bit: the in-grid neighbours of every row, columns ascending.
+ * A kappa that is not finite and > 0 (cells, and the ghost cells behind Dirichlet walls), a sigma that is not finite and
+ * >= 0, a scale factor that is not finite and > 0, an unknown wall or sigma kind: OMG_ERR_INVALID — for a value of a field
+ * the text names the first such cell (z, y, x), a ghost cell with -1 or the extent; nothing faults, the next call works. */
+#define OMG_WALL_DIRICHLET 0
+#define OMG_WALL_NEUMANN   1
+#define OMG_SIGMA_NONE   0
+#define OMG_SIGMA_SCALAR 1
+#define OMG_SIGMA_FIELD  2
+/* The CSR arrays: indptr (n + 1), indices and data (nnz = 7 n - 2 (nx ny + nx nz + ny nz)), all in host memory or
+ * — out_on_device != 0 — all in HBM.  indptr and indices may both be NULL: the values alone. */
+int omg_kappa_assemble(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls, const double *sigma,
+                       int sigma_kind, int sigma_on_device, const double *scale, int32_t *indptr, int32_t *indices, double *data,
+                       int out_on_device);
+/* omg_hierarchy_create_from_fine_opt of that operator without the operator ever being on the host: level 0 is assembled
+ * in HBM, the Galerkin chain starts from it, everything after that is omg_hierarchy_create_from_fine_opt's own sequence
+ * — the result is the object it builds from operators.stencil7_kappa's matrix (the same level kinds, the same answer of
+ * omg_hierarchy_can_update_fine, the same bits).  The assembled operator is fetched to the host once in two cases: for
+ * OMG_DTYPE_MIXED (the fp64 outer operator of level 0 is coded by the host), and — with the whole chain — where a level
+ * does not qualify for a fused path and the ordinary route sets the hierarchy up. */
+int omg_hierarchy_create_from_kappa(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls,
+                                    const double *sigma, int sigma_kind, int sigma_on_device, const double *scale,
+                                    int n_restrictions, const omg_hierarchy_options *opt, omg_hierarchy **out);
+/* omg_hierarchy_update_fine with the new values made from a coefficient field: they are written into a value array the
+ * hierarchy holds in HBM (nnz doubles, allocated at the first call) and take the device path of that entry; with kappa
+ * and sigma in HBM nothing crosses to the host but the error word.  Takes exactly the hierarchies for which
+ * omg_hierarchy_can_update_fine says 1 and whose level 0 is the 7-point operator on the grid `shape`; any other:
+ * OMG_ERR_INVALID, and the hierarchy is as before.  So it is after a refused kappa or sigma.  The resident right-hand side
+ * and iterate stay. */
+int omg_hierarchy_update_kappa(omg_hierarchy *h, const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls,
+                               const double *sigma, int sigma_kind, int sigma_on_device, const double *scale);
 int omg_hierarchy_dtype(const omg_hierarchy *h, int *dtype);
 int omg_hierarchy_destroy(omg_hierarchy *h);
 /* Run on a caller-owned hipStream_t instead of the hierarchy's own stream (NULL = own). */

@@ -328,7 +328,11 @@ def _setup(A_in, parameters, completed_from):
     dense = parameters["dense"]
     code, omega = _smoother_of(parameters)
     coarsening = _coarsening_of(parameters)
+    # (Solver.from_kappa: A_in is the coefficient field's arguments; the plain device route below assembles level 0 in HBM,
+    # every other route gets the operator assembled on the device into host arrays and runs as for any A_in)
+    kappa = A_in if isinstance(A_in, _hip.KappaArgs) else None
     if coarsening is not None:
+        A_in = A_in if kappa is None else kappa.matrix()
         return _setup_semicoarsened(A_in, parameters, coarsening, code, omega, nullspace) + (accel, shape, alpha)
 
     # (the device route qualifies levels for the FUSED paths, which exist for the colour orderings and 2-D weighted Jacobi; with
@@ -341,9 +345,13 @@ def _setup(A_in, parameters, completed_from):
         # for the fused paths stay in HBM (omg_hierarchy_create_from_fine); same hierarchy, same results
         R = A = None
         parameters["coarsestLevel"] = n_fused
-        hierarchy = _hip.Hierarchy.from_fine(A_in, problemShape, n_fused, smoother=code, omega=omega, dtype=_dtype_of(parameters),
-                                             nullspace=nullspace)
+        if kappa is not None:
+            hierarchy = _hip.Hierarchy.from_kappa(kappa, n_fused, smoother=code, omega=omega, dtype=_dtype_of(parameters), nullspace=nullspace)
+        else:
+            hierarchy = _hip.Hierarchy.from_fine(A_in, problemShape, n_fused, smoother=code, omega=omega, dtype=_dtype_of(parameters),
+                                                 nullspace=nullspace)
     else:
+        A_in = A_in if kappa is None else kappa.matrix()
         R = operators.restrictionList(problemShape, parameters["coarsestLevel"], parameters["minSize"],
                                       dense=dense, verbose=verbose)
         parameters["coarsestLevel"] = len(R)
@@ -494,7 +502,9 @@ def _device_setup_depth(A_in, problemShape, parameters):
     messages, or the shape is not one whose restriction is the plain aggregation at every level (2-D / 3-D, first and
     last extent equal, extents even on every restricted level) — then the ordinary route runs (and raises what the
     reference raises)."""
-    if parameters.get("giveInfo") or parameters.get("dense") or parameters.get("verbose") or not sp.issparse(A_in):
+    if parameters.get("giveInfo") or parameters.get("dense") or parameters.get("verbose"):
+        return 0
+    if not (sp.issparse(A_in) or isinstance(A_in, _hip.KappaArgs)):        # (KappaArgs.shape: the operator's, as a matrix has it)
         return 0
     try:
         shape = tuple(int(s) for s in problemShape)

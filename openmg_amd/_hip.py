@@ -74,6 +74,9 @@ SIGNATURES = {
     "omg_hierarchy_dtype": (_I, [_P, _IP]),
     "omg_hierarchy_update_fine": (_I, [_P, _P, ctypes.c_int64, _I]),
     "omg_hierarchy_can_update_fine": (_I, [_P, _IP]),
+    "omg_kappa_assemble": (_I, [_I64P, _P, _I, _IP, _P, _I, _I, _DP, _P, _P, _P, _I]),
+    "omg_hierarchy_create_from_kappa": (_I, [_I64P, _P, _I, _IP, _P, _I, _I, _DP, _I, _OPT, _PP]),
+    "omg_hierarchy_update_kappa": (_I, [_P, _I64P, _P, _I, _IP, _P, _I, _I, _DP]),
     "omg_resident_norms": (_I, [_P, _DP, _DP]),
     "omg_hierarchy_destroy": (_I, [_P]),
     "omg_hierarchy_set_stream": (_I, [_P, _P]),
@@ -374,6 +377,102 @@ def vec(x, n=None, copy=False):
     return a
 
 
+SIGMA_NONE, SIGMA_SCALAR, SIGMA_FIELD = 0, 1, 2
+
+
+class KappaArgs:
+    """The coefficient-field arguments of omg_kappa_assemble / omg_hierarchy_create_from_kappa / omg_hierarchy_update_kappa
+    (include/openmg_hip.h) from what the Python entries take: kappa a float64 array (nz + 2, ny + 2, nx + 2), NumPy or a
+    C-contiguous device array (__cuda_array_interface__); walls, sigma, scale as operators.stencil7_kappa takes them, sigma
+    a device array too.  ValueError for what operators.kappa_arguments refuses — before any device work; the fields' values
+    are checked by the kernel that reads them (HipError, ERR_INVALID, naming the cell).  .grid: problemShape; .shape: the
+    operator's (n, n); .call: the C arguments from `shape` to `scale`; the object keeps the arrays alive."""
+
+    def __init__(self, kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0)):
+        from . import _devarray, operators
+        if isinstance(kappa, KappaArgs):           # (already checked: Hierarchy.from_kappa / update_kappa take one as it is)
+            self.__dict__.update(kappa.__dict__)
+            return
+        k_dev = _devarray.is_device_array(kappa)
+        if k_dev:
+            k_shape = tuple(int(s) for s in kappa.__cuda_array_interface__["shape"])
+        else:
+            kappa = np.asarray(kappa)
+            if kappa.dtype != np.float64:
+                raise ValueError("kappa must be float64, not %s" % kappa.dtype)
+            kappa = np.ascontiguousarray(kappa)
+            k_shape = kappa.shape
+        self.grid, self.walls, self.scale = operators.kappa_arguments(k_shape, walls, sigma, scale)
+        self.n = int(np.prod(self.grid))
+        self.shape = (self.n, self.n)
+        nz, ny, nx = self.grid
+        self.nnz = 7 * self.n - 2 * (nx * ny + nx * nz + ny * nz)
+        if 7 * self.n >= 2 ** 31 - 1:
+            raise ValueError("operator too large for int32 indices; shard it first")
+        padded = int(np.prod(k_shape))
+        s_dev = _devarray.is_device_array(sigma)
+        if sigma is None:
+            kind, s_ptr = SIGMA_NONE, None
+        elif s_dev:
+            kind, s_ptr = SIGMA_FIELD, _devarray.address(sigma, self.n, "sigma")
+        elif np.ndim(sigma) == 0:
+            sigma = np.array([float(sigma)], dtype=np.float64)
+            kind, s_ptr = SIGMA_SCALAR, sigma.ctypes.data
+        else:
+            sigma = np.ascontiguousarray(sigma, dtype=np.float64)
+            kind, s_ptr = SIGMA_FIELD, sigma.ctypes.data
+        k_ptr = _devarray.address(kappa, padded, "kappa") if k_dev else kappa.ctypes.data
+        self.on_device = k_dev or s_dev
+        self._keep = (kappa, sigma)
+        self.call = ((ctypes.c_int64 * 3)(*self.grid), ctypes.c_void_p(k_ptr), int(k_dev), (ctypes.c_int * 6)(*self.walls),
+                     ctypes.c_void_p(s_ptr), kind, int(s_dev), (ctypes.c_double * 3)(*self.scale))
+
+    def matrix(self):
+        """The operator as a SciPy CSR in host memory, assembled on the device (kappa_assemble)."""
+        indptr, indices, data = kappa_assemble(self)
+        A = sp.csr_matrix((data, indices, indptr), shape=self.shape)
+        A.has_sorted_indices = True
+        return A
+
+    def synchronize(self):
+        """What the caller's library enqueued on the device arrays is complete before the library's own stream reads them."""
+        if self.on_device:
+            check(lib().omg_device_synchronize())
+
+
+def kappa_assemble(kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0), pattern=True, out=None):
+    """The 7-point operator of a coefficient field, assembled on the device (omg_kappa_assemble): the CSR arrays of
+    operators.stencil7_kappa(kappa, walls, sigma, scale), bit for bit.  kappa, sigma: NumPy arrays or device arrays.
+    Returns (indptr, indices, data) as NumPy arrays, indptr = indices = None with pattern=False (the values alone).
+    out = (indptr, indices, data): device arrays to write into instead — int32 (n + 1), int32 (nnz), float64 (nnz); the
+    first two None for the values alone — and returned as they are."""
+    from . import _devarray
+    a = KappaArgs(kappa, walls, sigma, scale)
+    if out is not None:
+        d_indptr, d_indices, d_data = out
+        if (d_indptr is None) != (d_indices is None):
+            raise ValueError("out: indptr and indices are given together or not at all")
+
+        def int32_address(arr, count, what):
+            iface = arr.__cuda_array_interface__
+            if iface["typestr"] not in ("<i4", "=i4", "|i4") or iface.get("strides") is not None or tuple(iface["shape"]) != (count,):
+                raise ValueError("out: %s must be a contiguous int32 device array of %d entries" % (what, count))
+            return int(iface["data"][0])
+        p_indptr = None if d_indptr is None else int32_address(d_indptr, a.n + 1, "indptr")
+        p_indices = None if d_indices is None else int32_address(d_indices, a.nnz, "indices")
+        p_data = _devarray.address(d_data, a.nnz, "out: data")
+        check(lib().omg_device_synchronize())
+        check(lib().omg_kappa_assemble(*a.call, ctypes.c_void_p(p_indptr), ctypes.c_void_p(p_indices), ctypes.c_void_p(p_data), 1))
+        return out
+    data = np.empty(a.nnz, dtype=np.float64)
+    indptr = np.empty(a.n + 1, dtype=np.int32) if pattern else None
+    indices = np.empty(a.nnz, dtype=np.int32) if pattern else None
+    a.synchronize()
+    check(lib().omg_kappa_assemble(*a.call, indptr.ctypes.data if pattern else None, indices.ctypes.data if pattern else None,
+                                   data.ctypes.data, 0))
+    return indptr, indices, data
+
+
 class Hierarchy:
     """Device-resident A/R hierarchy (omg_hierarchy)."""
 
@@ -495,6 +594,38 @@ class Hierarchy:
         else:
             d = np.ascontiguousarray(data, dtype=np.float64)
             check(lib().omg_hierarchy_update_fine(self._h, d.ctypes.data, d.size, 0))
+
+    @classmethod
+    def from_kappa(cls, kappa, n_restrictions, walls=None, sigma=None, scale=(1.0, 1.0, 1.0), smoother="gs", omega=1.0,
+                   dtype="float64", nullspace=None):
+        """from_fine of operators.stencil7_kappa(kappa, walls, sigma, scale) without that matrix ever being on the host
+        (omg_hierarchy_create_from_kappa): level 0 is assembled in HBM from the field — a NumPy array or a device array —,
+        the rest is from_fine's own sequence, the result the same object bit for bit."""
+        self = cls.__new__(cls)
+        self._h = None
+        self.nullspace_kind = nullspace_code(nullspace)
+        a = KappaArgs(kappa, walls, sigma, scale)
+        self.smoother = smoother_code(smoother)
+        self.omega = float(omega)
+        self.dtype = dtype_code(dtype)
+        self.n_levels = int(n_restrictions) + 1
+        self.sizes = [a.n // 8 ** l for l in range(self.n_levels)]
+        h = ctypes.c_void_p()
+        opt = HierarchyOptions(self.smoother, self.omega, self.dtype, self.nullspace_kind)
+        a.synchronize()
+        check(lib().omg_hierarchy_create_from_kappa(*a.call, int(n_restrictions), ctypes.byref(opt), ctypes.byref(h)))
+        self._h = h
+        self._A = self._R = None
+        return self
+
+    def update_kappa(self, kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0)):
+        """update_fine with the values of operators.stencil7_kappa(kappa, walls, sigma, scale), made on the device
+        (omg_hierarchy_update_kappa): with device arrays nothing crosses to the host.  Takes the hierarchies update_fine
+        takes whose level 0 is the 7-point operator on kappa's grid (HipError ERR_INVALID otherwise, and for a kappa or
+        sigma out of range — the hierarchy is then as before)."""
+        a = KappaArgs(kappa, walls, sigma, scale)
+        a.synchronize()
+        check(lib().omg_hierarchy_update_kappa(self._h, *a.call))
 
     def can_update_fine(self):
         """Whether update_fine takes this hierarchy (omg_hierarchy_can_update_fine)."""

@@ -4,6 +4,8 @@
     u, info = s.solve(b, initial=None, out=None, **overrides)
     z = s.apply(r, out=None)                    # one zero-start cycle, z = M r (a preconditioner for the caller's own iteration)
     s.update(A_new)                             # new values in the same pattern
+    s = openmg_amd.Solver.from_kappa(kappa, parameters, walls, sigma, scale)    # the 7-point operator of a coefficient field,
+    s.update_kappa(kappa_new, sigma=None)       # ... assembled in HBM (operators.stencil7_kappa: the definition)
     s.close()                                   # also a context manager
 
 The setup and the two loops are mgSolve's own (openmg_amd._setup, _solve_cycles, _solve_cg): a solve from zero has the
@@ -84,7 +86,37 @@ class Solver:
         self.parameters = completed
         self._pattern_of(A_in)
 
+    _kappa = None              # from_kappa: (problemShape, walls, scale) of construction, else None
+
+    @classmethod
+    def from_kappa(cls, kappa, parameters, walls=None, sigma=None, scale=(1.0, 1.0, 1.0)):
+        """The Solver of operators.stencil7_kappa(kappa, walls, sigma, scale) — same bits — from the coefficient field
+        itself: kappa float64 (nz + 2, ny + 2, nx + 2), the cells and one ghost layer, and sigma (None, a scalar, an array
+        of problemShape) as NumPy arrays or device arrays.  parameters['problemShape'] is taken from kappa; if given it
+        must agree.  Where the setup takes the plain device route (the colour smoother, no giveInfo / verbose / dense, no
+        'coarsening' / 'oddExtents', a shape the device setup takes) level 0 is assembled in HBM and no host matrix is ever
+        made; with any other parameters the operator is assembled on the device into host arrays and the setup runs as for
+        any A_in.  ValueError for bad arguments before any device work; a kappa or sigma value out of range: HipError
+        (ERR_INVALID) naming the first such cell."""
+        source = _hip.KappaArgs(kappa, walls, sigma, scale)
+        given = dict(parameters)
+        if given.get("problemShape") is not None:
+            try:
+                same = tuple(int(s) for s in given["problemShape"]) == source.grid
+            except TypeError:
+                same = False
+            if not same:
+                raise ValueError("parameters['problemShape'] = %r is not kappa's grid %r" % (given["problemShape"], source.grid))
+        given["problemShape"] = source.grid
+        self = cls(source, given)
+        self._kappa = (source.grid, walls, scale)
+        return self
+
     def _pattern_of(self, A_in):
+        if isinstance(A_in, _hip.KappaArgs):
+            # (the in-grid 7-point pattern: formed on the host when update(A_new) first asks for it)
+            self._shape, self._indptr, self._indices = A_in.shape, None, None
+            return
         A0 = _hip.as_csr(A_in)
         self._shape, self._indptr, self._indices = A0.shape, A0.indptr, A0.indices
 
@@ -230,15 +262,25 @@ class Solver:
         hierarchy is built with the FACTORS CHOSEN AT CONSTRUCTION ('auto' is not asked again: sizes and patterns cannot
         change under the caller), always as a new hierarchy: a semicoarsened one takes no update in place.  The same holds
         with parameters['oddExtents'] = 'merge': the factors and the key are kept, the hierarchy is built anew."""
-        from . import _setup, defaults
         h = self._open()
         A1 = _hip.as_csr(A_new)
+        if self._indptr is None:
+            from . import operators
+            P = operators.stencil_poisson(self._kappa[0])
+            self._indptr, self._indices = P.indptr, P.indices
         if (A1.shape != self._shape or A1.indptr.size != self._indptr.size or A1.indices.size != self._indices.size
                 or not np.array_equal(A1.indptr, self._indptr) or not np.array_equal(A1.indices, self._indices)):
             raise ValueError("Solver.update: A_new must have the pattern (indptr and indices) the solver was set up with")
         if h.can_update_fine():
             h.update_fine(A1.data)
             return
+        self._rebuild(A_new)
+        self._pattern_of(A1)
+
+    def _rebuild(self, A_new):
+        """A new hierarchy for A_new with the construction's parameters (and factors); the old one is closed after that succeeded."""
+        from . import _setup, defaults
+        h = self._open()
         given = dict(self._given)
         if h.coarsening is not None:
             given["coarsening"] = list(h.coarsening)
@@ -246,5 +288,22 @@ class Solver:
             given.pop("coarsestLevel", None)
         fresh, R, A = _setup(A_new, given, dict(defaults))[:3]
         self._hierarchy, self.R, self.A = fresh, R, A
-        self._pattern_of(A1)
         h.close()
+
+    def update_kappa(self, kappa, sigma=None):
+        """update() with the operator of a new coefficient field (and sigma), for a Solver made by from_kappa; walls and
+        scale are those of construction.  Where the hierarchy takes new coefficients in place the values are made on the
+        device and go straight into update_fine — with device arrays nothing crosses to the host; otherwise the operator
+        is assembled into host arrays and a new hierarchy built as update() does.  Either way later solves have the bits of
+        a fresh Solver.from_kappa(kappa, parameters, ...).  A refused field leaves the solver with the old operator."""
+        h = self._open()
+        if self._kappa is None:
+            raise ValueError("Solver.update_kappa: the solver was not made by Solver.from_kappa")
+        grid, walls, scale = self._kappa
+        source = _hip.KappaArgs(kappa, walls, sigma, scale)
+        if source.grid != grid:
+            raise ValueError("Solver.update_kappa: kappa's grid %r is not the solver's %r" % (source.grid, grid))
+        if h.can_update_fine():
+            h.update_kappa(source)
+            return
+        self._rebuild(source)

@@ -826,6 +826,30 @@ struct DevCsrPlain {
 // reference's depth rule).  (setup_device.hip)
 void galerkin_chain_device(const omg_csr &A0, int dim, const int64_t *shape, int n_restrictions, std::vector<DevCsrPlain> &A,
                            std::vector<DevCsrPlain> &R, hipStream_t s);
+// ... with A[0] already in HBM (omg_hierarchy_create_from_kappa: the operator a kernel assembled); A0 is moved into A[0]
+void galerkin_chain_device(DevCsrPlain &&A0, int dim, const int64_t *shape, int n_restrictions, std::vector<DevCsrPlain> &A,
+                           std::vector<DevCsrPlain> &R, hipStream_t s);
+// The 7-point operator of a cell-centred coefficient field (kappa.hip).  kappa_nnz: its entries;
+// kappa_pattern: indptr (n + 1) and indices (nnz) of the in-grid pattern, columns ascending, by closed form.
+int64_t kappa_nnz(int nx, int ny, int nz);
+void kappa_pattern(int nx, int ny, int nz, int32_t *indptr, int32_t *indices, hipStream_t s);
+// The arguments of one assembly, checked, and the fields in HBM (a host array is uploaded into own_*).
+struct KappaField {
+    int nx = 0, ny = 0, nz = 0;
+    const double *kappa_dev = nullptr, *sigma_dev = nullptr;
+    double sigma_value = 0.0;
+    int sigma_kind = 0;
+    int neumann[6] = {0, 0, 0, 0, 0, 0};
+    double scale[3] = {1.0, 1.0, 1.0};
+    DevBuf<double> own_kappa, own_sigma;
+    DevBuf<unsigned long long> err;
+    // shape (nz, ny, nx); walls / scale may be null (all Dirichlet / 1); OMG_ERR_INVALID for anything the header refuses
+    void prepare(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls, const double *sigma, int sigma_kind,
+                 int sigma_on_device, const double *scale, hipStream_t s);
+    // the value array in CSR order to data (device, kappa_nnz doubles); waits for the stream; a kappa or sigma out of
+    // range: OMG_ERR_INVALID naming the first such cell, `entry` in front
+    void values(double *data, hipStream_t s, const char *entry);
+};
 // The same chain with a factor (1 or 2) per axis and restriction instead of 2 everywhere (semicoarsening).
 // shape and every factor tuple are in the grid's C order (the last axis has unit stride).  factors: n_restrictions * dim
 // entries, or null = 'auto': per level the couplings kernel, semicoarsen_rule, the restriction kernel, the product.  Auto

@@ -246,6 +246,8 @@ struct Hier {
     bool upd7 = false;
     int g7[3] = {0, 0, 0};
     std::vector<DevBuf<double>> dense7;
+    // omg_hierarchy_update_kappa: the value array kappa_values writes, nnz0 doubles (made at the first such update)
+    DevBuf<double> kappa_vals;
     // resident state
     bool resident = false;
     // OMG_NO_FUSE=1: never fuse the last smoother set with the residual / norm (A/B switch;
@@ -1681,23 +1683,28 @@ std::unique_ptr<Hier<V>> create(int n_levels, const omg_csr *A, const omg_csr *R
 // 27-point kernels) — the grid is the caller's problemShape —, orderings and slot maps written by kernels.  What comes
 // back to the host: the coarsest operator (a few thousand entries) for its factorisation.  A hierarchy with a level
 // that does not qualify takes the ordinary route (its operators are fetched once): the result is the same object.
+// dev0 (omg_hierarchy_create_from_kappa): the fine operator is this device CSR — sorted, square, written by kappa.hip —
+// and A0 is not looked at; the chain takes it over, everything after that is the one sequence.
 template <typename V>
 std::unique_ptr<Hier<V>> create_from_fine(const omg_csr &A0, int dim, const int64_t *shape, int n_restrictions, int smoother, double omega,
-                                          int nullspace = OMG_NULLSPACE_NONE) {
+                                          int nullspace = OMG_NULLSPACE_NONE, DevCsrPlain *dev0 = nullptr) {
     using H = Hier<V>;
     using Lv = Level<V>;
-    refuse_line_smoother(smoother, "omg_hierarchy_create_from_fine");
+    refuse_line_smoother(smoother, dev0 ? "omg_hierarchy_create_from_kappa" : "omg_hierarchy_create_from_fine");
     OMG_REQUIRE(dim >= 2 && dim <= 3 && shape && n_restrictions >= 1, "device setup: 2-D / 3-D grids, at least one restriction");
     OMG_REQUIRE(smoother >= OMG_SMOOTH_GS_LEX && smoother <= OMG_SMOOTH_JACOBI, "unknown smoother");
-    validate_csr(A0, "A_in");
-    OMG_REQUIRE(A0.n_rows == A0.n_cols, "A_in must be square");
+    if (!dev0) {
+        validate_csr(A0, "A_in");
+        OMG_REQUIRE(A0.n_rows == A0.n_cols, "A_in must be square");
+    }
     // the reference's restriction is the plain aggregation when its quirky second-axis offset shape[0] (Q6) equals the
     // true one: first and last extent equal
     OMG_REQUIRE(shape[0] == shape[dim - 1], "device setup: first and last extent must be equal");
     require_device();
     std::unique_ptr<H> h = new_handle<V>(smoother, omega, nullspace);
     std::vector<DevCsrPlain> dA, dR;
-    galerkin_chain_device(A0, dim, shape, n_restrictions, dA, dR, h->stream);
+    if (dev0) galerkin_chain_device(std::move(*dev0), dim, shape, n_restrictions, dA, dR, h->stream);
+    else galerkin_chain_device(A0, dim, shape, n_restrictions, dA, dR, h->stream);
     const int n_levels = n_restrictions + 1;
     h->lv.resize(size_t(n_levels));
     const double w = 1.0 / double(1 << dim);
@@ -2684,6 +2691,94 @@ int omg_hierarchy_update_fine(omg_hierarchy *h, const double *data, int64_t nnz,
             update_fine(hh, dev, nnz, true);
             mixed_update_values(hh, dev, nnz);
         });
+    });
+}
+
+int omg_kappa_assemble(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls, const double *sigma, int sigma_kind,
+                       int sigma_on_device, const double *scale, int32_t *indptr, int32_t *indices, double *data, int out_on_device) {
+    return guarded([&] {
+        OMG_REQUIRE(data, "omg_kappa_assemble: data is null");
+        OMG_REQUIRE(!indptr == !indices, "omg_kappa_assemble: indptr and indices are given together or not at all");
+        OneShot one;
+        KappaField F;
+        F.prepare(shape, kappa, kappa_on_device, walls, sigma, sigma_kind, sigma_on_device, scale, one.s);
+        const int64_t n = int64_t(F.nx) * F.ny * F.nz, nnz = kappa_nnz(F.nx, F.ny, F.nz);
+        DevBuf<double> dv;
+        DevBuf<int32_t> dp, di;
+        if (!out_on_device) dv.alloc(size_t(nnz));
+        F.values(out_on_device ? data : dv.p, one.s, "omg_kappa_assemble");
+        if (indptr) {
+            if (!out_on_device) { dp.alloc(size_t(n) + 1); di.alloc(size_t(nnz)); }
+            kappa_pattern(F.nx, F.ny, F.nz, out_on_device ? indptr : dp.p, out_on_device ? indices : di.p, one.s);
+            if (!out_on_device) {
+                download_staged(indptr, dp.p, (size_t(n) + 1) * sizeof(int32_t), one.s);
+                download_staged(indices, di.p, size_t(nnz) * sizeof(int32_t), one.s);
+            }
+        }
+        if (!out_on_device) download_staged(data, dv.p, size_t(nnz) * sizeof(double), one.s);
+        OMG_HIP(hipStreamSynchronize(one.s));
+    });
+}
+
+int omg_hierarchy_create_from_kappa(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls, const double *sigma,
+                                    int sigma_kind, int sigma_on_device, const double *scale, int n_restrictions,
+                                    const omg_hierarchy_options *opt, omg_hierarchy **out) {
+    return guarded([&] {
+        OMG_REQUIRE(out, "out is null");
+        *out = nullptr;
+        OMG_REQUIRE(opt, "options are null");
+        const int dtype = opt->dtype;
+        OMG_REQUIRE(dtype == OMG_DTYPE_F64 || dtype == OMG_DTYPE_F32 || dtype == OMG_DTYPE_MIXED, "unknown dtype");
+        OMG_REQUIRE(opt->nullspace == OMG_NULLSPACE_NONE || opt->nullspace == OMG_NULLSPACE_CONSTANT, "unknown nullspace kind");
+        // level 0 in HBM: the pattern and the values, on a stream of this call's own (the hierarchy's does not exist yet)
+        DevCsrPlain A0;
+        HostCsr hostA0;
+        {
+            OneShot one;
+            KappaField F;
+            F.prepare(shape, kappa, kappa_on_device, walls, sigma, sigma_kind, sigma_on_device, scale, one.s);
+            SetupTimer tm("device setup: the fine operator from kappa");
+            A0.n_rows = A0.n_cols = int64_t(F.nx) * F.ny * F.nz;
+            A0.nnz = kappa_nnz(F.nx, F.ny, F.nz);
+            A0.indptr.alloc(size_t(A0.n_rows) + 1);
+            A0.indices.alloc(size_t(A0.nnz));
+            A0.data.alloc(size_t(A0.nnz));
+            kappa_pattern(F.nx, F.ny, F.nz, A0.indptr.p, A0.indices.p, one.s);
+            F.values(A0.data.p, one.s, "omg_hierarchy_create_from_kappa");
+            // (the fp64 outer operator of a mixed hierarchy is coded by the host: the one download of this route besides the
+            // fall-back of create_from_fine, which fetches the whole chain when a level does not qualify)
+            if (dtype == OMG_DTYPE_MIXED) hostA0 = download_csr(A0, one.s);
+        }
+        const omg_csr none = {};
+        std::unique_ptr<omg_hierarchy> h(new omg_hierarchy);
+        if (dtype != OMG_DTYPE_F64) h->f = create_from_fine<float>(none, 3, shape, n_restrictions, opt->smoother, opt->omega, opt->nullspace, &A0);
+        else h->d = create_from_fine<double>(none, 3, shape, n_restrictions, opt->smoother, opt->omega, opt->nullspace, &A0);
+        if (dtype == OMG_DTYPE_MIXED) build_mixed(h->f.get(), view(hostA0));
+        *out = h.release();
+    });
+}
+
+int omg_hierarchy_update_kappa(omg_hierarchy *h, const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls,
+                               const double *sigma, int sigma_kind, int sigma_on_device, const double *scale) {
+    return guarded([&] {
+        const double *vals = nullptr;
+        int64_t nnz = 0;
+        with(h, [&](auto *hh) {
+            OMG_REQUIRE(shape, "omg_hierarchy_update_kappa: shape is null");
+            OMG_REQUIRE(hh->upd7 && shape[0] == hh->g7[2] && shape[1] == hh->g7[1] && shape[2] == hh->g7[0],
+                        "omg_hierarchy_update_kappa: needs a hierarchy that omg_hierarchy_update_fine takes (omg_hierarchy_can_update_fine) "
+                        "whose level 0 is the 7-point operator on the grid `shape`");
+            KappaField F;
+            F.prepare(shape, kappa, kappa_on_device, walls, sigma, sigma_kind, sigma_on_device, scale, hh->stream);
+            nnz = kappa_nnz(F.nx, F.ny, F.nz);
+            OMG_REQUIRE(nnz == hh->nnz0, "internal: the fine pattern is not the in-grid 7-point pattern");
+            if (hh->kappa_vals.n != size_t(nnz)) hh->kappa_vals.alloc(size_t(nnz));
+            F.values(hh->kappa_vals.p, hh->stream, "omg_hierarchy_update_kappa");
+            vals = hh->kappa_vals.p;
+        });
+        // (the one update path: the values are in HBM)
+        const int rc = omg_hierarchy_update_fine(h, vals, nnz, 1);
+        if (rc != OMG_OK) throw Error(rc, g_last_error);
     });
 }
 

@@ -1,0 +1,264 @@
+// The 7-point operator of -div(kappa grad u) + sigma u from a cell-centred coefficient field in HBM:
+// cell-centred finite volumes on a box of nz x ny x nx cells, kappa given with one ghost layer, (nz + 2)(ny + 2)(nx + 2)
+// doubles in C order.  What the kernels write is the sorted CSR operators.stencil7_kappa assembles with SciPy, bit for bit
+// — the in-grid neighbours of every row in ascending column order (-K, -J, -I, D, +I, +J, +K) — and with it the input of
+// create_from_fine and omg_hierarchy_update_fine.
+//
+// Arithmetic (every operation rounded once in double; __dadd_rn / __dmul_rn / __ddiv_rn are never contracted):
+//     face(a, b) = ((2 a) b) / (a + b)         c = face scale[axis]        off-diagonal: -c
+//     diagonal   = (((((c-K + c-J) + c-I) + c+I) + c+J) + c+K) (+ sigma)
+// A Dirichlet wall face takes the ghost cell's kappa and enters the diagonal only; a Neumann wall face contributes +0.0.
+//
+// The row start is a closed form — 7 r minus the absent neighbours of the rows before r —, so neither kernel scans and
+// kappa_values needs no row pointers.  One thread per row, adjacent lanes on adjacent cells along x: kappa is read once
+// per cell by its own thread, the six neighbours come through the cache (the +-I neighbours are the adjacent lanes' own
+// loads, the +-J / +-K rows were or will be some other workgroup's).  Stores: a row holds 4 - 7 values, so a thread's own
+// stores are 32 - 56 bytes apart from its neighbour's; the staged variant collects the workgroup's rows — one contiguous
+// piece of the value array — in LDS and writes it out at unit stride.
+#include "common.h"
+
+namespace omg {
+
+namespace {
+
+constexpr int KAPPA_BLOCK = 256;                      // rows per workgroup: at most 7 * 256 staged values (14 KiB of LDS)
+
+struct KappaGrid { int nx, ny, nz; };
+
+// entries of the rows before r = (k ny + j) nx + i: seven each, minus every neighbour that lies outside the grid
+__device__ __forceinline__ int64_t row_start(const KappaGrid &g, int64_t r, int i, int j, int k) {
+    const int64_t plane = int64_t(g.nx) * g.ny, in_plane = int64_t(j) * g.nx + i, lines = int64_t(k) * g.ny + j;
+    int64_t absent = (r < plane ? r : plane);                                                  // -K: the rows of plane 0
+    const int64_t top = r - int64_t(g.nz - 1) * plane;
+    absent += top > 0 ? top : 0;                                                               // +K: the rows of the last plane
+    absent += int64_t(k) * g.nx + (in_plane < g.nx ? in_plane : g.nx);                         // -J: the first line of every plane
+    const int64_t lastj = in_plane - int64_t(g.ny - 1) * g.nx;
+    absent += int64_t(k) * g.nx + (lastj > 0 ? lastj : 0);                                     // +J: the last line of every plane
+    absent += lines + (i > 0 ? 1 : 0);                                                         // -I: the first cell of every line
+    absent += lines;                                                                           // +I: the last cell of every line
+    return 7 * r - absent;
+}
+
+__device__ __forceinline__ void cell_of(const KappaGrid &g, int64_t r, int &i, int &j, int &k) {
+    // (r < n < 2^31 / 7, KappaField::prepare: two 32-bit divisions instead of three 64-bit ones)
+    const uint32_t line = uint32_t(r) / uint32_t(g.nx);
+    i = int(uint32_t(r) - line * uint32_t(g.nx));
+    k = int(line / uint32_t(g.ny));
+    j = int(line - uint32_t(k) * uint32_t(g.ny));
+}
+
+// row pointers and columns; thread n writes indptr[n] = nnz
+__global__ void __launch_bounds__(KAPPA_BLOCK) kappa_pattern_kernel(KappaGrid g, int32_t *indptr, int32_t *indices) {
+    const int64_t n = int64_t(g.nx) * g.ny * g.nz;
+    const int64_t r = blockIdx.x * int64_t(KAPPA_BLOCK) + threadIdx.x;
+    if (r > n) return;
+    if (r == n) {
+        indptr[n] = int32_t(7 * n - 2 * (int64_t(g.nx) * g.ny + int64_t(g.nx) * g.nz + int64_t(g.ny) * g.nz));
+        return;
+    }
+    int i, j, k;
+    cell_of(g, r, i, j, k);
+    int64_t p = row_start(g, r, i, j, k);
+    indptr[r] = int32_t(p);
+    const int64_t sj = g.nx, sk = int64_t(g.nx) * g.ny;
+    if (k > 0) indices[p++] = int32_t(r - sk);
+    if (j > 0) indices[p++] = int32_t(r - sj);
+    if (i > 0) indices[p++] = int32_t(r - 1);
+    indices[p++] = int32_t(r);
+    if (i + 1 < g.nx) indices[p++] = int32_t(r + 1);
+    if (j + 1 < g.ny) indices[p++] = int32_t(r + sj);
+    if (k + 1 < g.nz) indices[p++] = int32_t(r + sk);
+}
+
+struct KappaValuesArgs {
+    KappaGrid g;
+    const double *kappa;          // (nz + 2)(ny + 2)(nx + 2)
+    const double *sigma;          // null: sigma_value (sigma_kind != 0); else one double (kind 1) or one per cell (kind 2)
+    double sigma_value;
+    int sigma_kind;               // OMG_SIGMA_*
+    int neumann[6];               // -z, +z, -y, +y, -x, +x
+    double scale[3];              // z, y, x
+    double *data;
+    unsigned long long *err;      // the smallest key of an offending value: 2 * (index in the padded field) + (1: sigma)
+};
+
+__device__ __forceinline__ bool kappa_ok(double v) { return v > 0.0 && v < HUGE_VAL; }
+__device__ __forceinline__ bool sigma_ok(double v) { return v >= 0.0 && v < HUGE_VAL; }
+
+__device__ __forceinline__ double face_of(double a, double b, double scale) {
+    return __dmul_rn(__ddiv_rn(__dmul_rn(__dmul_rn(2.0, a), b), __dadd_rn(a, b)), scale);
+}
+
+// the row of cell r: its values in CSR order to out[0 .. count), count returned
+template <bool STAGED>
+__global__ void __launch_bounds__(KAPPA_BLOCK) kappa_values_kernel(KappaValuesArgs a) {
+    __shared__ double stage[STAGED ? 7 * KAPPA_BLOCK : 1];
+    const KappaGrid g = a.g;
+    const int64_t n = int64_t(g.nx) * g.ny * g.nz;
+    const int64_t r0 = blockIdx.x * int64_t(KAPPA_BLOCK);
+    const int64_t r = r0 + threadIdx.x;
+    int64_t base = 0;
+    if (STAGED) {
+        int i0, j0, k0;
+        cell_of(g, r0, i0, j0, k0);
+        base = row_start(g, r0, i0, j0, k0);
+    }
+    if (r < n) {
+        int i, j, k;
+        cell_of(g, r, i, j, k);
+        const int64_t px = g.nx + 2, pxy = px * (g.ny + 2);
+        const int64_t c = int64_t(k + 1) * pxy + int64_t(j + 1) * px + (i + 1);
+        const double kc = a.kappa[c];
+        unsigned long long bad = ~0ull;
+        if (!kappa_ok(kc)) bad = 2ull * (unsigned long long)c;
+        // the six faces in the order of the diagonal's sum: -K, -J, -I, +I, +J, +K
+        const int64_t off[6] = {-pxy, -px, -1, 1, px, pxy};
+        const bool inside[6] = {k > 0, j > 0, i > 0, i + 1 < g.nx, j + 1 < g.ny, k + 1 < g.nz};
+        const int wall[6] = {0, 2, 4, 5, 3, 1};
+        const int axis[6] = {0, 1, 2, 2, 1, 0};
+        double w[6];
+#pragma unroll
+        for (int e = 0; e < 6; ++e) {
+            if (!inside[e] && a.neumann[wall[e]]) { w[e] = 0.0; continue; }
+            const double kn = a.kappa[c + off[e]];
+            // (an inner neighbour is checked by its own thread; a ghost cell by the thread of the cell it bounds)
+            if (!inside[e] && !kappa_ok(kn)) {
+                const unsigned long long key = 2ull * (unsigned long long)(c + off[e]);
+                bad = key < bad ? key : bad;
+            }
+            w[e] = face_of(kc, kn, a.scale[axis[e]]);
+        }
+        double d = __dadd_rn(__dadd_rn(__dadd_rn(__dadd_rn(__dadd_rn(w[0], w[1]), w[2]), w[3]), w[4]), w[5]);
+        if (a.sigma_kind != OMG_SIGMA_NONE) {
+            const double s = a.sigma ? a.sigma[a.sigma_kind == OMG_SIGMA_FIELD ? r : 0] : a.sigma_value;
+            if (!sigma_ok(s)) {
+                const unsigned long long key = 2ull * (unsigned long long)c + 1ull;
+                bad = key < bad ? key : bad;
+            }
+            d = __dadd_rn(d, s);
+        }
+        if (bad != ~0ull) atomicMin(a.err, bad);
+        const int64_t p = row_start(g, r, i, j, k);
+        double *out = STAGED ? stage + (p - base) : a.data + p;
+        int q = 0;
+#pragma unroll
+        for (int e = 0; e < 3; ++e)
+            if (inside[e]) out[q++] = -w[e];
+        out[q++] = d;
+#pragma unroll
+        for (int e = 3; e < 6; ++e)
+            if (inside[e]) out[q++] = -w[e];
+    }
+    if (STAGED) {
+        __syncthreads();
+        const int64_t r1 = r0 + KAPPA_BLOCK < n ? r0 + KAPPA_BLOCK : n;
+        int64_t end;
+        if (r1 == n) {
+            end = 7 * n - 2 * (int64_t(g.nx) * g.ny + int64_t(g.nx) * g.nz + int64_t(g.ny) * g.nz);
+        } else {
+            int i1, j1, k1;
+            cell_of(g, r1, i1, j1, k1);
+            end = row_start(g, r1, i1, j1, k1);
+        }
+        const int count = int(end - base);                      // <= 7 * KAPPA_BLOCK
+        for (int t = threadIdx.x; t < count; t += KAPPA_BLOCK) a.data[base + t] = stage[t];
+    }
+}
+
+// OMG_KAPPA_STAGE=0|1: the workgroup's values straight from the threads, or through LDS at unit stride (the default: DESIGN.md §5q)
+bool kappa_staged() {
+    static const bool v = [] { const char *e = getenv("OMG_KAPPA_STAGE"); return !(e && e[0] == '0'); }();
+    return v;
+}
+
+bool finite_pos(double v) { return v > 0.0 && v < HUGE_VAL; }
+
+}  // namespace
+
+int64_t kappa_nnz(int nx, int ny, int nz) {
+    const int64_t n = int64_t(nx) * ny * nz;
+    return 7 * n - 2 * (int64_t(nx) * ny + int64_t(nx) * nz + int64_t(ny) * nz);
+}
+
+void kappa_pattern(int nx, int ny, int nz, int32_t *indptr, int32_t *indices, hipStream_t s) {
+    const int64_t n = int64_t(nx) * ny * nz;
+    const KappaGrid g = {nx, ny, nz};
+    hipLaunchKernelGGL(kappa_pattern_kernel, dim3((unsigned)((n + 1 + KAPPA_BLOCK - 1) / KAPPA_BLOCK)), dim3(KAPPA_BLOCK), 0, s, g, indptr, indices);
+    OMG_HIP(hipGetLastError());
+}
+
+void KappaField::prepare(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls, const double *sigma, int kind,
+                         int sigma_on_device, const double *scale_in, hipStream_t s) {
+    OMG_REQUIRE(shape && kappa, "kappa: null argument");
+    for (int d = 0; d < 3; ++d)
+        OMG_REQUIRE(shape[d] >= 1 && shape[d] < (int64_t(1) << 30), "kappa: every extent of the shape must be >= 1");
+    nz = int(shape[0]); ny = int(shape[1]); nx = int(shape[2]);
+    const int64_t padded = int64_t(nz + 2) * (ny + 2) * (nx + 2);
+    OMG_REQUIRE(7 * int64_t(nx) * ny * nz < (int64_t(1) << 31) - 1 && padded < (int64_t(1) << 31) - 1,
+                "kappa: operator too large for int32 indices");
+    for (int f = 0; f < 6; ++f) {
+        const int wv = walls ? walls[f] : OMG_WALL_DIRICHLET;
+        OMG_REQUIRE(wv == OMG_WALL_DIRICHLET || wv == OMG_WALL_NEUMANN, "kappa: a wall must be OMG_WALL_DIRICHLET or OMG_WALL_NEUMANN");
+        neumann[f] = wv == OMG_WALL_NEUMANN;
+    }
+    for (int d = 0; d < 3; ++d) {
+        scale[d] = scale_in ? scale_in[d] : 1.0;
+        OMG_REQUIRE(finite_pos(scale[d]), "kappa: every scale factor must be finite and > 0");
+    }
+    OMG_REQUIRE(kind == OMG_SIGMA_NONE || kind == OMG_SIGMA_SCALAR || kind == OMG_SIGMA_FIELD, "kappa: sigma_kind must be one of OMG_SIGMA_*");
+    OMG_REQUIRE(kind == OMG_SIGMA_NONE || sigma, "kappa: sigma is null");
+    sigma_kind = kind;
+    sigma_dev = nullptr;
+    sigma_value = 0.0;
+    if (kind == OMG_SIGMA_SCALAR && !sigma_on_device) {
+        sigma_value = sigma[0];
+        OMG_REQUIRE(sigma_value >= 0.0 && sigma_value < HUGE_VAL, "kappa: sigma must be finite and >= 0");
+    } else if (kind != OMG_SIGMA_NONE) {
+        if (sigma_on_device) {
+            sigma_dev = sigma;
+        } else {
+            own_sigma.alloc(size_t(nx) * ny * nz);
+            own_sigma.upload(sigma, size_t(nx) * ny * nz, s);
+            sigma_dev = own_sigma.p;
+        }
+    }
+    if (kappa_on_device) {
+        kappa_dev = kappa;
+    } else {
+        own_kappa.alloc(size_t(padded));
+        own_kappa.upload(kappa, size_t(padded), s);
+        kappa_dev = own_kappa.p;
+    }
+    if (!err.p) err.alloc(1);
+}
+
+void KappaField::values(double *data, hipStream_t s, const char *entry) {
+    KappaValuesArgs a;
+    a.g = {nx, ny, nz};
+    a.kappa = kappa_dev;
+    a.sigma = sigma_dev;
+    a.sigma_value = sigma_value;
+    a.sigma_kind = sigma_kind;
+    for (int f = 0; f < 6; ++f) a.neumann[f] = neumann[f];
+    for (int d = 0; d < 3; ++d) a.scale[d] = scale[d];
+    a.data = data;
+    a.err = err.p;
+    const int64_t n = int64_t(nx) * ny * nz;
+    const dim3 grid((unsigned)((n + KAPPA_BLOCK - 1) / KAPPA_BLOCK));
+    OMG_HIP(hipMemsetAsync(err.p, 0xFF, sizeof(unsigned long long), s));
+    if (kappa_staged()) hipLaunchKernelGGL(kappa_values_kernel<true>, grid, dim3(KAPPA_BLOCK), 0, s, a);
+    else hipLaunchKernelGGL(kappa_values_kernel<false>, grid, dim3(KAPPA_BLOCK), 0, s, a);
+    OMG_HIP(hipGetLastError());
+    unsigned long long e = ~0ull;
+    OMG_HIP(hipMemcpyAsync(&e, err.p, sizeof(e), hipMemcpyDeviceToHost, s));
+    OMG_HIP(hipStreamSynchronize(s));
+    if (e == ~0ull) return;
+    // the key names a cell of the padded field: as a cell of the grid, a ghost cell has a coordinate of -1 or the extent
+    const int64_t c = int64_t(e >> 1), px = nx + 2, pxy = px * (ny + 2);
+    const long long z = (long long)(c / pxy) - 1, y = (long long)((c / px) % (ny + 2)) - 1, x = (long long)(c % px) - 1;
+    const std::string cell = "cell (" + std::to_string(z) + ", " + std::to_string(y) + ", " + std::to_string(x) + ")";
+    if (e & 1) throw Error(OMG_ERR_INVALID, std::string(entry) + ": sigma at " + cell + " is not finite and >= 0");
+    throw Error(OMG_ERR_INVALID, std::string(entry) + ": kappa at " + cell + " is not finite and > 0");
+}
+
+}  // namespace omg

@@ -785,11 +785,19 @@ HostCsr download_csr(const DevCsrPlain &M, hipStream_t s) {
 void galerkin_chain_device(const omg_csr &A0, int dim, const int64_t *shape, int n_restrictions, std::vector<DevCsrPlain> &A,
                            std::vector<DevCsrPlain> &R, hipStream_t s) {
     OMG_REQUIRE(dim >= 1 && dim <= 3 && n_restrictions >= 1, "bad argument");
+    DevCsrPlain fine;
+    { SetupTimer tm("device setup: upload the fine operator"); upload(fine, A0, s); OMG_HIP(hipStreamSynchronize(s)); }
+    galerkin_chain_device(std::move(fine), dim, shape, n_restrictions, A, R, s);
+}
+
+void galerkin_chain_device(DevCsrPlain &&A0, int dim, const int64_t *shape, int n_restrictions, std::vector<DevCsrPlain> &A,
+                           std::vector<DevCsrPlain> &R, hipStream_t s) {
+    OMG_REQUIRE(dim >= 1 && dim <= 3 && n_restrictions >= 1, "bad argument");
     A.clear();
     R.clear();
     A.resize(size_t(n_restrictions) + 1);
     R.resize(size_t(n_restrictions));
-    { SetupTimer tm("device setup: upload the fine operator"); upload(A[0], A0, s); OMG_HIP(hipStreamSynchronize(s)); }
+    A[0] = std::move(A0);
     int64_t ext[3] = {1, 1, 1};
     for (int d = 0; d < dim; ++d) ext[d] = shape[d];
     for (int l = 0; l < n_restrictions; ++l) {

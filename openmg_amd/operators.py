@@ -350,6 +350,105 @@ def stencil7_variable(shape, seed=2024):
     return A
 
 
+WALLS = ("dirichlet", "neumann")       # OMG_WALL_DIRICHLET, OMG_WALL_NEUMANN
+
+
+def kappa_arguments(kappa_shape, walls=None, sigma=None, scale=(1.0, 1.0, 1.0)):
+    """What stencil7_kappa, _hip.kappa_assemble and Solver.from_kappa check of their arguments besides the fields' values:
+    (problemShape, wall codes -z +z -y +y -x +x, scale z y x); ValueError for a kappa that is not 3-D with a ghost layer,
+    an unknown wall, a scale factor that is not finite and > 0, a scalar sigma that is not finite and >= 0, a sigma field
+    of another shape than problemShape (a field's values are the caller's to check: on the host here, on the device by
+    the kernel that reads them)."""
+    kappa_shape = tuple(int(s) for s in kappa_shape)
+    if len(kappa_shape) != 3 or min(kappa_shape) < 3:
+        raise ValueError("kappa must be 3-D with one ghost layer, shape (nz + 2, ny + 2, nx + 2), not %r" % (kappa_shape,))
+    shape = tuple(s - 2 for s in kappa_shape)
+    walls = ("dirichlet",) * 6 if walls is None else tuple(walls)
+    if len(walls) != 6 or any(not isinstance(w, str) or w not in WALLS for w in walls):
+        raise ValueError("walls must be six of 'dirichlet' / 'neumann' in the order -z, +z, -y, +y, -x, +x, not %r" % (walls,))
+    try:
+        scale = tuple(float(f) for f in scale)
+    except (TypeError, ValueError):
+        raise ValueError("scale must be three numbers (z, y, x), not %r" % (scale,))
+    if len(scale) != 3 or any(not (np.isfinite(f) and f > 0.0) for f in scale):
+        raise ValueError("scale must be three finite factors > 0 (z, y, x), not %r" % (scale,))
+    if sigma is not None and np.ndim(sigma) == 0 and not hasattr(sigma, "__cuda_array_interface__"):
+        try:
+            value = float(sigma)
+        except (TypeError, ValueError):
+            raise ValueError("sigma must be None, a number >= 0 or an array of problemShape, not %r" % (sigma,))
+        if not (np.isfinite(value) and value >= 0.0):
+            raise ValueError("sigma must be finite and >= 0, not %r" % (sigma,))
+    elif sigma is not None:
+        s_shape = tuple(int(s) for s in (sigma.__cuda_array_interface__["shape"] if hasattr(sigma, "__cuda_array_interface__")
+                                          and not isinstance(sigma, np.ndarray) else np.shape(sigma)))
+        if s_shape != shape:
+            raise ValueError("a sigma field must have problemShape %r, not %r" % (shape, s_shape))
+    return shape, tuple(WALLS.index(w) for w in walls), scale
+
+
+def stencil7_kappa(kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0)):
+    """7-point operator of -div(kappa grad u) + sigma u from a coefficient field (NOT in the reference; the definition the
+    device assembly — _hip.kappa_assemble, Solver.from_kappa — is pinned to bit for bit): cell-centred finite volumes on a
+    box of (nz, ny, nx) cells.  kappa: float64 (nz + 2, ny + 2, nx + 2), the cells and one ghost layer, as
+    stencil7_variable draws it.  walls: six of 'dirichlet' (default) / 'neumann' in the order -z, +z, -y, +y, -x, +x.
+    sigma: None, a scalar or an array of problemShape, >= 0.  scale: one factor per axis (z, y, x), e.g. dt / h_axis^2.
+
+    Every operation is rounded once in double: face(a, b) = ((2 a) b) / (a + b), c = face * scale[axis], the off-diagonal
+    entry is -c, the diagonal (((((c-K + c-J) + c-I) + c+I) + c+J) + c+K), then + sigma.  The face at a Dirichlet wall takes
+    the ghost cell's kappa and enters the diagonal only; at a Neumann wall it contributes +0.0.  With the defaults and
+    stencil7_variable's kappa this is stencil7_variable's matrix bit for bit.  C-order numbering, sorted CSR, int32 indices.
+
+    ValueError: kappa of another rank or without cells, not finite or <= 0 in a cell or in a ghost cell behind a
+    Dirichlet wall; sigma negative or not finite; scale not finite or <= 0; an unknown wall."""
+    kap = np.asarray(kappa)
+    if kap.dtype != np.float64:
+        raise ValueError("kappa must be float64, not %s" % kap.dtype)
+    shape, wall, scale = kappa_arguments(kap.shape, walls, sigma, scale)
+    nz, ny, nx = shape
+    c = kap[1:-1, 1:-1, 1:-1]
+    # (dz, dy, dx) -> (neighbour's kappa, axis, wall); in the order of the diagonal's sum
+    dirs = [((-1, 0, 0), kap[:-2, 1:-1, 1:-1], 0, 0), ((0, -1, 0), kap[1:-1, :-2, 1:-1], 1, 2), ((0, 0, -1), kap[1:-1, 1:-1, :-2], 2, 4),
+            ((0, 0, 1), kap[1:-1, 1:-1, 2:], 2, 5), ((0, 1, 0), kap[1:-1, 2:, 1:-1], 1, 3), ((1, 0, 0), kap[2:, 1:-1, 1:-1], 0, 1)]
+
+    def ghost(d, a):                                      # the ghost cells a face of the box reads: one layer of `a`
+        sel = [slice(None)] * 3
+        sel[[abs(v) for v in d].index(1)] = 0 if sum(d) < 0 else -1
+        return a[tuple(sel)]
+    checked = [c] + [ghost(d, nb) for d, nb, _, f in dirs if wall[f] == 0]
+    if any(not (np.isfinite(a).all() and (a > 0.0).all()) for a in checked):
+        raise ValueError("kappa must be finite and > 0 in every cell and in the ghost cells behind Dirichlet walls")
+    sig = None
+    if sigma is not None:
+        sig = np.asarray(sigma, dtype=np.float64)
+        if not (np.isfinite(sig).all() and (sig >= 0.0).all()):
+            raise ValueError("sigma must be finite and >= 0")
+    w = {}
+    with np.errstate(all="ignore"):                       # (ghost cells behind Neumann walls hold anything: their faces are replaced)
+        for d, nb, axis, f in dirs:
+            face = ((2.0 * c) * nb) / (c + nb) * scale[axis]
+            if wall[f] == 1:
+                face = face.copy()
+                ghost(d, face)[...] = 0.0
+            w[d] = face
+    diag = ((((w[(-1, 0, 0)] + w[(0, -1, 0)]) + w[(0, 0, -1)]) + w[(0, 0, 1)]) + w[(0, 1, 0)]) + w[(1, 0, 0)]
+    if sig is not None:
+        diag = diag + sig
+    n = nx * ny * nz
+    idx = np.arange(n, dtype=np.int64).reshape(nz, ny, nx)
+    rows, cols, vals = [idx.ravel()], [idx.ravel()], [diag.ravel()]
+    for (dz, dy, dx), ww in w.items():
+        sel = (slice(max(0, -dz), nz - max(0, dz)), slice(max(0, -dy), ny - max(0, dy)), slice(max(0, -dx), nx - max(0, dx)))
+        rows.append(idx[sel].ravel())
+        cols.append((idx[sel] + (dz * ny + dy) * nx + dx).ravel())
+        vals.append(-ww[sel].ravel())
+    A = sp.csr_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(n, n))
+    A.sort_indices()
+    A.indices = A.indices.astype(np.int32)
+    A.indptr = A.indptr.astype(np.int32)
+    return A
+
+
 def stencil27_variable(shape, seed=2024, rows=None):
     """27-point variable-coefficient operator of BASELINE.json configs[4] as SURVEY.md 8(d)
     specifies it (NOT in the reference): Q1 finite-element stiffness of -div(kappa grad u) on a
