@@ -218,6 +218,28 @@ int omg_hierarchy_create_from_kappa(const int64_t *shape, const double *kappa, i
  * and iterate stay. */
 int omg_hierarchy_update_kappa(omg_hierarchy *h, const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls,
                                const double *sigma, int sigma_kind, int sigma_on_device, const double *scale);
+/* The same three on a stretched tensor-product grid: hz, hy, hx — HOST memory, nz + 2, ny + 2 and nx + 2
+ * doubles — are the cell widths along each axis with one ghost entry at each end, like kappa's ghost layer.  The operator is
+ * the volume-integrated one (symmetric; the right-hand side is f times the cell volume); with a, da the cell's own kappa and
+ * width along the face's axis and b, db the neighbour's, every operation rounded once in double and nothing contracted:
+ *     c = (((2 a) b) / (da b + db a)) area[axis],  area_z = hy[j] hx[i], area_y = hz[k] hx[i], area_x = hz[k] hy[j],
+ *     off-diagonal entry -c,  diagonal (((((c-K + c-J) + c-I) + c+I) + c+J) + c+K), then + sigma ((hz[k] hy[j]) hx[i]).
+ * A Dirichlet wall face takes the ghost cell's kappa and the ghost width (0: the value sits on the wall face itself; the
+ * boundary cell's width: at the mirrored cell centre) and enters the diagonal only; a Neumann wall face is +0.0 and reads
+ * neither.  The result is operators.stencil7_kappa(..., spacing = (hz, hy, hx))'s matrix bit for bit.
+ * hz = hy = hx = NULL: the entry without widths.  Some but not all NULL, or widths together with a scale that is neither NULL
+ * nor all ones: OMG_ERR_INVALID.  An interior width that is not finite and > 0 or a ghost width that is not finite and >= 0:
+ * OMG_ERR_INVALID naming the axis and the index (-1 or the extent for a ghost entry), before any launch. */
+int omg_kappa_assemble_spaced(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls, const double *sigma,
+                              int sigma_kind, int sigma_on_device, const double *scale, const double *hz, const double *hy,
+                              const double *hx, int32_t *indptr, int32_t *indices, double *data, int out_on_device);
+int omg_hierarchy_create_from_kappa_spaced(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls,
+                                           const double *sigma, int sigma_kind, int sigma_on_device, const double *scale,
+                                           const double *hz, const double *hy, const double *hx, int n_restrictions,
+                                           const omg_hierarchy_options *opt, omg_hierarchy **out);
+int omg_hierarchy_update_kappa_spaced(omg_hierarchy *h, const int64_t *shape, const double *kappa, int kappa_on_device,
+                                      const int *walls, const double *sigma, int sigma_kind, int sigma_on_device, const double *scale,
+                                      const double *hz, const double *hy, const double *hx);
 int omg_hierarchy_dtype(const omg_hierarchy *h, int *dtype);
 int omg_hierarchy_destroy(omg_hierarchy *h);
 /* Run on a caller-owned hipStream_t instead of the hierarchy's own stream (NULL = own). */

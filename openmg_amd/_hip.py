@@ -77,6 +77,9 @@ SIGNATURES = {
     "omg_kappa_assemble": (_I, [_I64P, _P, _I, _IP, _P, _I, _I, _DP, _P, _P, _P, _I]),
     "omg_hierarchy_create_from_kappa": (_I, [_I64P, _P, _I, _IP, _P, _I, _I, _DP, _I, _OPT, _PP]),
     "omg_hierarchy_update_kappa": (_I, [_P, _I64P, _P, _I, _IP, _P, _I, _I, _DP]),
+    "omg_kappa_assemble_spaced": (_I, [_I64P, _P, _I, _IP, _P, _I, _I, _DP, _P, _P, _P, _P, _P, _P, _I]),
+    "omg_hierarchy_create_from_kappa_spaced": (_I, [_I64P, _P, _I, _IP, _P, _I, _I, _DP, _P, _P, _P, _I, _OPT, _PP]),
+    "omg_hierarchy_update_kappa_spaced": (_I, [_P, _I64P, _P, _I, _IP, _P, _I, _I, _DP, _P, _P, _P]),
     "omg_resident_norms": (_I, [_P, _DP, _DP]),
     "omg_hierarchy_destroy": (_I, [_P]),
     "omg_hierarchy_set_stream": (_I, [_P, _P]),
@@ -385,10 +388,13 @@ class KappaArgs:
     (include/openmg_hip.h) from what the Python entries take: kappa a float64 array (nz + 2, ny + 2, nx + 2), NumPy or a
     C-contiguous device array (__cuda_array_interface__); walls, sigma, scale as operators.stencil7_kappa takes them, sigma
     a device array too.  ValueError for what operators.kappa_arguments refuses — before any device work; the fields' values
-    are checked by the kernel that reads them (HipError, ERR_INVALID, naming the cell).  .grid: problemShape; .shape: the
-    operator's (n, n); .call: the C arguments from `shape` to `scale`; the object keeps the arrays alive."""
+    are checked by the kernel that reads them (HipError, ERR_INVALID, naming the cell).  spacing: None, or the cell widths
+    (hz, hy, hx) of a stretched grid as operators.spacing_arguments takes them — host arrays, in place of scale.  .grid:
+    problemShape; .shape: the operator's (n, n); .spacing: the checked widths or None; .call: the C arguments of the
+    *_spaced entries from `shape` to `hx` (three NULLs without widths: the entries without them); the object keeps the
+    arrays alive."""
 
-    def __init__(self, kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0)):
+    def __init__(self, kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0), spacing=None):
         from . import _devarray, operators
         if isinstance(kappa, KappaArgs):           # (already checked: Hierarchy.from_kappa / update_kappa take one as it is)
             self.__dict__.update(kappa.__dict__)
@@ -403,6 +409,11 @@ class KappaArgs:
             kappa = np.ascontiguousarray(kappa)
             k_shape = kappa.shape
         self.grid, self.walls, self.scale = operators.kappa_arguments(k_shape, walls, sigma, scale)
+        self.spacing = None
+        if spacing is not None:
+            if not operators.unit_scale(self.scale):
+                raise ValueError("spacing and scale exclude each other: the widths carry every factor")
+            self.spacing = operators.spacing_arguments(self.grid, spacing)
         self.n = int(np.prod(self.grid))
         self.shape = (self.n, self.n)
         nz, ny, nx = self.grid
@@ -424,8 +435,9 @@ class KappaArgs:
         k_ptr = _devarray.address(kappa, padded, "kappa") if k_dev else kappa.ctypes.data
         self.on_device = k_dev or s_dev
         self._keep = (kappa, sigma)
+        widths = (None,) * 3 if self.spacing is None else tuple(h.ctypes.data for h in self.spacing)
         self.call = ((ctypes.c_int64 * 3)(*self.grid), ctypes.c_void_p(k_ptr), int(k_dev), (ctypes.c_int * 6)(*self.walls),
-                     ctypes.c_void_p(s_ptr), kind, int(s_dev), (ctypes.c_double * 3)(*self.scale))
+                     ctypes.c_void_p(s_ptr), kind, int(s_dev), (ctypes.c_double * 3)(*self.scale)) + tuple(ctypes.c_void_p(p) for p in widths)
 
     def matrix(self):
         """The operator as a SciPy CSR in host memory, assembled on the device (kappa_assemble)."""
@@ -440,14 +452,15 @@ class KappaArgs:
             check(lib().omg_device_synchronize())
 
 
-def kappa_assemble(kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0), pattern=True, out=None):
-    """The 7-point operator of a coefficient field, assembled on the device (omg_kappa_assemble): the CSR arrays of
-    operators.stencil7_kappa(kappa, walls, sigma, scale), bit for bit.  kappa, sigma: NumPy arrays or device arrays.
+def kappa_assemble(kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0), pattern=True, out=None, spacing=None):
+    """The 7-point operator of a coefficient field, assembled on the device (omg_kappa_assemble_spaced): the CSR arrays of
+    operators.stencil7_kappa(kappa, walls, sigma, scale, spacing), bit for bit.  kappa, sigma: NumPy arrays or device arrays;
+    spacing: host arrays.
     Returns (indptr, indices, data) as NumPy arrays, indptr = indices = None with pattern=False (the values alone).
     out = (indptr, indices, data): device arrays to write into instead — int32 (n + 1), int32 (nnz), float64 (nnz); the
     first two None for the values alone — and returned as they are."""
     from . import _devarray
-    a = KappaArgs(kappa, walls, sigma, scale)
+    a = KappaArgs(kappa, walls, sigma, scale, spacing)
     if out is not None:
         d_indptr, d_indices, d_data = out
         if (d_indptr is None) != (d_indices is None):
@@ -462,14 +475,14 @@ def kappa_assemble(kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0), pattern
         p_indices = None if d_indices is None else int32_address(d_indices, a.nnz, "indices")
         p_data = _devarray.address(d_data, a.nnz, "out: data")
         check(lib().omg_device_synchronize())
-        check(lib().omg_kappa_assemble(*a.call, ctypes.c_void_p(p_indptr), ctypes.c_void_p(p_indices), ctypes.c_void_p(p_data), 1))
+        check(lib().omg_kappa_assemble_spaced(*a.call, ctypes.c_void_p(p_indptr), ctypes.c_void_p(p_indices), ctypes.c_void_p(p_data), 1))
         return out
     data = np.empty(a.nnz, dtype=np.float64)
     indptr = np.empty(a.n + 1, dtype=np.int32) if pattern else None
     indices = np.empty(a.nnz, dtype=np.int32) if pattern else None
     a.synchronize()
-    check(lib().omg_kappa_assemble(*a.call, indptr.ctypes.data if pattern else None, indices.ctypes.data if pattern else None,
-                                   data.ctypes.data, 0))
+    check(lib().omg_kappa_assemble_spaced(*a.call, indptr.ctypes.data if pattern else None, indices.ctypes.data if pattern else None,
+                                          data.ctypes.data, 0))
     return indptr, indices, data
 
 
@@ -597,14 +610,14 @@ class Hierarchy:
 
     @classmethod
     def from_kappa(cls, kappa, n_restrictions, walls=None, sigma=None, scale=(1.0, 1.0, 1.0), smoother="gs", omega=1.0,
-                   dtype="float64", nullspace=None):
-        """from_fine of operators.stencil7_kappa(kappa, walls, sigma, scale) without that matrix ever being on the host
-        (omg_hierarchy_create_from_kappa): level 0 is assembled in HBM from the field — a NumPy array or a device array —,
+                   dtype="float64", nullspace=None, spacing=None):
+        """from_fine of operators.stencil7_kappa(kappa, walls, sigma, scale, spacing) without that matrix ever being on the
+        host (omg_hierarchy_create_from_kappa_spaced): level 0 is assembled in HBM from the field — a NumPy array or a device array —,
         the rest is from_fine's own sequence, the result the same object bit for bit."""
         self = cls.__new__(cls)
         self._h = None
         self.nullspace_kind = nullspace_code(nullspace)
-        a = KappaArgs(kappa, walls, sigma, scale)
+        a = KappaArgs(kappa, walls, sigma, scale, spacing)
         self.smoother = smoother_code(smoother)
         self.omega = float(omega)
         self.dtype = dtype_code(dtype)
@@ -613,19 +626,19 @@ class Hierarchy:
         h = ctypes.c_void_p()
         opt = HierarchyOptions(self.smoother, self.omega, self.dtype, self.nullspace_kind)
         a.synchronize()
-        check(lib().omg_hierarchy_create_from_kappa(*a.call, int(n_restrictions), ctypes.byref(opt), ctypes.byref(h)))
+        check(lib().omg_hierarchy_create_from_kappa_spaced(*a.call, int(n_restrictions), ctypes.byref(opt), ctypes.byref(h)))
         self._h = h
         self._A = self._R = None
         return self
 
-    def update_kappa(self, kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0)):
-        """update_fine with the values of operators.stencil7_kappa(kappa, walls, sigma, scale), made on the device
-        (omg_hierarchy_update_kappa): with device arrays nothing crosses to the host.  Takes the hierarchies update_fine
+    def update_kappa(self, kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0), spacing=None):
+        """update_fine with the values of operators.stencil7_kappa(kappa, walls, sigma, scale, spacing), made on the device
+        (omg_hierarchy_update_kappa_spaced): with device arrays nothing crosses to the host.  Takes the hierarchies update_fine
         takes whose level 0 is the 7-point operator on kappa's grid (HipError ERR_INVALID otherwise, and for a kappa or
         sigma out of range — the hierarchy is then as before)."""
-        a = KappaArgs(kappa, walls, sigma, scale)
+        a = KappaArgs(kappa, walls, sigma, scale, spacing)
         a.synchronize()
-        check(lib().omg_hierarchy_update_kappa(self._h, *a.call))
+        check(lib().omg_hierarchy_update_kappa_spaced(self._h, *a.call))
 
     def can_update_fine(self):
         """Whether update_fine takes this hierarchy (omg_hierarchy_can_update_fine)."""

@@ -86,19 +86,22 @@ class Solver:
         self.parameters = completed
         self._pattern_of(A_in)
 
-    _kappa = None              # from_kappa: (problemShape, walls, scale) of construction, else None
+    _kappa = None              # from_kappa: (problemShape, walls, scale, spacing) of construction, else None
 
     @classmethod
-    def from_kappa(cls, kappa, parameters, walls=None, sigma=None, scale=(1.0, 1.0, 1.0)):
-        """The Solver of operators.stencil7_kappa(kappa, walls, sigma, scale) — same bits — from the coefficient field
-        itself: kappa float64 (nz + 2, ny + 2, nx + 2), the cells and one ghost layer, and sigma (None, a scalar, an array
-        of problemShape) as NumPy arrays or device arrays.  parameters['problemShape'] is taken from kappa; if given it
+    def from_kappa(cls, kappa, parameters, walls=None, sigma=None, scale=(1.0, 1.0, 1.0), spacing=None):
+        """The Solver of operators.stencil7_kappa(kappa, walls, sigma, scale, spacing) — same bits — from the coefficient
+        field itself: kappa float64 (nz + 2, ny + 2, nx + 2), the cells and one ghost layer, and sigma (None, a scalar, an
+        array of problemShape) as NumPy arrays or device arrays.  spacing: None, or the cell widths (hz, hy, hx) of a
+        stretched tensor-product grid (operators.spacing_arguments: host arrays, in place of scale); the operator is then the
+        volume-integrated one and the right-hand side f * operators.cell_volumes(spacing); the widths are kept for
+        update_kappa and have no say in the route.  parameters['problemShape'] is taken from kappa; if given it
         must agree.  Where the setup takes the plain device route (the colour smoother, no giveInfo / verbose / dense, no
         'coarsening' / 'oddExtents', a shape the device setup takes) level 0 is assembled in HBM and no host matrix is ever
         made; with any other parameters the operator is assembled on the device into host arrays and the setup runs as for
         any A_in.  ValueError for bad arguments before any device work; a kappa or sigma value out of range: HipError
         (ERR_INVALID) naming the first such cell."""
-        source = _hip.KappaArgs(kappa, walls, sigma, scale)
+        source = _hip.KappaArgs(kappa, walls, sigma, scale, spacing)
         given = dict(parameters)
         if given.get("problemShape") is not None:
             try:
@@ -109,7 +112,7 @@ class Solver:
                 raise ValueError("parameters['problemShape'] = %r is not kappa's grid %r" % (given["problemShape"], source.grid))
         given["problemShape"] = source.grid
         self = cls(source, given)
-        self._kappa = (source.grid, walls, scale)
+        self._kappa = (source.grid, walls, scale, source.spacing)
         return self
 
     def _pattern_of(self, A_in):
@@ -291,16 +294,16 @@ class Solver:
         h.close()
 
     def update_kappa(self, kappa, sigma=None):
-        """update() with the operator of a new coefficient field (and sigma), for a Solver made by from_kappa; walls and
-        scale are those of construction.  Where the hierarchy takes new coefficients in place the values are made on the
+        """update() with the operator of a new coefficient field (and sigma), for a Solver made by from_kappa; walls,
+        scale and spacing are those of construction.  Where the hierarchy takes new coefficients in place the values are made on the
         device and go straight into update_fine — with device arrays nothing crosses to the host; otherwise the operator
         is assembled into host arrays and a new hierarchy built as update() does.  Either way later solves have the bits of
         a fresh Solver.from_kappa(kappa, parameters, ...).  A refused field leaves the solver with the old operator."""
         h = self._open()
         if self._kappa is None:
             raise ValueError("Solver.update_kappa: the solver was not made by Solver.from_kappa")
-        grid, walls, scale = self._kappa
-        source = _hip.KappaArgs(kappa, walls, sigma, scale)
+        grid, walls, scale, spacing = self._kappa
+        source = _hip.KappaArgs(kappa, walls, sigma, scale, spacing)
         if source.grid != grid:
             raise ValueError("Solver.update_kappa: kappa's grid %r is not the solver's %r" % (source.grid, grid))
         if h.can_update_fine():

@@ -841,11 +841,14 @@ struct KappaField {
     int sigma_kind = 0;
     int neumann[6] = {0, 0, 0, 0, 0, 0};
     double scale[3] = {1.0, 1.0, 1.0};
+    bool spaced = false;             // per-axis cell widths instead of the scale factors
     DevBuf<double> own_kappa, own_sigma;
+    DevBuf<double> widths;           // spaced: hz (nz + 2), hy (ny + 2), hx (nx + 2) one after the other
     DevBuf<unsigned long long> err;
-    // shape (nz, ny, nx); walls / scale may be null (all Dirichlet / 1); OMG_ERR_INVALID for anything the header refuses
+    // shape (nz, ny, nx); walls / scale may be null (all Dirichlet / 1); hz, hy, hx: host arrays with one ghost entry at
+    // each end, all three or all null; OMG_ERR_INVALID for anything the header refuses — a bad width naming axis and index
     void prepare(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls, const double *sigma, int sigma_kind,
-                 int sigma_on_device, const double *scale, hipStream_t s);
+                 int sigma_on_device, const double *scale, const double *hz, const double *hy, const double *hx, hipStream_t s);
     // the value array in CSR order to data (device, kappa_nnz doubles); waits for the stream; a kappa or sigma out of
     // range: OMG_ERR_INVALID naming the first such cell, `entry` in front
     void values(double *data, hipStream_t s, const char *entry);

@@ -2694,14 +2694,22 @@ int omg_hierarchy_update_fine(omg_hierarchy *h, const double *data, int64_t nnz,
     });
 }
 
+// (the three entries without widths are the *_spaced ones with hz = hy = hx = NULL)
 int omg_kappa_assemble(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls, const double *sigma, int sigma_kind,
                        int sigma_on_device, const double *scale, int32_t *indptr, int32_t *indices, double *data, int out_on_device) {
+    return omg_kappa_assemble_spaced(shape, kappa, kappa_on_device, walls, sigma, sigma_kind, sigma_on_device, scale, nullptr, nullptr, nullptr,
+                                     indptr, indices, data, out_on_device);
+}
+
+int omg_kappa_assemble_spaced(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls, const double *sigma,
+                              int sigma_kind, int sigma_on_device, const double *scale, const double *hz, const double *hy, const double *hx,
+                              int32_t *indptr, int32_t *indices, double *data, int out_on_device) {
     return guarded([&] {
         OMG_REQUIRE(data, "omg_kappa_assemble: data is null");
         OMG_REQUIRE(!indptr == !indices, "omg_kappa_assemble: indptr and indices are given together or not at all");
         OneShot one;
         KappaField F;
-        F.prepare(shape, kappa, kappa_on_device, walls, sigma, sigma_kind, sigma_on_device, scale, one.s);
+        F.prepare(shape, kappa, kappa_on_device, walls, sigma, sigma_kind, sigma_on_device, scale, hz, hy, hx, one.s);
         const int64_t n = int64_t(F.nx) * F.ny * F.nz, nnz = kappa_nnz(F.nx, F.ny, F.nz);
         DevBuf<double> dv;
         DevBuf<int32_t> dp, di;
@@ -2723,6 +2731,14 @@ int omg_kappa_assemble(const int64_t *shape, const double *kappa, int kappa_on_d
 int omg_hierarchy_create_from_kappa(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls, const double *sigma,
                                     int sigma_kind, int sigma_on_device, const double *scale, int n_restrictions,
                                     const omg_hierarchy_options *opt, omg_hierarchy **out) {
+    return omg_hierarchy_create_from_kappa_spaced(shape, kappa, kappa_on_device, walls, sigma, sigma_kind, sigma_on_device, scale, nullptr,
+                                                  nullptr, nullptr, n_restrictions, opt, out);
+}
+
+int omg_hierarchy_create_from_kappa_spaced(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls,
+                                           const double *sigma, int sigma_kind, int sigma_on_device, const double *scale, const double *hz,
+                                           const double *hy, const double *hx, int n_restrictions, const omg_hierarchy_options *opt,
+                                           omg_hierarchy **out) {
     return guarded([&] {
         OMG_REQUIRE(out, "out is null");
         *out = nullptr;
@@ -2736,7 +2752,7 @@ int omg_hierarchy_create_from_kappa(const int64_t *shape, const double *kappa, i
         {
             OneShot one;
             KappaField F;
-            F.prepare(shape, kappa, kappa_on_device, walls, sigma, sigma_kind, sigma_on_device, scale, one.s);
+            F.prepare(shape, kappa, kappa_on_device, walls, sigma, sigma_kind, sigma_on_device, scale, hz, hy, hx, one.s);
             SetupTimer tm("device setup: the fine operator from kappa");
             A0.n_rows = A0.n_cols = int64_t(F.nx) * F.ny * F.nz;
             A0.nnz = kappa_nnz(F.nx, F.ny, F.nz);
@@ -2760,6 +2776,13 @@ int omg_hierarchy_create_from_kappa(const int64_t *shape, const double *kappa, i
 
 int omg_hierarchy_update_kappa(omg_hierarchy *h, const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls,
                                const double *sigma, int sigma_kind, int sigma_on_device, const double *scale) {
+    return omg_hierarchy_update_kappa_spaced(h, shape, kappa, kappa_on_device, walls, sigma, sigma_kind, sigma_on_device, scale, nullptr, nullptr,
+                                             nullptr);
+}
+
+int omg_hierarchy_update_kappa_spaced(omg_hierarchy *h, const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls,
+                                      const double *sigma, int sigma_kind, int sigma_on_device, const double *scale, const double *hz,
+                                      const double *hy, const double *hx) {
     return guarded([&] {
         const double *vals = nullptr;
         int64_t nnz = 0;
@@ -2769,7 +2792,7 @@ int omg_hierarchy_update_kappa(omg_hierarchy *h, const int64_t *shape, const dou
                         "omg_hierarchy_update_kappa: needs a hierarchy that omg_hierarchy_update_fine takes (omg_hierarchy_can_update_fine) "
                         "whose level 0 is the 7-point operator on the grid `shape`");
             KappaField F;
-            F.prepare(shape, kappa, kappa_on_device, walls, sigma, sigma_kind, sigma_on_device, scale, hh->stream);
+            F.prepare(shape, kappa, kappa_on_device, walls, sigma, sigma_kind, sigma_on_device, scale, hz, hy, hx, hh->stream);
             nnz = kappa_nnz(F.nx, F.ny, F.nz);
             OMG_REQUIRE(nnz == hh->nnz0, "internal: the fine pattern is not the in-grid 7-point pattern");
             if (hh->kappa_vals.n != size_t(nnz)) hh->kappa_vals.alloc(size_t(nnz));

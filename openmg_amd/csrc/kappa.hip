@@ -9,6 +9,15 @@
 //     diagonal   = (((((c-K + c-J) + c-I) + c+I) + c+J) + c+K) (+ sigma)
 // A Dirichlet wall face takes the ghost cell's kappa and enters the diagonal only; a Neumann wall face contributes +0.0.
 //
+// With per-axis cell widths (SPACED, DESIGN.md §5r: a tensor-product grid, the widths hz, hy, hx with one ghost entry at each
+// end like kappa's ghost layer) the operator is the volume-integrated one; a, da the cell's own kappa and width along the
+// face's axis, b, db the neighbour's:
+//     c = (((2 a) b) / (da b + db a)) area[axis]       area_z = hy[j] hx[i], area_y = hz[k] hx[i], area_x = hz[k] hy[j]
+//     diagonal = the same sum, then + sigma ((hz[k] hy[j]) hx[i])
+// The widths are three small arrays in HBM, checked on the host before any launch; a workgroup is 256 consecutive rows, so
+// hy[j], hz[k] and with them area_x are nearly wave-uniform and only hx varies per lane.  A Neumann wall face reads
+// neither the ghost kappa nor the ghost width.
+//
 // The row start is a closed form — 7 r minus the absent neighbours of the rows before r —, so neither kernel scans and
 // kappa_values needs no row pointers.  One thread per row, adjacent lanes on adjacent cells along x: kappa is read once
 // per cell by its own thread, the six neighbours come through the cache (the +-I neighbours are the adjacent lanes' own
@@ -16,6 +25,10 @@
 // stores are 32 - 56 bytes apart from its neighbour's; the staged variant collects the workgroup's rows — one contiguous
 // piece of the value array — in LDS and writes it out at unit stride.
 #include "common.h"
+
+// (This file is compiled with -ffp-contract=off, the Makefile's rule for kappa.hip.o: __dmul_rn / __dadd_rn are plain
+// operators defined in the compiler's header, out of a pragma's reach, and without the flag a product that feeds a sum
+// — da b + db a, the diagonal plus sigma vol — becomes one fused operation, rounded once instead of twice.)
 
 namespace omg {
 
@@ -89,9 +102,20 @@ __device__ __forceinline__ double face_of(double a, double b, double scale) {
     return __dmul_rn(__ddiv_rn(__dmul_rn(__dmul_rn(2.0, a), b), __dadd_rn(a, b)), scale);
 }
 
+// SPACED: the padded width arrays behind the unspaced arguments (whose kernels keep their argument block as it is)
+struct KappaSpacedArgs : KappaValuesArgs {
+    const double *hz, *hy, *hx;   // nz + 2, ny + 2, nx + 2
+};
+template <bool SPACED> using kappa_args_t = std::conditional_t<SPACED, KappaSpacedArgs, KappaValuesArgs>;
+
+__device__ __forceinline__ double face_spaced(double a, double b, double da, double db, double area) {
+    const double den = __dadd_rn(__dmul_rn(da, b), __dmul_rn(db, a));
+    return __dmul_rn(__ddiv_rn(__dmul_rn(__dmul_rn(2.0, a), b), den), area);
+}
+
 // the row of cell r: its values in CSR order to out[0 .. count), count returned
-template <bool STAGED>
-__global__ void __launch_bounds__(KAPPA_BLOCK) kappa_values_kernel(KappaValuesArgs a) {
+template <bool STAGED, bool SPACED>
+__global__ void __launch_bounds__(KAPPA_BLOCK) kappa_values_kernel(kappa_args_t<SPACED> a) {
     __shared__ double stage[STAGED ? 7 * KAPPA_BLOCK : 1];
     const KappaGrid g = a.g;
     const int64_t n = int64_t(g.nx) * g.ny * g.nz;
@@ -116,6 +140,15 @@ __global__ void __launch_bounds__(KAPPA_BLOCK) kappa_values_kernel(KappaValuesAr
         const bool inside[6] = {k > 0, j > 0, i > 0, i + 1 < g.nx, j + 1 < g.ny, k + 1 < g.nz};
         const int wall[6] = {0, 2, 4, 5, 3, 1};
         const int axis[6] = {0, 1, 2, 2, 1, 0};
+        // SPACED: the cell's own widths (z, y, x), the areas of its faces by axis, and its neighbours' widths by face
+        const double *hp[3] = {nullptr, nullptr, nullptr};
+        double own[3] = {0.0, 0.0, 0.0}, area[3] = {0.0, 0.0, 0.0};
+        if constexpr (SPACED) {
+            hp[0] = a.hz + (k + 1); hp[1] = a.hy + (j + 1); hp[2] = a.hx + (i + 1);
+            own[0] = *hp[0]; own[1] = *hp[1]; own[2] = *hp[2];
+            area[0] = __dmul_rn(own[1], own[2]); area[1] = __dmul_rn(own[0], own[2]); area[2] = __dmul_rn(own[0], own[1]);
+        }
+        const int step[6] = {-1, -1, -1, 1, 1, 1};
         double w[6];
 #pragma unroll
         for (int e = 0; e < 6; ++e) {
@@ -126,7 +159,8 @@ __global__ void __launch_bounds__(KAPPA_BLOCK) kappa_values_kernel(KappaValuesAr
                 const unsigned long long key = 2ull * (unsigned long long)(c + off[e]);
                 bad = key < bad ? key : bad;
             }
-            w[e] = face_of(kc, kn, a.scale[axis[e]]);
+            if constexpr (SPACED) w[e] = face_spaced(kc, kn, own[axis[e]], hp[axis[e]][step[e]], area[axis[e]]);
+            else w[e] = face_of(kc, kn, a.scale[axis[e]]);
         }
         double d = __dadd_rn(__dadd_rn(__dadd_rn(__dadd_rn(__dadd_rn(w[0], w[1]), w[2]), w[3]), w[4]), w[5]);
         if (a.sigma_kind != OMG_SIGMA_NONE) {
@@ -135,7 +169,8 @@ __global__ void __launch_bounds__(KAPPA_BLOCK) kappa_values_kernel(KappaValuesAr
                 const unsigned long long key = 2ull * (unsigned long long)c + 1ull;
                 bad = key < bad ? key : bad;
             }
-            d = __dadd_rn(d, s);
+            if constexpr (SPACED) d = __dadd_rn(d, __dmul_rn(s, __dmul_rn(__dmul_rn(own[0], own[1]), own[2])));
+            else d = __dadd_rn(d, s);
         }
         if (bad != ~0ull) atomicMin(a.err, bad);
         const int64_t p = row_start(g, r, i, j, k);
@@ -188,7 +223,7 @@ void kappa_pattern(int nx, int ny, int nz, int32_t *indptr, int32_t *indices, hi
 }
 
 void KappaField::prepare(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls, const double *sigma, int kind,
-                         int sigma_on_device, const double *scale_in, hipStream_t s) {
+                         int sigma_on_device, const double *scale_in, const double *hz, const double *hy, const double *hx, hipStream_t s) {
     OMG_REQUIRE(shape && kappa, "kappa: null argument");
     for (int d = 0; d < 3; ++d)
         OMG_REQUIRE(shape[d] >= 1 && shape[d] < (int64_t(1) << 30), "kappa: every extent of the shape must be >= 1");
@@ -204,6 +239,29 @@ void KappaField::prepare(const int64_t *shape, const double *kappa, int kappa_on
     for (int d = 0; d < 3; ++d) {
         scale[d] = scale_in ? scale_in[d] : 1.0;
         OMG_REQUIRE(finite_pos(scale[d]), "kappa: every scale factor must be finite and > 0");
+    }
+    // the cell widths: all three axes or none, in place of the scale factors; checked here, before any launch
+    OMG_REQUIRE((!hz && !hy && !hx) || (hz && hy && hx), "kappa: the widths hz, hy, hx are given together or not at all");
+    spaced = hz != nullptr;
+    if (spaced) {
+        OMG_REQUIRE(scale[0] == 1.0 && scale[1] == 1.0 && scale[2] == 1.0, "kappa: widths and scale factors exclude each other");
+        const double *const h[3] = {hz, hy, hx};
+        const int extent[3] = {nz, ny, nx};
+        static const char *const axis_name[3] = {"z", "y", "x"};
+        for (int d = 0; d < 3; ++d)
+            for (int m = 0; m < extent[d] + 2; ++m) {
+                const double v = h[d][m];
+                const bool ghost = m == 0 || m == extent[d] + 1;
+                if (v < HUGE_VAL && (ghost ? v >= 0.0 : v > 0.0)) continue;
+                throw Error(OMG_ERR_INVALID, std::string("kappa: the width along ") + axis_name[d] + " at index " + std::to_string(m - 1) +
+                                                 (ghost ? " (a ghost entry) is not finite and >= 0" : " is not finite and > 0"));
+            }
+        widths.alloc(size_t(nz) + ny + nx + 6);
+        size_t at = 0;
+        for (int d = 0; d < 3; ++d) {
+            OMG_HIP(hipMemcpyAsync(widths.p + at, h[d], size_t(extent[d] + 2) * sizeof(double), hipMemcpyHostToDevice, s));
+            at += size_t(extent[d] + 2);
+        }
     }
     OMG_REQUIRE(kind == OMG_SIGMA_NONE || kind == OMG_SIGMA_SCALAR || kind == OMG_SIGMA_FIELD, "kappa: sigma_kind must be one of OMG_SIGMA_*");
     OMG_REQUIRE(kind == OMG_SIGMA_NONE || sigma, "kappa: sigma is null");
@@ -233,7 +291,7 @@ void KappaField::prepare(const int64_t *shape, const double *kappa, int kappa_on
 }
 
 void KappaField::values(double *data, hipStream_t s, const char *entry) {
-    KappaValuesArgs a;
+    KappaSpacedArgs a;
     a.g = {nx, ny, nz};
     a.kappa = kappa_dev;
     a.sigma = sigma_dev;
@@ -246,8 +304,17 @@ void KappaField::values(double *data, hipStream_t s, const char *entry) {
     const int64_t n = int64_t(nx) * ny * nz;
     const dim3 grid((unsigned)((n + KAPPA_BLOCK - 1) / KAPPA_BLOCK));
     OMG_HIP(hipMemsetAsync(err.p, 0xFF, sizeof(unsigned long long), s));
-    if (kappa_staged()) hipLaunchKernelGGL(kappa_values_kernel<true>, grid, dim3(KAPPA_BLOCK), 0, s, a);
-    else hipLaunchKernelGGL(kappa_values_kernel<false>, grid, dim3(KAPPA_BLOCK), 0, s, a);
+    a.hz = spaced ? widths.p : nullptr;
+    a.hy = spaced ? widths.p + (nz + 2) : nullptr;
+    a.hx = spaced ? widths.p + (nz + 2) + (ny + 2) : nullptr;
+    const KappaValuesArgs &plain = a;
+    if (spaced) {
+        if (kappa_staged()) hipLaunchKernelGGL((kappa_values_kernel<true, true>), grid, dim3(KAPPA_BLOCK), 0, s, a);
+        else hipLaunchKernelGGL((kappa_values_kernel<false, true>), grid, dim3(KAPPA_BLOCK), 0, s, a);
+    } else {
+        if (kappa_staged()) hipLaunchKernelGGL((kappa_values_kernel<true, false>), grid, dim3(KAPPA_BLOCK), 0, s, plain);
+        else hipLaunchKernelGGL((kappa_values_kernel<false, false>), grid, dim3(KAPPA_BLOCK), 0, s, plain);
+    }
     OMG_HIP(hipGetLastError());
     unsigned long long e = ~0ull;
     OMG_HIP(hipMemcpyAsync(&e, err.p, sizeof(e), hipMemcpyDeviceToHost, s));

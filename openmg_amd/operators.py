@@ -387,7 +387,65 @@ def kappa_arguments(kappa_shape, walls=None, sigma=None, scale=(1.0, 1.0, 1.0)):
     return shape, tuple(WALLS.index(w) for w in walls), scale
 
 
-def stencil7_kappa(kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0)):
+def spacing_arguments(shape, spacing):
+    """The cell widths of a tensor-product grid as stencil7_kappa, _hip.KappaArgs and Solver.from_kappa take them:
+    spacing = (hz, hy, hx), three 1-D sequences of nz + 2, ny + 2 and nx + 2 widths — the cells' along that axis and one
+    ghost entry at each end, like kappa's ghost layer.  Returns three contiguous float64 arrays.  ValueError for another
+    count of sequences, other lengths, a value that is not finite, an interior width <= 0, a ghost width < 0, and for a
+    device array (the widths are host arrays: the library checks them before any launch)."""
+    shape = tuple(int(s) for s in shape)
+    if hasattr(spacing, "__cuda_array_interface__") and not isinstance(spacing, np.ndarray):
+        raise ValueError("spacing must be host arrays, not a device array: pass NumPy arrays or sequences")
+    try:
+        spacing = tuple(spacing)
+    except TypeError:
+        raise ValueError("spacing must be three sequences of cell widths (hz, hy, hx), not %r" % (spacing,))
+    if len(spacing) != len(shape):
+        raise ValueError("spacing must be %d sequences of cell widths, one per axis, not %d" % (len(shape), len(spacing)))
+    out = []
+    for name, extent, widths in zip("zyx"[-len(shape):], shape, spacing):
+        if hasattr(widths, "__cuda_array_interface__") and not isinstance(widths, np.ndarray):
+            raise ValueError("spacing: the widths along %s are a device array: pass host arrays (NumPy arrays or sequences)" % name)
+        try:
+            h = np.ascontiguousarray(widths, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("spacing: the widths along %s are not numbers" % name)
+        if h.ndim != 1 or h.size != extent + 2:
+            raise ValueError("spacing: the widths along %s must be a 1-D sequence of %d entries (the %d cells and one ghost "
+                             "entry at each end), not shape %r" % (name, extent + 2, extent, h.shape))
+        if not np.isfinite(h).all():
+            raise ValueError("spacing: the widths along %s must be finite" % name)
+        if not (h[1:-1] > 0.0).all():
+            raise ValueError("spacing: the width of every cell along %s must be > 0" % name)
+        if h[0] < 0.0 or h[-1] < 0.0:
+            raise ValueError("spacing: the ghost widths along %s must be >= 0" % name)
+        out.append(h)
+    return tuple(out)
+
+
+def cell_volumes(spacing):
+    """The cell volumes (hz[k] hy[j]) hx[i] of a tensor-product grid as an (nz, ny, nx) float64 array, with the rounding
+    stencil7_kappa(..., spacing=spacing) uses for sigma: that operator is the volume-integrated one, so its right-hand
+    side is b = f * cell_volumes(spacing).  spacing as spacing_arguments takes it (the ghost entries are not used)."""
+    try:
+        shape = tuple(len(h) - 2 for h in spacing)
+    except TypeError:
+        raise ValueError("spacing must be three sequences of cell widths (hz, hy, hx), not %r" % (spacing,))
+    if len(shape) != 3:
+        raise ValueError("spacing must be three sequences of cell widths (hz, hy, hx), not %d" % len(shape))
+    hz, hy, hx = spacing_arguments(shape, spacing)
+    return (hz[1:-1, None, None] * hy[None, 1:-1, None]) * hx[None, None, 1:-1]
+
+
+def unit_scale(scale):
+    """Whether scale is the default (1, 1, 1): the only one that goes with spacing."""
+    try:
+        return tuple(float(f) for f in scale) == (1.0, 1.0, 1.0)
+    except (TypeError, ValueError):
+        return False
+
+
+def stencil7_kappa(kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0), spacing=None):
     """7-point operator of -div(kappa grad u) + sigma u from a coefficient field (NOT in the reference; the definition the
     device assembly — _hip.kappa_assemble, Solver.from_kappa — is pinned to bit for bit): cell-centred finite volumes on a
     box of (nz, ny, nx) cells.  kappa: float64 (nz + 2, ny + 2, nx + 2), the cells and one ghost layer, as
@@ -399,13 +457,31 @@ def stencil7_kappa(kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0)):
     the ghost cell's kappa and enters the diagonal only; at a Neumann wall it contributes +0.0.  With the defaults and
     stencil7_variable's kappa this is stencil7_variable's matrix bit for bit.  C-order numbering, sorted CSR, int32 indices.
 
+    spacing = (hz, hy, hx) (spacing_arguments; in place of scale): the cell widths of a stretched tensor-product grid, one
+    ghost entry at each end of every axis.  The operator is then the volume-integrated one — symmetric, the right-hand side
+    is f * cell_volumes(spacing).  With a, da the cell's own kappa and width along the face's axis and b, db the neighbour's:
+    c = (((2 a) b) / (da b + db a)) * area[axis], area_z = hy[j] hx[i], area_y = hz[k] hx[i], area_x = hz[k] hy[j]; the
+    diagonal is the same sum, then + sigma * ((hz[k] hy[j]) hx[i]).  A Dirichlet wall face takes the ghost cell's kappa and
+    the ghost width: 0 puts the boundary value on the wall face itself, the boundary cell's width at the mirrored cell centre
+    (what the operator without spacing does); a Neumann wall face reads neither.  Equal power-of-two widths h along every
+    axis give stencil7_kappa(kappa, walls, sigma V, scale=(V / hz^2, V / hy^2, V / hx^2)), V = hz hy hx, bit for bit.
+
     ValueError: kappa of another rank or without cells, not finite or <= 0 in a cell or in a ghost cell behind a
-    Dirichlet wall; sigma negative or not finite; scale not finite or <= 0; an unknown wall."""
+    Dirichlet wall; sigma negative or not finite; scale not finite or <= 0; an unknown wall; what spacing_arguments
+    refuses; spacing together with a scale other than (1, 1, 1)."""
     kap = np.asarray(kappa)
     if kap.dtype != np.float64:
         raise ValueError("kappa must be float64, not %s" % kap.dtype)
     shape, wall, scale = kappa_arguments(kap.shape, walls, sigma, scale)
     nz, ny, nx = shape
+    if spacing is not None:
+        if not unit_scale(scale):
+            raise ValueError("spacing and scale exclude each other: the widths carry every factor")
+        hz, hy, hx = spacing_arguments(shape, spacing)
+        along = (lambda h: h[:, None, None], lambda h: h[None, :, None], lambda h: h[None, None, :])   # broadcast over the grid
+        H = (hz, hy, hx)
+        own = [along[a](H[a][1:-1]) for a in range(3)]
+        area = (own[1] * own[2], own[0] * own[2], own[0] * own[1])
     c = kap[1:-1, 1:-1, 1:-1]
     # (dz, dy, dx) -> (neighbour's kappa, axis, wall); in the order of the diagonal's sum
     dirs = [((-1, 0, 0), kap[:-2, 1:-1, 1:-1], 0, 0), ((0, -1, 0), kap[1:-1, :-2, 1:-1], 1, 2), ((0, 0, -1), kap[1:-1, 1:-1, :-2], 2, 4),
@@ -426,14 +502,18 @@ def stencil7_kappa(kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0)):
     w = {}
     with np.errstate(all="ignore"):                       # (ghost cells behind Neumann walls hold anything: their faces are replaced)
         for d, nb, axis, f in dirs:
-            face = ((2.0 * c) * nb) / (c + nb) * scale[axis]
+            if spacing is not None:
+                other = along[axis](H[axis][1 + sum(d):H[axis].size - 1 + sum(d)])     # the neighbour's width
+                face = ((2.0 * c) * nb) / (own[axis] * nb + other * c) * area[axis]
+            else:
+                face = ((2.0 * c) * nb) / (c + nb) * scale[axis]
             if wall[f] == 1:
                 face = face.copy()
                 ghost(d, face)[...] = 0.0
             w[d] = face
     diag = ((((w[(-1, 0, 0)] + w[(0, -1, 0)]) + w[(0, 0, -1)]) + w[(0, 0, 1)]) + w[(0, 1, 0)]) + w[(1, 0, 0)]
     if sig is not None:
-        diag = diag + sig
+        diag = diag + (sig * ((own[0] * own[1]) * own[2]) if spacing is not None else sig)
     n = nx * ny * nz
     idx = np.arange(n, dtype=np.int64).reshape(nz, ny, nx)
     rows, cols, vals = [idx.ravel()], [idx.ravel()], [diag.ravel()]
