@@ -190,13 +190,21 @@ int omg_hierarchy_can_update_fine(const omg_hierarchy *h, int *yes);
  * The result is operators.stencil7_kappa's matrix bit for bit: the in-grid neighbours of every row, columns ascending.
  * A kappa that is not finite and > 0 (cells, and the ghost cells behind Dirichlet walls), a sigma that is not finite and
  * >= 0, a scale factor that is not finite and > 0, an unknown wall or sigma kind: OMG_ERR_INVALID — for a value of a field
- * the text names the first such cell (z, y, x), a ghost cell with -1 or the extent; nothing faults, the next call works. */
+ * the text names the first such cell (z, y, x), a ghost cell with -1 or the extent; nothing faults, the next call works.
+ * Periodic axes: OMG_WALL_PERIODIC on BOTH walls of an axis whose extent is >= 3 (on one wall only, or on a
+ * smaller extent: OMG_ERR_INVALID naming the axis).  Every row then holds both neighbours along that axis; the one across
+ * the seam is the cell at the other end of the line, its face the inner-face expression with that cell's kappa (and width),
+ * its column at its own place in the ascending order; the diagonal is the same sum in the same order.  The ghost layer of
+ * kappa along a periodic axis is never read.  omg_hierarchy_create_from_kappa sets such an operator up by the ordinary
+ * route (no fused path takes a wrap-around row), so omg_hierarchy_update_kappa answers OMG_ERR_INVALID on the result. */
 #define OMG_WALL_DIRICHLET 0
 #define OMG_WALL_NEUMANN   1
+#define OMG_WALL_PERIODIC  2
 #define OMG_SIGMA_NONE   0
 #define OMG_SIGMA_SCALAR 1
 #define OMG_SIGMA_FIELD  2
-/* The CSR arrays: indptr (n + 1), indices and data (nnz = 7 n - 2 (nx ny + nx nz + ny nz)), all in host memory or
+/* The CSR arrays: indptr (n + 1), indices and data (nnz = 7 n - 2 (nx ny + nx nz + ny nz), each of the three products
+ * counted only where the axis it leaves out — z, y, x in this order — is not periodic), all in host memory or
  * — out_on_device != 0 — all in HBM.  indptr and indices may both be NULL: the values alone. */
 int omg_kappa_assemble(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls, const double *sigma,
                        int sigma_kind, int sigma_on_device, const double *scale, int32_t *indptr, int32_t *indices, double *data,

@@ -390,7 +390,8 @@ class KappaArgs:
     a device array too.  ValueError for what operators.kappa_arguments refuses — before any device work; the fields' values
     are checked by the kernel that reads them (HipError, ERR_INVALID, naming the cell).  spacing: None, or the cell widths
     (hz, hy, hx) of a stretched grid as operators.spacing_arguments takes them — host arrays, in place of scale.  .grid:
-    problemShape; .shape: the operator's (n, n); .spacing: the checked widths or None; .call: the C arguments of the
+    problemShape; .shape: the operator's (n, n); .walls: the six codes (operators.WALL_CODES); .periodic: per axis (z, y, x)
+    whether its walls are periodic; .nnz: the operator's entries; .spacing: the checked widths or None; .call: the C arguments of the
     *_spaced entries from `shape` to `hx` (three NULLs without widths: the entries without them); the object keeps the
     arrays alive."""
 
@@ -417,7 +418,8 @@ class KappaArgs:
         self.n = int(np.prod(self.grid))
         self.shape = (self.n, self.n)
         nz, ny, nx = self.grid
-        self.nnz = 7 * self.n - 2 * (nx * ny + nx * nz + ny * nz)
+        self.periodic = operators.periodic_axes(self.walls)      # (z, y, x): along such an axis no neighbour is absent
+        self.nnz = 7 * self.n - 2 * sum(self.n // e for e, wraps in zip(self.grid, self.periodic) if not wraps)
         if 7 * self.n >= 2 ** 31 - 1:
             raise ValueError("operator too large for int32 indices; shard it first")
         padded = int(np.prod(k_shape))
@@ -455,7 +457,8 @@ class KappaArgs:
 def kappa_assemble(kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0), pattern=True, out=None, spacing=None):
     """The 7-point operator of a coefficient field, assembled on the device (omg_kappa_assemble_spaced): the CSR arrays of
     operators.stencil7_kappa(kappa, walls, sigma, scale, spacing), bit for bit.  kappa, sigma: NumPy arrays or device arrays;
-    spacing: host arrays.
+    spacing: host arrays.  walls may name 'periodic' for both walls of an axis: nnz and with it the sizes of `out` grow by
+    2 n / extent per periodic axis (KappaArgs.nnz).
     Returns (indptr, indices, data) as NumPy arrays, indptr = indices = None with pattern=False (the values alone).
     out = (indptr, indices, data): device arrays to write into instead — int32 (n + 1), int32 (nnz), float64 (nnz); the
     first two None for the values alone — and returned as they are."""
@@ -613,7 +616,9 @@ class Hierarchy:
                    dtype="float64", nullspace=None, spacing=None):
         """from_fine of operators.stencil7_kappa(kappa, walls, sigma, scale, spacing) without that matrix ever being on the
         host (omg_hierarchy_create_from_kappa_spaced): level 0 is assembled in HBM from the field — a NumPy array or a device array —,
-        the rest is from_fine's own sequence, the result the same object bit for bit."""
+        the rest is from_fine's own sequence, the result the same object bit for bit.  With periodic walls no fused path takes
+        the levels: the chain is made in HBM, fetched once and set up by the ordinary route — Hierarchy(A_list, R_list) of the
+        definition's lists, bit for bit; can_update_fine() is then False."""
         self = cls.__new__(cls)
         self._h = None
         self.nullspace_kind = nullspace_code(nullspace)
@@ -634,8 +639,9 @@ class Hierarchy:
     def update_kappa(self, kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0), spacing=None):
         """update_fine with the values of operators.stencil7_kappa(kappa, walls, sigma, scale, spacing), made on the device
         (omg_hierarchy_update_kappa_spaced): with device arrays nothing crosses to the host.  Takes the hierarchies update_fine
-        takes whose level 0 is the 7-point operator on kappa's grid (HipError ERR_INVALID otherwise, and for a kappa or
-        sigma out of range — the hierarchy is then as before)."""
+        takes whose level 0 is the 7-point operator on kappa's grid (HipError ERR_INVALID otherwise — a hierarchy with
+        periodic walls among them, and periodic walls on a hierarchy with the in-grid pattern — and for a kappa or sigma
+        out of range; the hierarchy is then as before)."""
         a = KappaArgs(kappa, walls, sigma, scale, spacing)
         a.synchronize()
         check(lib().omg_hierarchy_update_kappa_spaced(self._h, *a.call))

@@ -100,7 +100,15 @@ class Solver:
         'coarsening' / 'oddExtents', a shape the device setup takes) level 0 is assembled in HBM and no host matrix is ever
         made; with any other parameters the operator is assembled on the device into host arrays and the setup runs as for
         any A_in.  ValueError for bad arguments before any device work; a kappa or sigma value out of range: HipError
-        (ERR_INVALID) naming the first such cell."""
+        (ERR_INVALID) naming the first such cell.
+
+        walls may name 'periodic' for both walls of an axis (extent >= 3): the operator then holds the wrap-around
+        couplings, assembled in HBM like every other; no fused pass takes such a level, so the hierarchy is the one
+        Solver(operators.stencil7_kappa(...), parameters) builds by the ordinary route, update_kappa builds a new
+        hierarchy, and update(A_new) wants A_new in the periodic pattern.  With every wall periodic or Neumann and no
+        sigma the operator is singular: parameters['nullspace'] = 'constant'.  'smoother': 'line' and 'coarsening':
+        'auto' read the grid off the in-grid pattern and raise HipError (ERR_UNSUPPORTED) on a periodic operator, as they
+        do for a periodic matrix; named 'coarsening' factors and 'oddExtents' work."""
         source = _hip.KappaArgs(kappa, walls, sigma, scale, spacing)
         given = dict(parameters)
         if given.get("problemShape") is not None:
@@ -269,7 +277,12 @@ class Solver:
         A1 = _hip.as_csr(A_new)
         if self._indptr is None:
             from . import operators
-            P = operators.stencil_poisson(self._kappa[0])
+            grid, walls = self._kappa[:2]
+            if walls is not None and "periodic" in tuple(walls):
+                # (the pattern with the wrapped columns: the definition's own, of a field of ones)
+                P = operators.stencil7_kappa(np.ones(tuple(s + 2 for s in grid)), walls)
+            else:
+                P = operators.stencil_poisson(grid)
             self._indptr, self._indices = P.indptr, P.indices
         if (A1.shape != self._shape or A1.indptr.size != self._indptr.size or A1.indices.size != self._indices.size
                 or not np.array_equal(A1.indptr, self._indptr) or not np.array_equal(A1.indices, self._indices)):

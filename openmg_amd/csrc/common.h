@@ -831,8 +831,10 @@ void galerkin_chain_device(DevCsrPlain &&A0, int dim, const int64_t *shape, int 
                            std::vector<DevCsrPlain> &R, hipStream_t s);
 // The 7-point operator of a cell-centred coefficient field (kappa.hip).  kappa_nnz: its entries;
 // kappa_pattern: indptr (n + 1) and indices (nnz) of the in-grid pattern, columns ascending, by closed form.
-int64_t kappa_nnz(int nx, int ny, int nz);
-void kappa_pattern(int nx, int ny, int nz, int32_t *indptr, int32_t *indices, hipStream_t s);
+// periodic (z, y, x; null: none): along such an axis every row holds both neighbours, the one across the
+// seam at its own place in the column order.
+int64_t kappa_nnz(int nx, int ny, int nz, const int *periodic = nullptr);
+void kappa_pattern(int nx, int ny, int nz, int32_t *indptr, int32_t *indices, hipStream_t s, const int *periodic = nullptr);
 // The arguments of one assembly, checked, and the fields in HBM (a host array is uploaded into own_*).
 struct KappaField {
     int nx = 0, ny = 0, nz = 0;
@@ -840,13 +842,16 @@ struct KappaField {
     double sigma_value = 0.0;
     int sigma_kind = 0;
     int neumann[6] = {0, 0, 0, 0, 0, 0};
+    int periodic[3] = {0, 0, 0};     // z, y, x: both walls of the axis are OMG_WALL_PERIODIC
+    bool any_periodic() const { return periodic[0] || periodic[1] || periodic[2]; }
     double scale[3] = {1.0, 1.0, 1.0};
     bool spaced = false;             // per-axis cell widths instead of the scale factors
     DevBuf<double> own_kappa, own_sigma;
     DevBuf<double> widths;           // spaced: hz (nz + 2), hy (ny + 2), hx (nx + 2) one after the other
     DevBuf<unsigned long long> err;
     // shape (nz, ny, nx); walls / scale may be null (all Dirichlet / 1); hz, hy, hx: host arrays with one ghost entry at
-    // each end, all three or all null; OMG_ERR_INVALID for anything the header refuses — a bad width naming axis and index
+    // each end, all three or all null; OMG_ERR_INVALID for anything the header refuses — a bad width naming axis and index,
+    // a periodic wall without its partner or on an extent below 3 naming the axis
     void prepare(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls, const double *sigma, int sigma_kind,
                  int sigma_on_device, const double *scale, const double *hz, const double *hy, const double *hx, hipStream_t s);
     // the value array in CSR order to data (device, kappa_nnz doubles); waits for the stream; a kappa or sigma out of

@@ -2710,14 +2710,14 @@ int omg_kappa_assemble_spaced(const int64_t *shape, const double *kappa, int kap
         OneShot one;
         KappaField F;
         F.prepare(shape, kappa, kappa_on_device, walls, sigma, sigma_kind, sigma_on_device, scale, hz, hy, hx, one.s);
-        const int64_t n = int64_t(F.nx) * F.ny * F.nz, nnz = kappa_nnz(F.nx, F.ny, F.nz);
+        const int64_t n = int64_t(F.nx) * F.ny * F.nz, nnz = kappa_nnz(F.nx, F.ny, F.nz, F.periodic);
         DevBuf<double> dv;
         DevBuf<int32_t> dp, di;
         if (!out_on_device) dv.alloc(size_t(nnz));
         F.values(out_on_device ? data : dv.p, one.s, "omg_kappa_assemble");
         if (indptr) {
             if (!out_on_device) { dp.alloc(size_t(n) + 1); di.alloc(size_t(nnz)); }
-            kappa_pattern(F.nx, F.ny, F.nz, out_on_device ? indptr : dp.p, out_on_device ? indices : di.p, one.s);
+            kappa_pattern(F.nx, F.ny, F.nz, out_on_device ? indptr : dp.p, out_on_device ? indices : di.p, one.s, F.periodic);
             if (!out_on_device) {
                 download_staged(indptr, dp.p, (size_t(n) + 1) * sizeof(int32_t), one.s);
                 download_staged(indices, di.p, size_t(nnz) * sizeof(int32_t), one.s);
@@ -2755,11 +2755,11 @@ int omg_hierarchy_create_from_kappa_spaced(const int64_t *shape, const double *k
             F.prepare(shape, kappa, kappa_on_device, walls, sigma, sigma_kind, sigma_on_device, scale, hz, hy, hx, one.s);
             SetupTimer tm("device setup: the fine operator from kappa");
             A0.n_rows = A0.n_cols = int64_t(F.nx) * F.ny * F.nz;
-            A0.nnz = kappa_nnz(F.nx, F.ny, F.nz);
+            A0.nnz = kappa_nnz(F.nx, F.ny, F.nz, F.periodic);
             A0.indptr.alloc(size_t(A0.n_rows) + 1);
             A0.indices.alloc(size_t(A0.nnz));
             A0.data.alloc(size_t(A0.nnz));
-            kappa_pattern(F.nx, F.ny, F.nz, A0.indptr.p, A0.indices.p, one.s);
+            kappa_pattern(F.nx, F.ny, F.nz, A0.indptr.p, A0.indices.p, one.s, F.periodic);
             F.values(A0.data.p, one.s, "omg_hierarchy_create_from_kappa");
             // (the fp64 outer operator of a mixed hierarchy is coded by the host: the one download of this route besides the
             // fall-back of create_from_fine, which fetches the whole chain when a level does not qualify)
@@ -2793,6 +2793,8 @@ int omg_hierarchy_update_kappa_spaced(omg_hierarchy *h, const int64_t *shape, co
                         "whose level 0 is the 7-point operator on the grid `shape`");
             KappaField F;
             F.prepare(shape, kappa, kappa_on_device, walls, sigma, sigma_kind, sigma_on_device, scale, hz, hy, hx, hh->stream);
+            // (a hierarchy this entry takes has the in-grid pattern on level 0: no fused path holds a wrap-around row)
+            OMG_REQUIRE(!F.any_periodic(), "omg_hierarchy_update_kappa: the hierarchy's fine operator has the in-grid pattern, the walls name a periodic axis");
             nnz = kappa_nnz(F.nx, F.ny, F.nz);
             OMG_REQUIRE(nnz == hh->nnz0, "internal: the fine pattern is not the in-grid 7-point pattern");
             if (hh->kappa_vals.n != size_t(nnz)) hh->kappa_vals.alloc(size_t(nnz));

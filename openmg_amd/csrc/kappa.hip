@@ -24,6 +24,17 @@
 // loads, the +-J / +-K rows were or will be some other workgroup's).  Stores: a row holds 4 - 7 values, so a thread's own
 // stores are 32 - 56 bytes apart from its neighbour's; the staged variant collects the workgroup's rows — one contiguous
 // piece of the value array — in LDS and writes it out at unit stride.
+//
+// Periodic axes (PERIODIC, DESIGN.md §5s: both walls of an axis OMG_WALL_PERIODIC, extent >= 3): every row holds both
+// neighbours along such an axis, the one across the seam being the cell at the other end of the line — the same face
+// expression with that cell's kappa (and width), its address a select (i == 0 ? +(nx - 1) : -1), no ghost cell read.  The
+// wrapped column is out of face order (at i = 0 the -I neighbour is column r + nx - 1, between +I and +J); since the
+// offsets of the x, y and z neighbours lie in disjoint ranges (|x| <= nx - 1 < nx <= |y| <= (ny - 1) nx < nx ny <= |z|),
+// the thirteen possible entries have ONE ascending order
+//     +K wrapped, -K, +J wrapped, -J, +I wrapped, -I, D, +I, -I wrapped, +J, -J wrapped, +K, -K wrapped
+// and an entry's slot is the number of present entries before it in that list: a running count over predicated stores.
+// The row start stays a closed form: the "absent neighbour" terms of the periodic axes drop out.  These are instantiations
+// of their own with the flags behind the arguments; the kernels without them keep their argument blocks and their code.
 #include "common.h"
 
 // (This file is compiled with -ffp-contract=off, the Makefile's rule for kappa.hip.o: __dmul_rn / __dadd_rn are plain
@@ -50,6 +61,29 @@ __device__ __forceinline__ int64_t row_start(const KappaGrid &g, int64_t r, int 
     absent += lines + (i > 0 ? 1 : 0);                                                         // -I: the first cell of every line
     absent += lines;                                                                           // +I: the last cell of every line
     return 7 * r - absent;
+}
+
+// PERIODIC: per axis, whether its walls are periodic; row_start without the absent-neighbour terms of those axes
+struct KappaWrap { int z, y, x; };
+
+__device__ __forceinline__ int64_t row_start_wrap(const KappaGrid &g, const KappaWrap &wr, int64_t r, int i, int j, int k) {
+    const int64_t plane = int64_t(g.nx) * g.ny, in_plane = int64_t(j) * g.nx + i, lines = int64_t(k) * g.ny + j;
+    int64_t absent = 0;
+    if (!wr.z) {
+        const int64_t top = r - int64_t(g.nz - 1) * plane;
+        absent += (r < plane ? r : plane) + (top > 0 ? top : 0);
+    }
+    if (!wr.y) {
+        const int64_t lastj = in_plane - int64_t(g.ny - 1) * g.nx;
+        absent += 2 * int64_t(k) * g.nx + (in_plane < g.nx ? in_plane : g.nx) + (lastj > 0 ? lastj : 0);
+    }
+    if (!wr.x) absent += 2 * lines + (i > 0 ? 1 : 0);
+    return 7 * r - absent;
+}
+
+__device__ __forceinline__ int64_t nnz_wrap(const KappaGrid &g, const KappaWrap &wr) {
+    const int64_t n = int64_t(g.nx) * g.ny * g.nz;
+    return 7 * n - 2 * ((wr.z ? 0 : int64_t(g.nx) * g.ny) + (wr.y ? 0 : int64_t(g.nx) * g.nz) + (wr.x ? 0 : int64_t(g.ny) * g.nz));
 }
 
 __device__ __forceinline__ void cell_of(const KappaGrid &g, int64_t r, int &i, int &j, int &k) {
@@ -83,6 +117,36 @@ __global__ void __launch_bounds__(KAPPA_BLOCK) kappa_pattern_kernel(KappaGrid g,
     if (k + 1 < g.nz) indices[p++] = int32_t(r + sk);
 }
 
+// the same with periodic axes: the thirteen possible entries in ascending column order (the head of this file)
+__global__ void __launch_bounds__(KAPPA_BLOCK) kappa_pattern_wrap_kernel(KappaGrid g, KappaWrap wr, int32_t *indptr, int32_t *indices) {
+    const int64_t n = int64_t(g.nx) * g.ny * g.nz;
+    const int64_t r = blockIdx.x * int64_t(KAPPA_BLOCK) + threadIdx.x;
+    if (r > n) return;
+    if (r == n) {
+        indptr[n] = int32_t(nnz_wrap(g, wr));
+        return;
+    }
+    int i, j, k;
+    cell_of(g, r, i, j, k);
+    int64_t p = row_start_wrap(g, wr, r, i, j, k);
+    indptr[r] = int32_t(p);
+    const int64_t sj = g.nx, sk = int64_t(g.nx) * g.ny;
+    const bool lo_i = i > 0, hi_i = i + 1 < g.nx, lo_j = j > 0, hi_j = j + 1 < g.ny, lo_k = k > 0, hi_k = k + 1 < g.nz;
+    if (!hi_k && wr.z) indices[p++] = int32_t(r - (g.nz - 1) * sk);
+    if (lo_k) indices[p++] = int32_t(r - sk);
+    if (!hi_j && wr.y) indices[p++] = int32_t(r - (g.ny - 1) * sj);
+    if (lo_j) indices[p++] = int32_t(r - sj);
+    if (!hi_i && wr.x) indices[p++] = int32_t(r - (g.nx - 1));
+    if (lo_i) indices[p++] = int32_t(r - 1);
+    indices[p++] = int32_t(r);
+    if (hi_i) indices[p++] = int32_t(r + 1);
+    if (!lo_i && wr.x) indices[p++] = int32_t(r + (g.nx - 1));
+    if (hi_j) indices[p++] = int32_t(r + sj);
+    if (!lo_j && wr.y) indices[p++] = int32_t(r + (g.ny - 1) * sj);
+    if (hi_k) indices[p++] = int32_t(r + sk);
+    if (!lo_k && wr.z) indices[p++] = int32_t(r + (g.nz - 1) * sk);
+}
+
 struct KappaValuesArgs {
     KappaGrid g;
     const double *kappa;          // (nz + 2)(ny + 2)(nx + 2)
@@ -108,14 +172,18 @@ struct KappaSpacedArgs : KappaValuesArgs {
 };
 template <bool SPACED> using kappa_args_t = std::conditional_t<SPACED, KappaSpacedArgs, KappaValuesArgs>;
 
+// PERIODIC: the per-axis flags behind either block
+template <bool SPACED> struct KappaWrapArgs : kappa_args_t<SPACED> { KappaWrap wrap; };
+template <bool SPACED, bool PERIODIC> using kappa_kernel_args_t = std::conditional_t<PERIODIC, KappaWrapArgs<SPACED>, kappa_args_t<SPACED>>;
+
 __device__ __forceinline__ double face_spaced(double a, double b, double da, double db, double area) {
     const double den = __dadd_rn(__dmul_rn(da, b), __dmul_rn(db, a));
     return __dmul_rn(__ddiv_rn(__dmul_rn(__dmul_rn(2.0, a), b), den), area);
 }
 
 // the row of cell r: its values in CSR order to out[0 .. count), count returned
-template <bool STAGED, bool SPACED>
-__global__ void __launch_bounds__(KAPPA_BLOCK) kappa_values_kernel(kappa_args_t<SPACED> a) {
+template <bool STAGED, bool SPACED, bool PERIODIC>
+__global__ void __launch_bounds__(KAPPA_BLOCK) kappa_values_kernel(kappa_kernel_args_t<SPACED, PERIODIC> a) {
     __shared__ double stage[STAGED ? 7 * KAPPA_BLOCK : 1];
     const KappaGrid g = a.g;
     const int64_t n = int64_t(g.nx) * g.ny * g.nz;
@@ -125,7 +193,8 @@ __global__ void __launch_bounds__(KAPPA_BLOCK) kappa_values_kernel(kappa_args_t<
     if (STAGED) {
         int i0, j0, k0;
         cell_of(g, r0, i0, j0, k0);
-        base = row_start(g, r0, i0, j0, k0);
+        if constexpr (PERIODIC) base = row_start_wrap(g, a.wrap, r0, i0, j0, k0);
+        else base = row_start(g, r0, i0, j0, k0);
     }
     if (r < n) {
         int i, j, k;
@@ -149,18 +218,42 @@ __global__ void __launch_bounds__(KAPPA_BLOCK) kappa_values_kernel(kappa_args_t<
             area[0] = __dmul_rn(own[1], own[2]); area[1] = __dmul_rn(own[0], own[2]); area[2] = __dmul_rn(own[0], own[1]);
         }
         const int step[6] = {-1, -1, -1, 1, 1, 1};
+        // PERIODIC: a face on a periodic wall takes the cell at the other end of its line, `across` cells away (a select of
+        // the offset; never a ghost)
+        bool wrapped[6] = {false, false, false, false, false, false};
+        int across[3] = {0, 0, 0};
+        if constexpr (PERIODIC) {
+            const int periodic[3] = {a.wrap.z, a.wrap.y, a.wrap.x};
+#pragma unroll
+            for (int e = 0; e < 6; ++e) wrapped[e] = !inside[e] && periodic[axis[e]];
+            across[0] = g.nz - 1; across[1] = g.ny - 1; across[2] = g.nx - 1;
+        }
         double w[6];
 #pragma unroll
         for (int e = 0; e < 6; ++e) {
-            if (!inside[e] && a.neumann[wall[e]]) { w[e] = 0.0; continue; }
-            const double kn = a.kappa[c + off[e]];
-            // (an inner neighbour is checked by its own thread; a ghost cell by the thread of the cell it bounds)
-            if (!inside[e] && !kappa_ok(kn)) {
-                const unsigned long long key = 2ull * (unsigned long long)(c + off[e]);
-                bad = key < bad ? key : bad;
+            if constexpr (PERIODIC) {
+                const bool ghost = !inside[e] && !wrapped[e];
+                if (ghost && a.neumann[wall[e]]) { w[e] = 0.0; continue; }
+                const int st = wrapped[e] ? -step[e] * across[axis[e]] : step[e];
+                const int64_t at = c + (wrapped[e] ? -off[e] * across[axis[e]] : off[e]);
+                const double kn = a.kappa[at];
+                if (ghost && !kappa_ok(kn)) {
+                    const unsigned long long key = 2ull * (unsigned long long)at;
+                    bad = key < bad ? key : bad;
+                }
+                if constexpr (SPACED) w[e] = face_spaced(kc, kn, own[axis[e]], hp[axis[e]][st], area[axis[e]]);
+                else w[e] = face_of(kc, kn, a.scale[axis[e]]);
+            } else {
+                if (!inside[e] && a.neumann[wall[e]]) { w[e] = 0.0; continue; }
+                const double kn = a.kappa[c + off[e]];
+                // (an inner neighbour is checked by its own thread; a ghost cell by the thread of the cell it bounds)
+                if (!inside[e] && !kappa_ok(kn)) {
+                    const unsigned long long key = 2ull * (unsigned long long)(c + off[e]);
+                    bad = key < bad ? key : bad;
+                }
+                if constexpr (SPACED) w[e] = face_spaced(kc, kn, own[axis[e]], hp[axis[e]][step[e]], area[axis[e]]);
+                else w[e] = face_of(kc, kn, a.scale[axis[e]]);
             }
-            if constexpr (SPACED) w[e] = face_spaced(kc, kn, own[axis[e]], hp[axis[e]][step[e]], area[axis[e]]);
-            else w[e] = face_of(kc, kn, a.scale[axis[e]]);
         }
         double d = __dadd_rn(__dadd_rn(__dadd_rn(__dadd_rn(__dadd_rn(w[0], w[1]), w[2]), w[3]), w[4]), w[5]);
         if (a.sigma_kind != OMG_SIGMA_NONE) {
@@ -173,27 +266,38 @@ __global__ void __launch_bounds__(KAPPA_BLOCK) kappa_values_kernel(kappa_args_t<
             else d = __dadd_rn(d, s);
         }
         if (bad != ~0ull) atomicMin(a.err, bad);
-        const int64_t p = row_start(g, r, i, j, k);
+        int64_t p;
+        if constexpr (PERIODIC) p = row_start_wrap(g, a.wrap, r, i, j, k);
+        else p = row_start(g, r, i, j, k);
         double *out = STAGED ? stage + (p - base) : a.data + p;
         int q = 0;
+        // (PERIODIC: before an inner entry comes the wrapped one of the opposite face, whose column lies further down; after it, further up)
 #pragma unroll
-        for (int e = 0; e < 3; ++e)
+        for (int e = 0; e < 3; ++e) {
+            if constexpr (PERIODIC)
+                if (wrapped[5 - e]) out[q++] = -w[5 - e];
             if (inside[e]) out[q++] = -w[e];
+        }
         out[q++] = d;
 #pragma unroll
-        for (int e = 3; e < 6; ++e)
+        for (int e = 3; e < 6; ++e) {
             if (inside[e]) out[q++] = -w[e];
+            if constexpr (PERIODIC)
+                if (wrapped[5 - e]) out[q++] = -w[5 - e];
+        }
     }
     if (STAGED) {
         __syncthreads();
         const int64_t r1 = r0 + KAPPA_BLOCK < n ? r0 + KAPPA_BLOCK : n;
         int64_t end;
         if (r1 == n) {
-            end = 7 * n - 2 * (int64_t(g.nx) * g.ny + int64_t(g.nx) * g.nz + int64_t(g.ny) * g.nz);
+            if constexpr (PERIODIC) end = nnz_wrap(g, a.wrap);
+            else end = 7 * n - 2 * (int64_t(g.nx) * g.ny + int64_t(g.nx) * g.nz + int64_t(g.ny) * g.nz);
         } else {
             int i1, j1, k1;
             cell_of(g, r1, i1, j1, k1);
-            end = row_start(g, r1, i1, j1, k1);
+            if constexpr (PERIODIC) end = row_start_wrap(g, a.wrap, r1, i1, j1, k1);
+            else end = row_start(g, r1, i1, j1, k1);
         }
         const int count = int(end - base);                      // <= 7 * KAPPA_BLOCK
         for (int t = threadIdx.x; t < count; t += KAPPA_BLOCK) a.data[base + t] = stage[t];
@@ -210,15 +314,22 @@ bool finite_pos(double v) { return v > 0.0 && v < HUGE_VAL; }
 
 }  // namespace
 
-int64_t kappa_nnz(int nx, int ny, int nz) {
+int64_t kappa_nnz(int nx, int ny, int nz, const int *periodic) {
     const int64_t n = int64_t(nx) * ny * nz;
-    return 7 * n - 2 * (int64_t(nx) * ny + int64_t(nx) * nz + int64_t(ny) * nz);
+    const bool pz = periodic && periodic[0], py = periodic && periodic[1], px = periodic && periodic[2];
+    return 7 * n - 2 * ((pz ? 0 : int64_t(nx) * ny) + (py ? 0 : int64_t(nx) * nz) + (px ? 0 : int64_t(ny) * nz));
 }
 
-void kappa_pattern(int nx, int ny, int nz, int32_t *indptr, int32_t *indices, hipStream_t s) {
+void kappa_pattern(int nx, int ny, int nz, int32_t *indptr, int32_t *indices, hipStream_t s, const int *periodic) {
     const int64_t n = int64_t(nx) * ny * nz;
     const KappaGrid g = {nx, ny, nz};
-    hipLaunchKernelGGL(kappa_pattern_kernel, dim3((unsigned)((n + 1 + KAPPA_BLOCK - 1) / KAPPA_BLOCK)), dim3(KAPPA_BLOCK), 0, s, g, indptr, indices);
+    const dim3 grid((unsigned)((n + 1 + KAPPA_BLOCK - 1) / KAPPA_BLOCK));
+    if (periodic && (periodic[0] || periodic[1] || periodic[2])) {
+        const KappaWrap wr = {periodic[0], periodic[1], periodic[2]};
+        hipLaunchKernelGGL(kappa_pattern_wrap_kernel, grid, dim3(KAPPA_BLOCK), 0, s, g, wr, indptr, indices);
+    } else {
+        hipLaunchKernelGGL(kappa_pattern_kernel, grid, dim3(KAPPA_BLOCK), 0, s, g, indptr, indices);
+    }
     OMG_HIP(hipGetLastError());
 }
 
@@ -233,8 +344,21 @@ void KappaField::prepare(const int64_t *shape, const double *kappa, int kappa_on
                 "kappa: operator too large for int32 indices");
     for (int f = 0; f < 6; ++f) {
         const int wv = walls ? walls[f] : OMG_WALL_DIRICHLET;
-        OMG_REQUIRE(wv == OMG_WALL_DIRICHLET || wv == OMG_WALL_NEUMANN, "kappa: a wall must be OMG_WALL_DIRICHLET or OMG_WALL_NEUMANN");
+        OMG_REQUIRE(wv == OMG_WALL_DIRICHLET || wv == OMG_WALL_NEUMANN || wv == OMG_WALL_PERIODIC,
+                    "kappa: a wall must be OMG_WALL_DIRICHLET or OMG_WALL_NEUMANN, or OMG_WALL_PERIODIC on both walls of an axis");
         neumann[f] = wv == OMG_WALL_NEUMANN;
+    }
+    // a periodic axis: both of its walls, and three distinct columns (the cell and its two neighbours) in every row
+    for (int d = 0; d < 3; ++d) {
+        static const char *const axis_name[3] = {"z", "y", "x"};
+        const bool lo = walls && walls[2 * d] == OMG_WALL_PERIODIC, hi = walls && walls[2 * d + 1] == OMG_WALL_PERIODIC;
+        periodic[d] = lo && hi;
+        if (lo != hi)
+            throw Error(OMG_ERR_INVALID, std::string("kappa: OMG_WALL_PERIODIC must be given for both walls of an axis: only one wall of axis ") +
+                                             axis_name[d] + " has it");
+        if (periodic[d] && shape[d] < 3)
+            throw Error(OMG_ERR_INVALID, std::string("kappa: a periodic axis needs an extent >= 3: axis ") + axis_name[d] + " has " +
+                                             std::to_string((long long)shape[d]));
     }
     for (int d = 0; d < 3; ++d) {
         scale[d] = scale_in ? scale_in[d] : 1.0;
@@ -308,12 +432,25 @@ void KappaField::values(double *data, hipStream_t s, const char *entry) {
     a.hy = spaced ? widths.p + (nz + 2) : nullptr;
     a.hx = spaced ? widths.p + (nz + 2) + (ny + 2) : nullptr;
     const KappaValuesArgs &plain = a;
-    if (spaced) {
-        if (kappa_staged()) hipLaunchKernelGGL((kappa_values_kernel<true, true>), grid, dim3(KAPPA_BLOCK), 0, s, a);
-        else hipLaunchKernelGGL((kappa_values_kernel<false, true>), grid, dim3(KAPPA_BLOCK), 0, s, a);
+    if (any_periodic()) {
+        KappaWrapArgs<true> ws;
+        KappaWrapArgs<false> wp;
+        static_cast<KappaSpacedArgs &>(ws) = a;
+        static_cast<KappaValuesArgs &>(wp) = plain;
+        ws.wrap = wp.wrap = {periodic[0], periodic[1], periodic[2]};
+        if (spaced) {
+            if (kappa_staged()) hipLaunchKernelGGL((kappa_values_kernel<true, true, true>), grid, dim3(KAPPA_BLOCK), 0, s, ws);
+            else hipLaunchKernelGGL((kappa_values_kernel<false, true, true>), grid, dim3(KAPPA_BLOCK), 0, s, ws);
+        } else {
+            if (kappa_staged()) hipLaunchKernelGGL((kappa_values_kernel<true, false, true>), grid, dim3(KAPPA_BLOCK), 0, s, wp);
+            else hipLaunchKernelGGL((kappa_values_kernel<false, false, true>), grid, dim3(KAPPA_BLOCK), 0, s, wp);
+        }
+    } else if (spaced) {
+        if (kappa_staged()) hipLaunchKernelGGL((kappa_values_kernel<true, true, false>), grid, dim3(KAPPA_BLOCK), 0, s, a);
+        else hipLaunchKernelGGL((kappa_values_kernel<false, true, false>), grid, dim3(KAPPA_BLOCK), 0, s, a);
     } else {
-        if (kappa_staged()) hipLaunchKernelGGL((kappa_values_kernel<true, false>), grid, dim3(KAPPA_BLOCK), 0, s, plain);
-        else hipLaunchKernelGGL((kappa_values_kernel<false, false>), grid, dim3(KAPPA_BLOCK), 0, s, plain);
+        if (kappa_staged()) hipLaunchKernelGGL((kappa_values_kernel<true, false, false>), grid, dim3(KAPPA_BLOCK), 0, s, plain);
+        else hipLaunchKernelGGL((kappa_values_kernel<false, false, false>), grid, dim3(KAPPA_BLOCK), 0, s, plain);
     }
     OMG_HIP(hipGetLastError());
     unsigned long long e = ~0ull;

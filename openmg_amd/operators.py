@@ -351,21 +351,29 @@ def stencil7_variable(shape, seed=2024):
 
 
 WALLS = ("dirichlet", "neumann")       # OMG_WALL_DIRICHLET, OMG_WALL_NEUMANN
+WALL_CODES = {"dirichlet": 0, "neumann": 1, "periodic": 2}     # ... and OMG_WALL_PERIODIC: both walls of an axis or neither
 
 
 def kappa_arguments(kappa_shape, walls=None, sigma=None, scale=(1.0, 1.0, 1.0)):
     """What stencil7_kappa, _hip.kappa_assemble and Solver.from_kappa check of their arguments besides the fields' values:
     (problemShape, wall codes -z +z -y +y -x +x, scale z y x); ValueError for a kappa that is not 3-D with a ghost layer,
-    an unknown wall, a scale factor that is not finite and > 0, a scalar sigma that is not finite and >= 0, a sigma field
-    of another shape than problemShape (a field's values are the caller's to check: on the host here, on the device by
-    the kernel that reads them)."""
+    an unknown wall, 'periodic' on one wall of an axis only or on an axis of extent 1 or 2, a scale factor that is not
+    finite and > 0, a scalar sigma that is not finite and >= 0, a sigma field of another shape than problemShape (a field's
+    values are the caller's to check: on the host here, on the device by the kernel that reads them)."""
     kappa_shape = tuple(int(s) for s in kappa_shape)
     if len(kappa_shape) != 3 or min(kappa_shape) < 3:
         raise ValueError("kappa must be 3-D with one ghost layer, shape (nz + 2, ny + 2, nx + 2), not %r" % (kappa_shape,))
     shape = tuple(s - 2 for s in kappa_shape)
     walls = ("dirichlet",) * 6 if walls is None else tuple(walls)
-    if len(walls) != 6 or any(not isinstance(w, str) or w not in WALLS for w in walls):
-        raise ValueError("walls must be six of 'dirichlet' / 'neumann' in the order -z, +z, -y, +y, -x, +x, not %r" % (walls,))
+    if len(walls) != 6 or any(not isinstance(w, str) or w not in WALL_CODES for w in walls):
+        raise ValueError("walls must be six of 'dirichlet' / 'neumann' / 'periodic' in the order -z, +z, -y, +y, -x, +x, not %r" % (walls,))
+    for axis, name in enumerate("zyx"):
+        lo, hi = walls[2 * axis] == "periodic", walls[2 * axis + 1] == "periodic"
+        if lo != hi:
+            raise ValueError("walls: 'periodic' must be given for both walls of an axis, not for one wall of %s alone: %r" % (name, walls))
+        if lo and shape[axis] < 3:
+            raise ValueError("walls: a periodic axis needs an extent >= 3 (the cell and its two neighbours are three columns): "
+                             "%s has %d" % (name, shape[axis]))
     try:
         scale = tuple(float(f) for f in scale)
     except (TypeError, ValueError):
@@ -384,7 +392,12 @@ def kappa_arguments(kappa_shape, walls=None, sigma=None, scale=(1.0, 1.0, 1.0)):
                                           and not isinstance(sigma, np.ndarray) else np.shape(sigma)))
         if s_shape != shape:
             raise ValueError("a sigma field must have problemShape %r, not %r" % (shape, s_shape))
-    return shape, tuple(WALLS.index(w) for w in walls), scale
+    return shape, tuple(WALL_CODES[w] for w in walls), scale
+
+
+def periodic_axes(walls):
+    """Per axis (z, y, x) whether `walls` — six names or six codes, checked — makes it periodic."""
+    return tuple(walls[2 * axis] in ("periodic", WALL_CODES["periodic"]) for axis in range(3))
 
 
 def spacing_arguments(shape, spacing):
@@ -449,7 +462,8 @@ def stencil7_kappa(kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0), spacing
     """7-point operator of -div(kappa grad u) + sigma u from a coefficient field (NOT in the reference; the definition the
     device assembly — _hip.kappa_assemble, Solver.from_kappa — is pinned to bit for bit): cell-centred finite volumes on a
     box of (nz, ny, nx) cells.  kappa: float64 (nz + 2, ny + 2, nx + 2), the cells and one ghost layer, as
-    stencil7_variable draws it.  walls: six of 'dirichlet' (default) / 'neumann' in the order -z, +z, -y, +y, -x, +x.
+    stencil7_variable draws it.  walls: six of 'dirichlet' (default) / 'neumann' / 'periodic' in the order -z, +z, -y, +y,
+    -x, +x, 'periodic' for both walls of an axis or neither.
     sigma: None, a scalar or an array of problemShape, >= 0.  scale: one factor per axis (z, y, x), e.g. dt / h_axis^2.
 
     Every operation is rounded once in double: face(a, b) = ((2 a) b) / (a + b), c = face * scale[axis], the off-diagonal
@@ -466,9 +480,15 @@ def stencil7_kappa(kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0), spacing
     (what the operator without spacing does); a Neumann wall face reads neither.  Equal power-of-two widths h along every
     axis give stencil7_kappa(kappa, walls, sigma V, scale=(V / hz^2, V / hy^2, V / hx^2)), V = hz hy hx, bit for bit.
 
+    A periodic axis (extent >= 3): every row holds both neighbours along it, the one across the seam being the cell at the
+    other end of the line; its face is the inner-face expression — own a, that cell's b (and width db) —, so the matrix
+    stays symmetric bit for bit; the diagonal is the same sum in the same order wherever the wrapped column lands in the
+    row.  The ghost layer of kappa and the ghost entries of spacing along a periodic axis are not read (kappa's may hold
+    anything; spacing_arguments checks the widths' as ever).  nnz = 7 n - 2 sum of n / extent over the axes that are not periodic.
+
     ValueError: kappa of another rank or without cells, not finite or <= 0 in a cell or in a ghost cell behind a
-    Dirichlet wall; sigma negative or not finite; scale not finite or <= 0; an unknown wall; what spacing_arguments
-    refuses; spacing together with a scale other than (1, 1, 1)."""
+    Dirichlet wall; sigma negative or not finite; scale not finite or <= 0; an unknown wall, 'periodic' on one wall of
+    an axis alone or on an extent below 3; what spacing_arguments refuses; spacing together with a scale other than (1, 1, 1)."""
     kap = np.asarray(kappa)
     if kap.dtype != np.float64:
         raise ValueError("kappa must be float64, not %s" % kap.dtype)
@@ -486,6 +506,9 @@ def stencil7_kappa(kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0), spacing
     # (dz, dy, dx) -> (neighbour's kappa, axis, wall); in the order of the diagonal's sum
     dirs = [((-1, 0, 0), kap[:-2, 1:-1, 1:-1], 0, 0), ((0, -1, 0), kap[1:-1, :-2, 1:-1], 1, 2), ((0, 0, -1), kap[1:-1, 1:-1, :-2], 2, 4),
             ((0, 0, 1), kap[1:-1, 1:-1, 2:], 2, 5), ((0, 1, 0), kap[1:-1, 2:, 1:-1], 1, 3), ((1, 0, 0), kap[2:, 1:-1, 1:-1], 0, 1)]
+    periodic = periodic_axes(wall)
+    # (a periodic axis: the neighbour is the cell one step round the line; no ghost cell is looked at)
+    dirs = [(d, np.roll(c, -sum(d), axis) if periodic[axis] else nb, axis, f) for d, nb, axis, f in dirs]
 
     def ghost(d, a):                                      # the ghost cells a face of the box reads: one layer of `a`
         sel = [slice(None)] * 3
@@ -504,6 +527,8 @@ def stencil7_kappa(kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0), spacing
         for d, nb, axis, f in dirs:
             if spacing is not None:
                 other = along[axis](H[axis][1 + sum(d):H[axis].size - 1 + sum(d)])     # the neighbour's width
+                if periodic[axis]:
+                    other = along[axis](np.roll(H[axis][1:-1], -sum(d)))
                 face = ((2.0 * c) * nb) / (own[axis] * nb + other * c) * area[axis]
             else:
                 face = ((2.0 * c) * nb) / (c + nb) * scale[axis]
@@ -518,6 +543,12 @@ def stencil7_kappa(kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0), spacing
     idx = np.arange(n, dtype=np.int64).reshape(nz, ny, nx)
     rows, cols, vals = [idx.ravel()], [idx.ravel()], [diag.ravel()]
     for (dz, dy, dx), ww in w.items():
+        axis = (dz, dy, dx).index(dz + dy + dx)
+        if periodic[axis]:                                # (every cell of the line has this neighbour: the seam's is the other end)
+            rows.append(idx.ravel())
+            cols.append(np.roll(idx, -(dz + dy + dx), axis).ravel())
+            vals.append(-ww.ravel())
+            continue
         sel = (slice(max(0, -dz), nz - max(0, dz)), slice(max(0, -dy), ny - max(0, dy)), slice(max(0, -dx), nx - max(0, dx)))
         rows.append(idx[sel].ravel())
         cols.append((idx[sel] + (dz * ny + dy) * nx + dx).ravel())
