@@ -498,47 +498,58 @@ class Hierarchy:
         entries); host vectors are float64 either way.  nullspace: None, or 'constant' for a singular operator with
         zero row and column sums (pure Neumann, periodic): the coarsest operator is inverted on the complement of the
         constants, resident_load projects the right-hand side and resident_fetch the iterate (OMG_NULLSPACE_CONSTANT)."""
+        self._h = None
         if len(R_list) != len(A_list) - 1:
             raise ValueError("need len(R) == len(A) - 1")
         self.nullspace_kind = nullspace_code(nullspace)
-        self._A = [as_csr(M) for M in A_list]
-        self._R = [as_csr(M) for M in R_list]
-        arrA = (CsrView * len(self._A))(*[csr_view(M) for M in self._A])
-        arrR = (CsrView * max(len(self._R), 1))(*[csr_view(M) for M in self._R])
+        # (host copies for the call alone: the device copy is complete when it returns)
+        A = [as_csr(M) for M in A_list]
+        R = [as_csr(M) for M in R_list]
+        arrA = (CsrView * len(A))(*[csr_view(M) for M in A])
+        arrR = (CsrView * max(len(R), 1))(*[csr_view(M) for M in R])
+        opt, h = self._options(smoother, omega, dtype)
+        self.n_levels = len(A)
+        self.sizes = [M.shape[0] for M in A]
+        check(lib().omg_hierarchy_create_opt(self.n_levels, arrA, arrR, ctypes.byref(opt), ctypes.byref(h)))
+        self._adopt(h)
+
+    @classmethod
+    def _blank(cls, nullspace):
+        """An instance without a handle (what __del__ needs is set before anything can raise) that knows its null space:
+        the first check of every from_* constructor."""
+        self = cls.__new__(cls)
+        self._h = None
+        self.nullspace_kind = nullspace_code(nullspace)
+        return self
+
+    def _options(self, smoother, omega, dtype):
+        """Sets smoother, omega and dtype from the caller's names; returns the creating entry's options (with the null space
+        already set) and the empty handle it fills."""
         self.smoother = smoother_code(smoother)
         self.omega = float(omega)
-        self.n_levels = len(self._A)
-        self.sizes = [M.shape[0] for M in self._A]
-        h = ctypes.c_void_p()
         self.dtype = dtype_code(dtype)
-        opt = HierarchyOptions(self.smoother, self.omega, self.dtype, self.nullspace_kind)
-        check(lib().omg_hierarchy_create_opt(self.n_levels, arrA, arrR, ctypes.byref(opt), ctypes.byref(h)))
+        return HierarchyOptions(self.smoother, self.omega, self.dtype, self.nullspace_kind), ctypes.c_void_p()
+
+    def _adopt(self, h):
+        """Takes over the handle a creating entry returned."""
         self._h = h
-        # the device copy is complete; the host copies are only kept for .sizes
         self._A = self._R = None
 
     @classmethod
     def from_fine(cls, A_in, shape, n_restrictions, smoother="gs", omega=1.0, dtype="float64", nullspace=None):
         """mgSolve's setup on the device (omg_hierarchy_create_from_fine_opt): restrictions, Galerkin products and the
         qualification of the levels all in HBM; len(sizes) = n_restrictions + 1.  nullspace: as for Hierarchy()."""
-        self = cls.__new__(cls)
-        self._h = None
-        self.nullspace_kind = nullspace_code(nullspace)
+        self = cls._blank(nullspace)
         A0 = as_csr(A_in)
         shape = tuple(int(s) for s in shape)
         arr = (ctypes.c_int64 * len(shape))(*shape)
-        self.smoother = smoother_code(smoother)
-        self.omega = float(omega)
-        self.dtype = dtype_code(dtype)
+        opt, h = self._options(smoother, omega, dtype)
         self.n_levels = int(n_restrictions) + 1
         self.sizes = [A0.shape[0] // (2 ** len(shape)) ** l for l in range(self.n_levels)]
-        h = ctypes.c_void_p()
         v = csr_view(A0)
-        opt = HierarchyOptions(self.smoother, self.omega, self.dtype, self.nullspace_kind)
         check(lib().omg_hierarchy_create_from_fine_opt(ctypes.byref(v), len(shape), arr, int(n_restrictions), ctypes.byref(opt),
                                                        ctypes.byref(h)))
-        self._h = h
-        self._A = self._R = None
+        self._adopt(h)
         return self
 
     @classmethod
@@ -549,9 +560,7 @@ class Hierarchy:
         most n_restrictions of them, ending early where no axis can be coarsened or (after the first restriction) the coarse level
         would have <= min_size rows.  .coarsening lists what was built, .level_shapes every level's grid.
         oddExtents: None, or 'merge' — a factor 2 on any extent >= 4 (omg_hierarchy_create_from_fine_ragged)."""
-        self = cls.__new__(cls)
-        self._h = None
-        self.nullspace_kind = nullspace_code(nullspace)
+        self = cls._blank(nullspace)
         A0 = as_csr(A_in)
         shape = tuple(int(s) for s in shape)
         dim = len(shape)
@@ -563,16 +572,11 @@ class Hierarchy:
             if len(factors) != n_restrictions or any(len(entry) != dim for entry in factors):
                 raise ValueError("factors needs n_restrictions entries of one factor per axis of the shape")
             flat = (ctypes.c_int * max(n_restrictions * dim, 1))(*[f for entry in factors for f in entry])
-        self.smoother = smoother_code(smoother)
-        self.omega = float(omega)
-        self.dtype = dtype_code(dtype)
-        h = ctypes.c_void_p()
+        opt, h = self._options(smoother, omega, dtype)
         v = csr_view(A0)
-        opt = HierarchyOptions(self.smoother, self.omega, self.dtype, self.nullspace_kind)
         check(lib().omg_hierarchy_create_from_fine_ragged(ctypes.byref(v), dim, arr, n_restrictions, flat, int(min_size),
                                                           odd_code(oddExtents), ctypes.byref(opt), ctypes.byref(h)))
-        self._h = h
-        self._A = self._R = None
+        self._adopt(h)
         used = []
         f3 = (ctypes.c_int * 3)()
         for level in range(n_restrictions):
@@ -619,21 +623,14 @@ class Hierarchy:
         the rest is from_fine's own sequence, the result the same object bit for bit.  With periodic walls no fused path takes
         the levels: the chain is made in HBM, fetched once and set up by the ordinary route — Hierarchy(A_list, R_list) of the
         definition's lists, bit for bit; can_update_fine() is then False."""
-        self = cls.__new__(cls)
-        self._h = None
-        self.nullspace_kind = nullspace_code(nullspace)
+        self = cls._blank(nullspace)
         a = KappaArgs(kappa, walls, sigma, scale, spacing)
-        self.smoother = smoother_code(smoother)
-        self.omega = float(omega)
-        self.dtype = dtype_code(dtype)
+        opt, h = self._options(smoother, omega, dtype)
         self.n_levels = int(n_restrictions) + 1
         self.sizes = [a.n // 8 ** l for l in range(self.n_levels)]
-        h = ctypes.c_void_p()
-        opt = HierarchyOptions(self.smoother, self.omega, self.dtype, self.nullspace_kind)
         a.synchronize()
         check(lib().omg_hierarchy_create_from_kappa_spaced(*a.call, int(n_restrictions), ctypes.byref(opt), ctypes.byref(h)))
-        self._h = h
-        self._A = self._R = None
+        self._adopt(h)
         return self
 
     def update_kappa(self, kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0), spacing=None):

@@ -829,12 +829,18 @@ void galerkin_chain_device(const omg_csr &A0, int dim, const int64_t *shape, int
 // ... with A[0] already in HBM (omg_hierarchy_create_from_kappa: the operator a kernel assembled); A0 is moved into A[0]
 void galerkin_chain_device(DevCsrPlain &&A0, int dim, const int64_t *shape, int n_restrictions, std::vector<DevCsrPlain> &A,
                            std::vector<DevCsrPlain> &R, hipStream_t s);
-// The 7-point operator of a cell-centred coefficient field (kappa.hip).  kappa_nnz: its entries;
-// kappa_pattern: indptr (n + 1) and indices (nnz) of the in-grid pattern, columns ascending, by closed form.
-// periodic (z, y, x; null: none): along such an axis every row holds both neighbours, the one across the
-// seam at its own place in the column order.
-int64_t kappa_nnz(int nx, int ny, int nz, const int *periodic = nullptr);
-void kappa_pattern(int nx, int ny, int nz, int32_t *indptr, int32_t *indices, hipStream_t s, const int *periodic = nullptr);
+// The 7-point operator of a cell-centred coefficient field (kappa.hip).
+// What the caller of a kappa entry names of the field, as the header's entries take it.  shape (nz, ny, nx); walls / scale
+// may be null (all Dirichlet / 1); hz, hy, hx: host arrays with one ghost entry at each end, all three or all null.
+struct KappaInput {
+    const int64_t *shape;
+    const double *kappa;
+    int kappa_on_device;
+    const int *walls;
+    const double *sigma;
+    int sigma_kind, sigma_on_device;
+    const double *scale, *hz, *hy, *hx;
+};
 // The arguments of one assembly, checked, and the fields in HBM (a host array is uploaded into own_*).
 struct KappaField {
     int nx = 0, ny = 0, nz = 0;
@@ -849,14 +855,21 @@ struct KappaField {
     DevBuf<double> own_kappa, own_sigma;
     DevBuf<double> widths;           // spaced: hz (nz + 2), hy (ny + 2), hx (nx + 2) one after the other
     DevBuf<unsigned long long> err;
-    // shape (nz, ny, nx); walls / scale may be null (all Dirichlet / 1); hz, hy, hx: host arrays with one ghost entry at
-    // each end, all three or all null; OMG_ERR_INVALID for anything the header refuses — a bad width naming axis and index,
-    // a periodic wall without its partner or on an extent below 3 naming the axis
-    void prepare(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls, const double *sigma, int sigma_kind,
-                 int sigma_on_device, const double *scale, const double *hz, const double *hy, const double *hx, hipStream_t s);
-    // the value array in CSR order to data (device, kappa_nnz doubles); waits for the stream; a kappa or sigma out of
+    // OMG_ERR_INVALID for anything the header refuses — a bad width naming axis and index, a periodic wall without its
+    // partner or on an extent below 3 naming the axis
+    void prepare(const KappaInput &in, hipStream_t s);
+    int64_t rows() const { return int64_t(nx) * ny * nz; }
+    // the operator's entries (the one host statement of the closed form): along a periodic axis every row holds both
+    // neighbours, the one across the seam at its own place in the column order
+    int64_t nnz() const;
+    // the value array in CSR order to data (device, nnz() doubles); waits for the stream; a kappa or sigma out of
     // range: OMG_ERR_INVALID naming the first such cell, `entry` in front
     void values(double *data, hipStream_t s, const char *entry);
+    // the operator in HBM: indptr (rows() + 1) and indices (nnz()), columns ascending, by closed form — both null: the
+    // values alone —, then values(data)
+    void assemble(int32_t *indptr, int32_t *indices, double *data, hipStream_t s, const char *entry);
+    // ... into a CSR allocated here
+    void assemble(DevCsrPlain &A, hipStream_t s, const char *entry);
 };
 // The same chain with a factor (1 or 2) per axis and restriction instead of 2 everywhere (semicoarsening).
 // shape and every factor tuple are in the grid's C order (the last axis has unit stride).  factors: n_restrictions * dim

@@ -1577,6 +1577,44 @@ void finish_setup(const std::unique_ptr<Hier<V>> &h, CoarseThread &inverter) {
 }
 
 
+// Which fused path a smoothed level runs, decided once for both constructors: the plane passes, else the 27-point kernels,
+// else the 7-point passes with per-row coefficients; the first plan whose build takes the level is moved into it.  The three
+// callables build a plan from what the caller holds of the level (host CSRs: build; operators in HBM: build_device) and
+// say whether the level qualifies, leaving its closed-form ordering in L.ord.  beyond_plane: may the level take the two
+// kinds after the plane passes (create_from_fine: 3-D grids only).  none: the caller orders the level itself.
+enum class Fused { none, plane, s27, var7 };
+template <typename V, typename Plane, typename S27, typename Var7>
+Fused fused_level(Hier<V> *h, Level<V> &L, bool beyond_plane, Plane &&plane, S27 &&s27, Var7 &&var7) {
+    const int smoother = h->smoother;
+    if (smoother == OMG_SMOOTH_GS_COLOUR || smoother == OMG_SMOOTH_JACOBI) {
+        SetupTimer tp("plane-pipelined passes: does the level qualify (+ its parity ordering)");
+        std::unique_ptr<PlanePlan<V>> plan(new PlanePlan<V>);
+        L.march.reset();
+        // (weighted Jacobi: 2-D levels only — BASELINE configs[1] — in their natural ordering)
+        if (plane(*plan)) {
+            if (!h->plane_status.p) { h->plane_status.alloc(1); h->plane_status.zero(h->stream); }
+            plan->status = h->plane_status.p;
+            L.plane = std::move(plan);
+            return Fused::plane;
+        }
+        std::unique_ptr<Stencil27Plan<V>> p27(new Stencil27Plan<V>);
+        if (smoother == OMG_SMOOTH_GS_COLOUR && beyond_plane && s27(*p27)) {
+            L.s27 = std::move(p27);
+            return Fused::s27;
+        }
+    }
+    // (OMG_PLANE=0 asks for the set-by-set schedule: no fused path of any kind)
+    if (smoother == OMG_SMOOTH_GS_COLOUR && beyond_plane && !getenv_flag0("OMG_VAR7") && !getenv_flag0("OMG_PLANE")) {
+        SetupTimer tv("7-point level with per-row coefficients: does it qualify (+ its coefficient arrays, its parity ordering)");
+        std::unique_ptr<Var7Plan<V>> v7(new Var7Plan<V>);
+        if (var7(*v7)) {
+            L.var7 = std::move(v7);
+            return Fused::var7;
+        }
+    }
+    return Fused::none;
+}
+
 template <typename V>
 std::unique_ptr<Hier<V>> create(int n_levels, const omg_csr *A, const omg_csr *R, int smoother,
                                 double omega, int nullspace = OMG_NULLSPACE_NONE) {
@@ -1613,7 +1651,6 @@ std::unique_ptr<Hier<V>> create(int n_levels, const omg_csr *A, const omg_csr *R
     for (int l = 0; l + 1 < n_levels; ++l) {
         Lv &L = h->lv[l];
         L.n = A[l].n_rows;
-        auto check_parity = [&] { check_closed_form(A[l], smoother, L.ord, "internal: the parity ordering differs from the greedy colouring"); };
         if (is_line_smoother(smoother)) {
             SetupTimer tl("line smoother: the level's grid, its ordering, the lines' factorisations");
             std::unique_ptr<LinePlan<V>> plan(new LinePlan<V>);
@@ -1629,34 +1666,14 @@ std::unique_ptr<Hier<V>> create(int n_levels, const omg_csr *A, const omg_csr *R
             L.line = std::move(plan);
             continue;
         }
-        if (smoother == OMG_SMOOTH_GS_COLOUR || smoother == OMG_SMOOTH_JACOBI) {
-            SetupTimer tp("plane-pipelined passes: does the level qualify (+ its parity ordering)");
-            std::unique_ptr<PlanePlan<V>> plan(new PlanePlan<V>);
-            L.march.reset();
-            // (weighted Jacobi: 2-D levels only — BASELINE configs[1] — in their natural ordering)
-            if (plan->build(A[l], R[l], L.ord, smoother == OMG_SMOOTH_JACOBI, omega)) {
-                if (!h->plane_status.p) { h->plane_status.alloc(1); h->plane_status.zero(h->stream); }
-                plan->status = h->plane_status.p;
-                L.plane = std::move(plan);
-                check_parity();
-                continue;
-            }
-            std::unique_ptr<Stencil27Plan<V>> s27(new Stencil27Plan<V>);
-            if (smoother == OMG_SMOOTH_GS_COLOUR && s27->build(A[l], R[l], L.ord, h->stream)) {
-                L.s27 = std::move(s27);
-                check_closed_form(A[l], smoother, L.ord, "internal: the octant ordering differs from the greedy colouring");
-                continue;
-            }
-        }
-        // (OMG_PLANE=0 asks for the set-by-set schedule: no fused path of any kind)
-        if (smoother == OMG_SMOOTH_GS_COLOUR && !getenv_flag0("OMG_VAR7") && !getenv_flag0("OMG_PLANE")) {
-            SetupTimer tv("7-point level with per-row coefficients: does it qualify (+ its coefficient arrays, its parity ordering)");
-            std::unique_ptr<Var7Plan<V>> v7(new Var7Plan<V>);
-            if (v7->build(A[l], R[l], L.ord, h->stream)) {
-                L.var7 = std::move(v7);
-                check_parity();
-                continue;
-            }
+        const Fused kind = fused_level(h.get(), L, true,
+                                       [&](PlanePlan<V> &p) { return p.build(A[l], R[l], L.ord, smoother == OMG_SMOOTH_JACOBI, omega); },
+                                       [&](Stencil27Plan<V> &p) { return p.build(A[l], R[l], L.ord, h->stream); },
+                                       [&](Var7Plan<V> &p) { return p.build(A[l], R[l], L.ord, h->stream); });
+        if (kind != Fused::none) {
+            check_closed_form(A[l], smoother, L.ord, kind == Fused::s27 ? "internal: the octant ordering differs from the greedy colouring"
+                                                                        : "internal: the parity ordering differs from the greedy colouring");
+            continue;
         }
         SetupTimer tm("ordering (colouring / level schedule / wavefront plan)");
         order_level(L, A[l], smoother, h->stream);
@@ -1727,26 +1744,14 @@ std::unique_ptr<Hier<V>> create_from_fine(const omg_csr &A0, int dim, const int6
         int nx, ny, nz;
         dims(l, nx, ny, nz);
         SetupTimer tp("device setup: does the level qualify for a fused path");
-        std::unique_ptr<PlanePlan<V>> plan(new PlanePlan<V>);
-        if (plan->build_device(dA[size_t(l)], nx, ny, nz, w, L.ord, smoother == OMG_SMOOTH_JACOBI, omega, h->stream)) {
-            if (!h->plane_status.p) { h->plane_status.alloc(1); h->plane_status.zero(h->stream); }
-            plan->status = h->plane_status.p;
-            L.plane = std::move(plan);
-            continue;
-        }
-        std::unique_ptr<Stencil27Plan<V>> s27(new Stencil27Plan<V>);
-        if (smoother == OMG_SMOOTH_GS_COLOUR && dim == 3 && s27->build_device(dA[size_t(l)], nx, ny, nz, w, L.ord, h->stream)) {
-            L.s27 = std::move(s27);
-            continue;
-        }
-        if (smoother == OMG_SMOOTH_GS_COLOUR && dim == 3 && !getenv_flag0("OMG_VAR7") && !getenv_flag0("OMG_PLANE")) {
-            std::unique_ptr<Var7Plan<V>> v7(new Var7Plan<V>);
-            if (v7->build_device(dA[size_t(l)], nx, ny, nz, w, L.ord, h->stream)) {
-                L.var7 = std::move(v7);
-                any_var7 = true;
-                continue;
-            }
-        }
+        const DevCsrPlain &M = dA[size_t(l)];
+        // (the 27-point and the per-row-coefficient kernels are 3-D ones)
+        const Fused kind = fused_level(h.get(), L, dim == 3,
+                                       [&](PlanePlan<V> &p) { return p.build_device(M, nx, ny, nz, w, L.ord, smoother == OMG_SMOOTH_JACOBI, omega, h->stream); },
+                                       [&](Stencil27Plan<V> &p) { return p.build_device(M, nx, ny, nz, w, L.ord, h->stream); },
+                                       [&](Var7Plan<V> &p) { return p.build_device(M, nx, ny, nz, w, L.ord, h->stream); });
+        any_var7 = any_var7 || kind == Fused::var7;
+        if (kind != Fused::none) continue;
         if (any_var7 && L.n <= HOST_LEVEL_MAX) {
             host_level[size_t(l)] = 1;
             hostA[size_t(l)] = download_csr(dA[size_t(l)], h->stream);
@@ -2542,6 +2547,24 @@ void resident_norms(Hier<V> *hh, double *rhs_norm, double *residual_norm) {
     if (residual_norm) *residual_norm = host[1];
 }
 
+// What every creating entry does around its own builder: the options are checked — before the builder, which asks for the
+// device —, the handle made, build(V(), handle) run in the options' precision, a mixed hierarchy given its fp64 outer
+// operator from *fine (read after the builder: it may be the builder that fills it in), the handle handed out.
+template <typename Build>
+void create_handle(const omg_hierarchy_options *opt, omg_hierarchy **out, const omg_csr *fine, Build &&build) {
+    OMG_REQUIRE(out, "out is null");
+    *out = nullptr;
+    OMG_REQUIRE(opt, "options are null");
+    const int dtype = opt->dtype;
+    OMG_REQUIRE(dtype == OMG_DTYPE_F64 || dtype == OMG_DTYPE_F32 || dtype == OMG_DTYPE_MIXED, "unknown dtype");
+    OMG_REQUIRE(opt->nullspace == OMG_NULLSPACE_NONE || opt->nullspace == OMG_NULLSPACE_CONSTANT, "unknown nullspace kind");
+    std::unique_ptr<omg_hierarchy> h(new omg_hierarchy);
+    if (dtype != OMG_DTYPE_F64) h->f = build(float(), *h);
+    else h->d = build(double(), *h);
+    if (dtype == OMG_DTYPE_MIXED) build_mixed(h->f.get(), *fine);
+    *out = h.release();
+}
+
 }  // namespace
 }  // namespace omg
 
@@ -2582,17 +2605,9 @@ int omg_device_synchronize(void) {
 
 int omg_hierarchy_create_opt(int n_levels, const omg_csr *A, const omg_csr *R, const omg_hierarchy_options *opt, omg_hierarchy **out) {
     return guarded([&] {
-        OMG_REQUIRE(out, "out is null");
-        *out = nullptr;
-        OMG_REQUIRE(opt, "options are null");
-        const int dtype = opt->dtype;
-        OMG_REQUIRE(dtype == OMG_DTYPE_F64 || dtype == OMG_DTYPE_F32 || dtype == OMG_DTYPE_MIXED, "unknown dtype");
-        OMG_REQUIRE(opt->nullspace == OMG_NULLSPACE_NONE || opt->nullspace == OMG_NULLSPACE_CONSTANT, "unknown nullspace kind");
-        std::unique_ptr<omg_hierarchy> h(new omg_hierarchy);
-        if (dtype != OMG_DTYPE_F64) h->f = create<float>(n_levels, A, R, opt->smoother, opt->omega, opt->nullspace);
-        else h->d = create<double>(n_levels, A, R, opt->smoother, opt->omega, opt->nullspace);
-        if (dtype == OMG_DTYPE_MIXED) build_mixed(h->f.get(), A[0]);
-        *out = h.release();
+        create_handle(opt, out, A, [&](auto v, omg_hierarchy &) {
+            return create<decltype(v)>(n_levels, A, R, opt->smoother, opt->omega, opt->nullspace);
+        });
     });
 }
 
@@ -2611,16 +2626,9 @@ int omg_hierarchy_create_from_fine_opt(const omg_csr *A_in, int dim, const int64
                                        const omg_hierarchy_options *opt, omg_hierarchy **out) {
     return guarded([&] {
         OMG_REQUIRE(out && A_in, "null argument");
-        *out = nullptr;
-        OMG_REQUIRE(opt, "options are null");
-        const int dtype = opt->dtype;
-        OMG_REQUIRE(dtype == OMG_DTYPE_F64 || dtype == OMG_DTYPE_F32 || dtype == OMG_DTYPE_MIXED, "unknown dtype");
-        OMG_REQUIRE(opt->nullspace == OMG_NULLSPACE_NONE || opt->nullspace == OMG_NULLSPACE_CONSTANT, "unknown nullspace kind");
-        std::unique_ptr<omg_hierarchy> h(new omg_hierarchy);
-        if (dtype != OMG_DTYPE_F64) h->f = create_from_fine<float>(*A_in, dim, shape, n_restrictions, opt->smoother, opt->omega, opt->nullspace);
-        else h->d = create_from_fine<double>(*A_in, dim, shape, n_restrictions, opt->smoother, opt->omega, opt->nullspace);
-        if (dtype == OMG_DTYPE_MIXED) build_mixed(h->f.get(), *A_in);
-        *out = h.release();
+        create_handle(opt, out, A_in, [&](auto v, omg_hierarchy &) {
+            return create_from_fine<decltype(v)>(*A_in, dim, shape, n_restrictions, opt->smoother, opt->omega, opt->nullspace);
+        });
     });
 }
 
@@ -2640,19 +2648,13 @@ int omg_hierarchy_create_from_fine_ragged(const omg_csr *A_in, int dim, const in
     return guarded([&] {
         OMG_REQUIRE(out && A_in, "null argument");
         *out = nullptr;
-        OMG_REQUIRE(opt, "options are null");
-        OMG_REQUIRE(odd == OMG_ODD_REFUSE || odd == OMG_ODD_MERGE, "odd must be OMG_ODD_REFUSE or OMG_ODD_MERGE");
-        const int dtype = opt->dtype;
-        OMG_REQUIRE(dtype == OMG_DTYPE_F64 || dtype == OMG_DTYPE_F32 || dtype == OMG_DTYPE_MIXED, "unknown dtype");
-        OMG_REQUIRE(opt->nullspace == OMG_NULLSPACE_NONE || opt->nullspace == OMG_NULLSPACE_CONSTANT, "unknown nullspace kind");
-        std::unique_ptr<omg_hierarchy> h(new omg_hierarchy);
-        h->semi_dim = dim;
-        if (dtype != OMG_DTYPE_F64)
-            h->f = create_from_fine_semi<float>(*A_in, dim, shape, n_restrictions, factors, min_size, odd, opt->smoother, opt->omega, opt->nullspace, h->semi_factors);
-        else
-            h->d = create_from_fine_semi<double>(*A_in, dim, shape, n_restrictions, factors, min_size, odd, opt->smoother, opt->omega, opt->nullspace, h->semi_factors);
-        if (dtype == OMG_DTYPE_MIXED) build_mixed(h->f.get(), *A_in);
-        *out = h.release();
+        // (between the options' presence and their contents, where this entry has always checked it)
+        OMG_REQUIRE(!opt || odd == OMG_ODD_REFUSE || odd == OMG_ODD_MERGE, "odd must be OMG_ODD_REFUSE or OMG_ODD_MERGE");
+        create_handle(opt, out, A_in, [&](auto v, omg_hierarchy &h) {
+            h.semi_dim = dim;
+            return create_from_fine_semi<decltype(v)>(*A_in, dim, shape, n_restrictions, factors, min_size, odd, opt->smoother, opt->omega,
+                                                      opt->nullspace, h.semi_factors);
+        });
     });
 }
 
@@ -2709,21 +2711,23 @@ int omg_kappa_assemble_spaced(const int64_t *shape, const double *kappa, int kap
         OMG_REQUIRE(!indptr == !indices, "omg_kappa_assemble: indptr and indices are given together or not at all");
         OneShot one;
         KappaField F;
-        F.prepare(shape, kappa, kappa_on_device, walls, sigma, sigma_kind, sigma_on_device, scale, hz, hy, hx, one.s);
-        const int64_t n = int64_t(F.nx) * F.ny * F.nz, nnz = kappa_nnz(F.nx, F.ny, F.nz, F.periodic);
+        F.prepare({shape, kappa, kappa_on_device, walls, sigma, sigma_kind, sigma_on_device, scale, hz, hy, hx}, one.s);
+        // (host outputs: assembled into staging arrays in HBM, fetched once the values are known to be good)
+        const size_t n = size_t(F.rows()), nnz = size_t(F.nnz());
         DevBuf<double> dv;
         DevBuf<int32_t> dp, di;
-        if (!out_on_device) dv.alloc(size_t(nnz));
-        F.values(out_on_device ? data : dv.p, one.s, "omg_kappa_assemble");
-        if (indptr) {
-            if (!out_on_device) { dp.alloc(size_t(n) + 1); di.alloc(size_t(nnz)); }
-            kappa_pattern(F.nx, F.ny, F.nz, out_on_device ? indptr : dp.p, out_on_device ? indices : di.p, one.s, F.periodic);
-            if (!out_on_device) {
-                download_staged(indptr, dp.p, (size_t(n) + 1) * sizeof(int32_t), one.s);
-                download_staged(indices, di.p, size_t(nnz) * sizeof(int32_t), one.s);
-            }
+        if (!out_on_device) {
+            dv.alloc(nnz);
+            if (indptr) { dp.alloc(n + 1); di.alloc(nnz); }
         }
-        if (!out_on_device) download_staged(data, dv.p, size_t(nnz) * sizeof(double), one.s);
+        F.assemble(out_on_device ? indptr : dp.p, out_on_device ? indices : di.p, out_on_device ? data : dv.p, one.s, "omg_kappa_assemble");
+        if (!out_on_device) {
+            if (indptr) {
+                download_staged(indptr, dp.p, (n + 1) * sizeof(int32_t), one.s);
+                download_staged(indices, di.p, nnz * sizeof(int32_t), one.s);
+            }
+            download_staged(data, dv.p, nnz * sizeof(double), one.s);
+        }
         OMG_HIP(hipStreamSynchronize(one.s));
     });
 }
@@ -2740,37 +2744,26 @@ int omg_hierarchy_create_from_kappa_spaced(const int64_t *shape, const double *k
                                            const double *hy, const double *hx, int n_restrictions, const omg_hierarchy_options *opt,
                                            omg_hierarchy **out) {
     return guarded([&] {
-        OMG_REQUIRE(out, "out is null");
-        *out = nullptr;
-        OMG_REQUIRE(opt, "options are null");
-        const int dtype = opt->dtype;
-        OMG_REQUIRE(dtype == OMG_DTYPE_F64 || dtype == OMG_DTYPE_F32 || dtype == OMG_DTYPE_MIXED, "unknown dtype");
-        OMG_REQUIRE(opt->nullspace == OMG_NULLSPACE_NONE || opt->nullspace == OMG_NULLSPACE_CONSTANT, "unknown nullspace kind");
-        // level 0 in HBM: the pattern and the values, on a stream of this call's own (the hierarchy's does not exist yet)
-        DevCsrPlain A0;
         HostCsr hostA0;
-        {
-            OneShot one;
-            KappaField F;
-            F.prepare(shape, kappa, kappa_on_device, walls, sigma, sigma_kind, sigma_on_device, scale, hz, hy, hx, one.s);
-            SetupTimer tm("device setup: the fine operator from kappa");
-            A0.n_rows = A0.n_cols = int64_t(F.nx) * F.ny * F.nz;
-            A0.nnz = kappa_nnz(F.nx, F.ny, F.nz, F.periodic);
-            A0.indptr.alloc(size_t(A0.n_rows) + 1);
-            A0.indices.alloc(size_t(A0.nnz));
-            A0.data.alloc(size_t(A0.nnz));
-            kappa_pattern(F.nx, F.ny, F.nz, A0.indptr.p, A0.indices.p, one.s, F.periodic);
-            F.values(A0.data.p, one.s, "omg_hierarchy_create_from_kappa");
-            // (the fp64 outer operator of a mixed hierarchy is coded by the host: the one download of this route besides the
-            // fall-back of create_from_fine, which fetches the whole chain when a level does not qualify)
-            if (dtype == OMG_DTYPE_MIXED) hostA0 = download_csr(A0, one.s);
-        }
-        const omg_csr none = {};
-        std::unique_ptr<omg_hierarchy> h(new omg_hierarchy);
-        if (dtype != OMG_DTYPE_F64) h->f = create_from_fine<float>(none, 3, shape, n_restrictions, opt->smoother, opt->omega, opt->nullspace, &A0);
-        else h->d = create_from_fine<double>(none, 3, shape, n_restrictions, opt->smoother, opt->omega, opt->nullspace, &A0);
-        if (dtype == OMG_DTYPE_MIXED) build_mixed(h->f.get(), view(hostA0));
-        *out = h.release();
+        omg_csr fine = {};
+        create_handle(opt, out, &fine, [&](auto v, omg_hierarchy &) {
+            // level 0 in HBM: the pattern and the values, on a stream of this call's own (the hierarchy's does not exist yet)
+            DevCsrPlain A0;
+            {
+                OneShot one;
+                KappaField F;
+                F.prepare({shape, kappa, kappa_on_device, walls, sigma, sigma_kind, sigma_on_device, scale, hz, hy, hx}, one.s);
+                SetupTimer tm("device setup: the fine operator from kappa");
+                F.assemble(A0, one.s, "omg_hierarchy_create_from_kappa");
+                // (the fp64 outer operator of a mixed hierarchy is coded by the host: the one download of this route besides the
+                // fall-back of create_from_fine, which fetches the whole chain when a level does not qualify)
+                if (opt->dtype == OMG_DTYPE_MIXED) {
+                    hostA0 = download_csr(A0, one.s);
+                    fine = view(hostA0);
+                }
+            }
+            return create_from_fine<decltype(v)>(omg_csr(), 3, shape, n_restrictions, opt->smoother, opt->omega, opt->nullspace, &A0);
+        });
     });
 }
 
@@ -2792,10 +2785,10 @@ int omg_hierarchy_update_kappa_spaced(omg_hierarchy *h, const int64_t *shape, co
                         "omg_hierarchy_update_kappa: needs a hierarchy that omg_hierarchy_update_fine takes (omg_hierarchy_can_update_fine) "
                         "whose level 0 is the 7-point operator on the grid `shape`");
             KappaField F;
-            F.prepare(shape, kappa, kappa_on_device, walls, sigma, sigma_kind, sigma_on_device, scale, hz, hy, hx, hh->stream);
+            F.prepare({shape, kappa, kappa_on_device, walls, sigma, sigma_kind, sigma_on_device, scale, hz, hy, hx}, hh->stream);
             // (a hierarchy this entry takes has the in-grid pattern on level 0: no fused path holds a wrap-around row)
             OMG_REQUIRE(!F.any_periodic(), "omg_hierarchy_update_kappa: the hierarchy's fine operator has the in-grid pattern, the walls name a periodic axis");
-            nnz = kappa_nnz(F.nx, F.ny, F.nz);
+            nnz = F.nnz();
             OMG_REQUIRE(nnz == hh->nnz0, "internal: the fine pattern is not the in-grid 7-point pattern");
             if (hh->kappa_vals.n != size_t(nnz)) hh->kappa_vals.alloc(size_t(nnz));
             F.values(hh->kappa_vals.p, hh->stream, "omg_hierarchy_update_kappa");

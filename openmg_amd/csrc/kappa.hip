@@ -314,27 +314,15 @@ bool finite_pos(double v) { return v > 0.0 && v < HUGE_VAL; }
 
 }  // namespace
 
-int64_t kappa_nnz(int nx, int ny, int nz, const int *periodic) {
-    const int64_t n = int64_t(nx) * ny * nz;
-    const bool pz = periodic && periodic[0], py = periodic && periodic[1], px = periodic && periodic[2];
-    return 7 * n - 2 * ((pz ? 0 : int64_t(nx) * ny) + (py ? 0 : int64_t(nx) * nz) + (px ? 0 : int64_t(ny) * nz));
+int64_t KappaField::nnz() const {
+    return 7 * rows() - 2 * ((periodic[0] ? 0 : int64_t(nx) * ny) + (periodic[1] ? 0 : int64_t(nx) * nz) + (periodic[2] ? 0 : int64_t(ny) * nz));
 }
 
-void kappa_pattern(int nx, int ny, int nz, int32_t *indptr, int32_t *indices, hipStream_t s, const int *periodic) {
-    const int64_t n = int64_t(nx) * ny * nz;
-    const KappaGrid g = {nx, ny, nz};
-    const dim3 grid((unsigned)((n + 1 + KAPPA_BLOCK - 1) / KAPPA_BLOCK));
-    if (periodic && (periodic[0] || periodic[1] || periodic[2])) {
-        const KappaWrap wr = {periodic[0], periodic[1], periodic[2]};
-        hipLaunchKernelGGL(kappa_pattern_wrap_kernel, grid, dim3(KAPPA_BLOCK), 0, s, g, wr, indptr, indices);
-    } else {
-        hipLaunchKernelGGL(kappa_pattern_kernel, grid, dim3(KAPPA_BLOCK), 0, s, g, indptr, indices);
-    }
-    OMG_HIP(hipGetLastError());
-}
-
-void KappaField::prepare(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls, const double *sigma, int kind,
-                         int sigma_on_device, const double *scale_in, const double *hz, const double *hy, const double *hx, hipStream_t s) {
+void KappaField::prepare(const KappaInput &in, hipStream_t s) {
+    const int64_t *const shape = in.shape;
+    const int *const walls = in.walls;
+    const double *const kappa = in.kappa, *const sigma = in.sigma, *const hz = in.hz, *const hy = in.hy, *const hx = in.hx;
+    const int kind = in.sigma_kind;
     OMG_REQUIRE(shape && kappa, "kappa: null argument");
     for (int d = 0; d < 3; ++d)
         OMG_REQUIRE(shape[d] >= 1 && shape[d] < (int64_t(1) << 30), "kappa: every extent of the shape must be >= 1");
@@ -361,7 +349,7 @@ void KappaField::prepare(const int64_t *shape, const double *kappa, int kappa_on
                                              std::to_string((long long)shape[d]));
     }
     for (int d = 0; d < 3; ++d) {
-        scale[d] = scale_in ? scale_in[d] : 1.0;
+        scale[d] = in.scale ? in.scale[d] : 1.0;
         OMG_REQUIRE(finite_pos(scale[d]), "kappa: every scale factor must be finite and > 0");
     }
     // the cell widths: all three axes or none, in place of the scale factors; checked here, before any launch
@@ -392,11 +380,11 @@ void KappaField::prepare(const int64_t *shape, const double *kappa, int kappa_on
     sigma_kind = kind;
     sigma_dev = nullptr;
     sigma_value = 0.0;
-    if (kind == OMG_SIGMA_SCALAR && !sigma_on_device) {
+    if (kind == OMG_SIGMA_SCALAR && !in.sigma_on_device) {
         sigma_value = sigma[0];
         OMG_REQUIRE(sigma_value >= 0.0 && sigma_value < HUGE_VAL, "kappa: sigma must be finite and >= 0");
     } else if (kind != OMG_SIGMA_NONE) {
-        if (sigma_on_device) {
+        if (in.sigma_on_device) {
             sigma_dev = sigma;
         } else {
             own_sigma.alloc(size_t(nx) * ny * nz);
@@ -404,7 +392,7 @@ void KappaField::prepare(const int64_t *shape, const double *kappa, int kappa_on
             sigma_dev = own_sigma.p;
         }
     }
-    if (kappa_on_device) {
+    if (in.kappa_on_device) {
         kappa_dev = kappa;
     } else {
         own_kappa.alloc(size_t(padded));
@@ -414,44 +402,47 @@ void KappaField::prepare(const int64_t *shape, const double *kappa, int kappa_on
     if (!err.p) err.alloc(1);
 }
 
-void KappaField::values(double *data, hipStream_t s, const char *entry) {
-    KappaSpacedArgs a;
-    a.g = {nx, ny, nz};
-    a.kappa = kappa_dev;
-    a.sigma = sigma_dev;
-    a.sigma_value = sigma_value;
-    a.sigma_kind = sigma_kind;
-    for (int f = 0; f < 6; ++f) a.neumann[f] = neumann[f];
-    for (int d = 0; d < 3; ++d) a.scale[d] = scale[d];
+namespace {
+
+// the launch of one instantiation: its argument block filled from the field
+template <bool STAGED, bool SPACED, bool PERIODIC>
+void launch_values(const KappaField &F, double *data, hipStream_t s) {
+    kappa_kernel_args_t<SPACED, PERIODIC> a;
+    a.g = {F.nx, F.ny, F.nz};
+    a.kappa = F.kappa_dev;
+    a.sigma = F.sigma_dev;
+    a.sigma_value = F.sigma_value;
+    a.sigma_kind = F.sigma_kind;
+    for (int f = 0; f < 6; ++f) a.neumann[f] = F.neumann[f];
+    for (int d = 0; d < 3; ++d) a.scale[d] = F.scale[d];
     a.data = data;
-    a.err = err.p;
-    const int64_t n = int64_t(nx) * ny * nz;
-    const dim3 grid((unsigned)((n + KAPPA_BLOCK - 1) / KAPPA_BLOCK));
-    OMG_HIP(hipMemsetAsync(err.p, 0xFF, sizeof(unsigned long long), s));
-    a.hz = spaced ? widths.p : nullptr;
-    a.hy = spaced ? widths.p + (nz + 2) : nullptr;
-    a.hx = spaced ? widths.p + (nz + 2) + (ny + 2) : nullptr;
-    const KappaValuesArgs &plain = a;
-    if (any_periodic()) {
-        KappaWrapArgs<true> ws;
-        KappaWrapArgs<false> wp;
-        static_cast<KappaSpacedArgs &>(ws) = a;
-        static_cast<KappaValuesArgs &>(wp) = plain;
-        ws.wrap = wp.wrap = {periodic[0], periodic[1], periodic[2]};
-        if (spaced) {
-            if (kappa_staged()) hipLaunchKernelGGL((kappa_values_kernel<true, true, true>), grid, dim3(KAPPA_BLOCK), 0, s, ws);
-            else hipLaunchKernelGGL((kappa_values_kernel<false, true, true>), grid, dim3(KAPPA_BLOCK), 0, s, ws);
-        } else {
-            if (kappa_staged()) hipLaunchKernelGGL((kappa_values_kernel<true, false, true>), grid, dim3(KAPPA_BLOCK), 0, s, wp);
-            else hipLaunchKernelGGL((kappa_values_kernel<false, false, true>), grid, dim3(KAPPA_BLOCK), 0, s, wp);
-        }
-    } else if (spaced) {
-        if (kappa_staged()) hipLaunchKernelGGL((kappa_values_kernel<true, true, false>), grid, dim3(KAPPA_BLOCK), 0, s, a);
-        else hipLaunchKernelGGL((kappa_values_kernel<false, true, false>), grid, dim3(KAPPA_BLOCK), 0, s, a);
-    } else {
-        if (kappa_staged()) hipLaunchKernelGGL((kappa_values_kernel<true, false, false>), grid, dim3(KAPPA_BLOCK), 0, s, plain);
-        else hipLaunchKernelGGL((kappa_values_kernel<false, false, false>), grid, dim3(KAPPA_BLOCK), 0, s, plain);
+    a.err = F.err.p;
+    if constexpr (SPACED) {
+        a.hz = F.widths.p;
+        a.hy = F.widths.p + (F.nz + 2);
+        a.hx = F.widths.p + (F.nz + 2) + (F.ny + 2);
     }
+    if constexpr (PERIODIC) a.wrap = {F.periodic[0], F.periodic[1], F.periodic[2]};
+    const dim3 grid((unsigned)((F.rows() + KAPPA_BLOCK - 1) / KAPPA_BLOCK));
+    hipLaunchKernelGGL((kappa_values_kernel<STAGED, SPACED, PERIODIC>), grid, dim3(KAPPA_BLOCK), 0, s, a);
+}
+
+// f(std::true_type) or f(std::false_type): a run-time flag as a compile-time constant
+template <typename F>
+void as_constant(bool flag, F &&f) {
+    if (flag) f(std::true_type());
+    else f(std::false_type());
+}
+
+}  // namespace
+
+void KappaField::values(double *data, hipStream_t s, const char *entry) {
+    OMG_HIP(hipMemsetAsync(err.p, 0xFF, sizeof(unsigned long long), s));
+    as_constant(kappa_staged(), [&](auto staged) {
+        as_constant(spaced, [&](auto sp) {
+            as_constant(any_periodic(), [&](auto wrap) { launch_values<decltype(staged)::value, decltype(sp)::value, decltype(wrap)::value>(*this, data, s); });
+        });
+    });
     OMG_HIP(hipGetLastError());
     unsigned long long e = ~0ull;
     OMG_HIP(hipMemcpyAsync(&e, err.p, sizeof(e), hipMemcpyDeviceToHost, s));
@@ -463,6 +454,30 @@ void KappaField::values(double *data, hipStream_t s, const char *entry) {
     const std::string cell = "cell (" + std::to_string(z) + ", " + std::to_string(y) + ", " + std::to_string(x) + ")";
     if (e & 1) throw Error(OMG_ERR_INVALID, std::string(entry) + ": sigma at " + cell + " is not finite and >= 0");
     throw Error(OMG_ERR_INVALID, std::string(entry) + ": kappa at " + cell + " is not finite and > 0");
+}
+
+void KappaField::assemble(int32_t *indptr, int32_t *indices, double *data, hipStream_t s, const char *entry) {
+    if (indptr) {
+        const KappaGrid g = {nx, ny, nz};
+        const dim3 grid((unsigned)((rows() + 1 + KAPPA_BLOCK - 1) / KAPPA_BLOCK));
+        if (any_periodic()) {
+            const KappaWrap wr = {periodic[0], periodic[1], periodic[2]};
+            hipLaunchKernelGGL(kappa_pattern_wrap_kernel, grid, dim3(KAPPA_BLOCK), 0, s, g, wr, indptr, indices);
+        } else {
+            hipLaunchKernelGGL(kappa_pattern_kernel, grid, dim3(KAPPA_BLOCK), 0, s, g, indptr, indices);
+        }
+        OMG_HIP(hipGetLastError());
+    }
+    values(data, s, entry);
+}
+
+void KappaField::assemble(DevCsrPlain &A, hipStream_t s, const char *entry) {
+    A.n_rows = A.n_cols = rows();
+    A.nnz = nnz();
+    A.indptr.alloc(size_t(A.n_rows) + 1);
+    A.indices.alloc(size_t(A.nnz));
+    A.data.alloc(size_t(A.nnz));
+    assemble(A.indptr.p, A.indices.p, A.data.p, s, entry);
 }
 
 }  // namespace omg

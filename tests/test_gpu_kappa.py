@@ -2,7 +2,6 @@
 omg_kappa_assemble against the SciPy definition operators.stencil7_kappa, Hierarchy.from_kappa / update_kappa against
 from_fine / update_fine of that definition, Solver.from_kappa / update_kappa against Solver(A) / update(A).  Every
 comparison is bit for bit and with the existing routes, never with the code under test.  Needs an MI355X: run with -m gpu."""
-import ctypes
 import os
 import subprocess
 import sys
@@ -14,43 +13,11 @@ import openmg_amd
 from openmg_amd import _hip, operators
 
 import kappa_cases as kc
+from kappa_gpu import DeviceArray, flags, params, run, run_pcg, same, same_solve, vectors
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-class DeviceArray:
-    """A NumPy array's copy in HBM with __cuda_array_interface__ (hipMalloc / hipMemcpy / hipFree through the HIP runtime
-    the library itself uses: no PyTorch in this process)."""
-    hip = None
-
-    def __init__(self, host):
-        if DeviceArray.hip is None:
-            hip = ctypes.CDLL("libamdhip64.so.7")
-            hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-            hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-            hip.hipFree.argtypes = [ctypes.c_void_p]
-            DeviceArray.hip = hip
-        host = np.ascontiguousarray(host)
-        self.shape, self.dtype, self.nbytes = host.shape, host.dtype, host.nbytes
-        self.d = ctypes.c_void_p()
-        assert self.hip.hipMalloc(ctypes.byref(self.d), max(host.nbytes, 8)) == 0
-        assert self.hip.hipMemcpy(self.d, host.ctypes.data, host.nbytes, 1) == 0
-
-    @property
-    def __cuda_array_interface__(self):
-        return {"shape": tuple(self.shape), "typestr": self.dtype.str, "data": (self.d.value, False), "version": 2, "strides": None}
-
-    def numpy(self):
-        out = np.empty(self.shape, dtype=self.dtype)
-        assert self.hip.hipMemcpy(out.ctypes.data, self.d, self.nbytes, 2) == 0
-        return out
-
-    def __del__(self):
-        if self.d:
-            self.hip.hipFree(self.d)
-            self.d = None
 
 
 # ---- assembly -------------------------------------------------------------------------------------------------------------
@@ -139,32 +106,6 @@ def test_a_bad_value_is_refused_naming_the_first_cell_and_the_next_call_works():
 
 
 # ---- creation and update ----------------------------------------------------------------------------------------------------
-def run(h, b, x0, cycles=5):
-    h.resident_load(b, x0)
-    return [h.resident_cycle(1, 1) for _ in range(cycles)], h.resident_fetch()
-
-
-def run_pcg(h, b, x0, iterations=5):
-    h.resident_load(b, x0)
-    it, norms, true_norm, breakdown = h.resident_pcg(1, 1, iterations)
-    return [it, true_norm, breakdown] + list(norms), h.resident_fetch()
-
-
-def same(a, b):
-    return a[0] == b[0] and np.array_equal(a[1], b[1])
-
-
-def flags(h):
-    return [h.level_flags(l) for l in range(h.n_levels - 1)]
-
-
-def vectors(shape, dtype):
-    b, x0 = kc.rhs_of(shape)
-    if dtype != "float64":
-        b, x0 = b.astype(np.float32).astype(np.float64), x0.astype(np.float32).astype(np.float64)
-    return b, x0
-
-
 VAR7 = [((16, 16, 16), 3, ["var7", "host"]), ((32, 32, 32), 4, ["var7", "var7", "host"])]
 SETTINGS = [("dirichlet", "none", (1.0, 1.0, 1.0)), ("mixed", "field", (4.0, 1.0, 0.25))]
 
@@ -185,17 +126,17 @@ def test_from_kappa_and_update_kappa_against_from_fine_and_update_fine(monkeypat
         assert ["var7" if f["var7"] else "host" for f in flags(h)] == kinds
         assert h.can_update_fine() and ref.can_update_fine()
         assert h.sizes == ref.sizes and h.device_dtype() == ref.device_dtype()
-        first = go(ref, b, x0)
-        assert same(go(h, b, x0), first)
+        first = go(ref, b, x0, 5)
+        assert same(go(h, b, x0, 5), first)
         # update: against a fresh from_kappa of the new field and against update_fine of the definition's values
         h.update_kappa(k2, walls, sigma, scale)
         ref.update_fine(A2.data)
-        second = go(ref, b, x0)
+        second = go(ref, b, x0, 5)
         assert not np.array_equal(second[1], first[1])
-        assert same(go(h, b, x0), second)
+        assert same(go(h, b, x0, 5), second)
         with _hip.Hierarchy.from_kappa(k2, grids - 1, walls, sigma, scale, smoother="colour", dtype=dtype) as fresh:
             assert flags(fresh) == flags(ref)
-            assert same(go(fresh, b, x0), second)
+            assert same(go(fresh, b, x0, 5), second)
         # back again (the value array of the hierarchy is reused), the resident b and x stay across an update
         h.resident_load(b, x0)
         h.update_kappa(k1, walls, sigma, scale)
@@ -203,7 +144,7 @@ def test_from_kappa_and_update_kappa_against_from_fine_and_update_fine(monkeypat
         ref.update_fine(A1.data)
         assert np.array_equal(h.resident_fetch(), ref.resident_fetch())
         assert h.resident_cycle(1, 1) == ref.resident_cycle(1, 1)
-        assert same(go(h, b, x0), first)
+        assert same(go(h, b, x0, 5), first)
         # a refused field leaves the hierarchy as it is; so does a field of another grid
         bad = k2.copy()
         bad[5, 5, 5] = np.nan
@@ -213,7 +154,7 @@ def test_from_kappa_and_update_kappa_against_from_fine_and_update_fine(monkeypat
         with pytest.raises(_hip.HipError) as e:
             h.update_kappa(kc.kappa_of((8, 8, 8)), walls, None, scale)
         assert e.value.code == _hip.ERR_INVALID
-        assert same(go(h, b, x0), first)
+        assert same(go(h, b, x0, 5), first)
 
 
 @pytest.mark.parametrize("dtype", ["float64", "float32", "mixed"])
@@ -227,12 +168,12 @@ def test_constant_kappa_gives_the_plane_hierarchy_and_update_kappa_refuses_it(dt
             _hip.Hierarchy.from_kappa(kappa, grids - 1, smoother="colour", dtype=dtype) as h:
         assert flags(h) == flags(ref) and all(f["plane"] for f in flags(h))
         assert h.can_update_fine() == ref.can_update_fine() and not h.can_update_fine()
-        want = go(ref, b, x0)
-        assert same(go(h, b, x0), want)
+        want = go(ref, b, x0, 5)
+        assert same(go(h, b, x0, 5), want)
         with pytest.raises(_hip.HipError) as e:
             h.update_kappa(kc.kappa_of(shape))
         assert e.value.code == _hip.ERR_INVALID
-        assert same(go(h, b, x0), want)                               # still cycles as before
+        assert same(go(h, b, x0, 5), want)                               # still cycles as before
 
 
 def test_a_hierarchy_made_from_lists_is_refused_by_update_kappa():
@@ -247,15 +188,6 @@ def test_a_hierarchy_made_from_lists_is_refused_by_update_kappa():
 
 
 # ---- Solver ---------------------------------------------------------------------------------------------------------------
-def params(shape, grids, **more):
-    return dict({"problemShape": shape, "gridLevels": grids, "preIterations": 1, "postIterations": 1, "smoother": "colour",
-                 "cycles": 6, "threshold": 0.0, "minSize": 8}, **more)
-
-
-def same_solve(a, b):
-    return np.array_equal(a[0], b[0]) and a[1]["norms"] == b[1]["norms"] and a[1]["cycle"] == b[1]["cycle"] and a[1]["norm"] == b[1]["norm"]
-
-
 @pytest.mark.parametrize("more", [{}, {"accel": "cg"}, {"cycle": "F", "overCorrection": 1.8}, {"dtype": "mixed", "accel": "cg"}],
                          ids=["plain", "cg", "F-1.8", "mixed-cg"])
 def test_solver_from_kappa_and_three_time_steps(monkeypatch, more):
@@ -264,7 +196,7 @@ def test_solver_from_kappa_and_three_time_steps(monkeypatch, more):
     walls, scale = kc.WALLS["mixed"], (4.0, 1.0, 0.25)
     sigma = kc.sigma_of("field", shape)
     b = kc.rhs_of(shape)[0]
-    p = params(shape, grids, **more)
+    p = params(shape, grids, 6, **more)
     fields = [kc.kappa_of(shape, seed=30 + step) for step in range(4)]
     matrices = [operators.stencil7_kappa(k, walls, sigma, scale) for k in fields]
     with openmg_amd.Solver(matrices[0], p) as ref, openmg_amd.Solver.from_kappa(fields[0], p, walls, sigma, scale) as s:
@@ -295,7 +227,7 @@ def test_solver_from_kappa_on_the_singular_all_neumann_operator(monkeypatch):
     b = kc.rhs_of(shape)[0]
     b -= b.mean()
     for more in ({}, {"accel": "cg"}):
-        p = params(shape, grids, nullspace="constant", **more)
+        p = params(shape, grids, 6, nullspace="constant", **more)
         with openmg_amd.Solver(A, p) as ref, openmg_amd.Solver.from_kappa(kappa, p, walls) as s:
             got, want = s.solve(b), ref.solve(b)
             assert same_solve(got, want) and abs(got[0].mean()) < 1e-10 * np.abs(got[0]).max()
@@ -309,7 +241,7 @@ def test_solver_from_kappa_with_parameters_of_the_ordinary_route(more):
     kappa, kappa2 = kc.kappa_of(shape, seed=50), kc.kappa_of(shape, seed=51)
     A, A2 = operators.stencil7_kappa(kappa, walls, sigma, scale), operators.stencil7_kappa(kappa2, walls, sigma, scale)
     b = kc.rhs_of(shape)[0]
-    p = params(shape, 2, **more)
+    p = params(shape, 2, 6, **more)
     with openmg_amd.Solver(A, p) as ref, openmg_amd.Solver.from_kappa(kappa, p, walls, sigma, scale) as s:
         assert not s.hierarchy.can_update_fine()
         assert same_solve(s.solve(b), ref.solve(b))

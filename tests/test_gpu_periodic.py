@@ -13,7 +13,7 @@ import openmg_amd
 from openmg_amd import _hip, operators
 
 import periodic_cases as pc
-from test_gpu_kappa import DeviceArray
+from kappa_gpu import DeviceArray, flags, params, run, run_pcg, same, same_solve, vectors
 
 pytestmark = pytest.mark.gpu
 
@@ -101,32 +101,6 @@ def test_ghost_layers_are_not_read_and_bad_cells_are_named():
 
 
 # ---- hierarchies ----------------------------------------------------------------------------------------------------------
-def run(h, b, x0, cycles=3):
-    h.resident_load(b, x0)
-    return [h.resident_cycle(1, 1) for _ in range(cycles)], h.resident_fetch()
-
-
-def run_pcg(h, b, x0, iterations=3):
-    h.resident_load(b, x0)
-    it, norms, true_norm, breakdown = h.resident_pcg(1, 1, iterations)
-    return [it, true_norm, breakdown] + list(norms), h.resident_fetch()
-
-
-def same(a, b):
-    return a[0] == b[0] and np.array_equal(a[1], b[1])
-
-
-def flags(h):
-    return [h.level_flags(l) for l in range(h.n_levels - 1)]
-
-
-def vectors(shape, dtype="float64"):
-    b, x0 = pc.rhs_of(shape)
-    if dtype != "float64":
-        b, x0 = b.astype(np.float32).astype(np.float64), x0.astype(np.float32).astype(np.float64)
-    return b, x0
-
-
 def lists_of(A0, shape, restrictions):
     R = operators.restrictionList(shape, restrictions - 1, 1)
     assert len(R) == restrictions
@@ -155,7 +129,7 @@ def test_from_kappa_is_the_hierarchy_made_from_the_definitions_lists(shape, smoo
     b, x0 = vectors(shape, dtype)
     go = run_pcg if dtype == "mixed" else run
     with _hip.Hierarchy(A, R, smoother=smoother, omega=omega, dtype=dtype, nullspace=nullspace) as ref:
-        want = go(ref, b, x0)
+        want = go(ref, b, x0, 3)
         assert np.isfinite(want[0]).all()
         if shape[0] == shape[2]:
             # omg_hierarchy_create_from_kappa: level 0 in HBM, the chain on the device, then the ordinary route
@@ -171,7 +145,7 @@ def test_from_kappa_is_the_hierarchy_made_from_the_definitions_lists(shape, smoo
             h = m if isinstance(m, _hip.Hierarchy) else m.hierarchy
             assert h.n_levels == 3 and flags(h) == flags(ref)
             assert not h.can_update_fine()
-            assert same(go(h, b, x0), want)
+            assert same(go(h, b, x0, 3), want)
 
 
 @pytest.mark.parametrize("shape,restrictions,constant", [((32, 32, 32), 3, True), ((128, 128, 128), 3, False)], ids=["constant-32", "random-128"])
@@ -197,33 +171,24 @@ def test_update_kappa_of_the_c_interface_refuses_a_periodic_hierarchy_and_leaves
     k1, k2 = pc.kappa_of(shape, seed=11, decades=1.0), pc.kappa_of(shape, seed=21, decades=1.0)
     b, x0 = vectors(shape)
     with _hip.Hierarchy.from_kappa(k1, 2, walls, smoother="colour") as h:
-        want = run(h, b, x0)
+        want = run(h, b, x0, 3)
         for w in (walls, None):                                          # the same walls; the in-grid ones
             with pytest.raises(_hip.HipError) as e:
                 h.update_kappa(k2, w)
             assert e.value.code == _hip.ERR_INVALID
-        assert same(run(h, b, x0), want)
+        assert same(run(h, b, x0, 3), want)
     # ... and a hierarchy with the in-grid pattern refuses periodic walls
     monkeypatch.setenv("OMG_VAR7_MIN", "4096")               # (by default only levels of 128^3 and more take the var7 passes)
     with _hip.Hierarchy.from_kappa(k1, 2, smoother="colour") as h:
         assert h.can_update_fine()
-        want = run(h, b, x0)
+        want = run(h, b, x0, 3)
         with pytest.raises(_hip.HipError) as e:
             h.update_kappa(k2, walls)
         assert e.value.code == _hip.ERR_INVALID
-        assert same(run(h, b, x0), want)
+        assert same(run(h, b, x0, 3), want)
 
 
 # ---- Solver ---------------------------------------------------------------------------------------------------------------
-def params(shape, grids, **more):
-    return dict({"problemShape": shape, "gridLevels": grids, "preIterations": 1, "postIterations": 1, "smoother": "colour",
-                 "cycles": 80, "threshold": 0.0, "rtol": 1e-8, "minSize": 8}, **more)
-
-
-def same_solve(a, b):
-    return np.array_equal(a[0], b[0]) and a[1]["norms"] == b[1]["norms"] and a[1]["cycle"] == b[1]["cycle"] and a[1]["norm"] == b[1]["norm"]
-
-
 @pytest.mark.parametrize("more", [{}, {"accel": "cg"}, {"cycle": "F", "overCorrection": 1.8, "accel": "cg", "dtype": "mixed"}],
                          ids=["plain", "cg", "mixed-F-cg"])
 @pytest.mark.parametrize("shape", [(16, 16, 16), (16, 8, 16)])
@@ -233,7 +198,7 @@ def test_solver_with_periodic_x_and_z_between_dirichlet_walls(shape, more):
     k1, k2 = pc.nan_ghosts(pc.kappa_of(shape, 30, 1.0), (0, 2)), pc.nan_ghosts(pc.kappa_of(shape, 31, 1.0), (0, 2))
     A1, A2 = operators.stencil7_kappa(k1, walls, sigma, pc.SCALE), operators.stencil7_kappa(k2, walls, sigma, pc.SCALE)
     b = pc.rhs_of(shape)[0]
-    p = params(shape, 3, **more)
+    p = params(shape, 3, 80, rtol=1e-8, **more)
     with openmg_amd.Solver(A1, p) as ref, openmg_amd.Solver.from_kappa(k1, p, walls, sigma, pc.SCALE) as s:
         assert s.A is None and s.R is None and not s.hierarchy.can_update_fine() and flags(s.hierarchy) == flags(ref.hierarchy)
         first = ref.solve(b)
@@ -269,7 +234,7 @@ def test_solver_on_the_periodic_box_returns_a_zero_mean_solution(more):
     # without a Dirichlet wall or a sigma, and how fast it converges is not what this test is about)
     A = operators.stencil7_kappa(kappa, walls)
     b = pc.rhs_of(shape)[0]
-    p = params(shape, 3, nullspace="constant", cycles=300, **more)
+    p = params(shape, 3, 300, rtol=1e-8, nullspace="constant", **more)
     with openmg_amd.Solver(A, p) as ref, openmg_amd.Solver.from_kappa(kappa, p, walls) as s:
         got, want = s.solve(b), ref.solve(b)
         assert same_solve(got, want) and got[1]["norm"] <= 1e-8 * got[1]["rhs_norm"]
@@ -283,17 +248,17 @@ def test_named_factors_solve_and_line_and_auto_stay_clean_errors():
     kappa, sigma = pc.kappa_of(shape, 50, 1.0), 0.375
     A = operators.stencil7_kappa(kappa, walls, sigma)
     b = pc.rhs_of(shape)[0]
-    p = params(shape, 2, coarsening=[(1, 2, 2), (2, 2, 2)])       # (gridLevels 2: up to two restrictions, the list is consumed exactly)
+    p = params(shape, 2, 80, rtol=1e-8, coarsening=[(1, 2, 2), (2, 2, 2)])       # (gridLevels 2: up to two restrictions, the list is consumed exactly)
     with openmg_amd.Solver(A, p) as ref, openmg_amd.Solver.from_kappa(kappa, p, walls, sigma) as s:
         got = s.solve(b)
         assert same_solve(got, ref.solve(b)) and got[1]["coarsening"] == [(1, 2, 2), (2, 2, 2)] and got[1]["cycle"] < 80
-    p = params(shape, 3, oddExtents="merge")
+    p = params(shape, 3, 80, rtol=1e-8, oddExtents="merge")
     with openmg_amd.Solver(A, p) as ref, openmg_amd.Solver.from_kappa(kappa, p, walls, sigma) as s:
         assert same_solve(s.solve(b), ref.solve(b))
     for more in ({"smoother": "line"}, {"coarsening": "auto"}):
         for make in (lambda q: openmg_amd.Solver.from_kappa(kappa, q, walls, sigma), lambda q: openmg_amd.Solver(A, q)):
             with pytest.raises(_hip.HipError) as e:
-                make(params(shape, 3, **more))
+                make(params(shape, 3, 80, rtol=1e-8, **more))
             assert e.value.code == _hip.ERR_UNSUPPORTED, more
 
 
@@ -305,8 +270,8 @@ def test_device_fields_give_the_bits_of_host_fields():
     d_kappa, d_sigma = DeviceArray(kappa), DeviceArray(sigma)
     with _hip.Hierarchy.from_kappa(kappa, 2, walls, sigma, pc.SCALE, smoother="colour") as host, \
             _hip.Hierarchy.from_kappa(d_kappa, 2, walls, d_sigma, pc.SCALE, smoother="colour") as dev:
-        assert same(run(dev, b, x0), run(host, b, x0))
-    p = params(shape, 3, accel="cg")
+        assert same(run(dev, b, x0, 3), run(host, b, x0, 3))
+    p = params(shape, 3, 80, rtol=1e-8, accel="cg")
     with openmg_amd.Solver.from_kappa(kappa, p, walls, sigma, pc.SCALE) as host, \
             openmg_amd.Solver.from_kappa(d_kappa, p, walls, d_sigma, pc.SCALE) as dev:
         assert same_solve(dev.solve(b), host.solve(b))

@@ -16,43 +16,11 @@ from openmg_amd import _hip, operators
 
 import kappa_cases as kc
 import stretched_cases as sc
+from kappa_gpu import DeviceArray, flags, params, run, run_pcg, same, same_solve, vectors
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-class DeviceArray:
-    """A NumPy array's copy in HBM with __cuda_array_interface__ (hipMalloc / hipMemcpy / hipFree through the HIP runtime
-    the library itself uses: no PyTorch in this process)."""
-    hip = None
-
-    def __init__(self, host):
-        if DeviceArray.hip is None:
-            hip = ctypes.CDLL("libamdhip64.so.7")
-            hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-            hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-            hip.hipFree.argtypes = [ctypes.c_void_p]
-            DeviceArray.hip = hip
-        host = np.ascontiguousarray(host)
-        self.shape, self.dtype, self.nbytes = host.shape, host.dtype, host.nbytes
-        self.d = ctypes.c_void_p()
-        assert self.hip.hipMalloc(ctypes.byref(self.d), max(host.nbytes, 8)) == 0
-        assert self.hip.hipMemcpy(self.d, host.ctypes.data, host.nbytes, 1) == 0
-
-    @property
-    def __cuda_array_interface__(self):
-        return {"shape": tuple(self.shape), "typestr": self.dtype.str, "data": (self.d.value, False), "version": 2, "strides": None}
-
-    def numpy(self):
-        out = np.empty(self.shape, dtype=self.dtype)
-        assert self.hip.hipMemcpy(out.ctypes.data, self.d, self.nbytes, 2) == 0
-        return out
-
-    def __del__(self):
-        if self.d:
-            self.hip.hipFree(self.d)
-            self.d = None
 
 
 # ---- assembly -------------------------------------------------------------------------------------------------------------
@@ -169,32 +137,6 @@ def test_bad_values_and_bad_widths_are_refused_and_the_next_call_works():
 
 
 # ---- creation and update ----------------------------------------------------------------------------------------------------
-def run(h, b, x0, cycles=5):
-    h.resident_load(b, x0)
-    return [h.resident_cycle(1, 1) for _ in range(cycles)], h.resident_fetch()
-
-
-def run_pcg(h, b, x0, iterations=5):
-    h.resident_load(b, x0)
-    it, norms, true_norm, breakdown = h.resident_pcg(1, 1, iterations)
-    return [it, true_norm, breakdown] + list(norms), h.resident_fetch()
-
-
-def same(a, b):
-    return a[0] == b[0] and np.array_equal(a[1], b[1])
-
-
-def flags(h):
-    return [h.level_flags(l) for l in range(h.n_levels - 1)]
-
-
-def vectors(shape, dtype):
-    b, x0 = kc.rhs_of(shape)
-    if dtype != "float64":
-        b, x0 = b.astype(np.float32).astype(np.float64), x0.astype(np.float32).astype(np.float64)
-    return b, x0
-
-
 VAR7 = [((16, 16, 16), 3, ["var7", "host"]), ((32, 32, 32), 4, ["var7", "var7", "host"])]
 SETTINGS = [("dirichlet", "none", False), ("mixed", "field", True)]
 
@@ -215,14 +157,14 @@ def test_from_kappa_and_update_kappa_against_from_fine_and_update_fine(monkeypat
         assert ["var7" if f["var7"] else "host" for f in flags(h)] == kinds
         assert h.can_update_fine() and ref.can_update_fine()
         assert h.sizes == ref.sizes and h.device_dtype() == ref.device_dtype()
-        first = go(ref, b, x0)
-        assert same(go(h, b, x0), first)
+        first = go(ref, b, x0, 5)
+        assert same(go(h, b, x0, 5), first)
         # update: against update_fine of the definition's values
         h.update_kappa(k2, walls, sigma, spacing=sp)
         ref.update_fine(A2.data)
-        second = go(ref, b, x0)
+        second = go(ref, b, x0, 5)
         assert not np.array_equal(second[1], first[1])
-        assert same(go(h, b, x0), second)
+        assert same(go(h, b, x0, 5), second)
         # back again (the value array of the hierarchy is reused), the resident b and x stay across an update
         h.resident_load(b, x0)
         h.update_kappa(k1, walls, sigma, spacing=sp)
@@ -230,26 +172,17 @@ def test_from_kappa_and_update_kappa_against_from_fine_and_update_fine(monkeypat
         ref.update_fine(A1.data)
         assert np.array_equal(h.resident_fetch(), ref.resident_fetch())
         assert h.resident_cycle(1, 1) == ref.resident_cycle(1, 1)
-        assert same(go(h, b, x0), first)
+        assert same(go(h, b, x0, 5), first)
         # a refused field leaves the hierarchy as it is
         bad = k2.copy()
         bad[5, 5, 5] = np.nan
         with pytest.raises(_hip.HipError) as e:
             h.update_kappa(bad, walls, sigma, spacing=sp)
         assert e.value.code == _hip.ERR_INVALID and "kappa at cell (4, 4, 4)" in str(e.value)
-        assert same(go(h, b, x0), first)
+        assert same(go(h, b, x0, 5), first)
 
 
 # ---- Solver ---------------------------------------------------------------------------------------------------------------
-def params(shape, grids, **more):
-    return dict({"problemShape": shape, "gridLevels": grids, "preIterations": 1, "postIterations": 1, "smoother": "colour",
-                 "cycles": 6, "threshold": 0.0, "minSize": 8}, **more)
-
-
-def same_solve(a, b):
-    return np.array_equal(a[0], b[0]) and a[1]["norms"] == b[1]["norms"] and a[1]["cycle"] == b[1]["cycle"] and a[1]["norm"] == b[1]["norm"]
-
-
 @pytest.mark.parametrize("more", [{}, {"accel": "cg"}, {"cycle": "F", "overCorrection": 1.8}, {"dtype": "mixed", "accel": "cg"}],
                          ids=["plain", "cg", "F-1.8", "mixed-cg"])
 def test_solver_from_kappa_and_three_time_steps(monkeypatch, more):
@@ -258,7 +191,7 @@ def test_solver_from_kappa_and_three_time_steps(monkeypatch, more):
     walls, sp = kc.WALLS["mixed"], sc.widths_of(shape, zero=True)
     sigma = kc.sigma_of("field", shape)
     b = kc.rhs_of(shape)[0]
-    p = params(shape, grids, **more)
+    p = params(shape, grids, 6, **more)
     fields = [kc.kappa_of(shape, seed=30 + step) for step in range(4)]
     matrices = [operators.stencil7_kappa(k, walls, sigma, spacing=sp) for k in fields]
     with openmg_amd.Solver(matrices[0], p) as ref, openmg_amd.Solver.from_kappa(fields[0], p, walls, sigma, spacing=sp) as s:
@@ -282,7 +215,7 @@ def test_solver_from_kappa_on_the_singular_all_neumann_operator(monkeypatch):
     b = kc.rhs_of(shape)[0]
     b -= b.mean()
     for more in ({}, {"accel": "cg"}):
-        p = params(shape, grids, nullspace="constant", **more)
+        p = params(shape, grids, 6, nullspace="constant", **more)
         with openmg_amd.Solver(A, p) as ref, openmg_amd.Solver.from_kappa(kappa, p, walls, spacing=sp) as s:
             assert same_solve(s.solve(b), ref.solve(b))
 
@@ -307,7 +240,7 @@ def test_solver_from_kappa_with_parameters_of_the_ordinary_route(more):
     kappa, kappa2 = smooth_kappa(shape, sp), smooth_kappa(shape, sp, shift=0.7)
     A, A2 = operators.stencil7_kappa(kappa, walls, sigma, spacing=sp), operators.stencil7_kappa(kappa2, walls, sigma, spacing=sp)
     b = kc.rhs_of(shape)[0]
-    p = params(shape, 2, **more)
+    p = params(shape, 2, 6, **more)
     with openmg_amd.Solver(A, p) as ref, openmg_amd.Solver.from_kappa(kappa, p, walls, sigma, spacing=sp) as s:
         assert not s.hierarchy.can_update_fine()
         got, want = s.solve(b), ref.solve(b)
@@ -340,6 +273,7 @@ import openmg_amd
 from openmg_amd import operators
 import kappa_cases as kc
 import stretched_cases as sc
+from kappa_gpu import DeviceArray, flags, params, run, run_pcg, same, same_solve, vectors
 
 shape, grids = (16, 16, 16), 3
 walls = kc.WALLS["mixed"]

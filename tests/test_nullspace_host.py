@@ -83,6 +83,19 @@ def test_bad_options_are_refused_without_a_device():
         assert code == _hip.ERR_INVALID and not out.value
     assert b"nullspace" in _hip.lib().omg_last_error() or b"dtype" in _hip.lib().omg_last_error()
     assert _hip.lib().omg_hierarchy_create_opt(1, arrA, arrR, None, ctypes.byref(out)) == _hip.ERR_INVALID
+    # every creating entry checks its options in the one place: the same refusals, the handle null, no device asked for
+    shape = (ctypes.c_int64 * 2)(4, 2)
+    field = _hip.KappaArgs(np.ones((6, 6, 6)), None, None, (1.0, 1.0, 1.0), None)
+    entries = {"create_opt": lambda o: _hip.lib().omg_hierarchy_create_opt(1, arrA, arrR, o, ctypes.byref(out)),
+               "from_fine_opt": lambda o: _hip.lib().omg_hierarchy_create_from_fine_opt(arrA, 2, shape, 1, o, ctypes.byref(out)),
+               "from_fine_ragged": lambda o: _hip.lib().omg_hierarchy_create_from_fine_ragged(arrA, 2, shape, 1, None, 0, 0, o, ctypes.byref(out)),
+               "from_kappa_spaced": lambda o: _hip.lib().omg_hierarchy_create_from_kappa_spaced(*field.call, 1, o, ctypes.byref(out))}
+    for name, entry in entries.items():
+        for opt, text in ((_hip.HierarchyOptions(0, 1.0, 0, 2), b"unknown nullspace kind"), (_hip.HierarchyOptions(0, 1.0, 0, -1), b"unknown nullspace kind"),
+                          (_hip.HierarchyOptions(0, 1.0, 7, 1), b"unknown dtype"), (None, b"options are null")):
+            out.value = 1                                                # (the entry itself clears the handle)
+            code = entry(None if opt is None else ctypes.byref(opt))
+            assert code == _hip.ERR_INVALID and not out.value and _hip.lib().omg_last_error() == text, (name, _hip.lib().omg_last_error())
     kind = ctypes.c_int(5)
     assert _hip.lib().omg_hierarchy_nullspace(None, ctypes.byref(kind)) == _hip.ERR_INVALID
     assert _hip.lib().omg_level_project(None, 0, None, None) == _hip.ERR_INVALID
