@@ -55,6 +55,37 @@ def _clib():
     return _LIB
 
 
+_ROWS_READY = False
+
+
+def _rows_clib():
+    """_clib() with the rows_* restatement's prototypes set.  A library built before gs_oracle.c had
+    them is refused here, by name, instead of failing with an AttributeError inside a test."""
+    global _ROWS_READY
+    lib = _clib()
+    if not _ROWS_READY:
+        i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
+        for sfx, dt in (("f32", np.float32), ("f64", np.float64)):
+            vp = np.ctypeslib.ndpointer(dt, flags="C_CONTIGUOUS")
+            csr = [ctypes.c_int64, i32p, i32p, vp]
+            protos = {"rows_sum": (csr + [vp, vp, vp], None),
+                      "rows_spmv": (csr + [vp, vp], None),
+                      "rows_residual": (csr + [vp, vp, vp], None),
+                      "rows_axpy": (csr + [vp, vp], None),
+                      "rows_gs_ordered": (csr + [vp, vp, i32p, ctypes.c_int], ctypes.c_int),
+                      "rows_jacobi": (csr + [vp, vp, vp, ctypes.c_double], ctypes.c_int)}
+            for name, (argtypes, restype) in protos.items():
+                try:
+                    fn = getattr(lib, "%s_%s" % (name, sfx))
+                except AttributeError:
+                    raise RuntimeError("oracle/libmg_oracle.so has no %s_%s: it was built before the row-kernel "
+                                       "restatement was added to gs_oracle.c; rebuild it with `make -C oracle`"
+                                       % (name, sfx)) from None
+                fn.argtypes, fn.restype = argtypes, restype
+        _ROWS_READY = True
+    return lib
+
+
 def _csr(A):
     """CSR view with int32 index arrays and float64 data, stored column order untouched."""
     A = A if sp.isspmatrix_csr(A) else sp.csr_matrix(A)
@@ -461,3 +492,91 @@ def make_smoother(kind, A_list, omega=2.0 / 3.0):
     if kind == "jacobi":
         return lambda A, b, x, its, level: jacobi(A, b, x, its, omega)
     raise ValueError("unknown smoother %r" % (kind,))
+
+
+# ----------------------------------------------------------------------------
+# The row kernels' arithmetic, exactly (gs_oracle.c rows_*): fma chains in the association of
+# openmg_amd/csrc/common.h ASSOC_LEN, in float32 or float64.  Operands are rounded to `dtype`
+# first, the way the library narrows an operator and every host vector at upload; results come
+# back widened to float64 (exact), the way the library hands vectors back.  A device result is
+# compared with these by np.array_equal.  UNPINNED by the reference, which has one precision and
+# no fused multiply-add; pinned to exact rational arithmetic in tests/test_rows_oracle_host.py.
+# ----------------------------------------------------------------------------
+def _rows_sfx(dtype):
+    dt = np.dtype(dtype)
+    if dt == np.float32:
+        return "f32", dt
+    if dt == np.float64:
+        return "f64", dt
+    raise ValueError("dtype must be float64 or float32, not %r" % (dtype,))
+
+
+def _rows_args(A, dtype):
+    sfx, dt = _rows_sfx(dtype)
+    A = A if sp.isspmatrix_csr(A) else sp.csr_matrix(A)
+    return sfx, dt, (A.shape[0], np.ascontiguousarray(A.indptr, dtype=np.int32),
+                     np.ascontiguousarray(A.indices, dtype=np.int32), np.ascontiguousarray(A.data, dtype=dt))
+
+
+def _rows_vec(v, dt, n):
+    out = np.array(np.asarray(v, dtype=np.float64).ravel(), dtype=dt, order="C", copy=True)
+    if out.size != n:
+        raise ValueError("vector has %d entries, expected %d" % (out.size, n))
+    return out
+
+
+def rows_sum(A, x, dtype=np.float64):
+    """(row sums, diagonals) of A under the row kernels' association rule."""
+    sfx, dt, csr = _rows_args(A, dtype)
+    s, d = np.empty(csr[0], dt), np.empty(csr[0], dt)
+    getattr(_rows_clib(), "rows_sum_" + sfx)(*csr, _rows_vec(x, dt, A.shape[1]), s, d)
+    return s.astype(np.float64), d.astype(np.float64)
+
+
+def rows_spmv(A, x, dtype=np.float64):
+    """ROW_SPMV: A x."""
+    sfx, dt, csr = _rows_args(A, dtype)
+    y = np.empty(csr[0], dt)
+    getattr(_rows_clib(), "rows_spmv_" + sfx)(*csr, _rows_vec(x, dt, A.shape[1]), y)
+    return y.astype(np.float64)
+
+
+def rows_residual(A, b, x, dtype=np.float64):
+    """ROW_RESIDUAL: b - sum."""
+    sfx, dt, csr = _rows_args(A, dtype)
+    r = np.empty(csr[0], dt)
+    getattr(_rows_clib(), "rows_residual_" + sfx)(*csr, _rows_vec(b, dt, csr[0]), _rows_vec(x, dt, A.shape[1]), r)
+    return r.astype(np.float64)
+
+
+def rows_axpy(A, x, y, dtype=np.float64):
+    """ROW_AXPY: y + sum (a new array)."""
+    sfx, dt, csr = _rows_args(A, dtype)
+    out = _rows_vec(y, dt, csr[0])
+    getattr(_rows_clib(), "rows_axpy_" + sfx)(*csr, _rows_vec(x, dt, A.shape[1]), out)
+    return out.astype(np.float64)
+
+
+def rows_gs_ordered(A, b, x, order=None, iterations=1, dtype=np.float64):
+    """ROW_GS, in-place sweeps over the rows in `order` (None: lexicographic); returns a new array."""
+    sfx, dt, csr = _rows_args(A, dtype)
+    n = csr[0]
+    order = np.arange(n, dtype=np.int32) if order is None else np.ascontiguousarray(order, dtype=np.int32)
+    work = _rows_vec(x, dt, n)
+    rc = getattr(_rows_clib(), "rows_gs_ordered_" + sfx)(*csr, _rows_vec(b, dt, n), work, order, int(iterations))
+    if rc:
+        raise ZeroDivisionError("row %d has a zero diagonal" % (rc - 1))
+    return work.astype(np.float64)
+
+
+def rows_jacobi(A, b, x, iterations=1, omega=2.0 / 3.0, dtype=np.float64):
+    """ROW_JACOBI sweeps, fma(omega, (b - sum) / diag, x) with omega rounded to `dtype`; returns a new array."""
+    sfx, dt, csr = _rows_args(A, dtype)
+    n = csr[0]
+    bb, cur, nxt = _rows_vec(b, dt, n), _rows_vec(x, dt, n), np.empty(n, dt)
+    for _ in range(int(iterations)):
+        rc = getattr(_rows_clib(), "rows_jacobi_" + sfx)(*csr, bb, cur, nxt, float(omega))
+        if rc:
+            raise ZeroDivisionError("row %d has a zero diagonal" % (rc - 1))
+        cur, nxt = nxt, cur
+    return cur.astype(np.float64)

@@ -51,19 +51,53 @@ def oracle_csr(A):
             np.ascontiguousarray(A.data, np.float64))
 
 
+DTYPES = st.sampled_from(["float64", "float32"])
+
+
+def coarse_of(n):
+    """Pair aggregation and a small dominant coarsest operator: what a two-level hierarchy over an n-row operator needs."""
+    nc = (n + 1) // 2
+    R = sp.csr_matrix((np.ones(n), (np.arange(n) // 2, np.arange(n))), shape=(nc, n))
+    Ac = sp.csr_matrix(sp.diags([-np.ones(max(nc - 1, 0)), 4.0 * np.ones(nc), -np.ones(max(nc - 1, 0))], [-1, 0, 1]))
+    return R, Ac
+
+
+def with_diagonal(A, rng):
+    """A with one more stored entry per row, a dominant diagonal at a random position: a hierarchy takes no operator row
+    without a diagonal.  Stored order and duplicates of the other entries are kept."""
+    n = A.shape[0]
+    rows = np.repeat(np.arange(n), np.diff(A.indptr))
+    absum = np.bincount(rows, weights=np.abs(A.data), minlength=n)
+    parts_i, parts_d, ptr = [], [], [0]
+    for i in range(n):
+        s, e = A.indptr[i], A.indptr[i + 1]
+        at = int(rng.integers(0, e - s + 1))
+        parts_i.append(np.insert(A.indices[s:e], at, i)); parts_d.append(np.insert(A.data[s:e], at, absum[i] + 1.0 + rng.random()))
+        ptr.append(ptr[-1] + e - s + 1)
+    D = sp.csr_matrix((np.concatenate(parts_d), np.concatenate(parts_i).astype(np.int32), np.array(ptr, dtype=np.int32)), shape=(n, n))
+    D.has_sorted_indices = False
+    return D
+
+
 @settings(**COMMON)
-@given(csr_matrices())
-def test_spmv_any_csr(case):
+@given(csr_matrices(), DTYPES)
+def test_spmv_any_csr(case, dtype):
     A, seed = case
     x = np.random.default_rng(seed + 1).standard_normal(A.shape[1])
     want = np.empty(A.shape[0])
     orc._clib().oracle_spmv(A.shape[0], *oracle_csr(A), x, want)
     np.testing.assert_allclose(_hip.spmv(A, x), want, rtol=1e-12, atol=1e-12)
+    # ... and in either precision to the bit: the same rows (rectangular, empty ones, no diagonal) as the restriction of a
+    # two-level hierarchy, against the exact restatement
+    n, m = A.shape
+    fine = sp.csr_matrix(sp.diags([4.0 * np.ones(m)], [0]))
+    with _hip.Hierarchy([fine, coarse_of(2 * n)[1]], [A], smoother="jacobi", dtype=dtype) as h:
+        assert np.array_equal(h.restrict(0, x), orc.rows_spmv(A, x, dtype))
 
 
 @settings(**COMMON)
-@given(csr_matrices(square=True))
-def test_residual_and_norm_any_csr(case):
+@given(csr_matrices(square=True), DTYPES)
+def test_residual_and_norm_any_csr(case, dtype):
     A, seed = case
     rng = np.random.default_rng(seed + 2)
     x, b = rng.standard_normal(A.shape[0]), rng.standard_normal(A.shape[0])
@@ -72,11 +106,18 @@ def test_residual_and_norm_any_csr(case):
     r, norm = _hip.residual(A, b, x, want_norm=True)
     np.testing.assert_allclose(r, want, rtol=1e-12, atol=1e-12)
     np.testing.assert_allclose(norm, np.linalg.norm(want), rtol=1e-12, atol=1e-14)
+    # ... and in either precision to the bit, as level 0 of a two-level hierarchy (the operator with a diagonal entry added
+    # to every row), against the exact restatement
+    D = with_diagonal(A, rng)
+    R, Ac = coarse_of(D.shape[0])
+    with _hip.Hierarchy([D, Ac], [R], smoother="colour", dtype=dtype) as h:
+        assert np.array_equal(h.residual(0, b, x), orc.rows_residual(D, b, x, dtype))
+        assert np.array_equal(h.spmv(0, x), orc.rows_spmv(D, x, dtype))
 
 
 @settings(**COMMON)
-@given(csr_matrices(square=True, dominant=True), st.sampled_from(["gs", "colour", "jacobi"]), st.integers(1, 3))
-def test_smoothers_any_dominant_csr(case, smoother, sweeps):
+@given(csr_matrices(square=True, dominant=True), st.sampled_from(["gs", "colour", "jacobi"]), st.integers(1, 3), DTYPES)
+def test_smoothers_any_dominant_csr(case, smoother, sweeps, dtype):
     """Lexicographic (level-scheduled), greedy multi-colour and Jacobi sweeps on arbitrary
     diagonally dominant operators — unsymmetric patterns and duplicate entries included."""
     A, seed = case
@@ -92,6 +133,17 @@ def test_smoothers_any_dominant_csr(case, smoother, sweeps):
     else:
         want = orc.jacobi(A, b, x0.copy(), sweeps, 0.7)
     np.testing.assert_allclose(x, want, rtol=1e-10, atol=1e-12)
+    # ... and in either precision to the bit through a two-level hierarchy, against the exact restatement
+    if smoother == "jacobi":
+        exact = orc.rows_jacobi(A, b, x0, sweeps, 0.7, dtype)
+    else:
+        order = None if smoother == "gs" else orc.colour_order(orc.greedy_colouring(A))
+        exact = orc.rows_gs_ordered(A, b, x0, order, sweeps, dtype)
+    R, Ac = coarse_of(n)
+    with _hip.Hierarchy([A, Ac], [R], smoother=smoother, omega=0.7, dtype=dtype) as h:
+        xs = x0.copy()
+        h.smooth(0, b, xs, sweeps)
+        assert np.array_equal(xs, exact)
 
 
 @settings(**dict(COMMON, max_examples=25))
@@ -171,6 +223,7 @@ def test_every_device_coding_gives_the_same_bits(case, dtype, smoother):
             os.environ.pop("OMG_COMPRESS", None)
         else:
             os.environ["OMG_COMPRESS"] = keep
+    assert np.array_equal(out["0"][0], orc.rows_residual(A0, b, x0, dtype))       # the exact restatement, in either precision
     for mode in ("3", "7", "15"):
         assert np.array_equal(out[mode][0], out["0"][0]), mode
         assert np.array_equal(out[mode][1], out["0"][1]), mode
