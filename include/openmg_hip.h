@@ -248,6 +248,40 @@ int omg_hierarchy_create_from_kappa_spaced(const int64_t *shape, const double *k
 int omg_hierarchy_update_kappa_spaced(omg_hierarchy *h, const int64_t *shape, const double *kappa, int kappa_on_device,
                                       const int *walls, const double *sigma, int sigma_kind, int sigma_on_device, const double *scale,
                                       const double *hz, const double *hy, const double *hx);
+/* ---- the right-hand side that goes with that operator ---------------------------------------------------
+ * b, n = nz ny nx doubles in C order: a source per cell and inhomogeneous boundary data for the operator the entries above
+ * make of (shape, kappa, walls, scale | hz, hy, hx); sigma plays no part.  operators.rhs_kappa is the definition; the result
+ * has its bits.  f: NULL (OMG_VALUE_NONE), one double in HOST memory (OMG_VALUE_SCALAR) or one per cell (OMG_VALUE_FIELD, in
+ * host memory or — f_on_device != 0 — in HBM).  value_kinds: six OMG_VALUE_* in the order of the walls (NULL: none has a
+ * value); value_scalars: six doubles, read where the kind is SCALAR; value_fields: six pointers, read where the kind is
+ * FIELD — one double per face of that wall, (ny, nx) for the z walls, (nz, nx) for the y walls, (nz, ny) for the x walls, C
+ * order, all of them in host memory or — values_on_device != 0 — all in HBM.  b lies in host memory or — b_on_device != 0 —
+ * in HBM, and may then be f itself (in place).  Host fields are staged in HBM by the entry, as omg_kappa_assemble stages them.
+ *   a Dirichlet wall's value g: the boundary value where the operator puts it (the mirrored ghost-cell centre; with widths,
+ *     where the ghost width says — 0: on the wall face).  The cell gets c_wall g, c_wall the face coefficient the operator's
+ *     diagonal took for this wall: the same expression with the ghost cell's kappa (and width), the same rounding.
+ *   a Neumann wall's value: the OUTWARD flux q = kappa du/dn; with widths the cell gets q area[axis].  Without widths the
+ *     library does not know the cell width h: the value is then q h, and the cell gets value * scale[axis].
+ * Every operation is rounded once in double, nothing is contracted: the volume term is f ((hz[k] hy[j]) hx[i]) with widths,
+ * f itself without, +0.0 for no f, and b = ((((((volume term + t-K) + t-J) + t-I) + t+I) + t+J) + t+K); an in-grid face and
+ * a wall without a value contribute +0.0.  One launch: f read and b written once (16 bytes per cell); only the cells at a
+ * Dirichlet wall with a value read kappa — their own and the ghost cell's — and the ghost width.  Ghost cells behind Neumann
+ * walls, periodic walls and Dirichlet walls without a value are never read.
+ * kappa is NOT validated here (omg_hierarchy_create_from_kappa / _update_kappa checked the same field), and may be NULL where
+ * no Dirichlet wall has a value.  OMG_ERR_INVALID: a value on a periodic wall, NULL where a field is announced, an unknown
+ * kind or wall, a periodic wall without its partner or on an extent below 3, widths or scale as the entries above refuse
+ * them, n or the padded field beyond int32. */
+#define OMG_VALUE_NONE   0
+#define OMG_VALUE_SCALAR 1
+#define OMG_VALUE_FIELD  2
+int omg_kappa_rhs(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls, const double *scale,
+                  const double *f, int f_kind, int f_on_device, const int *value_kinds, const double *value_scalars,
+                  const double *const *value_fields, int values_on_device, double *b, int b_on_device);
+/* ... with the cell widths (hz = hy = hx = NULL: the entry above) */
+int omg_kappa_rhs_spaced(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls, const double *scale,
+                         const double *hz, const double *hy, const double *hx, const double *f, int f_kind, int f_on_device,
+                         const int *value_kinds, const double *value_scalars, const double *const *value_fields,
+                         int values_on_device, double *b, int b_on_device);
 int omg_hierarchy_dtype(const omg_hierarchy *h, int *dtype);
 int omg_hierarchy_destroy(omg_hierarchy *h);
 /* Run on a caller-owned hipStream_t instead of the hierarchy's own stream (NULL = own). */
@@ -431,6 +465,12 @@ int omg_level_residual(omg_hierarchy *h, int level, const double *b, const doubl
  * holds it: a plane level (constant-coefficient grid stencil, red-black) applies it matrix-free, any other level walks
  * its device format; the same bits either way.                                                                        */
 int omg_level_spmv(omg_hierarchy *h, int level, const double *x, double *y);
+/* omg_level_spmv for DEVICE arrays (double, the caller's numbering): permuted in and out like omg_hierarchy_cycle_dev, on
+ * the hierarchy's stream, through two vectors the hierarchy keeps for this entry alone — the resident right-hand side and
+ * iterate stay as they are (a b - A u between omg_resident_load and omg_resident_fetch disturbs nothing).  y_dev may be
+ * x_dev.  Returns after the stream has finished.  The same bits as omg_level_spmv.  An OMG_DTYPE_MIXED hierarchy:
+ * OMG_ERR_UNSUPPORTED, like omg_hierarchy_cycle_dev. */
+int omg_level_spmv_dev(omg_hierarchy *h, int level, const double *x_dev, double *y_dev);
 
 /* replaces: flexibleMmult(R[l], residual) — openmg/__init__.py:210. */
 int omg_level_restrict(omg_hierarchy *h, int level, const double *fine, double *coarse);

@@ -80,6 +80,8 @@ SIGNATURES = {
     "omg_kappa_assemble_spaced": (_I, [_I64P, _P, _I, _IP, _P, _I, _I, _DP, _P, _P, _P, _P, _P, _P, _I]),
     "omg_hierarchy_create_from_kappa_spaced": (_I, [_I64P, _P, _I, _IP, _P, _I, _I, _DP, _P, _P, _P, _I, _OPT, _PP]),
     "omg_hierarchy_update_kappa_spaced": (_I, [_P, _I64P, _P, _I, _IP, _P, _I, _I, _DP, _P, _P, _P]),
+    "omg_kappa_rhs": (_I, [_I64P, _P, _I, _IP, _DP, _P, _I, _I, _IP, _DP, _PP, _I, _P, _I]),
+    "omg_kappa_rhs_spaced": (_I, [_I64P, _P, _I, _IP, _DP, _P, _P, _P, _P, _I, _I, _IP, _DP, _PP, _I, _P, _I]),
     "omg_resident_norms": (_I, [_P, _DP, _DP]),
     "omg_hierarchy_destroy": (_I, [_P]),
     "omg_hierarchy_set_stream": (_I, [_P, _P]),
@@ -117,6 +119,7 @@ SIGNATURES = {
     "omg_level_smooth": (_I, [_P, _I, _P, _P, _I]),
     "omg_level_residual": (_I, [_P, _I, _P, _P, _P, _DP]),
     "omg_level_spmv": (_I, [_P, _I, _P, _P]),
+    "omg_level_spmv_dev": (_I, [_P, _I, _P, _P]),
     "omg_level_restrict": (_I, [_P, _I, _P, _P]),
     "omg_level_prolong_add": (_I, [_P, _I, _P, _P]),
     "omg_coarse_solve": (_I, [_P, _P, _P]),
@@ -487,6 +490,100 @@ def kappa_assemble(kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0), pattern
     check(lib().omg_kappa_assemble_spaced(*a.call, indptr.ctypes.data if pattern else None, indices.ctypes.data if pattern else None,
                                           data.ctypes.data, 0))
     return indptr, indices, data
+
+
+VALUE_NONE, VALUE_SCALAR, VALUE_FIELD = 0, 1, 2
+
+
+def kappa_rhs(kappa, f=None, walls=None, values=None, scale=(1.0, 1.0, 1.0), spacing=None, out=None):
+    """operators.rhs_kappa(kappa, f, walls, values, scale, spacing) made on the device (omg_kappa_rhs_spaced), bit for bit:
+    the right-hand side that goes with the operator of kappa_assemble / Hierarchy.from_kappa — a source per cell, boundary
+    values on Dirichlet walls, outward fluxes on Neumann walls (without spacing: flux times the cell width along the axis;
+    the definition's docstring has the conventions).  kappa, f and the fields among `values`: NumPy arrays, or C-contiguous
+    float64 device arrays — all of the arrays on the same side; scalars and None go with either; spacing: host arrays.
+    out: with device arrays a device array of n entries to write into (may be f itself: in place), None for a new one; with
+    host arrays None or a writeable contiguous float64 NumPy array.  Returns b in problemShape (a given `out` as it is).
+    kappa's values are not checked here.  ValueError for what operators.rhs_kappa refuses, arrays on both sides, an `out`
+    of the wrong size or side — before any device work."""
+    from . import _devarray, operators
+    k_dev = _devarray.is_device_array(kappa)
+    if k_dev:
+        k_shape = tuple(int(s) for s in kappa.__cuda_array_interface__["shape"])
+    else:
+        kappa = np.asarray(kappa)
+        if kappa.dtype != np.float64:
+            raise ValueError("kappa must be float64, not %s" % kappa.dtype)
+        kappa = np.ascontiguousarray(kappa)
+        k_shape = kappa.shape
+    grid, wall, scale = operators.kappa_arguments(k_shape, walls, None, scale)
+    widths = (None,) * 3
+    if spacing is not None:
+        if not operators.unit_scale(scale):
+            raise ValueError("spacing and scale exclude each other: the widths carry every factor")
+        widths = operators.spacing_arguments(grid, spacing)
+    f = operators.source_argument(grid, f)
+    values = operators.wall_values_arguments(grid, wall, values)
+    n, padded = int(np.prod(grid)), int(np.prod(k_shape))
+    if padded >= 2 ** 31 - 1:
+        raise ValueError("grid too large for int32 indices; shard it first")
+    arrays = [("kappa", kappa)] + [(name, a) for name, a in [("f", f)] + [("values[%d]" % w, v) for w, v in enumerate(values)]
+                                    if a is not None and not isinstance(a, float)]
+    for name, a in arrays:
+        if _devarray.is_device_array(a) != k_dev:
+            raise ValueError("kappa_rhs: kappa, f and the value fields must all be device arrays or all host arrays; %s is not on kappa's side" % name)
+    if out is not None and _devarray.is_device_array(out) != k_dev:
+        raise ValueError("kappa_rhs: `out` must be a device array exactly when kappa and f are device arrays")
+
+    def pointer(a, count, what):
+        if k_dev:
+            try:
+                return _devarray.address(a, count, what)
+            except TypeError as e:
+                raise ValueError(str(e))
+        return a.ctypes.data
+    keep = [kappa]
+    k_ptr = pointer(kappa, padded, "kappa")
+    if f is None:
+        f_kind, f_ptr = VALUE_NONE, None
+    elif isinstance(f, float):
+        keep.append(np.array([f], dtype=np.float64))
+        f_kind, f_ptr = VALUE_SCALAR, keep[-1].ctypes.data
+    else:
+        if not k_dev:
+            f = np.ascontiguousarray(f, dtype=np.float64)
+            keep.append(f)
+        f_kind, f_ptr = VALUE_FIELD, pointer(f, n, "f")
+    kinds, scalars, fields = [VALUE_NONE] * 6, [0.0] * 6, [None] * 6
+    for w, v in enumerate(values):
+        if v is None:
+            continue
+        if isinstance(v, float):
+            kinds[w], scalars[w] = VALUE_SCALAR, v
+            continue
+        if not k_dev:
+            v = np.ascontiguousarray(v, dtype=np.float64)
+            keep.append(v)
+        kinds[w], fields[w] = VALUE_FIELD, pointer(v, int(np.prod([grid[a] for a in operators.WALL_FACES[w]])), "values[%d]" % w)
+    if k_dev:
+        b = _devarray.empty_like(kappa, n).reshape(grid) if out is None else out
+        try:
+            b_ptr = _devarray.address(b, n, "out")
+        except TypeError as e:
+            raise ValueError(str(e))
+        check(lib().omg_device_synchronize())
+    else:
+        if out is None:
+            b = np.empty(grid, dtype=np.float64)
+        elif isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous and out.flags.writeable and out.size == n:
+            b = out
+        else:
+            raise ValueError("out must be a writeable contiguous float64 array of %d entries" % n)
+        b_ptr = b.ctypes.data
+    check(lib().omg_kappa_rhs_spaced((ctypes.c_int64 * 3)(*grid), ctypes.c_void_p(k_ptr), int(k_dev), (ctypes.c_int * 6)(*wall),
+                                     (ctypes.c_double * 3)(*scale), *(ctypes.c_void_p(None if h is None else h.ctypes.data) for h in widths),
+                                     ctypes.c_void_p(f_ptr), f_kind, int(k_dev and f_kind == VALUE_FIELD), (ctypes.c_int * 6)(*kinds),
+                                     (ctypes.c_double * 6)(*scalars), (ctypes.c_void_p * 6)(*fields), int(k_dev), ctypes.c_void_p(b_ptr), int(k_dev)))
+    return b
 
 
 class Hierarchy:
@@ -922,6 +1019,11 @@ class Hierarchy:
         y = np.empty(n)
         check(lib().omg_level_spmv(self._h, level, x.ctypes.data, y.ctypes.data))
         return y
+
+    def spmv_dev(self, level, x_ptr, y_ptr):
+        """omg_level_spmv_dev: spmv on DEVICE arrays given by address (double, the caller's numbering; y may be x).  The
+        resident right-hand side and iterate are not touched; returns after the hierarchy's stream has finished."""
+        check(lib().omg_level_spmv_dev(self._h, level, ctypes.c_void_p(int(x_ptr)), ctypes.c_void_p(int(y_ptr))))
 
     def restrict(self, level, fine):
         fine = vec(fine, self.sizes[level])

@@ -6,6 +6,8 @@
     s.update(A_new)                             # new values in the same pattern
     s = openmg_amd.Solver.from_kappa(kappa, parameters, walls, sigma, scale)    # the 7-point operator of a coefficient field,
     s.update_kappa(kappa_new, sigma=None)       # ... assembled in HBM (operators.stencil7_kappa: the definition)
+    b = s.rhs(kappa, f=None, values=None)       # ... and its right-hand side: source, boundary values, fluxes (operators.rhs_kappa)
+    y = s.matvec(x, out=None)                   # y = A x on the operator as the hierarchy holds it (b - A u where u lives)
     s.close()                                   # also a context manager
 
 The setup and the two loops are mgSolve's own (openmg_amd._setup, _solve_cycles, _solve_cg): a solve from zero has the
@@ -263,6 +265,57 @@ class Solver:
         z = _host_out(out, n)
         h.vcycle_ex(np.asarray(r, dtype=np.float64).reshape(-1), None, z, None, pre, post, level=0)
         return z
+
+    # ---- matvec -------------------------------------------------------------------------------------------------------
+    def matvec(self, x, out=None):
+        """y = A x with the operator as the hierarchy holds it (level 0, the caller's numbering): the A p a Krylov
+        iteration around apply() needs, and b - A u where u lives — on the plain device route of from_kappa no host matrix
+        exists to form either with.  x, out: host arrays (Hierarchy.spmv(0, x); like every single-level host entry this
+        gives up what a resident_load left on the device), or device arrays (then y is a device array, `out` may be x, and the
+        resident right-hand side and iterate are not touched: omg_level_spmv_dev).  The argument rules of apply();
+        ValueError on a mixed hierarchy."""
+        h = self._open()
+        if h.dtype == _hip.DTYPE_MIXED:
+            raise ValueError("parameters['dtype'] = 'mixed' is for solve() (fp64 iterations around fp32 cycles); "
+                             "matvec would apply the fp32 operator: use 'float32' or 'float64'")
+        n = h.sizes[0]
+        on_device = _devarray.is_device_array(x)
+        if out is not None and _devarray.is_device_array(out) != on_device:
+            raise TypeError("Solver.matvec: `out` must be a device array exactly when `x` is one")
+        if on_device:
+            y = _devarray.empty_like(x, n) if out is None else out
+            x_ptr, y_ptr = _devarray.address(x, n, "x"), _devarray.address(y, n, "out")
+            _devarray.synchronize()
+            h.spmv_dev(0, x_ptr, y_ptr)
+            return y
+        y = _host_out(out, n)
+        y[...] = h.spmv(0, np.asarray(x, dtype=np.float64).reshape(-1)).reshape(y.shape)
+        return y
+
+    # ---- right-hand side ----------------------------------------------------------------------------------------------
+    def rhs(self, kappa, f=None, values=None, out=None):
+        """The right-hand side b that goes with the operator of a Solver made by from_kappa (ValueError otherwise, like
+        update_kappa): operators.rhs_kappa(kappa, f, walls, values, scale, spacing) — same bits — made on the device, with
+        the walls, scale and spacing of construction; kappa's grid must be the solver's.  f: the source per cell (None, a
+        scalar, an array of problemShape); values: None or six entries in the order of the walls, each None, a scalar or a
+        2-D array over that wall's faces — a Dirichlet wall's boundary value, a Neumann wall's outward flux kappa du/dn
+        (without spacing: times the cell width along that axis); a periodic wall takes None.  kappa, f and the value fields
+        are NumPy arrays or all device arrays (then b is a device array: `out`, which may be f, or a new one).  Returns b
+        flattened to n entries in the solver's numbering, ready for solve().
+
+        Nothing is projected here.  With parameters['nullspace'] = 'constant' (every wall Neumann or periodic, no sigma)
+        solve() projects b; the problem itself has a solution only if the data are compatible, sum(b) = 0 — the integral
+        of f over the box plus the fluxes into it through the Neumann walls vanish —, which the caller's f and fluxes
+        should meet: what solve() removes otherwise is the part of the data no u can answer."""
+        self._open()
+        if self._kappa is None:
+            raise ValueError("Solver.rhs: the solver was not made by Solver.from_kappa")
+        grid, walls, scale, spacing = self._kappa
+        k_shape = tuple(int(s) for s in (kappa.__cuda_array_interface__["shape"] if _devarray.is_device_array(kappa) else np.shape(kappa)))
+        if k_shape != tuple(s + 2 for s in grid):
+            raise ValueError("Solver.rhs: kappa's shape %r is not the solver's grid %r with one ghost layer" % (k_shape, grid))
+        b = _hip.kappa_rhs(kappa, f, walls, values, scale, spacing, out)
+        return b.reshape(-1) if out is None else b
 
     # ---- update -------------------------------------------------------------------------------------------------------
     def update(self, A_new):

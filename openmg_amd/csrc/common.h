@@ -871,6 +871,27 @@ struct KappaField {
     // ... into a CSR allocated here
     void assemble(DevCsrPlain &A, hipStream_t s, const char *entry);
 };
+// The right-hand side that goes with that operator (kappa.hip): what the caller of omg_kappa_rhs names, as
+// the header's entry takes it.  kind / value_kinds: OMG_VALUE_*; a scalar f is one host double.
+struct KappaRhsInput {
+    const int64_t *shape;
+    const double *kappa;
+    int kappa_on_device;
+    const int *walls;
+    const double *scale, *hz, *hy, *hx;
+    const double *f;
+    int f_kind, f_on_device;
+    const int *value_kinds;
+    const double *value_scalars;
+    const double *const *value_fields;
+    int values_on_device;
+    double *b;
+    int b_on_device;
+};
+// checks the arguments (OMG_ERR_INVALID; kappa's values are not looked at), stages what lies in host memory, launches the
+// one kernel — on a stream the call keeps per device, with the widths it holds in HBM from the call before where they are
+// the same — and, for a host b, fetches the result; waits for the stream
+void kappa_rhs(const KappaRhsInput &in);
 // The same chain with a factor (1 or 2) per axis and restriction instead of 2 everywhere (semicoarsening).
 // shape and every factor tuple are in the grid's C order (the last axis has unit stride).  factors: n_restrictions * dim
 // entries, or null = 'auto': per level the couplings kernel, semicoarsen_rule, the restriction kernel, the product.  Auto

@@ -248,6 +248,9 @@ struct Hier {
     std::vector<DevBuf<double>> dense7;
     // omg_hierarchy_update_kappa: the value array kappa_values writes, nnz0 doubles (made at the first such update)
     DevBuf<double> kappa_vals;
+    // omg_level_spmv_dev: the operand and the product in the level's numbering and precision, apart from every vector a
+    // cycle or the resident entries use (made at the first such call, grown to the largest level asked for)
+    DevBuf<V> mv_x, mv_y;
     // resident state
     bool resident = false;
     // OMG_NO_FUSE=1: never fuse the last smoother set with the residual / norm (A/B switch;
@@ -2732,6 +2735,24 @@ int omg_kappa_assemble_spaced(const int64_t *shape, const double *kappa, int kap
     });
 }
 
+int omg_kappa_rhs(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls, const double *scale, const double *f,
+                  int f_kind, int f_on_device, const int *value_kinds, const double *value_scalars, const double *const *value_fields,
+                  int values_on_device, double *b, int b_on_device) {
+    return omg_kappa_rhs_spaced(shape, kappa, kappa_on_device, walls, scale, nullptr, nullptr, nullptr, f, f_kind, f_on_device, value_kinds,
+                                value_scalars, value_fields, values_on_device, b, b_on_device);
+}
+
+int omg_kappa_rhs_spaced(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls, const double *scale,
+                         const double *hz, const double *hy, const double *hx, const double *f, int f_kind, int f_on_device,
+                         const int *value_kinds, const double *value_scalars, const double *const *value_fields, int values_on_device,
+                         double *b, int b_on_device) {
+    return guarded([&] {
+        require_device();
+        kappa_rhs({shape, kappa, kappa_on_device, walls, scale, hz, hy, hx, f, f_kind, f_on_device, value_kinds, value_scalars, value_fields,
+                   values_on_device, b, b_on_device});
+    });
+}
+
 int omg_hierarchy_create_from_kappa(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls, const double *sigma,
                                     int sigma_kind, int sigma_on_device, const double *scale, int n_restrictions,
                                     const omg_hierarchy_options *opt, omg_hierarchy **out) {
@@ -3373,6 +3394,36 @@ int omg_level_spmv(omg_hierarchy *h, int level, const double *x, double *y) {
                 launch_rows(L.A, ROW_SPMV, -1, a, hh->stream);
                 fetch_vec<V>(hh, level, L.r.p, y);
             }
+        });
+    });
+}
+
+// omg_level_spmv for a caller whose vectors live in HBM (double, the caller's numbering): permuted in and out as
+// omg_hierarchy_cycle_dev does, on the hierarchy's stream, through two vectors of its own — the resident right-hand side and
+// iterate, and with them a solve in progress, are not touched (the kernels read and write the library's own allocations
+// only, as everywhere; y_dev may be x_dev).  Waits for the stream.
+int omg_level_spmv_dev(omg_hierarchy *h, int level, const double *x_dev, double *y_dev) {
+    return guarded([&] {
+        with(h, [&](auto *hh) {
+            refuse_mixed(hh, "omg_level_spmv_dev");
+            using V = value_of<decltype(hh)>;
+            check_level(hh, level);
+            OMG_REQUIRE(level < (int)hh->lv.size() - 1, "use omg_spmv for the coarsest operator");
+            OMG_REQUIRE(x_dev && y_dev, "null vector");
+            auto &L = hh->lv[level];
+            const bool mf = use_plane(hh, L) && !L.plane->g.jacobi;
+            if (!mf) ensure_format(hh, level);
+            if (hh->mv_x.n < size_t(L.n)) { hh->mv_x.alloc(size_t(L.n)); hh->mv_y.alloc(size_t(L.n)); }
+            load_vec_dev(hh, level, x_dev, hh->mv_x.p);
+            if (mf) {
+                L.plane->spmv(hh->mv_x.p, hh->mv_y.p, hh->stream);
+            } else {
+                RowArgsT<V> a;
+                a.x = hh->mv_x.p; a.y = hh->mv_y.p;
+                launch_rows(L.A, ROW_SPMV, -1, a, hh->stream);
+            }
+            fetch_vec_dev(hh, level, hh->mv_y.p, y_dev);
+            OMG_HIP(hipStreamSynchronize(hh->stream));
         });
     });
 }

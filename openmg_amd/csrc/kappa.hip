@@ -37,6 +37,10 @@
 // of their own with the flags behind the arguments; the kernels without them keep their argument blocks and their code.
 #include "common.h"
 
+#include <cstring>
+#include <map>
+#include <mutex>
+
 // (This file is compiled with -ffp-contract=off, the Makefile's rule for kappa.hip.o: __dmul_rn / __dadd_rn are plain
 // operators defined in the compiler's header, out of a pragma's reach, and without the flag a product that feeds a sum
 // — da b + db a, the diagonal plus sigma vol — becomes one fused operation, rounded once instead of twice.)
@@ -478,6 +482,261 @@ void KappaField::assemble(DevCsrPlain &A, hipStream_t s, const char *entry) {
     A.indices.alloc(size_t(A.nnz));
     A.data.alloc(size_t(A.nnz));
     assemble(A.indptr.p, A.indices.p, A.data.p, s, entry);
+}
+
+// ---- the right-hand side that goes with the operator (operators.rhs_kappa is the definition) ---------------
+// b = ((((((volume term + t-K) + t-J) + t-I) + t+I) + t+J) + t+K): the source f (times the cell volume when SPACED) and, for
+// a cell at a wall that carries a value, c_wall g (Dirichlet: c_wall the face coefficient kappa_values_kernel added to the
+// diagonal, the same expression) or q area / q scale (Neumann: the outward flux).  One thread per cell, 256 consecutive cells
+// per workgroup as above: f is read and b written at unit stride, 16 bytes per cell; a lane that is not on a wall with a value
+// reads nothing else (the widths only where the volume needs them).  Lanes on such a wall read their own and the ghost kappa,
+// the ghost width and the value: whole workgroups of them on the z walls, one lane per line on the x walls — the branch is
+// short (one division) and the launch is bound by the stream, not by it.  b may be f: each thread reads its own f first.
+namespace {
+
+struct KappaRhsArgs {
+    KappaGrid g;
+    const double *__restrict__ kappa;   // (nz + 2)(ny + 2)(nx + 2); read only at Dirichlet walls with a value
+    double f_value;
+    int f_kind;                         // OMG_VALUE_*
+    int kind[6];                        // per wall -z, +z, -y, +y, -x, +x: OMG_VALUE_* (a periodic wall: NONE)
+    int neumann[6];
+    double value[6];
+    const double *__restrict__ field[6];   // one per face of the wall: (ny, nx), (nz, nx), (nz, ny)
+    double scale[3];                    // z, y, x
+};
+struct KappaRhsSpacedArgs : KappaRhsArgs {
+    const double *__restrict__ hz, *__restrict__ hy, *__restrict__ hx;   // nz + 2, ny + 2, nx + 2
+};
+template <bool SPACED> using kappa_rhs_args_t = std::conditional_t<SPACED, KappaRhsSpacedArgs, KappaRhsArgs>;
+
+// f (F_FIELD: one per cell; else null) and b are arguments of their own — the two streams of the launch, plain global
+// pointers that may be one array — and the thread's f is asked for before anything else, so that the index arithmetic runs
+// under the load.  (F_FIELD is a template flag, not a test of a.f_kind: the compiler turns `kind == FIELD ? f[r] : f_value`
+// into ONE load through a select of the two addresses — global memory and the argument block —, a flat load.)
+template <bool SPACED, bool F_FIELD>
+__global__ void __launch_bounds__(KAPPA_BLOCK) kappa_rhs_kernel(kappa_rhs_args_t<SPACED> a, const double *f, double *b) {
+    const KappaGrid g = a.g;
+    const int64_t n = int64_t(g.nx) * g.ny * g.nz;
+    const int64_t r = blockIdx.x * int64_t(KAPPA_BLOCK) + threadIdx.x;
+    if (r >= n) return;
+    double v;
+    if constexpr (F_FIELD) v = f[r];
+    else v = a.f_value;                                // (the scalar; +0.0 for no f)
+    int i, j, k;
+    cell_of(g, r, i, j, k);
+    // the six faces in the order of the sum: -K, -J, -I, +I, +J, +K
+    const bool inside[6] = {k > 0, j > 0, i > 0, i + 1 < g.nx, j + 1 < g.ny, k + 1 < g.nz};
+    const int wall[6] = {0, 2, 4, 5, 3, 1};
+    const int axis[6] = {0, 1, 2, 2, 1, 0};
+    bool valued[6], on_wall = false;
+#pragma unroll
+    for (int e = 0; e < 6; ++e) {
+        valued[e] = !inside[e] && a.kind[wall[e]] != OMG_VALUE_NONE;
+        on_wall = on_wall || valued[e];
+    }
+    double own[3] = {0.0, 0.0, 0.0}, area[3] = {0.0, 0.0, 0.0};
+    if constexpr (SPACED) {
+        if (on_wall || a.f_kind != OMG_VALUE_NONE) {
+            own[0] = a.hz[k + 1]; own[1] = a.hy[j + 1]; own[2] = a.hx[i + 1];
+        }
+    }
+    if constexpr (SPACED) {
+        if (a.f_kind != OMG_VALUE_NONE) v = __dmul_rn(v, __dmul_rn(__dmul_rn(own[0], own[1]), own[2]));
+    }
+    double t[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (on_wall) {
+        if constexpr (SPACED) {
+            area[0] = __dmul_rn(own[1], own[2]); area[1] = __dmul_rn(own[0], own[2]); area[2] = __dmul_rn(own[0], own[1]);
+        }
+        const int64_t px = g.nx + 2, pxy = px * (g.ny + 2);
+        const int64_t c = int64_t(k + 1) * pxy + int64_t(j + 1) * px + (i + 1);
+        const int64_t off[6] = {-pxy, -px, -1, 1, px, pxy};
+        // the cell's face on a z, y, x wall: (j, i) of (ny, nx), (k, i) of (nz, nx), (k, j) of (nz, ny)
+        const int64_t at[3] = {int64_t(j) * g.nx + i, int64_t(k) * g.nx + i, int64_t(k) * g.ny + j};
+#pragma unroll
+        for (int e = 0; e < 6; ++e) {
+            if (!valued[e]) continue;
+            const int w = wall[e], ax = axis[e];
+            double val = a.value[w];
+            if (a.kind[w] == OMG_VALUE_FIELD) val = a.field[w][at[ax]];
+            if (a.neumann[w]) {
+                t[e] = __dmul_rn(val, SPACED ? area[ax] : a.scale[ax]);
+                continue;
+            }
+            const double kc = a.kappa[c], kn = a.kappa[c + off[e]];
+            double coeff;
+            if constexpr (SPACED) {
+                const double *const h = ax == 0 ? a.hz + (k + 1) : ax == 1 ? a.hy + (j + 1) : a.hx + (i + 1);
+                coeff = face_spaced(kc, kn, own[ax], h[e < 3 ? -1 : 1], area[ax]);
+            } else {
+                coeff = face_of(kc, kn, a.scale[ax]);
+            }
+            t[e] = __dmul_rn(coeff, val);
+        }
+    }
+    b[r] = __dadd_rn(__dadd_rn(__dadd_rn(__dadd_rn(__dadd_rn(__dadd_rn(v, t[0]), t[1]), t[2]), t[3]), t[4]), t[5]);
+}
+
+// What a call keeps per DEVICE from one call to the next (a right-hand side is made every time step, and the launch itself
+// takes a tenth of a millisecond at 256^3): the stream, and the widths in HBM with the host copy they were made from — the same
+// widths again cost a comparison, not an allocation and three copies.  Made on first use and kept for the life of the
+// process, like download_staged's pinned buffers; one call at a time per device.
+struct RhsDevice {
+    std::mutex mu;
+    hipStream_t s = nullptr;
+    double *widths = nullptr;
+    size_t capacity = 0;
+    std::vector<double> held;
+};
+
+RhsDevice &rhs_device() {
+    static std::mutex table_mu;
+    static std::map<int, RhsDevice *> table;
+    int device = 0;
+    OMG_HIP(hipGetDevice(&device));
+    std::lock_guard<std::mutex> lock(table_mu);
+    RhsDevice *&slot = table[device];
+    if (!slot) slot = new RhsDevice;
+    return *slot;
+}
+
+}  // namespace
+
+void kappa_rhs(const KappaRhsInput &in) {
+    RhsDevice &dev = rhs_device();
+    std::lock_guard<std::mutex> lock(dev.mu);
+    if (!dev.s) OMG_HIP(hipStreamCreateWithFlags(&dev.s, hipStreamNonBlocking));
+    const hipStream_t s = dev.s;
+    OMG_REQUIRE(in.shape && in.b, "omg_kappa_rhs: null argument");
+    for (int d = 0; d < 3; ++d)
+        OMG_REQUIRE(in.shape[d] >= 1 && in.shape[d] < (int64_t(1) << 30), "omg_kappa_rhs: every extent of the shape must be >= 1");
+    const int nz = int(in.shape[0]), ny = int(in.shape[1]), nx = int(in.shape[2]);
+    const int64_t n = int64_t(nx) * ny * nz, padded = int64_t(nz + 2) * (ny + 2) * (nx + 2);
+    OMG_REQUIRE(n < (int64_t(1) << 31) - 1 && padded < (int64_t(1) << 31) - 1, "omg_kappa_rhs: grid too large for int32 indices");
+    kappa_rhs_args_t<true> a;
+    a.g = {nx, ny, nz};
+    bool periodic[6];
+    for (int w = 0; w < 6; ++w) {
+        const int wv = in.walls ? in.walls[w] : OMG_WALL_DIRICHLET;
+        OMG_REQUIRE(wv == OMG_WALL_DIRICHLET || wv == OMG_WALL_NEUMANN || wv == OMG_WALL_PERIODIC,
+                    "omg_kappa_rhs: a wall must be OMG_WALL_DIRICHLET or OMG_WALL_NEUMANN, or OMG_WALL_PERIODIC on both walls of an axis");
+        a.neumann[w] = wv == OMG_WALL_NEUMANN;
+        periodic[w] = wv == OMG_WALL_PERIODIC;
+    }
+    for (int d = 0; d < 3; ++d) {
+        OMG_REQUIRE(periodic[2 * d] == periodic[2 * d + 1], "omg_kappa_rhs: OMG_WALL_PERIODIC must be given for both walls of an axis");
+        OMG_REQUIRE(!periodic[2 * d] || in.shape[d] >= 3, "omg_kappa_rhs: a periodic axis needs an extent >= 3");
+        a.scale[d] = in.scale ? in.scale[d] : 1.0;
+        OMG_REQUIRE(finite_pos(a.scale[d]), "omg_kappa_rhs: every scale factor must be finite and > 0");
+    }
+    OMG_REQUIRE((!in.hz && !in.hy && !in.hx) || (in.hz && in.hy && in.hx), "omg_kappa_rhs: the widths hz, hy, hx are given together or not at all");
+    const bool spaced = in.hz != nullptr;
+    const int extent[3] = {nz, ny, nx};
+    if (spaced) {
+        OMG_REQUIRE(a.scale[0] == 1.0 && a.scale[1] == 1.0 && a.scale[2] == 1.0, "omg_kappa_rhs: widths and scale factors exclude each other");
+        const double *const h[3] = {in.hz, in.hy, in.hx};
+        std::vector<double> all;
+        all.reserve(size_t(nz) + ny + nx + 6);
+        for (int d = 0; d < 3; ++d)
+            for (int m = 0; m < extent[d] + 2; ++m) {
+                const double v = h[d][m];
+                const bool ghost = m == 0 || m == extent[d] + 1;
+                OMG_REQUIRE(v < HUGE_VAL && (ghost ? v >= 0.0 : v > 0.0),
+                            "omg_kappa_rhs: a cell width must be finite and > 0, a ghost width finite and >= 0");
+                all.push_back(v);
+            }
+        // (hz, hy, hx one after the other; compared as bytes: what is held is what the kernel reads)
+        if (all.size() != dev.held.size() || std::memcmp(all.data(), dev.held.data(), all.size() * sizeof(double)) != 0) {
+            dev.held.clear();
+            if (dev.capacity < all.size()) {
+                if (dev.widths) OMG_HIP(hipFree(dev.widths));
+                dev.widths = nullptr;
+                dev.capacity = 0;
+                OMG_HIP(hipMalloc(reinterpret_cast<void **>(&dev.widths), all.size() * sizeof(double)));
+                dev.capacity = all.size();
+            }
+            OMG_HIP(hipMemcpyAsync(dev.widths, all.data(), all.size() * sizeof(double), hipMemcpyHostToDevice, s));
+            OMG_HIP(hipStreamSynchronize(s));               // (`all` is this call's: the copy has left it)
+            dev.held = std::move(all);
+        }
+        a.hz = dev.widths;
+        a.hy = dev.widths + (nz + 2);
+        a.hx = dev.widths + (nz + 2) + (ny + 2);
+    }
+    // the source
+    OMG_REQUIRE(in.f_kind == OMG_VALUE_NONE || in.f_kind == OMG_VALUE_SCALAR || in.f_kind == OMG_VALUE_FIELD, "omg_kappa_rhs: f_kind must be one of OMG_VALUE_*");
+    OMG_REQUIRE(in.f_kind == OMG_VALUE_NONE || in.f, "omg_kappa_rhs: f is null");
+    OMG_REQUIRE(in.f_kind != OMG_VALUE_SCALAR || !in.f_on_device, "omg_kappa_rhs: a scalar f is one double in host memory");
+    DevBuf<double> own_f, own_b, own_kappa, own_fields;
+    a.f_kind = in.f_kind;
+    const double *f_dev = nullptr;
+    double *b_dev = nullptr;
+    a.f_value = in.f_kind == OMG_VALUE_SCALAR ? in.f[0] : 0.0;
+    if (in.b_on_device) {
+        b_dev = in.b;
+    } else {
+        own_b.alloc(size_t(n));
+        b_dev = own_b.p;
+    }
+    if (in.f_kind == OMG_VALUE_FIELD) {
+        if (in.f_on_device) {
+            f_dev = in.f;
+        } else if (!in.b_on_device) {
+            own_b.upload(in.f, size_t(n), s);          // (a host f and a host b: staged in one array, in place)
+            f_dev = own_b.p;
+        } else {
+            own_f.alloc(size_t(n));
+            own_f.upload(in.f, size_t(n), s);
+            f_dev = own_f.p;
+        }
+    }
+    // the walls' values
+    const int64_t faces[3] = {int64_t(ny) * nx, int64_t(nz) * nx, int64_t(nz) * ny};
+    bool reads_kappa = false;
+    size_t staged = 0;
+    for (int w = 0; w < 6; ++w) {
+        const int kind = in.value_kinds ? in.value_kinds[w] : OMG_VALUE_NONE;
+        OMG_REQUIRE(kind == OMG_VALUE_NONE || kind == OMG_VALUE_SCALAR || kind == OMG_VALUE_FIELD, "omg_kappa_rhs: a value kind must be one of OMG_VALUE_*");
+        OMG_REQUIRE(kind == OMG_VALUE_NONE || !periodic[w], "omg_kappa_rhs: a periodic wall takes no value");
+        OMG_REQUIRE(kind != OMG_VALUE_SCALAR || in.value_scalars, "omg_kappa_rhs: value_scalars is null");
+        OMG_REQUIRE(kind != OMG_VALUE_FIELD || (in.value_fields && in.value_fields[w]), "omg_kappa_rhs: a value field is announced and null");
+        a.kind[w] = kind;
+        a.value[w] = kind == OMG_VALUE_SCALAR ? in.value_scalars[w] : 0.0;
+        a.field[w] = kind == OMG_VALUE_FIELD ? in.value_fields[w] : nullptr;
+        reads_kappa = reads_kappa || (kind != OMG_VALUE_NONE && !a.neumann[w]);
+        if (kind == OMG_VALUE_FIELD && !in.values_on_device) staged += size_t(faces[w / 2]);
+    }
+    if (staged) {                                       // host fields: one after the other in one array
+        own_fields.alloc(staged);
+        size_t at = 0;
+        for (int w = 0; w < 6; ++w) {
+            if (a.kind[w] != OMG_VALUE_FIELD) continue;
+            OMG_HIP(hipMemcpyAsync(own_fields.p + at, in.value_fields[w], size_t(faces[w / 2]) * sizeof(double), hipMemcpyHostToDevice, s));
+            a.field[w] = own_fields.p + at;
+            at += size_t(faces[w / 2]);
+        }
+    }
+    a.kappa = nullptr;
+    if (reads_kappa) {
+        OMG_REQUIRE(in.kappa, "omg_kappa_rhs: kappa is null");
+        if (in.kappa_on_device) {
+            a.kappa = in.kappa;
+        } else {
+            own_kappa.alloc(size_t(padded));
+            own_kappa.upload(in.kappa, size_t(padded), s);
+            a.kappa = own_kappa.p;
+        }
+    }
+    const dim3 grid((unsigned)((n + KAPPA_BLOCK - 1) / KAPPA_BLOCK));
+    as_constant(f_dev != nullptr, [&](auto field) {
+        constexpr bool F = decltype(field)::value;
+        if (spaced) hipLaunchKernelGGL((kappa_rhs_kernel<true, F>), grid, dim3(KAPPA_BLOCK), 0, s, a, f_dev, b_dev);
+        else hipLaunchKernelGGL((kappa_rhs_kernel<false, F>), grid, dim3(KAPPA_BLOCK), 0, s, static_cast<const KappaRhsArgs &>(a), f_dev, b_dev);
+    });
+    OMG_HIP(hipGetLastError());
+    if (!in.b_on_device) download_staged(in.b, own_b.p, size_t(n) * sizeof(double), s);
+    OMG_HIP(hipStreamSynchronize(s));
 }
 
 }  // namespace omg

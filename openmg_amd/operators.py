@@ -560,6 +560,141 @@ def stencil7_kappa(kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0), spacing
     return A
 
 
+WALL_FACES = ((1, 2), (1, 2), (0, 2), (0, 2), (0, 1), (0, 1))     # per wall: the two axes (of z, y, x) its faces run over
+
+
+def wall_values_arguments(shape, wall, values):
+    """The boundary data of rhs_kappa, _hip.kappa_rhs and Solver.rhs, checked: values None, or six entries in the order of
+    the walls (-z, +z, -y, +y, -x, +x), each None, a scalar or a 2-D array over that wall's faces — (ny, nx) for the z
+    walls, (nz, nx) for the y walls, (nz, ny) for the x walls; shape = problemShape, wall = the six codes kappa_arguments
+    returned.  Returns a tuple of six: None, a float, or the array as it came (a device array's shape is read off its
+    interface; its dtype is the caller's to get right, checked where its address is taken).  ValueError for another
+    count, a value on a periodic wall, another shape, an entry that is neither."""
+    if values is None:
+        return (None,) * 6
+    try:
+        values = tuple(values)
+    except TypeError:
+        raise ValueError("values must be None or six entries in the order -z, +z, -y, +y, -x, +x, not %r" % (values,))
+    if len(values) != 6:
+        raise ValueError("values must be None or six entries in the order -z, +z, -y, +y, -x, +x, not %d" % len(values))
+    out = []
+    for f, v in enumerate(values):
+        name = ("-z", "+z", "-y", "+y", "-x", "+x")[f]
+        if v is None:
+            out.append(None)
+            continue
+        if wall[f] == WALL_CODES["periodic"]:
+            raise ValueError("values: the wall %s is periodic and takes None only" % name)
+        on_device = hasattr(v, "__cuda_array_interface__") and not isinstance(v, np.ndarray)
+        if not on_device and np.ndim(v) == 0:
+            try:
+                out.append(float(v))
+            except (TypeError, ValueError):
+                raise ValueError("values: the entry of wall %s must be None, a number or a 2-D array, not %r" % (name, v))
+            continue
+        v_shape = tuple(int(s) for s in (v.__cuda_array_interface__["shape"] if on_device else np.shape(v)))
+        faces = tuple(shape[a] for a in WALL_FACES[f])
+        if v_shape != faces:
+            raise ValueError("values: the field of wall %s must have that wall's faces %r, not %r" % (name, faces, v_shape))
+        out.append(v)
+    return tuple(out)
+
+
+def source_argument(shape, f):
+    """The source f of rhs_kappa and its device twins, checked: None, a float, or the array as it came; ValueError for an
+    array of another shape than problemShape or an entry that is neither."""
+    if f is None:
+        return None
+    on_device = hasattr(f, "__cuda_array_interface__") and not isinstance(f, np.ndarray)
+    if not on_device and np.ndim(f) == 0:
+        try:
+            return float(f)
+        except (TypeError, ValueError):
+            raise ValueError("f must be None, a number or an array of problemShape, not %r" % (f,))
+    f_shape = tuple(int(s) for s in (f.__cuda_array_interface__["shape"] if on_device else np.shape(f)))
+    if f_shape != tuple(shape):
+        raise ValueError("a source field f must have problemShape %r, not %r" % (tuple(shape), f_shape))
+    return f
+
+
+def rhs_kappa(kappa, f=None, walls=None, values=None, scale=(1.0, 1.0, 1.0), spacing=None):
+    """The right-hand side b that goes with stencil7_kappa(kappa, walls, sigma, scale, spacing) (NOT in the reference; the
+    definition the device kernel — _hip.kappa_rhs, Solver.rhs — is pinned to bit for bit): a source per cell and
+    inhomogeneous boundary data, as a float64 array of problemShape.  sigma plays no part.  kappa, walls, scale, spacing:
+    as stencil7_kappa takes them.  f: the source per cell — None (zero), a scalar or an array of problemShape.  values:
+    None, or six entries in the order of walls (-z, +z, -y, +y, -x, +x), each None, a scalar or a 2-D float64 array over
+    that wall's faces ((ny, nx) for z, (nz, nx) for y, (nz, ny) for x walls); a periodic wall takes None only.
+
+    What a wall's value means:
+      - a Dirichlet wall: the boundary value g, located where the operator puts it — with spacing, where the ghost width
+        says (0: on the wall face; the boundary cell's width: at the mirrored ghost-cell centre), without spacing at the
+        mirrored ghost-cell centre.  The cell gets c_wall * g, c_wall being the very face coefficient stencil7_kappa
+        added to that cell's diagonal for this wall (the same expression with the ghost cell's kappa and width, the same
+        rounding, times scale[axis] or the spaced area[axis]).
+      - a Neumann wall: the OUTWARD flux q = kappa du/dn.  With spacing the cell gets q * area[axis].  WITHOUT spacing the
+        library does not know the cell width h: the value is then q TIMES THE CELL WIDTH ALONG THAT AXIS, q h, and the
+        cell gets value * scale[axis] (with scale = 1 / h_axis^2 that is q / h, the flux per cell volume).
+
+    Every operation is rounded once in double.  The volume term is f * ((hz[k] hy[j]) hx[i]) (cell_volumes' rounding)
+    with spacing, f itself without, +0.0 for f = None, and
+        b = ((((((volume term + t-K) + t-J) + t-I) + t+I) + t+J) + t+K),
+    the order of the diagonal's sum; an in-grid face and a wall without a value contribute +0.0.
+
+    Only the cells at a Dirichlet wall WITH a value read kappa (their own and the ghost cell's) and the ghost width; ghost
+    cells behind Neumann walls, periodic walls and Dirichlet walls without a value are never read and may hold anything.
+    kappa's values are not checked here: stencil7_kappa (Solver.from_kappa, update_kappa) checked the same field.
+
+    ValueError: what kappa_arguments and spacing_arguments refuse, spacing together with a scale other than (1, 1, 1), an f
+    of another shape, values of another count, a value on a periodic wall, a value field of another shape than its wall."""
+    kap = np.asarray(kappa)
+    if kap.dtype != np.float64:
+        raise ValueError("kappa must be float64, not %s" % kap.dtype)
+    shape, wall, scale = kappa_arguments(kap.shape, walls, None, scale)
+    f = source_argument(shape, f)
+    values = wall_values_arguments(shape, wall, values)
+    H = None
+    if spacing is not None:
+        if not unit_scale(scale):
+            raise ValueError("spacing and scale exclude each other: the widths carry every factor")
+        H = spacing_arguments(shape, spacing)
+        own = (H[0][1:-1, None, None], H[1][None, 1:-1, None], H[2][None, None, 1:-1])
+        area = (own[1] * own[2], own[0] * own[2], own[0] * own[1])
+    if f is None:
+        volume = np.zeros(shape)
+    else:
+        source = np.broadcast_to(np.asarray(f, dtype=np.float64), shape)
+        volume = source * ((own[0] * own[1]) * own[2]) if H is not None else source.copy()
+    c = kap[1:-1, 1:-1, 1:-1]
+    terms = {}
+    for face in range(6):
+        axis, hi = face // 2, face % 2
+        t = np.zeros(shape)
+        terms[face] = t
+        if values[face] is None:
+            continue
+        g = np.asarray(values[face], dtype=np.float64)
+        layer = [slice(None)] * 3
+        layer[axis] = -1 if hi else 0                      # the cells at this wall ...
+        layer = tuple(layer)
+        behind = list(layer)
+        behind[axis] = -1 if hi else 0                     # ... and, in the padded field, the ghost cells behind them
+        behind = tuple(slice(1, -1) if isinstance(s, slice) else s for s in behind)
+        if wall[face] == WALL_CODES["neumann"]:
+            t[layer] = g * (np.broadcast_to(area[axis], shape)[layer] if H is not None else scale[axis])
+            continue
+        a, b = c[layer], kap[behind]
+        if H is not None:
+            da = np.broadcast_to(own[axis], shape)[layer]
+            db = H[axis][-1 if hi else 0]
+            coeff = ((2.0 * a) * b) / (da * b + db * a) * np.broadcast_to(area[axis], shape)[layer]
+        else:
+            coeff = ((2.0 * a) * b) / (a + b) * scale[axis]
+        t[layer] = coeff * g
+    # faces in the order of the diagonal's sum: -K, -J, -I, +I, +J, +K = walls 0, 2, 4, 5, 3, 1
+    return (((((volume + terms[0]) + terms[2]) + terms[4]) + terms[5]) + terms[3]) + terms[1]
+
+
 def stencil27_variable(shape, seed=2024, rows=None):
     """27-point variable-coefficient operator of BASELINE.json configs[4] as SURVEY.md 8(d)
     specifies it (NOT in the reference): Q1 finite-element stiffness of -div(kappa grad u) on a
