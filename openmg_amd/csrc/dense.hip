@@ -142,8 +142,8 @@ int grid1d(int64_t n) {
 // untouched: n columns in all) per 64 pivots, 3 launches per block.  Tiles that hold only zeros — below and right of a
 // banded operator's band, which is what a grid's coarsest operator is — are found as the step's operands are staged and
 // skipped: a third of the products remain.  No pivoting ACROSS blocks: exact for the symmetric positive definite /
-// diagonally dominant operators a Galerkin hierarchy ends in; the caller checks the result against the operator and falls
-// back to the pivoted elimination where it is not an inverse.
+// diagonally dominant operators a Galerkin hierarchy ends in; the result is checked against the operator, at a threshold scaled
+// by || M || || M^-1 || (blocked_inverse), and the pivoted elimination takes over where it is not as good an inverse.
 constexpr int GJB = 64;
 typedef double gj_v4d __attribute__((ext_vector_type(4)));
 
@@ -399,7 +399,7 @@ void gjb_eliminate_kernel(double *W, int64_t n, int64_t ld, int64_t k0, int nb, 
     gjb_diag_block<true>(W, ld, k0 + nb, next_nb, dinv, singular);
 }
 
-// || M (Minv v) - v ||_inf / || v ||_inf for one fixed vector: is Minv an inverse of M?  (M: n x n row-major)
+// y = M x, a workgroup per row: the two products of the check below.  (M: n x n row-major)
 __global__ __launch_bounds__(256) void gjb_matvec_kernel(const double *M, int64_t n, int64_t ld, const double *x, double *y) {
     __shared__ double s_red[256];
     const int64_t r = blockIdx.x;
@@ -414,7 +414,32 @@ __global__ __launch_bounds__(256) void gjb_matvec_kernel(const double *M, int64_
     if (threadIdx.x == 0) y[r] = s_red[0];
 }
 
+// y[r] = sum_c |M[r, c]|: the terms of || M ||_inf
+__global__ __launch_bounds__(256) void gjb_rowabs_kernel(const double *M, int64_t n, int64_t ld, double *y) {
+    __shared__ double s_red[256];
+    const int64_t r = blockIdx.x;
+    double acc = 0.0;
+    for (int64_t c = threadIdx.x; c < n; c += 256) acc += fabs(M[r * ld + c]);
+    s_red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (int(threadIdx.x) < off) s_red[threadIdx.x] += s_red[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) y[r] = s_red[0];
+}
+
 // true: Minv holds the inverse.  W = [M | I] is destroyed either way; `keep` (n x n) must hold a copy of M.
+// The acceptance: || M (Minv v) - v ||_inf for one fixed v, || v ||_inf = 1, against what ROUNDING alone leaves there for an
+// inverse as good as the pivoted elimination's: every entry of M (Minv v) is two nested sums of n products, each rounded at
+// 2^-53 of its size, so the entry is off by a random walk of about sqrt(n) 2^-53 (|M| |Minv| |v|) <= sqrt(n) 2^-53 || M ||_inf
+// || Minv ||_inf; the inverse's own backward error has the same form.  Accepted: at most TWICE that.  The threshold follows
+// the operator: a fixed 1e-9 (what stood here before) is 1e5 roundings wide on a well-conditioned operator — elimination
+// without pivoting across blocks can grow by orders on an operator whose diagonal blocks are weak against its couplings and
+// still pass it, with a stored inverse up to 2000 times worse than the pivoted one (tests/test_gpu_coarse_edges.py, the growth
+// family; profiles/coarse_edges.txt) — and too narrow for a sound inverse of an operator with || M || || Minv || above 1e7, which it sent down the slow
+// route.  Growth shows in this residual at its full size (hundreds of roundings and more on that family), sound inverses
+// stay below six; a wrong refusal costs setup time only: the pivoted elimination answers.
 bool blocked_inverse(double *W, int64_t n, const double *keep, double *Minv, hipStream_t s) {
     const int64_t ld = 2 * n;
     const int64_t row_tiles = (n + GJB - 1) / GJB, n_pad = row_tiles * GJB;
@@ -450,9 +475,13 @@ bool blocked_inverse(double *W, int64_t n, const double *keep, double *Minv, hip
     dv.upload(v.data(), size_t(n), s);
     hipLaunchKernelGGL(gjb_matvec_kernel, dim3(unsigned(n)), dim3(256), 0, s, Minv, n, n, dv.p, dy.p);
     hipLaunchKernelGGL(gjb_matvec_kernel, dim3(unsigned(n)), dim3(256), 0, s, keep, n, n, dy.p, dz.p);
-    std::vector<double> z((size_t)(n));
+    DevBuf<double> dnorm((size_t)(2 * n));
+    hipLaunchKernelGGL(gjb_rowabs_kernel, dim3(unsigned(n)), dim3(256), 0, s, keep, n, n, dnorm.p);
+    hipLaunchKernelGGL(gjb_rowabs_kernel, dim3(unsigned(n)), dim3(256), 0, s, Minv, n, n, dnorm.p + n);
+    std::vector<double> z((size_t)(n)), rowabs((size_t)(2 * n));
     int bad = 0;
     dz.download(z.data(), size_t(n), s);
+    dnorm.download(rowabs.data(), size_t(2 * n), s);
     OMG_HIP(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
     OMG_HIP(hipStreamSynchronize(s));
     if (bad) return false;
@@ -462,7 +491,13 @@ bool blocked_inverse(double *W, int64_t n, const double *keep, double *Minv, hip
         if (!(d == d)) return false;
         err = std::max(err, std::fabs(d));
     }
-    return err <= 1e-9;
+    double m_norm = 0.0, inv_norm = 0.0;
+    for (int64_t i = 0; i < n; ++i) {
+        m_norm = std::max(m_norm, rowabs[size_t(i)]);
+        inv_norm = std::max(inv_norm, rowabs[size_t(n + i)]);
+    }
+    const double tol = 2.0 * std::sqrt(double(n)) * 0x1p-53 * m_norm * inv_norm;      // (|| v ||_inf = 1)
+    return std::isfinite(tol) && err <= tol;
 }
 
 __global__ void copy_block_kernel(const double *W, int64_t n, int64_t ld, double *out) {
