@@ -439,6 +439,34 @@ int omg_resident_pcg(omg_hierarchy *h, int pre, int post, int max_iter, double t
  * levels' vectors untouched: a cycle, an omg_resident_pcg run or a replayed graph after it has the bits it would have
  * had without it.  A relative stop rule, or "the warm start is already good enough", is decided from these two. */
 int omg_resident_norms(omg_hierarchy *h, double *rhs_norm, double *residual_norm);
+/* Projection onto earlier solutions (Fischer 1998) for a sequence of right-hand sides on one operator: the hierarchy keeps
+ * up to `capacity` vectors X_i with X_i^T A X_j = delta_ij — A level 0's operator as omg_resident_norms applies it —, in
+ * the layout and precision of the resident iterate (double on OMG_DTYPE_F64 and OMG_DTYPE_MIXED hierarchies, float on
+ * OMG_DTYPE_F32), every sum and scalar in double with the deterministic reductions of omg_resident_pcg.
+ * omg_resident_projection allocates capacity + 1 vectors (1 <= capacity <= 64) and clears the set; 0 frees it.  Out of
+ * memory: OMG_ERR_ALLOC, and the hierarchy stays usable without a set.  A single-level hierarchy: OMG_ERR_INVALID.  A new
+ * hierarchy has no set; omg_hierarchy_update_fine and omg_hierarchy_update_kappa[_spaced] empty it (the vectors are
+ * A-orthonormal for the old operator only) and keep the capacity.
+ * omg_resident_project, after omg_resident_load[_dev]: the resident iterate becomes sum_i (X_i, b) X_i, b the resident
+ * right-hand side (after its null-space projection), accumulated in double with i ascending and rounded once.  *used: the
+ * vectors used; with none nothing is launched and the iterate stays what the load made it.  Enqueued only.
+ * omg_resident_project_update, after the solve that followed omg_resident_project (a caller whose solve ran no cycle or
+ * iteration skips it): a full set is emptied first and d = x, the whole solution; otherwise d = x - sum_i alpha_i X_i with
+ * that projection's alphas.  With a null space d loses its mean.  Then w = A d, e0 = (d, w), beta_i = (X_i, w),
+ * d -= sum_i beta_i X_i, w = A d once more, s2 = (d, w); d / sqrt(s2) joins the set exactly when s2 is finite, s2 > 0
+ * and s2 >= 2^-26 e0 (decided on the device), otherwise the set stays as it was.  *size: the set's size afterwards;
+ * *kept: whether d joined.  The resident right-hand side and iterate are not touched.
+ * omg_resident_projection_fetch: vector `index` (< size) in the caller's numbering, to the host. */
+int omg_resident_projection(omg_hierarchy *h, int capacity);
+int omg_resident_project(omg_hierarchy *h, int *used /* nullable */);
+int omg_resident_project_update(omg_hierarchy *h, int *size /* nullable */, int *kept /* nullable */);
+int omg_resident_projection_fetch(omg_hierarchy *h, int index, double *v);
+/* Average milliseconds of one launch, `reps` of each between hipEvents on the hierarchy's stream after a warm-up: the
+ * inner products of the set's vectors with the resident right-hand side (what omg_resident_project launches for them:
+ * the streaming kernel and its fold), the linear combination behind them (into a scratch vector), and the single inner
+ * product of omg_resident_pcg's dot kernel on two vectors of the same length — the yardstick.  Needs a set that holds at
+ * least one vector; any pointer may be NULL. */
+int omg_resident_projection_time(omg_hierarchy *h, int reps, double *dots_ms, double *dot_ms, double *lincomb_ms);
 /* Capture one resident cycle into a hipGraph and replay it on later omg_resident_cycle
  * calls with the same (pre, post).  enable = 0 drops the graph.                          */
 int omg_resident_use_graph(omg_hierarchy *h, int enable);

@@ -83,6 +83,11 @@ SIGNATURES = {
     "omg_kappa_rhs": (_I, [_I64P, _P, _I, _IP, _DP, _P, _I, _I, _IP, _DP, _PP, _I, _P, _I]),
     "omg_kappa_rhs_spaced": (_I, [_I64P, _P, _I, _IP, _DP, _P, _P, _P, _P, _I, _I, _IP, _DP, _PP, _I, _P, _I]),
     "omg_resident_norms": (_I, [_P, _DP, _DP]),
+    "omg_resident_projection": (_I, [_P, _I]),
+    "omg_resident_project": (_I, [_P, _IP]),
+    "omg_resident_project_update": (_I, [_P, _IP, _IP]),
+    "omg_resident_projection_fetch": (_I, [_P, _I, _P]),
+    "omg_resident_projection_time": (_I, [_P, _I, _DP, _DP, _DP]),
     "omg_hierarchy_destroy": (_I, [_P]),
     "omg_hierarchy_set_stream": (_I, [_P, _P]),
     "omg_hierarchy_sync": (_I, [_P]),
@@ -867,6 +872,37 @@ class Hierarchy:
         nb, nr = ctypes.c_double(0.0), ctypes.c_double(0.0)
         check(lib().omg_resident_norms(self._h, ctypes.byref(nb) if rhs else None, ctypes.byref(nr) if residual else None))
         return (nb.value if rhs else None), (nr.value if residual else None)
+
+    def projection(self, capacity):
+        """Room for `capacity` (1..64) earlier solutions, the set empty; 0 frees it (omg_resident_projection)."""
+        check(lib().omg_resident_projection(self._h, int(capacity)))
+
+    def resident_project(self):
+        """The resident iterate <- the A-best approximation of the solution in the set's span, from the resident b
+        (omg_resident_project; enqueued only).  Returns the vectors used; 0: nothing was launched."""
+        used = ctypes.c_int(0)
+        check(lib().omg_resident_project(self._h, ctypes.byref(used)))
+        return int(used.value)
+
+    def resident_project_update(self):
+        """After the solve: what the resident iterate adds to the projected start joins the set
+        (omg_resident_project_update).  Returns (the set's size afterwards, whether the direction was kept)."""
+        size, kept = ctypes.c_int(0), ctypes.c_int(0)
+        check(lib().omg_resident_project_update(self._h, ctypes.byref(size), ctypes.byref(kept)))
+        return int(size.value), bool(kept.value)
+
+    def projection_fetch(self, index):
+        """Vector `index` of the set as a host array in the caller's numbering (omg_resident_projection_fetch)."""
+        v = np.empty(self.sizes[0], dtype=np.float64)
+        check(lib().omg_resident_projection_fetch(self._h, int(index), v.ctypes.data))
+        return v
+
+    def projection_time(self, reps=20):
+        """Average milliseconds of one launch of (the set's inner products with the resident b, pcg's single inner product
+        on the same length, the linear combination over the set): omg_resident_projection_time."""
+        dots, dot, comb = ctypes.c_double(0.0), ctypes.c_double(0.0), ctypes.c_double(0.0)
+        check(lib().omg_resident_projection_time(self._h, int(reps), ctypes.byref(dots), ctypes.byref(dot), ctypes.byref(comb)))
+        return dots.value, dot.value, comb.value
 
     def spmv_time(self, reps=20):
         """Average milliseconds of one fine-grid y = A[0] x launch on the resident operator."""

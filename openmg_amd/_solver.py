@@ -8,6 +8,8 @@
     s.update_kappa(kappa_new, sigma=None)       # ... assembled in HBM (operators.stencil7_kappa: the definition)
     b = s.rhs(kappa, f=None, values=None)       # ... and its right-hand side: source, boundary values, fluxes (operators.rhs_kappa)
     y = s.matvec(x, out=None)                   # y = A x on the operator as the hierarchy holds it (b - A u where u lives)
+    s = openmg_amd.Solver(A_in, parameters, projection=8)       # every solve starts from its projection onto up to 8 earlier
+    x0 = s.project(b); s.projection_size; s.projection_basis(); s.projection_clear()      # ... solutions kept in HBM
     s.close()                                   # also a context manager
 
 The setup and the two loops are mgSolve's own (openmg_amd._setup, _solve_cycles, _solve_cg): a solve from zero has the
@@ -69,17 +71,35 @@ def _check_keys(parameters):
         raise ValueError("parameters['dtype'] must be 'float64', 'float32' or 'mixed', not %r" % (parameters.get("dtype"),))
 
 
+PROJECTION_MAX = 64
+
+
+def _projection_of(projection):
+    """The capacity `projection` asks for: 0 (also for None), or an integer in 1..64; anything else: ValueError."""
+    if projection is None:
+        return 0
+    if isinstance(projection, (bool, np.bool_)) or not isinstance(projection, (int, np.integer)) or not 0 <= projection <= PROJECTION_MAX:
+        raise ValueError("projection must be None or an integer in 0..%d (the earlier solutions kept), not %r" % (PROJECTION_MAX, projection))
+    return int(projection)
+
+
 class Solver:
     """A hierarchy set up once for A_in and `parameters` (every key mgSolve understands, and 'rtol'), solving many
     right-hand sides.  .parameters: the solver's own completed copy (the caller's dict and openmg_amd.defaults are not
     touched); .hierarchy: the _hip.Hierarchy; .A / .R: the operator lists when parameters['giveInfo'] asked for the
-    lists route, else None."""
+    lists route, else None.
 
-    def __init__(self, A_in, parameters):
+    projection = L (1..64): every solve starts from the A-best approximation of its solution in the span of up to L
+    earlier solutions kept in HBM as an A-orthonormal set, and adds what it found beyond that to the set (Fischer's
+    projection for successive right-hand sides; a full set restarts from the last solution).  0 or None: none is kept
+    and no solve differs from before."""
+
+    def __init__(self, A_in, parameters, *, projection=0):
         from . import _setup, defaults
         self._hierarchy = None
         given = dict(parameters)
         _check_keys(given)
+        self._capacity = _projection_of(projection)
         stop_target(1, 0.0, given.get("rtol", 0.0))                 # (rtol alone: the stop rules are checked per solve)
         self._given = given
         completed = dict(given)
@@ -87,11 +107,19 @@ class Solver:
         completed.setdefault("rtol", 0.0)
         self.parameters = completed
         self._pattern_of(A_in)
+        if self._capacity:
+            try:
+                self._hierarchy.projection(self._capacity)
+            except Exception:
+                self.close()
+                raise
 
     _kappa = None              # from_kappa: (problemShape, walls, scale, spacing) of construction, else None
+    _capacity = 0              # projection: the vectors the set may hold (0: no set) ...
+    _basis = 0                 # ... and how many it holds
 
     @classmethod
-    def from_kappa(cls, kappa, parameters, walls=None, sigma=None, scale=(1.0, 1.0, 1.0), spacing=None):
+    def from_kappa(cls, kappa, parameters, walls=None, sigma=None, scale=(1.0, 1.0, 1.0), spacing=None, *, projection=0):
         """The Solver of operators.stencil7_kappa(kappa, walls, sigma, scale, spacing) — same bits — from the coefficient
         field itself: kappa float64 (nz + 2, ny + 2, nx + 2), the cells and one ghost layer, and sigma (None, a scalar, an
         array of problemShape) as NumPy arrays or device arrays.  spacing: None, or the cell widths (hz, hy, hx) of a
@@ -111,6 +139,7 @@ class Solver:
         sigma the operator is singular: parameters['nullspace'] = 'constant'.  'smoother': 'line' and 'coarsening':
         'auto' read the grid off the in-grid pattern and raise HipError (ERR_UNSUPPORTED) on a periodic operator, as they
         do for a periodic matrix; named 'coarsening' factors and 'oddExtents' work."""
+        _projection_of(projection)
         source = _hip.KappaArgs(kappa, walls, sigma, scale, spacing)
         given = dict(parameters)
         if given.get("problemShape") is not None:
@@ -121,7 +150,7 @@ class Solver:
             if not same:
                 raise ValueError("parameters['problemShape'] = %r is not kappa's grid %r" % (given["problemShape"], source.grid))
         given["problemShape"] = source.grid
-        self = cls(source, given)
+        self = cls(source, given, projection=projection)
         self._kappa = (source.grid, walls, scale, source.spacing)
         return self
 
@@ -164,7 +193,7 @@ class Solver:
             pass
 
     # ---- solve --------------------------------------------------------------------------------------------------------
-    def solve(self, b, initial=None, out=None, **overrides):
+    def solve(self, b, initial=None, out=None, project=None, **overrides):
         """Solve A u = b from `initial` (None: zero).  Stops below max(threshold, rtol * ||b||) or after `cycles` (> 0)
         cycles / FCG iterations; a start that is already below the target returns at once with info['cycle'] == 0.
         overrides: SOLVE_KEYS, for this call only.  b, initial, out: host arrays, or contiguous float64 device arrays
@@ -173,9 +202,24 @@ class Solver:
 
         Returns (u, info): info['cycle'], ['norm'] (mgSolve's meaning: the true fp64 norm for 'cg' and 'mixed'),
         ['norms'] (one per cycle or iteration), ['rhs_norm'], ['initial_norm'].  A norm that is not finite raises
-        RuntimeError naming the cycle; the solver stays usable."""
+        RuntimeError naming the cycle; the solver stays usable.
+
+        project (None: on exactly when the solver was made with projection=L > 0; True without that: ValueError): the
+        solve starts from the projection of the solution onto the earlier ones — after b is loaded (and projected, with a
+        null space) the iterate becomes sum_i (x_i . b) x_i over the set —, runs the same loop from there, and what it
+        added to that start joins the set afterwards (nothing does when no cycle ran).  info['initial_norm'] is then the
+        projected start's residual, and a start that already meets the target returns with info['cycle'] == 0.
+        `initial` together with a projected start: ValueError — pass project=False for that solve, which leaves the set
+        alone.  On a solver with a set info also has ['projected'], the vectors this solve started from, and ['basis'],
+        the set's size afterwards."""
         from . import _accel_of, _cycle_of, _solve_cg, _solve_cycles
         h = self._open()
+        if project is None:
+            project = self._capacity > 0
+        elif project and not self._capacity:
+            raise ValueError("Solver.solve: project=True needs a solver made with projection=L (1..%d)" % PROJECTION_MAX)
+        if project and initial is not None:
+            raise ValueError("Solver.solve: `initial` and the projected start exclude each other: pass project=False for this solve")
         for key in overrides:
             if key not in SOLVE_KEYS:
                 raise ValueError("solve() cannot override %r (it defines the hierarchy); allowed: %s" % (key, ", ".join(SOLVE_KEYS)))
@@ -204,9 +248,11 @@ class Solver:
         else:
             out = _host_out(out, n)
             h.resident_load(np.asarray(b, dtype=np.float64).reshape(-1), initial)
-        # ||b|| as it is held, and the start's residual: without `initial` that is ||b|| itself (no SpMV)
-        rhs_norm, initial_norm = h.resident_norms(rhs=True, residual=initial is not None)
-        if initial is None:
+        used = h.resident_project() if project else 0
+        # ||b|| as it is held, and the start's residual: from zero (no `initial`, an empty set) that is ||b|| itself (no SpMV)
+        from_zero = initial is None and used == 0
+        rhs_norm, initial_norm = h.resident_norms(rhs=True, residual=not from_zero)
+        if from_zero:
             initial_norm = rhs_norm
         target = stop_target(cycles, threshold, rtol, rhs_norm)
         norms = []
@@ -224,18 +270,65 @@ class Solver:
             cycle, norm = run(h, loop, pre, post, self.parameters["coarsestLevel"], verbose, shape, observe)
             if not math.isfinite(norm):
                 raise RuntimeError("Solver.solve: the residual norm after cycle %d is not finite (%r)" % (cycle, norm))
+        if project and cycle > 0:
+            self._basis = h.resident_project_update()[0]
         if on_device:
             u = _devarray.empty_like(b, n) if out is None else out
             h.resident_fetch_dev(_devarray.address(u, n, "out"))
         else:
             u = h.resident_fetch(out)
         info = {"cycle": cycle, "norm": norm, "norms": norms, "rhs_norm": rhs_norm, "initial_norm": initial_norm}
+        if self._capacity:
+            info["projected"], info["basis"] = used, self._basis
         if _hip.is_line_smoother(h.smoother):
             info["lineAxis"] = h.line_axis          # ('smoother': 'line': the axis of the lines, an index into problemShape)
         if h.coarsening is not None:
             info["coarsening"] = list(h.coarsening)   # ('coarsening': the factors of every restriction, every level's grid)
             info["levelShapes"] = list(h.level_shapes)
         return u, info
+
+    # ---- projection ---------------------------------------------------------------------------------------------------
+    def project(self, b, out=None):
+        """The start a solve of b would take: sum_i (x_i . b) x_i over the set as it stands (zeros while it is empty);
+        with a null space b is projected first, as solve() does.  The set is not changed.  b, out: host arrays, or device
+        arrays (then the result is a device array), under apply()'s rules.  ValueError on a solver without a set."""
+        h = self._open()
+        if not self._capacity:
+            raise ValueError("Solver.project: needs a solver made with projection=L (1..%d)" % PROJECTION_MAX)
+        n = h.sizes[0]
+        on_device = _devarray.is_device_array(b)
+        if out is not None and _devarray.is_device_array(out) != on_device:
+            raise TypeError("Solver.project: `out` must be a device array exactly when `b` is one")
+        if on_device:
+            x = _devarray.empty_like(b, n) if out is None else out
+            b_ptr, x_ptr = _devarray.address(b, n, "b"), _devarray.address(x, n, "out")
+            _devarray.synchronize()
+            h.resident_load_dev(b_ptr, None)
+            h.resident_project()
+            h.resident_fetch_dev(x_ptr)
+            return x
+        x = _host_out(out, n)
+        h.resident_load(np.asarray(b, dtype=np.float64).reshape(-1), None)
+        h.resident_project()
+        return h.resident_fetch(x)
+
+    @property
+    def projection_size(self):
+        """How many earlier solutions the set holds now (0 .. the capacity; always 0 without one)."""
+        self._open()
+        return self._basis
+
+    def projection_clear(self):
+        """Empty the set; the capacity stays.  The next solve starts from zero, with the bits of a fresh solver's."""
+        h = self._open()
+        self._basis = 0
+        if self._capacity:
+            h.projection(self._capacity)
+
+    def projection_basis(self):
+        """The set as a list of host arrays in the caller's numbering: x_i^T A x_j = delta_ij."""
+        h = self._open()
+        return [h.projection_fetch(i) for i in range(self._basis)]
 
     # ---- apply --------------------------------------------------------------------------------------------------------
     def apply(self, r, out=None):
@@ -341,6 +434,7 @@ class Solver:
                 or not np.array_equal(A1.indptr, self._indptr) or not np.array_equal(A1.indices, self._indices)):
             raise ValueError("Solver.update: A_new must have the pattern (indptr and indices) the solver was set up with")
         if h.can_update_fine():
+            self._basis = 0                                         # (update_fine empties the set: it was A-orthonormal for the old operator)
             h.update_fine(A1.data)
             return
         self._rebuild(A_new)
@@ -356,7 +450,13 @@ class Solver:
             given["gridLevels"] = len(h.coarsening)  # (the depth built: the list is consumed exactly)
             given.pop("coarsestLevel", None)
         fresh, R, A = _setup(A_new, given, dict(defaults))[:3]
-        self._hierarchy, self.R, self.A = fresh, R, A
+        if self._capacity:
+            try:
+                fresh.projection(self._capacity)                    # (an empty set of the same capacity)
+            except Exception:
+                fresh.close()
+                raise
+        self._hierarchy, self.R, self.A, self._basis = fresh, R, A, 0
         h.close()
 
     def update_kappa(self, kappa, sigma=None):
@@ -373,6 +473,7 @@ class Solver:
         if source.grid != grid:
             raise ValueError("Solver.update_kappa: kappa's grid %r is not the solver's %r" % (source.grid, grid))
         if h.can_update_fine():
+            self._basis = 0
             h.update_kappa(source)
             return
         self._rebuild(source)

@@ -758,6 +758,26 @@ constexpr int PROJECT_SCRATCH = PROJECT_MAX_WG + 1;
 template <typename V>
 void launch_project_mean(V *x, int64_t n, double *scratch, hipStream_t s);
 
+// ---- projection onto earlier solutions (project.hip; driven by hierarchy.hip omg_resident_project[_update]) --------------
+// Up to PROJECTION_MAX A-orthonormal vectors and one free slot, `stride` values apart in one allocation.  The scalars: one
+// device array of PJ_NSC doubles — the alpha_i = (X_i, b) of the last projection, the beta_i = (X_i, A d) of the last update
+// with e0 = (d, A d) behind them (d lies in the slot behind the set, so it is one more vector of the same launch), and
+// s2 = (d, A d) after the orthogonalisation.
+constexpr int PROJECTION_MAX = 64;
+enum { PJ_ALPHA = 0, PJ_BETA = PROJECTION_MAX, PJ_S2 = 2 * PROJECTION_MAX + 1, PJ_NSC = 2 * PROJECTION_MAX + 4 };
+constexpr size_t PROJECTION_PARTIALS = size_t(PROJECTION_MAX + 1) * PROJECT_MAX_WG;
+// out[i] = (X_i, v) for i < count (X_i = X + i * stride), every sum in double; part: PROJECTION_PARTIALS doubles
+template <typename V>
+void project_dots(const V *X, int64_t stride, int count, const V *v, int64_t n, double *part, double *out, hipStream_t s);
+// out = (base or 0) +- sum_i c_i X_i, the c_i on the device; accumulated in double with i ascending, rounded once to V.
+// out may be base; count 0 copies base (or writes zeros)
+template <typename V>
+void project_lincomb(const V *base, const V *X, int64_t stride, int count, const double *c, bool subtract, V *out, int64_t n,
+                     hipStream_t s);
+// d <- d / sqrt(*s2) exactly when *s2 is finite, > 0 and >= 2^-26 *e0; status[0] = size + kept, status[1] = kept
+template <typename V>
+void project_keep_scale(V *d, int64_t n, const double *s2, const double *e0, int size, int32_t *status, hipStream_t s);
+
 // ---- lexicographic Gauss-Seidel of grid stencils (march.hip) ---------------------------------
 // The reference's own smoother (openmg/solvers.py:56-68) relaxes the rows in their natural order.
 // The general path runs it as a level schedule: one launch per set of mutually uncoupled rows —

@@ -251,6 +251,18 @@ struct Hier {
     // omg_level_spmv_dev: the operand and the product in the level's numbering and precision, apart from every vector a
     // cycle or the resident entries use (made at the first such call, grown to the largest level asked for)
     DevBuf<V> mv_x, mv_y;
+    // omg_resident_projection (project.hip): cap + 1 vectors of the resident iterate's type (double on a mixed hierarchy, else
+    // V) in level 0's numbering, `stride` values apart — the first `size` A-orthonormal, the one behind them free for the next
+    // direction; the scalars, the workgroup partials, the status word.  projected: omg_resident_project has run since the
+    // last load, so the alphas are this right-hand side's
+    struct Projection {
+        int cap = 0, size = 0;
+        bool projected = false;
+        int64_t stride = 0;
+        DevBuf<char> vecs;
+        DevBuf<double> sc, part;
+        DevBuf<int32_t> status;
+    } pj;
     // resident state
     bool resident = false;
     // OMG_NO_FUSE=1: never fuse the last smoother set with the residual / norm (A/B switch;
@@ -2374,6 +2386,7 @@ void mixed_cycles(Hier<V> *h, int pre, int post, int n_cycles, double *out) {
 template <typename V>
 void resident_load(Hier<V> *h, const double *b, const double *x0, bool dev) {
     Level<V> &L = h->lv[0];
+    h->pj.projected = false;                                       // (the alphas were another right-hand side's)
     auto load = [&](auto *b_dst, auto *x_dst, auto &&put) {
         put(b, b_dst);
         if (has_nullspace(h)) project_vec(h, b_dst, L.n);
@@ -2517,37 +2530,195 @@ void outer_norms(Hier<V> *hh, const Outer<T, V> &w, bool rhs, bool residual, dou
     }
 }
 
-template <typename V>
-void resident_norms(Hier<V> *hh, double *rhs_norm, double *residual_norm) {
+// The view the resident entries that only read the state take of level 0 (omg_resident_norms, the projection entries): the
+// resident b and x themselves (not FCG's copies), the operator, the zero scalars; apply: the operator will be applied
+// (outer_apply), so q and p2 exist as its product and scratch and the row-kernel format where no fused launch does it
+template <typename V, typename F>
+void with_resident_outer(Hier<V> *hh, bool apply, F &&f) {
     Level<V> &L = hh->lv[0];
-    hipStream_t s = hh->stream;
     if (hh->pcg_sc.n < size_t(2 * PCG_NSC)) hh->pcg_sc.alloc(2 * PCG_NSC);
     if (hh->pcg_part.n < size_t(2 * PCG_MAX_WG)) hh->pcg_part.alloc(2 * PCG_MAX_WG);
-    if (hh->norms2.n < 2) hh->norms2.alloc(2);
-    double *out = hh->norms2.p;
-    OMG_HIP(hipMemsetAsync(hh->pcg_sc.p + PCG_NSC, 0, PCG_NSC * sizeof(double), s));       // (beta = 0, nothing done)
+    OMG_HIP(hipMemsetAsync(hh->pcg_sc.p + PCG_NSC, 0, PCG_NSC * sizeof(double), hh->stream));   // (beta = 0, nothing done)
     if (hh->mixed) {
         Outer<double, V> w = mixed_outer(hh);
         w.rlo = nullptr;                                           // (the cycle's right-hand side stays as it is)
-        outer_norms(hh, w, rhs_norm != nullptr, residual_norm != nullptr, out);
-    } else {
-        if (residual_norm) {
-            OMG_REQUIRE(hh->lv.size() > 1, "omg_resident_norms: a single-level hierarchy has no smoothed operator to form a residual with");
-            const size_t vn = size_t(std::max<int64_t>(L.n, 1));
-            for (DevBuf<V> *b : {&hh->pcg_p2, &hh->pcg_q})
-                if (b->n < vn) b->alloc(vn);
-        }
-        Outer<V, V> w = plain_outer(hh);
-        w.b = L.b.p;                                               // (the resident b and x themselves, not FCG's copies)
-        w.x = L.xp;
-        if (residual_norm && !w.plane) ensure_format(hh, 0);
-        outer_norms(hh, w, rhs_norm != nullptr, residual_norm != nullptr, out);
+        f(w);
+        return;
     }
+    if (apply) {
+        OMG_REQUIRE(hh->lv.size() > 1, "omg_resident_norms: a single-level hierarchy has no smoothed operator to form a residual with");
+        const size_t vn = size_t(std::max<int64_t>(L.n, 1));
+        for (DevBuf<V> *b : {&hh->pcg_p2, &hh->pcg_q})
+            if (b->n < vn) b->alloc(vn);
+    }
+    Outer<V, V> w = plain_outer(hh);
+    w.b = L.b.p;
+    w.x = L.xp;
+    if (apply && !w.plane) ensure_format(hh, 0);
+    f(w);
+}
+
+template <typename V>
+void resident_norms(Hier<V> *hh, double *rhs_norm, double *residual_norm) {
+    hipStream_t s = hh->stream;
+    if (hh->norms2.n < 2) hh->norms2.alloc(2);
+    double *out = hh->norms2.p;
+    with_resident_outer(hh, residual_norm != nullptr, [&](auto &w) { outer_norms(hh, w, rhs_norm != nullptr, residual_norm != nullptr, out); });
     double host[2] = {0.0, 0.0};
     OMG_HIP(hipMemcpyAsync(host, out, sizeof(host), hipMemcpyDeviceToHost, s));
     OMG_HIP(hipStreamSynchronize(s));
     if (rhs_norm) *rhs_norm = host[0];
     if (residual_norm) *residual_norm = host[1];
+}
+
+// ---- omg_resident_projection / _project / _project_update: Fischer's projection onto earlier solutions (project.hip) --------
+// The set X_0 ... X_{l-1} is A-orthonormal for level 0's operator as omg_resident_norms applies it (outer_apply on the
+// Outer view: the fp64 outer operator of a mixed hierarchy), in that view's type T and the level's numbering.  Everything
+// is enqueued on the hierarchy's stream; the alphas, betas and s2 stay on the device and the keep-or-drop decision is taken
+// there (project_keep_scale); update reads one status word back.  w = A d goes to the view's q (p2 the plane launch's
+// scratch): vectors every resident entry fills again before it reads them.
+template <typename V>
+void projection_clear(Hier<V> *hh) {
+    hh->pj.size = 0;
+    hh->pj.projected = false;
+}
+
+template <typename V>
+void projection_alloc(Hier<V> *hh, int capacity) {
+    auto &P = hh->pj;
+    OMG_REQUIRE(capacity >= 0 && capacity <= PROJECTION_MAX, "omg_resident_projection: the capacity must lie in 0 .. 64");
+    OMG_HIP(hipStreamSynchronize(hh->stream));
+    projection_clear(hh);
+    if (capacity == P.cap) return;                                 // (the same room: emptied, nothing allocated anew)
+    P.vecs.release();
+    P.cap = 0;
+    if (capacity == 0) return;
+    OMG_REQUIRE(hh->lv.size() > 1, "omg_resident_projection: a single-level hierarchy solves directly: nothing to start from");
+    const size_t elem = hh->mixed ? sizeof(double) : sizeof(V);
+    // (a multiple of 16 bytes apart, so that every vector takes the 16-byte accesses)
+    P.stride = (std::max<int64_t>(hh->lv[0].n, 1) + 15) & ~int64_t(15);
+    P.vecs.alloc(size_t(capacity + 1) * size_t(P.stride) * elem);      // (out of memory: the hierarchy stays as it was, without a set)
+    P.vecs.zero(hh->stream);
+    if (P.sc.n < size_t(PJ_NSC)) P.sc.alloc(PJ_NSC);
+    if (P.part.n < PROJECTION_PARTIALS) P.part.alloc(PROJECTION_PARTIALS);
+    if (P.status.n < 2) P.status.alloc(2);
+    P.sc.zero(hh->stream);
+    OMG_HIP(hipStreamSynchronize(hh->stream));
+    P.cap = capacity;
+}
+
+// x <- sum_i (X_i, b) X_i; an empty set launches nothing (x stays what the load made it)
+template <typename V>
+void projection_project(Hier<V> *hh, int *used) {
+    auto &P = hh->pj;
+    OMG_REQUIRE(P.cap > 0, "omg_resident_project: the hierarchy has no set (omg_resident_projection)");
+    const int l = P.size;
+    if (l > 0)
+        with_resident_outer(hh, true, [&](auto &w) {
+            using T = typename std::remove_pointer<decltype(w.x)>::type;
+            const T *X = reinterpret_cast<const T *>(P.vecs.p);
+            const int64_t n = hh->lv[0].n;
+            project_dots<T>(X, P.stride, l, w.b, n, P.part.p, P.sc.p + PJ_ALPHA, hh->stream);
+            project_lincomb<T>(nullptr, X, P.stride, l, P.sc.p + PJ_ALPHA, false, w.x, n, hh->stream);
+        });
+    P.projected = true;
+    if (used) *used = l;
+}
+
+template <typename V>
+void projection_update(Hier<V> *hh, int *size, int *kept) {
+    auto &P = hh->pj;
+    OMG_REQUIRE(P.cap > 0, "omg_resident_project_update: the hierarchy has no set (omg_resident_projection)");
+    OMG_REQUIRE(P.projected, "omg_resident_project_update: omg_resident_project has not run on this right-hand side");
+    int32_t status[2] = {0, 0};
+    with_resident_outer(hh, true, [&](auto &w) {
+        using T = typename std::remove_pointer<decltype(w.x)>::type;
+        T *X = reinterpret_cast<T *>(P.vecs.p);
+        const int64_t n = hh->lv[0].n;
+        hipStream_t s = hh->stream;
+        double *sc = P.sc.p, *sc0 = hh->pcg_sc.p + PCG_NSC;
+        int l = P.size;                                            // (P.size itself changes with the status word alone)
+        if (l == P.cap) {
+            l = 0;                                                 // Fischer's restart: the whole solution is the first vector
+            OMG_HIP(hipMemcpyAsync(X, w.x, size_t(n) * sizeof(T), hipMemcpyDeviceToDevice, s));
+        } else {
+            project_lincomb<T>(w.x, X, P.stride, l, sc + PJ_ALPHA, true, X + int64_t(l) * P.stride, n, s);
+        }
+        T *d = X + int64_t(l) * P.stride;
+        if (has_nullspace(hh)) project_vec(hh, d, n);
+        outer_apply(hh, w, d, w.q, w.p2, sc0);                     // w = A d
+        project_dots<T>(X, P.stride, l + 1, w.q, n, P.part.p, sc + PJ_BETA, s);      // beta_i, and e0 = (d, w) behind them
+        if (l > 0) project_lincomb<T>(d, X, P.stride, l, sc + PJ_BETA, true, d, n, s);
+        outer_apply(hh, w, d, w.q, w.p2, sc0);                     // the operator once more: no e0 - sum beta^2
+        project_dots<T>(d, P.stride, 1, w.q, n, P.part.p, sc + PJ_S2, s);
+        project_keep_scale<T>(d, n, sc + PJ_S2, sc + PJ_BETA + l, l, P.status.p, s);
+        OMG_HIP(hipMemcpyAsync(status, P.status.p, sizeof(status), hipMemcpyDeviceToHost, s));
+        OMG_HIP(hipStreamSynchronize(s));
+    });
+    check_march(hh);
+    P.size = int(status[0]);
+    P.projected = false;
+    if (size) *size = P.size;
+    if (kept) *kept = int(status[1]);
+}
+
+// vector `index` of the set in the caller's numbering, on the host
+template <typename V>
+void projection_fetch(Hier<V> *hh, int index, double *v) {
+    auto &P = hh->pj;
+    Level<V> &L = hh->lv[0];
+    OMG_REQUIRE(v && index >= 0 && index < P.size, "omg_resident_projection_fetch: no such vector / v is null");
+    if (hh->mixed) {
+        const double *src = reinterpret_cast<const double *>(P.vecs.p) + int64_t(index) * P.stride;
+        ensure_nat(hh, 0);
+        launch_scatter<double, double>(src, L.ord.identity ? nullptr : L.perm.p, L.nat.p, L.n, hh->stream);
+        download_staged(v, L.nat.p, size_t(L.n) * sizeof(double), hh->stream);
+    } else {
+        fetch_vec<V>(hh, 0, reinterpret_cast<const V *>(P.vecs.p) + int64_t(index) * P.stride, v);
+    }
+}
+
+// omg_resident_projection_time: `reps` launches each of the set's inner products with the resident b (the l + 1 vectors of
+// omg_resident_project: kernel and fold), of the linear combination behind them (written to the scratch vector q) and of
+// pcg.hip's single inner product (b, q) on the same n, each bracketed by hipEvents on the hierarchy's stream after one
+// warm-up launch.  The alphas it leaves are those omg_resident_project would leave.
+template <typename V>
+void projection_time(Hier<V> *hh, int reps, double *dots_ms, double *dot_ms, double *lincomb_ms) {
+    auto &P = hh->pj;
+    OMG_REQUIRE(P.cap > 0 && P.size > 0 && reps > 0, "omg_resident_projection_time: needs a set that holds a vector / reps > 0");
+    hipStream_t s = hh->stream;
+    hipEvent_t e0, e1;
+    OMG_HIP(hipEventCreate(&e0));
+    OMG_HIP(hipEventCreate(&e1));
+    auto timed = [&](auto &&once) {
+        once();
+        OMG_HIP(hipEventRecord(e0, s));
+        for (int i = 0; i < reps; ++i) once();
+        OMG_HIP(hipEventRecord(e1, s));
+        OMG_HIP(hipEventSynchronize(e1));
+        float ms = 0.f;
+        OMG_HIP(hipEventElapsedTime(&ms, e0, e1));
+        return double(ms) / reps;
+    };
+    try {
+        with_resident_outer(hh, true, [&](auto &w) {
+            using T = typename std::remove_pointer<decltype(w.x)>::type;
+            const T *X = reinterpret_cast<const T *>(P.vecs.p);
+            const int64_t n = hh->lv[0].n;
+            const double d = timed([&] { project_dots<T>(X, P.stride, P.size, w.b, n, P.part.p, P.sc.p + PJ_ALPHA, s); });
+            const double c = timed([&] { project_lincomb<T>(nullptr, X, P.stride, P.size, P.sc.p + PJ_ALPHA, false, w.q, n, s); });
+            const double o = timed([&] { pcg_dot<T>(w.b, w.q, n, hh->pcg_part.p, hh->pcg_sc.p + PCG_NSC, s); });
+            if (dots_ms) *dots_ms = d;
+            if (lincomb_ms) *lincomb_ms = c;
+            if (dot_ms) *dot_ms = o;
+        });
+    } catch (...) {
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        throw;
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
 }
 
 // What every creating entry does around its own builder: the options are checked — before the builder, which asks for the
@@ -2681,6 +2852,7 @@ int omg_hierarchy_nullspace(const omg_hierarchy *h, int *kind) {
 int omg_hierarchy_update_fine(omg_hierarchy *h, const double *data, int64_t nnz, int on_device) {
     return guarded([&] {
         with(h, [&](auto *hh) {
+            projection_clear(hh);                                  // (the set is A-orthonormal for the old operator only)
             if (!hh->mixed) {
                 update_fine(hh, data, nnz, on_device != 0);
                 return;
@@ -3239,6 +3411,44 @@ int omg_resident_norms(omg_hierarchy *h, double *rhs_norm, double *residual_norm
             check_level(hh, 0);
             OMG_REQUIRE(hh->resident, "omg_resident_load has not been called");
             if (rhs_norm || residual_norm) resident_norms(hh, rhs_norm, residual_norm);
+        });
+    });
+}
+
+int omg_resident_projection(omg_hierarchy *h, int capacity) {
+    return guarded([&] { with(h, [&](auto *hh) { projection_alloc(hh, capacity); }); });
+}
+
+int omg_resident_project(omg_hierarchy *h, int *used) {
+    return guarded([&] {
+        with(h, [&](auto *hh) {
+            check_level(hh, 0);
+            OMG_REQUIRE(hh->resident, "omg_resident_load has not been called");
+            projection_project(hh, used);
+        });
+    });
+}
+
+int omg_resident_project_update(omg_hierarchy *h, int *size, int *kept) {
+    return guarded([&] {
+        with(h, [&](auto *hh) {
+            check_level(hh, 0);
+            OMG_REQUIRE(hh->resident, "omg_resident_load has not been called");
+            projection_update(hh, size, kept);
+        });
+    });
+}
+
+int omg_resident_projection_fetch(omg_hierarchy *h, int index, double *v) {
+    return guarded([&] { with(h, [&](auto *hh) { projection_fetch(hh, index, v); }); });
+}
+
+int omg_resident_projection_time(omg_hierarchy *h, int reps, double *dots_ms, double *dot_ms, double *lincomb_ms) {
+    return guarded([&] {
+        with(h, [&](auto *hh) {
+            check_level(hh, 0);
+            OMG_REQUIRE(hh->resident, "omg_resident_load has not been called");
+            projection_time(hh, reps, dots_ms, dot_ms, lincomb_ms);
         });
     });
 }
