@@ -282,6 +282,43 @@ int omg_kappa_rhs_spaced(const int64_t *shape, const double *kappa, int kappa_on
                          const double *hz, const double *hy, const double *hx, const double *f, int f_kind, int f_on_device,
                          const int *value_kinds, const double *value_scalars, const double *const *value_fields,
                          int values_on_device, double *b, int b_on_device);
+/* ---- the face fluxes of a solution under that operator, and their cell balance ---------------------------
+ * fz, fy, fx: (nz + 1) ny nx, nz (ny + 1) nx and nz ny (nx + 1) doubles in C order — F, the flux of -kappa grad u along the
+ * +AXIS direction through every face, times the operator's own factor (scale[axis]; with widths the face area), so that the
+ * differences of F are the operator's rows: for every u
+ *     omg_face_divergence(F) (+ sigma u, with widths sigma V u) = A u - omg_kappa_rhs(f = NULL, the same values)
+ * up to rounding.  operators.flux_kappa is the definition; the result has its bits.  shape, kappa, walls, scale | hz, hy, hx
+ * and the value arguments are omg_kappa_rhs's; u: n doubles, in host memory or — u_on_device != 0 — in HBM.  Face m of an
+ * axis of extent e lies between cell m - 1 (lo) and cell m (hi):
+ *   an in-grid face, m = 1 .. e - 1: F = c (u_lo - u_hi), c the bits of -A[lo, hi] = -A[hi, lo].
+ *   a periodic axis: faces 0 and e are one face and hold the same bits, c (u_{e-1} - u_0) with c of the cells e - 1 and 0.
+ *   a Dirichlet wall: F[0] = c_wall (g - u_0), F[e] = c_wall (u_{e-1} - g); c_wall as in omg_kappa_rhs (the ghost cell's
+ *     kappa and width), g the wall's value, +0.0 where it has none.
+ *   a Neumann wall: +0.0 where it has no value.  With a value under omg_kappa_rhs's convention — the OUTWARD flux
+ *     q = kappa du/dn; WITHOUT widths q times the cell width along the axis — t = value area[axis] (value scale[axis]) and
+ *     F[0] = t, F[e] = -t: the outward flux of -kappa grad u is -q.
+ * Every operation is rounded once in double, nothing is contracted: one subtraction and one multiplication per face, the
+ * coefficient as the operator rounds it.  The ghost cells of kappa behind Neumann and periodic walls are never read; behind a
+ * Dirichlet wall they are always read, with or without a value.  kappa is NOT validated, as in omg_kappa_rhs.
+ * alpha = NULL: F is stored.  Else (one double in HOST memory) every face gets out = out + alpha F — one multiplication, one
+ * addition; the two places of a periodic seam each from their own old value.  The outputs lie in host memory or —
+ * out_on_device != 0 — in HBM; host arrays are staged as omg_kappa_rhs stages them.  One launch, each face computed once.
+ * OMG_ERR_INVALID: what omg_kappa_rhs refuses; a NULL kappa, u or output; alpha not finite; an output that overlaps u, kappa
+ * or another output (threads read their neighbours' u: the fluxes cannot be made in place); a face array beyond int32. */
+int omg_kappa_flux(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls, const double *scale,
+                   const double *u, int u_on_device, const int *value_kinds, const double *value_scalars,
+                   const double *const *value_fields, int values_on_device, const double *alpha, double *fz, double *fy, double *fx,
+                   int out_on_device);
+/* ... with the cell widths (hz = hy = hx = NULL: the entry above) */
+int omg_kappa_flux_spaced(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls, const double *scale,
+                          const double *hz, const double *hy, const double *hx, const double *u, int u_on_device,
+                          const int *value_kinds, const double *value_scalars, const double *const *value_fields,
+                          int values_on_device, const double *alpha, double *fz, double *fy, double *fx, int out_on_device);
+/* out, n doubles: ((fz[k + 1] - fz[k]) + (fy[j + 1] - fy[j])) + (fx[i + 1] - fx[i]) per cell, in that order, each operation
+ * rounded once (operators.divergence_faces' bits).  The face arrays all in host memory or — faces_on_device != 0 — all in HBM.
+ * OMG_ERR_INVALID: a NULL argument, an extent below 1, a face array beyond int32, an output that overlaps a face array. */
+int omg_face_divergence(const int64_t *shape, const double *fz, const double *fy, const double *fx, int faces_on_device,
+                        double *out, int out_on_device);
 int omg_hierarchy_dtype(const omg_hierarchy *h, int *dtype);
 int omg_hierarchy_destroy(omg_hierarchy *h);
 /* Run on a caller-owned hipStream_t instead of the hierarchy's own stream (NULL = own). */

@@ -82,6 +82,9 @@ SIGNATURES = {
     "omg_hierarchy_update_kappa_spaced": (_I, [_P, _I64P, _P, _I, _IP, _P, _I, _I, _DP, _P, _P, _P]),
     "omg_kappa_rhs": (_I, [_I64P, _P, _I, _IP, _DP, _P, _I, _I, _IP, _DP, _PP, _I, _P, _I]),
     "omg_kappa_rhs_spaced": (_I, [_I64P, _P, _I, _IP, _DP, _P, _P, _P, _P, _I, _I, _IP, _DP, _PP, _I, _P, _I]),
+    "omg_kappa_flux": (_I, [_I64P, _P, _I, _IP, _DP, _P, _I, _IP, _DP, _PP, _I, _DP, _P, _P, _P, _I]),
+    "omg_kappa_flux_spaced": (_I, [_I64P, _P, _I, _IP, _DP, _P, _P, _P, _P, _I, _IP, _DP, _PP, _I, _DP, _P, _P, _P, _I]),
+    "omg_face_divergence": (_I, [_I64P, _P, _P, _P, _I, _P, _I]),
     "omg_resident_norms": (_I, [_P, _DP, _DP]),
     "omg_resident_projection": (_I, [_P, _I]),
     "omg_resident_project": (_I, [_P, _IP]),
@@ -500,6 +503,80 @@ def kappa_assemble(kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0), pattern
 VALUE_NONE, VALUE_SCALAR, VALUE_FIELD = 0, 1, 2
 
 
+class _WallCall:
+    """What kappa_rhs and kappa_flux share of their arguments, checked as operators.rhs_kappa checks them: kappa (NumPy, made
+    contiguous, or a device array: .k_dev says which side every array of the call lies on), .grid, .wall (the six codes),
+    .scale, .widths (three host arrays or three None), .values (None, a float or the array per wall), .n, .padded.
+    .head(): the C arguments from `shape` to `hx`; .wall_values(): the kinds, scalars, field pointers and their side;
+    .pointer(a, count, name): the address of an array on kappa's side; .host(a): a host array as contiguous float64,
+    kept alive with the object.  `what` names the entry in the messages."""
+
+    def __init__(self, what, kappa, walls, values, scale, spacing):
+        from . import _devarray, operators
+        self.what = what
+        self.k_dev = _devarray.is_device_array(kappa)
+        if self.k_dev:
+            k_shape = tuple(int(s) for s in kappa.__cuda_array_interface__["shape"])
+        else:
+            kappa = np.asarray(kappa)
+            if kappa.dtype != np.float64:
+                raise ValueError("kappa must be float64, not %s" % kappa.dtype)
+            kappa = np.ascontiguousarray(kappa)
+            k_shape = kappa.shape
+        self.kappa = kappa
+        self.grid, self.wall, self.scale = operators.kappa_arguments(k_shape, walls, None, scale)
+        self.widths = (None,) * 3
+        if spacing is not None:
+            if not operators.unit_scale(self.scale):
+                raise ValueError("spacing and scale exclude each other: the widths carry every factor")
+            self.widths = operators.spacing_arguments(self.grid, spacing)
+        self.values = operators.wall_values_arguments(self.grid, self.wall, values)
+        self.n, self.padded = int(np.prod(self.grid)), int(np.prod(k_shape))
+        if self.padded >= 2 ** 31 - 1:
+            raise ValueError("grid too large for int32 indices; shard it first")
+        self.keep = [kappa]
+
+    def same_side(self, named, names):
+        """ValueError unless the arrays among `named` = [(name, array or float or None)] and the value fields lie on kappa's side."""
+        from . import _devarray
+        for name, a in list(named) + [("values[%d]" % w, v) for w, v in enumerate(self.values)]:
+            if a is not None and not isinstance(a, float) and _devarray.is_device_array(a) != self.k_dev:
+                raise ValueError("%s: %s must all be device arrays or all host arrays; %s is not on kappa's side" % (self.what, names, name))
+
+    def pointer(self, a, count, name):
+        from . import _devarray
+        if self.k_dev:
+            try:
+                return _devarray.address(a, count, name)
+            except TypeError as e:
+                raise ValueError(str(e))
+        return a.ctypes.data
+
+    def host(self, a):
+        if not self.k_dev:
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            self.keep.append(a)
+        return a
+
+    def head(self):
+        return ((ctypes.c_int64 * 3)(*self.grid), ctypes.c_void_p(self.pointer(self.kappa, self.padded, "kappa")), int(self.k_dev),
+                (ctypes.c_int * 6)(*self.wall), (ctypes.c_double * 3)(*self.scale),
+                *(ctypes.c_void_p(None if h is None else h.ctypes.data) for h in self.widths))
+
+    def wall_values(self):
+        from . import operators
+        kinds, scalars, fields = [VALUE_NONE] * 6, [0.0] * 6, [None] * 6
+        for w, v in enumerate(self.values):
+            if v is None:
+                continue
+            if isinstance(v, float):
+                kinds[w], scalars[w] = VALUE_SCALAR, v
+                continue
+            count = int(np.prod([self.grid[a] for a in operators.WALL_FACES[w]]))
+            kinds[w], fields[w] = VALUE_FIELD, self.pointer(self.host(v), count, "values[%d]" % w)
+        return (ctypes.c_int * 6)(*kinds), (ctypes.c_double * 6)(*scalars), (ctypes.c_void_p * 6)(*fields), int(self.k_dev)
+
+
 def kappa_rhs(kappa, f=None, walls=None, values=None, scale=(1.0, 1.0, 1.0), spacing=None, out=None):
     """operators.rhs_kappa(kappa, f, walls, values, scale, spacing) made on the device (omg_kappa_rhs_spaced), bit for bit:
     the right-hand side that goes with the operator of kappa_assemble / Hierarchy.from_kappa — a source per cell, boundary
@@ -511,66 +588,23 @@ def kappa_rhs(kappa, f=None, walls=None, values=None, scale=(1.0, 1.0, 1.0), spa
     kappa's values are not checked here.  ValueError for what operators.rhs_kappa refuses, arrays on both sides, an `out`
     of the wrong size or side — before any device work."""
     from . import _devarray, operators
-    k_dev = _devarray.is_device_array(kappa)
-    if k_dev:
-        k_shape = tuple(int(s) for s in kappa.__cuda_array_interface__["shape"])
-    else:
-        kappa = np.asarray(kappa)
-        if kappa.dtype != np.float64:
-            raise ValueError("kappa must be float64, not %s" % kappa.dtype)
-        kappa = np.ascontiguousarray(kappa)
-        k_shape = kappa.shape
-    grid, wall, scale = operators.kappa_arguments(k_shape, walls, None, scale)
-    widths = (None,) * 3
-    if spacing is not None:
-        if not operators.unit_scale(scale):
-            raise ValueError("spacing and scale exclude each other: the widths carry every factor")
-        widths = operators.spacing_arguments(grid, spacing)
-    f = operators.source_argument(grid, f)
-    values = operators.wall_values_arguments(grid, wall, values)
-    n, padded = int(np.prod(grid)), int(np.prod(k_shape))
-    if padded >= 2 ** 31 - 1:
-        raise ValueError("grid too large for int32 indices; shard it first")
-    arrays = [("kappa", kappa)] + [(name, a) for name, a in [("f", f)] + [("values[%d]" % w, v) for w, v in enumerate(values)]
-                                    if a is not None and not isinstance(a, float)]
-    for name, a in arrays:
-        if _devarray.is_device_array(a) != k_dev:
-            raise ValueError("kappa_rhs: kappa, f and the value fields must all be device arrays or all host arrays; %s is not on kappa's side" % name)
+    c = _WallCall("kappa_rhs", kappa, walls, values, scale, spacing)
+    f = operators.source_argument(c.grid, f)
+    c.same_side([("f", f)], "kappa, f and the value fields")
+    k_dev, n, grid = c.k_dev, c.n, c.grid
     if out is not None and _devarray.is_device_array(out) != k_dev:
         raise ValueError("kappa_rhs: `out` must be a device array exactly when kappa and f are device arrays")
-
-    def pointer(a, count, what):
-        if k_dev:
-            try:
-                return _devarray.address(a, count, what)
-            except TypeError as e:
-                raise ValueError(str(e))
-        return a.ctypes.data
-    keep = [kappa]
-    k_ptr = pointer(kappa, padded, "kappa")
+    head = c.head()
     if f is None:
         f_kind, f_ptr = VALUE_NONE, None
     elif isinstance(f, float):
-        keep.append(np.array([f], dtype=np.float64))
-        f_kind, f_ptr = VALUE_SCALAR, keep[-1].ctypes.data
+        c.keep.append(np.array([f], dtype=np.float64))
+        f_kind, f_ptr = VALUE_SCALAR, c.keep[-1].ctypes.data
     else:
-        if not k_dev:
-            f = np.ascontiguousarray(f, dtype=np.float64)
-            keep.append(f)
-        f_kind, f_ptr = VALUE_FIELD, pointer(f, n, "f")
-    kinds, scalars, fields = [VALUE_NONE] * 6, [0.0] * 6, [None] * 6
-    for w, v in enumerate(values):
-        if v is None:
-            continue
-        if isinstance(v, float):
-            kinds[w], scalars[w] = VALUE_SCALAR, v
-            continue
-        if not k_dev:
-            v = np.ascontiguousarray(v, dtype=np.float64)
-            keep.append(v)
-        kinds[w], fields[w] = VALUE_FIELD, pointer(v, int(np.prod([grid[a] for a in operators.WALL_FACES[w]])), "values[%d]" % w)
+        f_kind, f_ptr = VALUE_FIELD, c.pointer(c.host(f), n, "f")
+    wall_values = c.wall_values()
     if k_dev:
-        b = _devarray.empty_like(kappa, n).reshape(grid) if out is None else out
+        b = _devarray.empty_like(c.kappa, n).reshape(grid) if out is None else out
         try:
             b_ptr = _devarray.address(b, n, "out")
         except TypeError as e:
@@ -584,11 +618,154 @@ def kappa_rhs(kappa, f=None, walls=None, values=None, scale=(1.0, 1.0, 1.0), spa
         else:
             raise ValueError("out must be a writeable contiguous float64 array of %d entries" % n)
         b_ptr = b.ctypes.data
-    check(lib().omg_kappa_rhs_spaced((ctypes.c_int64 * 3)(*grid), ctypes.c_void_p(k_ptr), int(k_dev), (ctypes.c_int * 6)(*wall),
-                                     (ctypes.c_double * 3)(*scale), *(ctypes.c_void_p(None if h is None else h.ctypes.data) for h in widths),
-                                     ctypes.c_void_p(f_ptr), f_kind, int(k_dev and f_kind == VALUE_FIELD), (ctypes.c_int * 6)(*kinds),
-                                     (ctypes.c_double * 6)(*scalars), (ctypes.c_void_p * 6)(*fields), int(k_dev), ctypes.c_void_p(b_ptr), int(k_dev)))
+    check(lib().omg_kappa_rhs_spaced(*head, ctypes.c_void_p(f_ptr), f_kind, int(k_dev and f_kind == VALUE_FIELD), *wall_values,
+                                     ctypes.c_void_p(b_ptr), int(k_dev)))
     return b
+
+
+def _extent_of(a, count):
+    """(address, bytes) of a contiguous float64 array of `count` entries, NumPy or device; ValueError otherwise."""
+    from . import _devarray
+    if _devarray.is_device_array(a):
+        try:
+            return _devarray.address(a, count, "array"), 8 * count
+        except TypeError as e:
+            raise ValueError(str(e))
+    return a.ctypes.data, 8 * count
+
+
+def _share_bytes(p, q):
+    return p[0] < q[0] + q[1] and q[0] < p[0] + p[1]
+
+
+def _face_outputs(what, out, counts, shapes, on_device, like):
+    """The three output arrays of kappa_flux — `out` checked (three contiguous float64 arrays of the face sizes on the
+    inputs' side) or new ones —, and their addresses."""
+    from . import _devarray
+    if out is None:
+        if on_device:
+            out = tuple(_devarray.empty_like(like, c).reshape(s) for c, s in zip(counts, shapes))
+        else:
+            out = tuple(np.empty(s, dtype=np.float64) for s in shapes)
+    else:
+        try:
+            out = tuple(out)
+        except TypeError:
+            raise ValueError("%s: `out` must be three face arrays (Fz, Fy, Fx)" % what)
+        if len(out) != 3:
+            raise ValueError("%s: `out` must be three face arrays (Fz, Fy, Fx), not %d" % (what, len(out)))
+    pointers = []
+    for name, a, count in zip(("Fz", "Fy", "Fx"), out, counts):
+        if _devarray.is_device_array(a) != on_device:
+            raise ValueError("%s: the face array %s must be a device array exactly when kappa and u are device arrays" % (what, name))
+        if on_device:
+            try:
+                pointers.append(_devarray.address(a, count, name))
+            except TypeError as e:
+                raise ValueError(str(e))
+        elif isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.flags.writeable and a.size == count:
+            pointers.append(a.ctypes.data)
+        else:
+            raise ValueError("%s: the face array %s must be a writeable contiguous float64 array of %d entries" % (what, name, count))
+    return out, pointers
+
+
+def kappa_flux(kappa, u, walls=None, values=None, scale=(1.0, 1.0, 1.0), spacing=None, out=None, alpha=None):
+    """operators.flux_kappa(kappa, u, walls, values, scale, spacing) made on the device (omg_kappa_flux_spaced), bit for bit,
+    in one launch: the fluxes (Fz, Fy, Fx) of -kappa grad u along +z, +y, +x through every face, with the operator's own
+    coefficients and factor — in-grid faces, the seam faces of periodic axes (faces 0 and e the same bits), Dirichlet and
+    Neumann wall faces with the boundary data `values` of kappa_rhs (the definition's docstring has the signs and
+    conventions).  kappa, u and the fields among `values`: NumPy arrays, or C-contiguous float64 device arrays — all on one
+    side; u of problemShape or of n entries; spacing: host arrays.  out: None for new arrays, or three arrays (Fz, Fy, Fx) on
+    the inputs' side to write into (returned as they are).  alpha (needs `out`): out = out + alpha * F instead — one
+    multiplication and one addition per face.  Returns the three arrays in face shape.  kappa's values are not checked.
+    ValueError — before any device work — for what operators.flux_kappa refuses, arrays on both sides, outputs of the
+    wrong size or side, alpha without `out` or not finite, an `out` that overlaps u, kappa or another output (threads read
+    their neighbours' u: the fluxes cannot be made in place)."""
+    from . import operators
+    c = _WallCall("kappa_flux", kappa, walls, values, scale, spacing)
+    u = operators.solution_argument(c.grid, u)
+    k_dev, n, padded, grid = c.k_dev, c.n, c.padded, c.grid
+    shapes = operators.face_shapes(grid)
+    counts = [int(np.prod(s)) for s in shapes]
+    if max(counts) >= 2 ** 31 - 1:
+        raise ValueError("grid too large for int32 indices; shard it first")
+    if alpha is not None:
+        if out is None:
+            raise ValueError("kappa_flux: alpha needs `out`, the arrays alpha * F is added to")
+        try:
+            alpha = float(alpha)
+        except (TypeError, ValueError):
+            raise ValueError("kappa_flux: alpha must be None or a finite number, not %r" % (alpha,))
+        if not np.isfinite(alpha):
+            raise ValueError("kappa_flux: alpha must be finite, not %r" % alpha)
+    c.same_side([("u", u)], "kappa, u and the value fields")
+    head = c.head()
+    k_ptr, u_ptr = head[1].value, c.pointer(c.host(u), n, "u")
+    wall_values = c.wall_values()
+    kappa = c.kappa
+    faces, f_ptrs = _face_outputs("kappa_flux", out, counts, shapes, k_dev, kappa)
+    spans = [(p, 8 * count) for p, count in zip(f_ptrs, counts)]
+    for d, span in enumerate(spans):
+        if _share_bytes(span, (u_ptr, 8 * n)) or _share_bytes(span, (k_ptr, 8 * padded)):
+            raise ValueError("kappa_flux: the face array %s of `out` overlaps u or kappa: the fluxes cannot be made in place" % "zyx"[d])
+        if any(_share_bytes(span, other) for other in spans[:d]):
+            raise ValueError("kappa_flux: the face arrays of `out` overlap each other")
+    if k_dev:
+        check(lib().omg_device_synchronize())
+    check(lib().omg_kappa_flux_spaced(*head, ctypes.c_void_p(u_ptr), int(k_dev), *wall_values,
+                                      None if alpha is None else ctypes.byref(ctypes.c_double(alpha)),
+                                      *(ctypes.c_void_p(p) for p in f_ptrs), int(k_dev)))
+    return faces
+
+
+def face_divergence(faces, out=None):
+    """operators.divergence_faces(Fz, Fy, Fx) made on the device (omg_face_divergence), bit for bit: the cell balance
+    ((Fz[k+1] - Fz[k]) + (Fy[j+1] - Fy[j])) + (Fx[i+1] - Fx[i]) of three face arrays — NumPy arrays, or C-contiguous float64
+    device arrays, all on one side, in the face shapes of one grid.  out: None for a new array, or an array of n entries on
+    the faces' side (returned as it is).  Returns the cell array in problemShape.  ValueError — before any device work — for
+    another count or other shapes, arrays on both sides, an `out` of the wrong size or side or one that overlaps a face array."""
+    from . import _devarray, operators
+    try:
+        faces = tuple(faces)
+    except TypeError:
+        raise ValueError("face_divergence: `faces` must be three face arrays (Fz, Fy, Fx)")
+    if len(faces) != 3:
+        raise ValueError("face_divergence: `faces` must be three face arrays (Fz, Fy, Fx), not %d" % len(faces))
+    on_device = _devarray.is_device_array(faces[0])
+    if any(_devarray.is_device_array(a) != on_device for a in faces):
+        raise ValueError("face_divergence: the face arrays must all be device arrays or all host arrays")
+    if not on_device:
+        faces = tuple(np.ascontiguousarray(a, dtype=np.float64) for a in faces)
+    grid = operators.grid_of_faces(tuple(a.__cuda_array_interface__["shape"] if on_device else a.shape for a in faces))
+    n = int(np.prod(grid))
+    counts = [int(np.prod(s)) for s in operators.face_shapes(grid)]
+    if max(counts) >= 2 ** 31 - 1:
+        raise ValueError("grid too large for int32 indices; shard it first")
+    if out is not None and _devarray.is_device_array(out) != on_device:
+        raise ValueError("face_divergence: `out` must be a device array exactly when the face arrays are device arrays")
+    spans = [_extent_of(a, c) for a, c in zip(faces, counts)]
+    if on_device:
+        d = _devarray.empty_like(faces[0], n).reshape(grid) if out is None else out
+        try:
+            d_ptr = _devarray.address(d, n, "out")
+        except TypeError as e:
+            raise ValueError(str(e))
+    else:
+        if out is None:
+            d = np.empty(grid, dtype=np.float64)
+        elif isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous and out.flags.writeable and out.size == n:
+            d = out
+        else:
+            raise ValueError("out must be a writeable contiguous float64 array of %d entries" % n)
+        d_ptr = d.ctypes.data
+    if any(_share_bytes((d_ptr, 8 * n), span) for span in spans):
+        raise ValueError("face_divergence: `out` overlaps a face array")
+    if on_device:
+        check(lib().omg_device_synchronize())
+    check(lib().omg_face_divergence((ctypes.c_int64 * 3)(*grid), *(ctypes.c_void_p(p) for p, _ in spans), int(on_device),
+                                    ctypes.c_void_p(d_ptr), int(on_device)))
+    return d
 
 
 class Hierarchy:

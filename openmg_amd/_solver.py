@@ -7,6 +7,8 @@
     s = openmg_amd.Solver.from_kappa(kappa, parameters, walls, sigma, scale)    # the 7-point operator of a coefficient field,
     s.update_kappa(kappa_new, sigma=None)       # ... assembled in HBM (operators.stencil7_kappa: the definition)
     b = s.rhs(kappa, f=None, values=None)       # ... and its right-hand side: source, boundary values, fluxes (operators.rhs_kappa)
+    Fz, Fy, Fx = s.fluxes(kappa, u, values=None, out=None, alpha=None)     # the face fluxes of a solution (operators.flux_kappa)
+    d = s.divergence((Fz, Fy, Fx), out=None)    # ... and the cell balance of face arrays (operators.divergence_faces)
     y = s.matvec(x, out=None)                   # y = A x on the operator as the hierarchy holds it (b - A u where u lives)
     s = openmg_amd.Solver(A_in, parameters, projection=8)       # every solve starts from its projection onto up to 8 earlier
     x0 = s.project(b); s.projection_size; s.projection_basis(); s.projection_clear()      # ... solutions kept in HBM
@@ -409,6 +411,51 @@ class Solver:
             raise ValueError("Solver.rhs: kappa's shape %r is not the solver's grid %r with one ghost layer" % (k_shape, grid))
         b = _hip.kappa_rhs(kappa, f, walls, values, scale, spacing, out)
         return b.reshape(-1) if out is None else b
+
+    # ---- face fluxes --------------------------------------------------------------------------------------------------
+    def fluxes(self, kappa, u, values=None, out=None, alpha=None):
+        """The face fluxes (Fz, Fy, Fx) of u under the operator of a Solver made by from_kappa (ValueError otherwise, like
+        rhs): operators.flux_kappa(kappa, u, walls, values, scale, spacing) — same bits — made on the device in one launch,
+        with the walls, scale and spacing of construction; kappa's grid must be the solver's.  F is the flux of
+        -kappa grad u along +z, +y, +x through every face — shapes (nz + 1, ny, nx), (nz, ny + 1, nx), (nz, ny, nx + 1) —
+        with the operator's own coefficients and factor (scale[axis]; with spacing the face area), so that
+        divergence(fluxes(kappa, u, values)) (+ the sigma term) = matvec(u) - rhs(kappa, None, values) to rounding.
+        u: flat, as solve returns it, or in problemShape; values: the boundary data as rhs takes them (a Dirichlet wall
+        without a value: 0; a Neumann wall's value: the outward flux kappa du/dn, without spacing times the cell width
+        along that axis — its face gets +value area at the low wall, -value area at the high wall).  kappa, u and the value
+        fields are NumPy arrays or all device arrays.  out: three arrays to write into, on the same side; alpha (needs
+        out): out = out + alpha * F — the velocity correction of a projection step is fluxes(kappa, p, out=W, alpha=-1.0).
+        An `out` that overlaps u or kappa is refused.  Nothing is projected, a resident solve is not disturbed and the
+        hierarchy is not touched."""
+        self._open()
+        if self._kappa is None:
+            raise ValueError("Solver.fluxes: the solver was not made by Solver.from_kappa")
+        grid, walls, scale, spacing = self._kappa
+        k_shape = tuple(int(s) for s in (kappa.__cuda_array_interface__["shape"] if _devarray.is_device_array(kappa) else np.shape(kappa)))
+        if k_shape != tuple(s + 2 for s in grid):
+            raise ValueError("Solver.fluxes: kappa's shape %r is not the solver's grid %r with one ghost layer" % (k_shape, grid))
+        return _hip.kappa_flux(kappa, u, walls, values, scale, spacing, out, alpha)
+
+    def divergence(self, faces, out=None):
+        """The cell balance of three face arrays (Fz, Fy, Fx) of the solver's grid, operators.divergence_faces — same bits —
+        made on the device: ((Fz[k+1] - Fz[k]) + (Fy[j+1] - Fy[j])) + (Fx[i+1] - Fx[i]) per cell.  For a Solver made by
+        from_kappa (ValueError otherwise); the arrays are NumPy arrays or all device arrays, `out` an array of n entries on
+        their side.  Returns the balance flattened to n entries in the solver's numbering, ready for solve() — the
+        right-hand side of a projection step is divergence(W) of the face velocities times area."""
+        self._open()
+        if self._kappa is None:
+            raise ValueError("Solver.divergence: the solver was not made by Solver.from_kappa")
+        grid = tuple(self._kappa[0])
+        from . import operators
+        try:
+            shapes = tuple(tuple(int(s) for s in (a.__cuda_array_interface__["shape"] if _devarray.is_device_array(a) else np.shape(a)))
+                           for a in faces)
+        except TypeError:
+            raise ValueError("Solver.divergence: `faces` must be three face arrays (Fz, Fy, Fx)")
+        if shapes != operators.face_shapes(grid):
+            raise ValueError("Solver.divergence: the face arrays' shapes %r are not those of the solver's grid %r" % (shapes, grid))
+        d = _hip.face_divergence(faces, out)
+        return d.reshape(-1) if out is None else d
 
     # ---- update -------------------------------------------------------------------------------------------------------
     def update(self, A_new):

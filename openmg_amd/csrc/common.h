@@ -912,6 +912,31 @@ struct KappaRhsInput {
 // one kernel — on a stream the call keeps per device, with the widths it holds in HBM from the call before where they are
 // the same — and, for a host b, fetches the result; waits for the stream
 void kappa_rhs(const KappaRhsInput &in);
+// The face fluxes of a solution under that operator (kappa.hip): what the caller of omg_kappa_flux names.
+// alpha null: the fluxes are stored; else out = out + alpha F.  fz, fy, fx: (nz + 1) ny nx, nz (ny + 1) nx, nz ny (nx + 1).
+struct KappaFluxInput {
+    const int64_t *shape;
+    const double *kappa;
+    int kappa_on_device;
+    const int *walls;
+    const double *scale, *hz, *hy, *hx;
+    const double *u;
+    int u_on_device;
+    const int *value_kinds;
+    const double *value_scalars;
+    const double *const *value_fields;
+    int values_on_device;
+    const double *alpha;
+    double *fz, *fy, *fx;
+    int out_on_device;
+};
+// checks the arguments as kappa_rhs does, and that the outputs overlap neither u, kappa nor each other; stages what lies in
+// host memory (with alpha the outputs too), launches the one kernel on kappa_rhs's stream with its held widths, fetches host
+// outputs; waits for the stream
+void kappa_flux(const KappaFluxInput &in);
+// out = the cell balance of the three face arrays (n doubles); out overlaps none of them
+void face_divergence(const int64_t *shape, const double *fz, const double *fy, const double *fx, int faces_on_device, double *out,
+                     int out_on_device);
 // The same chain with a factor (1 or 2) per axis and restriction instead of 2 everywhere (semicoarsening).
 // shape and every factor tuple are in the grid's C order (the last axis has unit stride).  factors: n_restrictions * dim
 // entries, or null = 'auto': per level the couplings kernel, semicoarsen_rule, the restriction kernel, the product.  Auto

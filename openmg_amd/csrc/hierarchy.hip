@@ -2925,6 +2925,32 @@ int omg_kappa_rhs_spaced(const int64_t *shape, const double *kappa, int kappa_on
     });
 }
 
+int omg_kappa_flux(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls, const double *scale, const double *u,
+                   int u_on_device, const int *value_kinds, const double *value_scalars, const double *const *value_fields,
+                   int values_on_device, const double *alpha, double *fz, double *fy, double *fx, int out_on_device) {
+    return omg_kappa_flux_spaced(shape, kappa, kappa_on_device, walls, scale, nullptr, nullptr, nullptr, u, u_on_device, value_kinds,
+                                 value_scalars, value_fields, values_on_device, alpha, fz, fy, fx, out_on_device);
+}
+
+int omg_kappa_flux_spaced(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls, const double *scale,
+                          const double *hz, const double *hy, const double *hx, const double *u, int u_on_device, const int *value_kinds,
+                          const double *value_scalars, const double *const *value_fields, int values_on_device, const double *alpha,
+                          double *fz, double *fy, double *fx, int out_on_device) {
+    return guarded([&] {
+        require_device();
+        kappa_flux({shape, kappa, kappa_on_device, walls, scale, hz, hy, hx, u, u_on_device, value_kinds, value_scalars, value_fields,
+                    values_on_device, alpha, fz, fy, fx, out_on_device});
+    });
+}
+
+int omg_face_divergence(const int64_t *shape, const double *fz, const double *fy, const double *fx, int faces_on_device, double *out,
+                        int out_on_device) {
+    return guarded([&] {
+        require_device();
+        face_divergence(shape, fz, fy, fx, faces_on_device, out, out_on_device);
+    });
+}
+
 int omg_hierarchy_create_from_kappa(const int64_t *shape, const double *kappa, int kappa_on_device, const int *walls, const double *sigma,
                                     int sigma_kind, int sigma_on_device, const double *scale, int n_restrictions,
                                     const omg_hierarchy_options *opt, omg_hierarchy **out) {

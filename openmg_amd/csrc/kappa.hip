@@ -578,6 +578,131 @@ __global__ void __launch_bounds__(KAPPA_BLOCK) kappa_rhs_kernel(kappa_rhs_args_t
     b[r] = __dadd_rn(__dadd_rn(__dadd_rn(__dadd_rn(__dadd_rn(__dadd_rn(v, t[0]), t[1]), t[2]), t[3]), t[4]), t[5]);
 }
 
+// ---- the face fluxes of a solution (operators.flux_kappa is the definition) --------------------------------
+// F = the flux of -kappa grad u along the +axis through every face, with the operator's own factor (scale[axis], or the face
+// area with widths): Fz (nz + 1, ny, nx), Fy (nz, ny + 1, nx), Fx (nz, ny, nx + 1) in C order.  Face m of an axis of extent e
+// lies between cell m - 1 (lo) and cell m (hi):
+//     in the grid       F = c (u_lo - u_hi)      c = face(kappa_lo, kappa_hi[, d_lo, d_hi, area]): the bits of -A[lo, hi]
+//     a periodic seam   faces 0 and e, both   c (u_{e-1} - u_0)   with c of the cells e - 1 and 0; no ghost is read
+//     a Dirichlet wall  F[0] = c_wall (g - u_0),  F[e] = c_wall (u_{e-1} - g)     c_wall kappa_rhs_kernel's, g = +0.0 without a value
+//     a Neumann wall    +0.0 without a value and nothing read; else t = value area[axis] (value scale[axis]): F[0] = t, F[e] = -t
+// One thread per cell, 256 consecutive cells per workgroup as above.  The thread owns the three LOW faces of its cell, so
+// every face is computed once; the cells of the last layer along an axis write that axis's high face too (a wall face), and
+// at a periodic seam the thread of cell 0 writes face e with the value of face 0.  With r the cell's number the low faces
+// are Fz[r], Fy[r + k nx], Fx[r + k ny + j]: three streams written at unit stride along x; a high face lies nx ny, nx or 1
+// further on, the seam's face e extent times that.  Read: the thread's own kappa and u, and those of its three lower
+// neighbours — the -I neighbour is the adjacent lane's own load, the -J and -K neighbours' lines were some other lane's own
+// loads nx and nx ny cells ago and come out of the caches (as the six neighbours of kappa_values_kernel do; no LDS, no
+// barrier: a workgroup is a piece of a LINE, not a tile, and a tile's halo would be read through the same caches).
+// ACCUMULATE: out = out + alpha F, one multiplication and one addition per face, every place with its own old value.
+struct KappaFluxArgs {
+    KappaGrid g;
+    KappaWrap wrap;                        // per axis z, y, x: periodic (read by the PERIODIC instantiations)
+    const double *__restrict__ kappa;      // (nz + 2)(ny + 2)(nx + 2)
+    const double *__restrict__ u;          // nz ny nx
+    int kind[6];                           // per wall -z, +z, -y, +y, -x, +x: OMG_VALUE_* (a periodic wall: NONE)
+    int neumann[6];
+    double value[6];
+    const double *__restrict__ field[6];   // one per face of the wall: (ny, nx), (nz, nx), (nz, ny)
+    double scale[3];                       // z, y, x
+    double alpha;                          // ACCUMULATE
+    double *fz, *fy, *fx;
+};
+struct KappaFluxSpacedArgs : KappaFluxArgs {
+    const double *__restrict__ hz, *__restrict__ hy, *__restrict__ hx;   // nz + 2, ny + 2, nx + 2
+};
+template <bool SPACED> using kappa_flux_args_t = std::conditional_t<SPACED, KappaFluxSpacedArgs, KappaFluxArgs>;
+
+template <bool ACCUMULATE>
+__device__ __forceinline__ void put_face(double *out, int64_t at, double v, double alpha) {
+    if constexpr (ACCUMULATE) out[at] = __dadd_rn(out[at], __dmul_rn(alpha, v));
+    else out[at] = v;
+}
+
+template <bool SPACED, bool PERIODIC, bool ACCUMULATE>
+__global__ void __launch_bounds__(KAPPA_BLOCK) kappa_flux_kernel(kappa_flux_args_t<SPACED> a) {
+    const KappaGrid g = a.g;
+    const int64_t n = int64_t(g.nx) * g.ny * g.nz;
+    const int64_t r = blockIdx.x * int64_t(KAPPA_BLOCK) + threadIdx.x;
+    if (r >= n) return;
+    const double uc = a.u[r];
+    int i, j, k;
+    cell_of(g, r, i, j, k);
+    const int64_t px = g.nx + 2, pxy = px * (g.ny + 2);
+    const int64_t c = int64_t(k + 1) * pxy + int64_t(j + 1) * px + (i + 1);
+    const double kc = a.kappa[c];
+    // by axis z, y, x: the cell's coordinate, the extent, the step to the next cell in kappa, and in u — which is the step
+    // to the next face of that axis in its face array too
+    const int coord[3] = {k, j, i}, extent[3] = {g.nz, g.ny, g.nx};
+    const int64_t kstep[3] = {pxy, px, 1}, ustep[3] = {int64_t(g.nx) * g.ny, g.nx, 1};
+    const int64_t low[3] = {r, r + int64_t(k) * g.nx, r + int64_t(k) * g.ny + j};
+    double *const out[3] = {a.fz, a.fy, a.fx};
+    // the cell's face on a z, y, x wall: (j, i) of (ny, nx), (k, i) of (nz, nx), (k, j) of (nz, ny)
+    const int64_t at[3] = {int64_t(j) * g.nx + i, int64_t(k) * g.nx + i, int64_t(k) * g.ny + j};
+    const double *hp[3] = {nullptr, nullptr, nullptr};
+    double own[3] = {0.0, 0.0, 0.0}, area[3] = {0.0, 0.0, 0.0};
+    if constexpr (SPACED) {
+        hp[0] = a.hz + (k + 1); hp[1] = a.hy + (j + 1); hp[2] = a.hx + (i + 1);
+        own[0] = *hp[0]; own[1] = *hp[1]; own[2] = *hp[2];
+        area[0] = __dmul_rn(own[1], own[2]); area[1] = __dmul_rn(own[0], own[2]); area[2] = __dmul_rn(own[0], own[1]);
+    }
+    int periodic[3] = {0, 0, 0};
+    if constexpr (PERIODIC) { periodic[0] = a.wrap.z; periodic[1] = a.wrap.y; periodic[2] = a.wrap.x; }
+    // a wall face of the cell: hi = 0 the low wall of the axis, 1 the high wall
+    auto wall_face = [&](int ax, int hi) __attribute__((always_inline)) -> double {
+        const int w = 2 * ax + hi;
+        const int kind = a.kind[w];
+        double val = a.value[w];                           // (+0.0 without a value)
+        if (kind == OMG_VALUE_FIELD) val = a.field[w][at[ax]];
+        if (a.neumann[w]) {
+            if (kind == OMG_VALUE_NONE) return 0.0;
+            const double t = __dmul_rn(val, SPACED ? area[ax] : a.scale[ax]);
+            return hi ? -t : t;
+        }
+        const double kn = a.kappa[hi ? c + kstep[ax] : c - kstep[ax]];
+        double coeff;
+        if constexpr (SPACED) coeff = face_spaced(kc, kn, own[ax], hp[ax][hi ? 1 : -1], area[ax]);
+        else coeff = face_of(kc, kn, a.scale[ax]);
+        return __dmul_rn(coeff, hi ? __dsub_rn(uc, val) : __dsub_rn(val, uc));
+    };
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) {
+        const int m = coord[ax], e = extent[ax];
+        const bool wraps = PERIODIC && periodic[ax];
+        if (m > 0 || wraps) {
+            // the lo cell: one step back, or e - 1 steps on across the seam
+            const int back = m > 0 ? 1 : -(e - 1);
+            const double kl = a.kappa[c - back * kstep[ax]], ul = a.u[r - back * ustep[ax]];
+            double coeff;
+            if constexpr (SPACED) coeff = face_spaced(kl, kc, hp[ax][-back], own[ax], area[ax]);
+            else coeff = face_of(kl, kc, a.scale[ax]);
+            const double F = __dmul_rn(coeff, __dsub_rn(ul, uc));
+            put_face<ACCUMULATE>(out[ax], low[ax], F, a.alpha);
+            if (m == 0) put_face<ACCUMULATE>(out[ax], low[ax] + e * ustep[ax], F, a.alpha);
+        } else {
+            put_face<ACCUMULATE>(out[ax], low[ax], wall_face(ax, 0), a.alpha);
+        }
+        if (m == e - 1 && !wraps) put_face<ACCUMULATE>(out[ax], low[ax] + ustep[ax], wall_face(ax, 1), a.alpha);
+    }
+}
+
+// the cell balance of three face arrays: ((Fz[k + 1] - Fz[k]) + (Fy[j + 1] - Fy[j])) + (Fx[i + 1] - Fx[i]), one thread per
+// cell; the low face indices are the flux kernel's.  32 bytes per cell: every face is read by the two cells it lies between
+// (the second time out of the caches) and the balance written once.
+__global__ void __launch_bounds__(KAPPA_BLOCK) face_divergence_kernel(KappaGrid g, const double *__restrict__ fz, const double *__restrict__ fy,
+                                                                       const double *__restrict__ fx, double *__restrict__ out) {
+    const int64_t n = int64_t(g.nx) * g.ny * g.nz;
+    const int64_t r = blockIdx.x * int64_t(KAPPA_BLOCK) + threadIdx.x;
+    if (r >= n) return;
+    int i, j, k;
+    cell_of(g, r, i, j, k);
+    const int64_t ly = r + int64_t(k) * g.nx, lx = r + int64_t(k) * g.ny + j;
+    const double dz = __dsub_rn(fz[r + int64_t(g.nx) * g.ny], fz[r]);
+    const double dy = __dsub_rn(fy[ly + g.nx], fy[ly]);
+    const double dx = __dsub_rn(fx[lx + 1], fx[lx]);
+    out[r] = __dadd_rn(__dadd_rn(dz, dy), dx);
+}
+
 // What a call keeps per DEVICE from one call to the next (a right-hand side is made every time step, and the launch itself
 // takes a tenth of a millisecond at 256^3): the stream, and the widths in HBM with the host copy they were made from — the same
 // widths again cost a comparison, not an allocation and three copies.  Made on first use and kept for the life of the
@@ -601,6 +726,110 @@ RhsDevice &rhs_device() {
     return *slot;
 }
 
+// What omg_kappa_rhs and omg_kappa_flux check alike of the grid they are given — shape, walls, scale factors, widths —, with
+// the widths in HBM behind it: the device's held copy where they are the same as the call before.
+struct CallGrid {
+    int nz, ny, nx;
+    int64_t n, padded;
+    bool periodic[6];
+    bool spaced;
+    const double *hz, *hy, *hx;         // in HBM (spaced)
+};
+
+// fills a.g, a.neumann and a.scale; `entry` in front of every refusal
+template <typename Args>
+CallGrid call_grid(RhsDevice &dev, hipStream_t s, const std::string &entry, const int64_t *shape, const int *walls, const double *scale,
+                   const double *hz, const double *hy, const double *hx, Args &a) {
+    CallGrid cg = {};
+    for (int d = 0; d < 3; ++d)
+        OMG_REQUIRE(shape[d] >= 1 && shape[d] < (int64_t(1) << 30), entry + ": every extent of the shape must be >= 1");
+    const int nz = cg.nz = int(shape[0]), ny = cg.ny = int(shape[1]), nx = cg.nx = int(shape[2]);
+    cg.n = int64_t(nx) * ny * nz;
+    cg.padded = int64_t(nz + 2) * (ny + 2) * (nx + 2);
+    OMG_REQUIRE(cg.n < (int64_t(1) << 31) - 1 && cg.padded < (int64_t(1) << 31) - 1, entry + ": grid too large for int32 indices");
+    a.g = {nx, ny, nz};
+    for (int w = 0; w < 6; ++w) {
+        const int wv = walls ? walls[w] : OMG_WALL_DIRICHLET;
+        OMG_REQUIRE(wv == OMG_WALL_DIRICHLET || wv == OMG_WALL_NEUMANN || wv == OMG_WALL_PERIODIC,
+                    entry + ": a wall must be OMG_WALL_DIRICHLET or OMG_WALL_NEUMANN, or OMG_WALL_PERIODIC on both walls of an axis");
+        a.neumann[w] = wv == OMG_WALL_NEUMANN;
+        cg.periodic[w] = wv == OMG_WALL_PERIODIC;
+    }
+    for (int d = 0; d < 3; ++d) {
+        OMG_REQUIRE(cg.periodic[2 * d] == cg.periodic[2 * d + 1], entry + ": OMG_WALL_PERIODIC must be given for both walls of an axis");
+        OMG_REQUIRE(!cg.periodic[2 * d] || shape[d] >= 3, entry + ": a periodic axis needs an extent >= 3");
+        a.scale[d] = scale ? scale[d] : 1.0;
+        OMG_REQUIRE(finite_pos(a.scale[d]), entry + ": every scale factor must be finite and > 0");
+    }
+    OMG_REQUIRE((!hz && !hy && !hx) || (hz && hy && hx), entry + ": the widths hz, hy, hx are given together or not at all");
+    cg.spaced = hz != nullptr;
+    if (!cg.spaced) return cg;
+    const int extent[3] = {nz, ny, nx};
+    OMG_REQUIRE(a.scale[0] == 1.0 && a.scale[1] == 1.0 && a.scale[2] == 1.0, entry + ": widths and scale factors exclude each other");
+    const double *const h[3] = {hz, hy, hx};
+    std::vector<double> all;
+    all.reserve(size_t(nz) + ny + nx + 6);
+    for (int d = 0; d < 3; ++d)
+        for (int m = 0; m < extent[d] + 2; ++m) {
+            const double v = h[d][m];
+            const bool ghost = m == 0 || m == extent[d] + 1;
+            OMG_REQUIRE(v < HUGE_VAL && (ghost ? v >= 0.0 : v > 0.0),
+                        entry + ": a cell width must be finite and > 0, a ghost width finite and >= 0");
+            all.push_back(v);
+        }
+    // (hz, hy, hx one after the other; compared as bytes: what is held is what the kernel reads)
+    if (all.size() != dev.held.size() || std::memcmp(all.data(), dev.held.data(), all.size() * sizeof(double)) != 0) {
+        dev.held.clear();
+        if (dev.capacity < all.size()) {
+            if (dev.widths) OMG_HIP(hipFree(dev.widths));
+            dev.widths = nullptr;
+            dev.capacity = 0;
+            OMG_HIP(hipMalloc(reinterpret_cast<void **>(&dev.widths), all.size() * sizeof(double)));
+            dev.capacity = all.size();
+        }
+        OMG_HIP(hipMemcpyAsync(dev.widths, all.data(), all.size() * sizeof(double), hipMemcpyHostToDevice, s));
+        OMG_HIP(hipStreamSynchronize(s));               // (`all` is this call's: the copy has left it)
+        dev.held = std::move(all);
+    }
+    cg.hz = dev.widths;
+    cg.hy = dev.widths + (nz + 2);
+    cg.hx = dev.widths + (nz + 2) + (ny + 2);
+    return cg;
+}
+
+// the walls' values into a.kind, a.value and a.field, host fields staged one after the other in own_fields; whether a
+// Dirichlet wall carries one
+template <typename Args>
+bool call_values(hipStream_t s, const std::string &entry, const CallGrid &cg, const int *value_kinds, const double *value_scalars,
+                 const double *const *value_fields, int values_on_device, Args &a, DevBuf<double> &own_fields) {
+    const int64_t faces[3] = {int64_t(cg.ny) * cg.nx, int64_t(cg.nz) * cg.nx, int64_t(cg.nz) * cg.ny};
+    bool dirichlet_value = false;
+    size_t staged = 0;
+    for (int w = 0; w < 6; ++w) {
+        const int kind = value_kinds ? value_kinds[w] : OMG_VALUE_NONE;
+        OMG_REQUIRE(kind == OMG_VALUE_NONE || kind == OMG_VALUE_SCALAR || kind == OMG_VALUE_FIELD, entry + ": a value kind must be one of OMG_VALUE_*");
+        OMG_REQUIRE(kind == OMG_VALUE_NONE || !cg.periodic[w], entry + ": a periodic wall takes no value");
+        OMG_REQUIRE(kind != OMG_VALUE_SCALAR || value_scalars, entry + ": value_scalars is null");
+        OMG_REQUIRE(kind != OMG_VALUE_FIELD || (value_fields && value_fields[w]), entry + ": a value field is announced and null");
+        a.kind[w] = kind;
+        a.value[w] = kind == OMG_VALUE_SCALAR ? value_scalars[w] : 0.0;
+        a.field[w] = kind == OMG_VALUE_FIELD ? value_fields[w] : nullptr;
+        dirichlet_value = dirichlet_value || (kind != OMG_VALUE_NONE && !a.neumann[w]);
+        if (kind == OMG_VALUE_FIELD && !values_on_device) staged += size_t(faces[w / 2]);
+    }
+    if (staged) {                                       // host fields: one after the other in one array
+        own_fields.alloc(staged);
+        size_t at = 0;
+        for (int w = 0; w < 6; ++w) {
+            if (a.kind[w] != OMG_VALUE_FIELD) continue;
+            OMG_HIP(hipMemcpyAsync(own_fields.p + at, value_fields[w], size_t(faces[w / 2]) * sizeof(double), hipMemcpyHostToDevice, s));
+            a.field[w] = own_fields.p + at;
+            at += size_t(faces[w / 2]);
+        }
+    }
+    return dirichlet_value;
+}
+
 }  // namespace
 
 void kappa_rhs(const KappaRhsInput &in) {
@@ -608,62 +837,13 @@ void kappa_rhs(const KappaRhsInput &in) {
     std::lock_guard<std::mutex> lock(dev.mu);
     if (!dev.s) OMG_HIP(hipStreamCreateWithFlags(&dev.s, hipStreamNonBlocking));
     const hipStream_t s = dev.s;
+    const std::string entry = "omg_kappa_rhs";
     OMG_REQUIRE(in.shape && in.b, "omg_kappa_rhs: null argument");
-    for (int d = 0; d < 3; ++d)
-        OMG_REQUIRE(in.shape[d] >= 1 && in.shape[d] < (int64_t(1) << 30), "omg_kappa_rhs: every extent of the shape must be >= 1");
-    const int nz = int(in.shape[0]), ny = int(in.shape[1]), nx = int(in.shape[2]);
-    const int64_t n = int64_t(nx) * ny * nz, padded = int64_t(nz + 2) * (ny + 2) * (nx + 2);
-    OMG_REQUIRE(n < (int64_t(1) << 31) - 1 && padded < (int64_t(1) << 31) - 1, "omg_kappa_rhs: grid too large for int32 indices");
     kappa_rhs_args_t<true> a;
-    a.g = {nx, ny, nz};
-    bool periodic[6];
-    for (int w = 0; w < 6; ++w) {
-        const int wv = in.walls ? in.walls[w] : OMG_WALL_DIRICHLET;
-        OMG_REQUIRE(wv == OMG_WALL_DIRICHLET || wv == OMG_WALL_NEUMANN || wv == OMG_WALL_PERIODIC,
-                    "omg_kappa_rhs: a wall must be OMG_WALL_DIRICHLET or OMG_WALL_NEUMANN, or OMG_WALL_PERIODIC on both walls of an axis");
-        a.neumann[w] = wv == OMG_WALL_NEUMANN;
-        periodic[w] = wv == OMG_WALL_PERIODIC;
-    }
-    for (int d = 0; d < 3; ++d) {
-        OMG_REQUIRE(periodic[2 * d] == periodic[2 * d + 1], "omg_kappa_rhs: OMG_WALL_PERIODIC must be given for both walls of an axis");
-        OMG_REQUIRE(!periodic[2 * d] || in.shape[d] >= 3, "omg_kappa_rhs: a periodic axis needs an extent >= 3");
-        a.scale[d] = in.scale ? in.scale[d] : 1.0;
-        OMG_REQUIRE(finite_pos(a.scale[d]), "omg_kappa_rhs: every scale factor must be finite and > 0");
-    }
-    OMG_REQUIRE((!in.hz && !in.hy && !in.hx) || (in.hz && in.hy && in.hx), "omg_kappa_rhs: the widths hz, hy, hx are given together or not at all");
-    const bool spaced = in.hz != nullptr;
-    const int extent[3] = {nz, ny, nx};
-    if (spaced) {
-        OMG_REQUIRE(a.scale[0] == 1.0 && a.scale[1] == 1.0 && a.scale[2] == 1.0, "omg_kappa_rhs: widths and scale factors exclude each other");
-        const double *const h[3] = {in.hz, in.hy, in.hx};
-        std::vector<double> all;
-        all.reserve(size_t(nz) + ny + nx + 6);
-        for (int d = 0; d < 3; ++d)
-            for (int m = 0; m < extent[d] + 2; ++m) {
-                const double v = h[d][m];
-                const bool ghost = m == 0 || m == extent[d] + 1;
-                OMG_REQUIRE(v < HUGE_VAL && (ghost ? v >= 0.0 : v > 0.0),
-                            "omg_kappa_rhs: a cell width must be finite and > 0, a ghost width finite and >= 0");
-                all.push_back(v);
-            }
-        // (hz, hy, hx one after the other; compared as bytes: what is held is what the kernel reads)
-        if (all.size() != dev.held.size() || std::memcmp(all.data(), dev.held.data(), all.size() * sizeof(double)) != 0) {
-            dev.held.clear();
-            if (dev.capacity < all.size()) {
-                if (dev.widths) OMG_HIP(hipFree(dev.widths));
-                dev.widths = nullptr;
-                dev.capacity = 0;
-                OMG_HIP(hipMalloc(reinterpret_cast<void **>(&dev.widths), all.size() * sizeof(double)));
-                dev.capacity = all.size();
-            }
-            OMG_HIP(hipMemcpyAsync(dev.widths, all.data(), all.size() * sizeof(double), hipMemcpyHostToDevice, s));
-            OMG_HIP(hipStreamSynchronize(s));               // (`all` is this call's: the copy has left it)
-            dev.held = std::move(all);
-        }
-        a.hz = dev.widths;
-        a.hy = dev.widths + (nz + 2);
-        a.hx = dev.widths + (nz + 2) + (ny + 2);
-    }
+    const CallGrid cg = call_grid(dev, s, entry, in.shape, in.walls, in.scale, in.hz, in.hy, in.hx, a);
+    const int64_t n = cg.n, padded = cg.padded;
+    const bool spaced = cg.spaced;
+    a.hz = cg.hz; a.hy = cg.hy; a.hx = cg.hx;
     // the source
     OMG_REQUIRE(in.f_kind == OMG_VALUE_NONE || in.f_kind == OMG_VALUE_SCALAR || in.f_kind == OMG_VALUE_FIELD, "omg_kappa_rhs: f_kind must be one of OMG_VALUE_*");
     OMG_REQUIRE(in.f_kind == OMG_VALUE_NONE || in.f, "omg_kappa_rhs: f is null");
@@ -692,31 +872,7 @@ void kappa_rhs(const KappaRhsInput &in) {
         }
     }
     // the walls' values
-    const int64_t faces[3] = {int64_t(ny) * nx, int64_t(nz) * nx, int64_t(nz) * ny};
-    bool reads_kappa = false;
-    size_t staged = 0;
-    for (int w = 0; w < 6; ++w) {
-        const int kind = in.value_kinds ? in.value_kinds[w] : OMG_VALUE_NONE;
-        OMG_REQUIRE(kind == OMG_VALUE_NONE || kind == OMG_VALUE_SCALAR || kind == OMG_VALUE_FIELD, "omg_kappa_rhs: a value kind must be one of OMG_VALUE_*");
-        OMG_REQUIRE(kind == OMG_VALUE_NONE || !periodic[w], "omg_kappa_rhs: a periodic wall takes no value");
-        OMG_REQUIRE(kind != OMG_VALUE_SCALAR || in.value_scalars, "omg_kappa_rhs: value_scalars is null");
-        OMG_REQUIRE(kind != OMG_VALUE_FIELD || (in.value_fields && in.value_fields[w]), "omg_kappa_rhs: a value field is announced and null");
-        a.kind[w] = kind;
-        a.value[w] = kind == OMG_VALUE_SCALAR ? in.value_scalars[w] : 0.0;
-        a.field[w] = kind == OMG_VALUE_FIELD ? in.value_fields[w] : nullptr;
-        reads_kappa = reads_kappa || (kind != OMG_VALUE_NONE && !a.neumann[w]);
-        if (kind == OMG_VALUE_FIELD && !in.values_on_device) staged += size_t(faces[w / 2]);
-    }
-    if (staged) {                                       // host fields: one after the other in one array
-        own_fields.alloc(staged);
-        size_t at = 0;
-        for (int w = 0; w < 6; ++w) {
-            if (a.kind[w] != OMG_VALUE_FIELD) continue;
-            OMG_HIP(hipMemcpyAsync(own_fields.p + at, in.value_fields[w], size_t(faces[w / 2]) * sizeof(double), hipMemcpyHostToDevice, s));
-            a.field[w] = own_fields.p + at;
-            at += size_t(faces[w / 2]);
-        }
-    }
+    const bool reads_kappa = call_values(s, entry, cg, in.value_kinds, in.value_scalars, in.value_fields, in.values_on_device, a, own_fields);
     a.kappa = nullptr;
     if (reads_kappa) {
         OMG_REQUIRE(in.kappa, "omg_kappa_rhs: kappa is null");
@@ -736,6 +892,120 @@ void kappa_rhs(const KappaRhsInput &in) {
     });
     OMG_HIP(hipGetLastError());
     if (!in.b_on_device) download_staged(in.b, own_b.p, size_t(n) * sizeof(double), s);
+    OMG_HIP(hipStreamSynchronize(s));
+}
+
+namespace {
+
+// do [p, p + np) and [q, q + nq) doubles share a byte (addresses of one side: both host or both HBM)
+bool overlaps(const double *p, int64_t np, const double *q, int64_t nq) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+    return a < b + uintptr_t(nq) * sizeof(double) && b < a + uintptr_t(np) * sizeof(double);
+}
+
+}  // namespace
+
+void kappa_flux(const KappaFluxInput &in) {
+    RhsDevice &dev = rhs_device();
+    std::lock_guard<std::mutex> lock(dev.mu);
+    if (!dev.s) OMG_HIP(hipStreamCreateWithFlags(&dev.s, hipStreamNonBlocking));
+    const hipStream_t s = dev.s;
+    const std::string entry = "omg_kappa_flux";
+    OMG_REQUIRE(in.shape && in.kappa && in.u && in.fz && in.fy && in.fx, "omg_kappa_flux: null argument");
+    OMG_REQUIRE(!in.alpha || (*in.alpha - *in.alpha == 0.0), "omg_kappa_flux: alpha must be finite");
+    kappa_flux_args_t<true> a;
+    const CallGrid cg = call_grid(dev, s, entry, in.shape, in.walls, in.scale, in.hz, in.hy, in.hx, a);
+    a.hz = cg.hz; a.hy = cg.hy; a.hx = cg.hx;
+    const int64_t n = cg.n, padded = cg.padded;
+    const int64_t count[3] = {n + int64_t(cg.ny) * cg.nx, n + int64_t(cg.nz) * cg.nx, n + int64_t(cg.nz) * cg.ny};
+    for (int d = 0; d < 3; ++d) OMG_REQUIRE(count[d] < (int64_t(1) << 31) - 1, "omg_kappa_flux: face arrays too large for int32 indices");
+    // threads read their neighbours' u and kappa: the flux cannot be made in place
+    double *const out[3] = {in.fz, in.fy, in.fx};
+    for (int d = 0; d < 3; ++d) {
+        OMG_REQUIRE(!(!!in.out_on_device == !!in.u_on_device && overlaps(out[d], count[d], in.u, n)), "omg_kappa_flux: an output overlaps u");
+        OMG_REQUIRE(!(!!in.out_on_device == !!in.kappa_on_device && overlaps(out[d], count[d], in.kappa, padded)),
+                    "omg_kappa_flux: an output overlaps kappa");
+        for (int e = 0; e < d; ++e) OMG_REQUIRE(!overlaps(out[d], count[d], out[e], count[e]), "omg_kappa_flux: the outputs overlap each other");
+    }
+    a.wrap = {cg.periodic[0], cg.periodic[2], cg.periodic[4]};
+    const bool any_periodic = cg.periodic[0] || cg.periodic[2] || cg.periodic[4];
+    a.alpha = in.alpha ? *in.alpha : 0.0;
+    DevBuf<double> own_u, own_kappa, own_fields, own_out;
+    call_values(s, entry, cg, in.value_kinds, in.value_scalars, in.value_fields, in.values_on_device, a, own_fields);
+    a.kappa = in.kappa;
+    if (!in.kappa_on_device) {
+        own_kappa.alloc(size_t(padded));
+        own_kappa.upload(in.kappa, size_t(padded), s);
+        a.kappa = own_kappa.p;
+    }
+    a.u = in.u;
+    if (!in.u_on_device) {
+        own_u.alloc(size_t(n));
+        own_u.upload(in.u, size_t(n), s);
+        a.u = own_u.p;
+    }
+    double *face[3] = {in.fz, in.fy, in.fx};
+    if (!in.out_on_device) {                            // host outputs: one after the other in one array, with alpha their old values
+        own_out.alloc(size_t(count[0] + count[1] + count[2]));
+        size_t at = 0;
+        for (int d = 0; d < 3; ++d) {
+            face[d] = own_out.p + at;
+            if (in.alpha) OMG_HIP(hipMemcpyAsync(face[d], out[d], size_t(count[d]) * sizeof(double), hipMemcpyHostToDevice, s));
+            at += size_t(count[d]);
+        }
+    }
+    a.fz = face[0]; a.fy = face[1]; a.fx = face[2];
+    const dim3 grid((unsigned)((n + KAPPA_BLOCK - 1) / KAPPA_BLOCK));
+    as_constant(any_periodic, [&](auto wrap) {
+        as_constant(in.alpha != nullptr, [&](auto acc) {
+            constexpr bool P = decltype(wrap)::value, A = decltype(acc)::value;
+            if (cg.spaced) hipLaunchKernelGGL((kappa_flux_kernel<true, P, A>), grid, dim3(KAPPA_BLOCK), 0, s, a);
+            else hipLaunchKernelGGL((kappa_flux_kernel<false, P, A>), grid, dim3(KAPPA_BLOCK), 0, s, static_cast<const KappaFluxArgs &>(a));
+        });
+    });
+    OMG_HIP(hipGetLastError());
+    if (!in.out_on_device)
+        for (int d = 0; d < 3; ++d) download_staged(out[d], face[d], size_t(count[d]) * sizeof(double), s);
+    OMG_HIP(hipStreamSynchronize(s));
+}
+
+void face_divergence(const int64_t *shape, const double *fz, const double *fy, const double *fx, int faces_on_device, double *out,
+                     int out_on_device) {
+    RhsDevice &dev = rhs_device();
+    std::lock_guard<std::mutex> lock(dev.mu);
+    if (!dev.s) OMG_HIP(hipStreamCreateWithFlags(&dev.s, hipStreamNonBlocking));
+    const hipStream_t s = dev.s;
+    OMG_REQUIRE(shape && fz && fy && fx && out, "omg_face_divergence: null argument");
+    for (int d = 0; d < 3; ++d)
+        OMG_REQUIRE(shape[d] >= 1 && shape[d] < (int64_t(1) << 30), "omg_face_divergence: every extent of the shape must be >= 1");
+    const int nz = int(shape[0]), ny = int(shape[1]), nx = int(shape[2]);
+    const int64_t n = int64_t(nx) * ny * nz;
+    const int64_t count[3] = {n + int64_t(ny) * nx, n + int64_t(nz) * nx, n + int64_t(nz) * ny};
+    for (int d = 0; d < 3; ++d) OMG_REQUIRE(count[d] < (int64_t(1) << 31) - 1, "omg_face_divergence: face arrays too large for int32 indices");
+    const double *const given[3] = {fz, fy, fx};
+    if (!!faces_on_device == !!out_on_device)
+        for (int d = 0; d < 3; ++d) OMG_REQUIRE(!overlaps(out, n, given[d], count[d]), "omg_face_divergence: the output overlaps a face array");
+    DevBuf<double> own_faces, own_out;
+    const double *face[3] = {fz, fy, fx};
+    if (!faces_on_device) {
+        own_faces.alloc(size_t(count[0] + count[1] + count[2]));
+        size_t at = 0;
+        for (int d = 0; d < 3; ++d) {
+            OMG_HIP(hipMemcpyAsync(own_faces.p + at, given[d], size_t(count[d]) * sizeof(double), hipMemcpyHostToDevice, s));
+            face[d] = own_faces.p + at;
+            at += size_t(count[d]);
+        }
+    }
+    double *out_dev = out;
+    if (!out_on_device) {
+        own_out.alloc(size_t(n));
+        out_dev = own_out.p;
+    }
+    const KappaGrid g = {nx, ny, nz};
+    const dim3 grid((unsigned)((n + KAPPA_BLOCK - 1) / KAPPA_BLOCK));
+    hipLaunchKernelGGL(face_divergence_kernel, grid, dim3(KAPPA_BLOCK), 0, s, g, face[0], face[1], face[2], out_dev);
+    OMG_HIP(hipGetLastError());
+    if (!out_on_device) download_staged(out, own_out.p, size_t(n) * sizeof(double), s);
     OMG_HIP(hipStreamSynchronize(s));
 }
 

@@ -695,6 +695,130 @@ def rhs_kappa(kappa, f=None, walls=None, values=None, scale=(1.0, 1.0, 1.0), spa
     return (((((volume + terms[0]) + terms[2]) + terms[4]) + terms[5]) + terms[3]) + terms[1]
 
 
+def face_shapes(shape):
+    """The shapes of the three face arrays (Fz, Fy, Fx) of a grid of problemShape (nz, ny, nx): one more along the own axis."""
+    shape = tuple(int(s) for s in shape)
+    return tuple(tuple(s + (1 if a == axis else 0) for a, s in enumerate(shape)) for axis in range(3))
+
+
+def solution_argument(shape, u):
+    """The solution u of flux_kappa and its device twins, checked: an array of problemShape or of n entries ((n,) or (n, 1),
+    as solve returns it), returned as it came; ValueError for anything else."""
+    on_device = hasattr(u, "__cuda_array_interface__") and not isinstance(u, np.ndarray)
+    if u is None or (not on_device and np.ndim(u) == 0):
+        raise ValueError("u must be an array of problemShape %r or of its n entries, not %r" % (tuple(shape), u))
+    u_shape = tuple(int(s) for s in (u.__cuda_array_interface__["shape"] if on_device else np.shape(u)))
+    n = int(np.prod(shape))
+    if u_shape != tuple(shape) and u_shape != (n,) and u_shape != (n, 1):
+        raise ValueError("u must have problemShape %r or its %d entries, not shape %r" % (tuple(shape), n, u_shape))
+    return u
+
+
+def flux_kappa(kappa, u, walls=None, values=None, scale=(1.0, 1.0, 1.0), spacing=None):
+    """The face fluxes of a solution u under stencil7_kappa(kappa, walls, sigma, scale, spacing) with the boundary data of
+    rhs_kappa(kappa, None, walls, values, scale, spacing) (NOT in the reference; the definition the device kernel —
+    _hip.kappa_flux, Solver.fluxes — is pinned to bit for bit).  Returns (Fz, Fy, Fx), float64 arrays of shapes
+    (nz + 1, ny, nx), (nz, ny + 1, nx), (nz, ny, nx + 1): F is the flux of -kappa grad u ALONG THE +AXIS DIRECTION through
+    each face, times the operator's own factor — scale[axis] without spacing, the face area with spacing —, so that the
+    differences of F are the operator's rows: for every u
+        divergence_faces(*flux_kappa(kappa, u, walls, values, ...)) (+ sigma u; with spacing sigma cell_volumes u)
+            = stencil7_kappa(...) @ u - rhs_kappa(kappa, None, walls, values, ...)
+    up to rounding.  kappa, walls, scale, spacing, values: as stencil7_kappa and rhs_kappa take them; sigma plays no part.
+    u: an array of problemShape or of n entries.
+
+    Face m of an axis of extent e lies between cell m - 1 ("lo") and cell m ("hi").
+      - an in-grid face, m = 1 .. e - 1: F = c * (u_lo - u_hi), c the face coefficient as the lo cell computes its + face
+        in stencil7_kappa (a = kappa_lo, b = kappa_hi, da, db their widths, area[axis]): the bits of -A[lo, hi] = -A[hi, lo].
+      - a periodic axis: faces 0 and e are the same face and hold the same bits, c * (u_{e-1} - u_0) with the inner-face
+        expression of a = kappa_{e-1}, b = kappa_0 and their widths; no ghost kappa or ghost width is read.
+      - a Dirichlet wall: F[0] = c_wall * (g - u_0), F[e] = c_wall * (u_{e-1} - g); c_wall is rhs_kappa's (own kappa, ghost
+        kappa, own width, ghost width, the same rounding), g the wall's value, +0.0 where it has none.
+      - a Neumann wall: +0.0 where it has no value, and nothing is read.  With a value v under rhs_kappa's convention (the
+        OUTWARD flux q = kappa du/dn; WITHOUT spacing q times the cell width along the axis) t = v * area[axis] with
+        spacing, v * scale[axis] without, and F[0] = t, F[e] = -t: the outward flux of -kappa grad u is -q.
+    Every operation is rounded once in double: one subtraction and one multiplication per face, the coefficient as the
+    operator rounds it.  The ghost cells of kappa behind Neumann and periodic walls are never read and may hold anything;
+    behind a Dirichlet wall they are always read, with or without a value.  kappa's values are not checked, as in rhs_kappa.
+
+    ValueError: what rhs_kappa refuses of kappa, walls, values, scale and spacing; a u of another shape."""
+    kap = np.asarray(kappa)
+    if kap.dtype != np.float64:
+        raise ValueError("kappa must be float64, not %s" % kap.dtype)
+    shape, wall, scale = kappa_arguments(kap.shape, walls, None, scale)
+    values = wall_values_arguments(shape, wall, values)
+    H = None
+    if spacing is not None:
+        if not unit_scale(scale):
+            raise ValueError("spacing and scale exclude each other: the widths carry every factor")
+        H = spacing_arguments(shape, spacing)
+        own = (H[0][1:-1, None, None], H[1][None, 1:-1, None], H[2][None, None, 1:-1])
+        area = (own[1] * own[2], own[0] * own[2], own[0] * own[1])
+    u = np.asarray(solution_argument(shape, u), dtype=np.float64).reshape(shape)
+    c = kap[1:-1, 1:-1, 1:-1]
+    periodic = periodic_axes(wall)
+    out = []
+    for axis, faces in enumerate(face_shapes(shape)):
+        e = shape[axis]
+
+        def at(m, a=None):                                 # layer m (or layers m) along the axis, of `a` broadcast over the grid
+            sel = [slice(None)] * 3
+            sel[axis] = m
+            return np.broadcast_to(c if a is None else a, shape)[tuple(sel)]
+
+        def coefficient(a, b, da, db, lo):                 # the face between kappa a and b; area of the cells in layers `lo`
+            if H is not None:
+                return ((2.0 * a) * b) / (da * b + db * a) * at(lo, area[axis])
+            return ((2.0 * a) * b) / (a + b) * scale[axis]
+        F = np.zeros(faces)
+        inner = [slice(None)] * 3
+        inner[axis] = slice(1, e)
+        lo, hi = slice(0, e - 1), slice(1, e)
+        widths = own[axis] if H is not None else None
+        F[tuple(inner)] = coefficient(at(lo), at(hi), at(lo, widths), at(hi, widths), lo) * (at(lo, u) - at(hi, u))
+        first, last = [slice(None)] * 3, [slice(None)] * 3
+        first[axis], last[axis] = 0, e
+        first, last = tuple(first), tuple(last)
+        if periodic[axis]:
+            seam = coefficient(at(e - 1), at(0), at(e - 1, widths), at(0, widths), e - 1) * (at(e - 1, u) - at(0, u))
+            F[first] = seam
+            F[last] = seam
+            out.append(F)
+            continue
+        for side, place, cell in ((0, first, 0), (1, last, e - 1)):
+            w = 2 * axis + side
+            if wall[w] == WALL_CODES["neumann"]:
+                if values[w] is not None:
+                    t = np.asarray(values[w], dtype=np.float64) * (at(cell, area[axis]) if H is not None else scale[axis])
+                    F[place] = -t if side else t
+                continue
+            behind = [slice(1, -1)] * 3
+            behind[axis] = -1 if side else 0               # in the padded field: the ghost cells behind the wall's cells
+            g = 0.0 if values[w] is None else np.asarray(values[w], dtype=np.float64)
+            c_wall = coefficient(at(cell), kap[tuple(behind)], at(cell, widths), H[axis][-1 if side else 0] if H is not None else None, cell)
+            F[place] = c_wall * (at(cell, u) - g if side else g - at(cell, u))
+        out.append(F)
+    return tuple(out)
+
+
+def divergence_faces(Fz, Fy, Fx):
+    """The cell balance of three face arrays, ((Fz[k+1] - Fz[k]) + (Fy[j+1] - Fy[j])) + (Fx[i+1] - Fx[i]) in that order, as
+    a float64 array of problemShape (the definition _hip.face_divergence and Solver.divergence are pinned to bit for bit).
+    ValueError for shapes that are not the three face shapes (nz + 1, ny, nx), (nz, ny + 1, nx), (nz, ny, nx + 1) of one grid."""
+    F = tuple(np.asarray(a, dtype=np.float64) for a in (Fz, Fy, Fx))
+    grid_of_faces(tuple(a.shape for a in F))
+    return ((F[0][1:] - F[0][:-1]) + (F[1][:, 1:] - F[1][:, :-1])) + (F[2][:, :, 1:] - F[2][:, :, :-1])
+
+
+def grid_of_faces(shapes):
+    """problemShape of the grid whose face shapes (Fz, Fy, Fx) these three are; ValueError if they are not one grid's."""
+    shapes = tuple(tuple(int(s) for s in sh) for sh in shapes)
+    if len(shapes) == 3 and len(shapes[0]) == 3 and shapes[0][0] >= 2:
+        shape = (shapes[0][0] - 1,) + shapes[0][1:]
+        if min(shape) >= 1 and shapes == face_shapes(shape):
+            return shape
+    raise ValueError("the face arrays must have the shapes (nz + 1, ny, nx), (nz, ny + 1, nx), (nz, ny, nx + 1) of one grid, not %r" % (shapes,))
+
+
 def stencil27_variable(shape, seed=2024, rows=None):
     """27-point variable-coefficient operator of BASELINE.json configs[4] as SURVEY.md 8(d)
     specifies it (NOT in the reference): Q1 finite-element stiffness of -div(kappa grad u) on a
