@@ -319,6 +319,54 @@ int omg_kappa_flux_spaced(const int64_t *shape, const double *kappa, int kappa_o
  * OMG_ERR_INVALID: a NULL argument, an extent below 1, a face array beyond int32, an output that overlaps a face array. */
 int omg_face_divergence(const int64_t *shape, const double *fz, const double *fy, const double *fx, int faces_on_device,
                         double *out, int out_on_device);
+/* ---- the 7-point operator of one coefficient per FACE ----------------------------------------------------
+ * For callers that hold their coefficients on the faces (a MAC grid's 1 / rho, orthotropic media, metric factors): cz, cy, cx
+ * are (nz + 1) ny nx, nz (ny + 1) nx and nz ny (nx + 1) doubles in C order — the face arrays omg_kappa_flux writes and
+ * omg_face_divergence reads —, all three in host memory or — faces_on_device != 0 — all in HBM.  Along an axis of extent e,
+ * face m lies between cell m - 1 and cell m.  The coefficients carry every factor: there is no scale and there are no widths.
+ *   an in-grid face, m = 1 .. e - 1: A[lo, hi] = A[hi, lo] = -C[m].
+ *   a Dirichlet wall: C[0] and C[e] enter the diagonal of the cell at the wall only.
+ *   a Neumann wall: its face contributes +0.0 and its entry of C is never read (it may hold NaN).
+ *   a periodic axis (both walls, extent >= 3): the seam's coefficient is C[0]; C[e] is never read.
+ *   diagonal (((((c-K + c-J) + c-I) + c+I) + c+J) + c+K), then + sigma (no volume factor), every operation rounded once.
+ * walls, sigma, the outputs and the pattern are omg_kappa_assemble's; the result is operators.stencil7_faces' matrix bit for bit.
+ * A coefficient on a face that is read which is not finite and > 0, a sigma that is not finite and >= 0: OMG_ERR_INVALID
+ * naming ONE offender — of the arrays in the order Cz, Cy, Cx, sigma the first that has one, and in it the smallest flat
+ * index, as face (k, j, i) of that array's own shape (sigma: the cell) —; nothing faults, the next call works. */
+int omg_faces_assemble(const int64_t *shape, const double *cz, const double *cy, const double *cx, int faces_on_device, const int *walls,
+                       const double *sigma, int sigma_kind, int sigma_on_device, int32_t *indptr, int32_t *indices, double *data,
+                       int out_on_device);
+/* omg_hierarchy_create_from_kappa's sequence with that assembly: level 0 is assembled in HBM, the rest is
+ * omg_hierarchy_create_from_fine_opt's own — the object it builds from operators.stencil7_faces' matrix, bit for bit (one
+ * download of level 0 for OMG_DTYPE_MIXED; periodic walls and levels that do not qualify: the ordinary route). */
+int omg_hierarchy_create_from_faces(const int64_t *shape, const double *cz, const double *cy, const double *cx, int faces_on_device,
+                                    const int *walls, const double *sigma, int sigma_kind, int sigma_on_device, int n_restrictions,
+                                    const omg_hierarchy_options *opt, omg_hierarchy **out);
+/* omg_hierarchy_update_kappa with that assembly: the values go into the same array the hierarchy holds in HBM and take
+ * omg_hierarchy_update_fine's device path.  The same hierarchies (omg_hierarchy_can_update_fine, level 0 the 7-point
+ * operator on `shape`, no periodic wall); any other, and a refused coefficient or sigma: OMG_ERR_INVALID, the hierarchy as before. */
+int omg_hierarchy_update_faces(omg_hierarchy *h, const int64_t *shape, const double *cz, const double *cy, const double *cx,
+                               int faces_on_device, const int *walls, const double *sigma, int sigma_kind, int sigma_on_device);
+/* The right-hand side that goes with that operator (operators.rhs_faces' bits): b = ((((((f + t-K) + t-J) + t-I) + t+I) +
+ * t+J) + t+K).  A Dirichlet wall with the value g gives the cell at it C_wall g (C[0] or C[e]); a Neumann wall's value is the
+ * OUTWARD flux through the face already integrated over it, t = value with no factor; an in-grid face and a wall without a
+ * value give +0.0.  f, the values and b as omg_kappa_rhs takes them.  Only the cells at a Dirichlet wall with a value read a
+ * coefficient; the arrays may be NULL where there is none.  The coefficients are NOT validated here. */
+int omg_faces_rhs(const int64_t *shape, const double *cz, const double *cy, const double *cx, int faces_on_device, const int *walls,
+                  const double *f, int f_kind, int f_on_device, const int *value_kinds, const double *value_scalars,
+                  const double *const *value_fields, int values_on_device, double *b, int b_on_device);
+/* The face fluxes of u under that operator (operators.flux_faces' bits), omg_kappa_flux's outputs, alpha and mapping:
+ *   an in-grid face F[m] = C[m] (u_lo - u_hi); a periodic axis F[0] = F[e] = C[0] (u_{e-1} - u_0);
+ *   a Dirichlet wall F[0] = C[0] (g - u_0), F[e] = C[e] (u_{e-1} - g), g = +0.0 without a value;
+ *   a Neumann wall +0.0 without a value and nothing read, else F[0] = value, F[e] = -value.
+ * One subtraction and one multiplication per face; with alpha out = out + alpha F, one multiplication and one addition.
+ * omg_face_divergence(F) + sigma u = A u - omg_faces_rhs(f = NULL, the same values) up to rounding.
+ * OMG_ERR_INVALID: what omg_faces_rhs refuses; a NULL array; alpha not finite; an output that overlaps u, a coefficient
+ * array or another output. */
+int omg_faces_flux(const int64_t *shape, const double *cz, const double *cy, const double *cx, int faces_on_device, const int *walls,
+                   const double *u, int u_on_device, const int *value_kinds, const double *value_scalars,
+                   const double *const *value_fields, int values_on_device, const double *alpha, double *fz, double *fy, double *fx,
+                   int out_on_device);
 int omg_hierarchy_dtype(const omg_hierarchy *h, int *dtype);
 int omg_hierarchy_destroy(omg_hierarchy *h);
 /* Run on a caller-owned hipStream_t instead of the hierarchy's own stream (NULL = own). */

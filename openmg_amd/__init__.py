@@ -330,7 +330,8 @@ def _setup(A_in, parameters, completed_from):
     coarsening = _coarsening_of(parameters)
     # (Solver.from_kappa: A_in is the coefficient field's arguments; the plain device route below assembles level 0 in HBM,
     # every other route gets the operator assembled on the device into host arrays and runs as for any A_in)
-    kappa = A_in if isinstance(A_in, _hip.KappaArgs) else None
+    # (Solver.from_faces: the same with the face coefficients' arguments)
+    kappa = A_in if isinstance(A_in, (_hip.KappaArgs, _hip.FaceArgs)) else None
     if coarsening is not None:
         A_in = A_in if kappa is None else kappa.matrix()
         return _setup_semicoarsened(A_in, parameters, coarsening, code, omega, nullspace) + (accel, shape, alpha)
@@ -346,7 +347,8 @@ def _setup(A_in, parameters, completed_from):
         R = A = None
         parameters["coarsestLevel"] = n_fused
         if kappa is not None:
-            hierarchy = _hip.Hierarchy.from_kappa(kappa, n_fused, smoother=code, omega=omega, dtype=_dtype_of(parameters), nullspace=nullspace)
+            from_field = _hip.Hierarchy.from_faces if isinstance(kappa, _hip.FaceArgs) else _hip.Hierarchy.from_kappa
+            hierarchy = from_field(kappa, n_fused, smoother=code, omega=omega, dtype=_dtype_of(parameters), nullspace=nullspace)
         else:
             hierarchy = _hip.Hierarchy.from_fine(A_in, problemShape, n_fused, smoother=code, omega=omega, dtype=_dtype_of(parameters),
                                                  nullspace=nullspace)
@@ -504,7 +506,7 @@ def _device_setup_depth(A_in, problemShape, parameters):
     reference raises)."""
     if parameters.get("giveInfo") or parameters.get("dense") or parameters.get("verbose"):
         return 0
-    if not (sp.issparse(A_in) or isinstance(A_in, _hip.KappaArgs)):        # (KappaArgs.shape: the operator's, as a matrix has it)
+    if not (sp.issparse(A_in) or isinstance(A_in, (_hip.KappaArgs, _hip.FaceArgs))):        # (their .shape: the operator's, as a matrix has it)
         return 0
     try:
         shape = tuple(int(s) for s in problemShape)

@@ -85,6 +85,11 @@ SIGNATURES = {
     "omg_kappa_flux": (_I, [_I64P, _P, _I, _IP, _DP, _P, _I, _IP, _DP, _PP, _I, _DP, _P, _P, _P, _I]),
     "omg_kappa_flux_spaced": (_I, [_I64P, _P, _I, _IP, _DP, _P, _P, _P, _P, _I, _IP, _DP, _PP, _I, _DP, _P, _P, _P, _I]),
     "omg_face_divergence": (_I, [_I64P, _P, _P, _P, _I, _P, _I]),
+    "omg_faces_assemble": (_I, [_I64P, _P, _P, _P, _I, _IP, _P, _I, _I, _P, _P, _P, _I]),
+    "omg_hierarchy_create_from_faces": (_I, [_I64P, _P, _P, _P, _I, _IP, _P, _I, _I, _I, _OPT, _PP]),
+    "omg_hierarchy_update_faces": (_I, [_P, _I64P, _P, _P, _P, _I, _IP, _P, _I, _I]),
+    "omg_faces_rhs": (_I, [_I64P, _P, _P, _P, _I, _IP, _P, _I, _I, _IP, _DP, _PP, _I, _P, _I]),
+    "omg_faces_flux": (_I, [_I64P, _P, _P, _P, _I, _IP, _P, _I, _IP, _DP, _PP, _I, _DP, _P, _P, _P, _I]),
     "omg_resident_norms": (_I, [_P, _DP, _DP]),
     "omg_resident_projection": (_I, [_P, _I]),
     "omg_resident_project": (_I, [_P, _IP]),
@@ -768,6 +773,232 @@ def face_divergence(faces, out=None):
     return d
 
 
+class FaceArgs:
+    """KappaArgs' twin for one coefficient per face: the arguments of omg_faces_assemble / omg_hierarchy_create_from_faces /
+    omg_hierarchy_update_faces from what the Python entries take.  faces = (Cz, Cy, Cx): three float64 arrays in the face
+    shapes of one grid (operators.face_shapes), all NumPy arrays or all C-contiguous device arrays; walls and sigma as
+    operators.stencil7_faces takes them, sigma a device array too.  ValueError for what operators.faces_arguments refuses,
+    another count, dtype or size, arrays on both sides — before any device work; the coefficients' values are checked by the
+    kernel that reads them (HipError, ERR_INVALID, naming the face).  .grid: problemShape; .shape: the operator's (n, n);
+    .walls: the six codes; .periodic: per axis; .nnz; .counts: the entries of the three arrays; .faces_on_device; .pointers;
+    .head: the C arguments from `shape` to `walls`; .call: those and sigma's; the object keeps the arrays alive."""
+
+    def __init__(self, faces, walls=None, sigma=None):
+        from . import _devarray, operators
+        if isinstance(faces, FaceArgs):            # (already checked: Hierarchy.from_faces / update_faces take one as it is)
+            self.__dict__.update(faces.__dict__)
+            return
+        try:
+            faces = tuple(faces)
+        except TypeError:
+            raise ValueError("faces must be three coefficient arrays (Cz, Cy, Cx), not %r" % (faces,))
+        if len(faces) != 3:
+            raise ValueError("faces must be three coefficient arrays (Cz, Cy, Cx), not %d" % len(faces))
+        f_dev = _devarray.is_device_array(faces[0])
+        if any(_devarray.is_device_array(a) != f_dev for a in faces):
+            raise ValueError("the face coefficients must all be device arrays or all host arrays")
+        if f_dev:
+            shapes = tuple(tuple(int(s) for s in a.__cuda_array_interface__["shape"]) for a in faces)
+        else:
+            faces = tuple(np.asarray(a) for a in faces)
+            for name, a in zip(("Cz", "Cy", "Cx"), faces):
+                if a.dtype != np.float64:
+                    raise ValueError("the face coefficients %s must be float64, not %s" % (name, a.dtype))
+            faces = tuple(np.ascontiguousarray(a) for a in faces)
+            shapes = tuple(a.shape for a in faces)
+        self.grid, self.walls = operators.faces_arguments(shapes, walls, sigma)
+        self.n = int(np.prod(self.grid))
+        self.shape = (self.n, self.n)
+        self.periodic = operators.periodic_axes(self.walls)
+        self.nnz = 7 * self.n - 2 * sum(self.n // e for e, wraps in zip(self.grid, self.periodic) if not wraps)
+        self.counts = [int(np.prod(s)) for s in shapes]
+        if 7 * self.n >= 2 ** 31 - 1 or max(self.counts) >= 2 ** 31 - 1:
+            raise ValueError("operator too large for int32 indices; shard it first")
+        if f_dev:
+            try:
+                self.pointers = [_devarray.address(a, c, name) for a, c, name in zip(faces, self.counts, ("Cz", "Cy", "Cx"))]
+            except TypeError as e:
+                raise ValueError(str(e))
+        else:
+            self.pointers = [a.ctypes.data for a in faces]
+        s_dev = _devarray.is_device_array(sigma)
+        if sigma is None:
+            kind, s_ptr = SIGMA_NONE, None
+        elif s_dev:
+            kind, s_ptr = SIGMA_FIELD, _devarray.address(sigma, self.n, "sigma")
+        elif np.ndim(sigma) == 0:
+            sigma = np.array([float(sigma)], dtype=np.float64)
+            kind, s_ptr = SIGMA_SCALAR, sigma.ctypes.data
+        else:
+            sigma = np.ascontiguousarray(sigma, dtype=np.float64)
+            kind, s_ptr = SIGMA_FIELD, sigma.ctypes.data
+        self.faces = faces
+        self.faces_on_device = f_dev
+        self.on_device = f_dev or s_dev
+        self._keep = (faces, sigma)
+        self.head = ((ctypes.c_int64 * 3)(*self.grid), *(ctypes.c_void_p(p) for p in self.pointers), int(f_dev), (ctypes.c_int * 6)(*self.walls))
+        self.call = self.head + (ctypes.c_void_p(s_ptr), kind, int(s_dev))
+
+    def matrix(self):
+        """The operator as a SciPy CSR in host memory, assembled on the device (faces_assemble)."""
+        indptr, indices, data = faces_assemble(self)
+        A = sp.csr_matrix((data, indices, indptr), shape=self.shape)
+        A.has_sorted_indices = True
+        return A
+
+    def synchronize(self):
+        """What the caller's library enqueued on the device arrays is complete before the library's own stream reads them."""
+        if self.on_device:
+            check(lib().omg_device_synchronize())
+
+
+def faces_assemble(faces, walls=None, sigma=None, pattern=True, out=None):
+    """The 7-point operator of one coefficient per face, assembled on the device (omg_faces_assemble): the CSR arrays of
+    operators.stencil7_faces(faces, walls, sigma), bit for bit.  faces: three NumPy arrays or three device arrays; sigma
+    either.  Returns (indptr, indices, data) as NumPy arrays, indptr = indices = None with pattern=False; out = (indptr,
+    indices, data): device arrays to write into instead, as kappa_assemble takes them."""
+    from . import _devarray
+    a = FaceArgs(faces, walls, sigma)
+    if out is not None:
+        d_indptr, d_indices, d_data = out
+        if (d_indptr is None) != (d_indices is None):
+            raise ValueError("out: indptr and indices are given together or not at all")
+
+        def int32_address(arr, count, what):
+            iface = arr.__cuda_array_interface__
+            if iface["typestr"] not in ("<i4", "=i4", "|i4") or iface.get("strides") is not None or tuple(iface["shape"]) != (count,):
+                raise ValueError("out: %s must be a contiguous int32 device array of %d entries" % (what, count))
+            return int(iface["data"][0])
+        p_indptr = None if d_indptr is None else int32_address(d_indptr, a.n + 1, "indptr")
+        p_indices = None if d_indices is None else int32_address(d_indices, a.nnz, "indices")
+        p_data = _devarray.address(d_data, a.nnz, "out: data")
+        check(lib().omg_device_synchronize())
+        check(lib().omg_faces_assemble(*a.call, ctypes.c_void_p(p_indptr), ctypes.c_void_p(p_indices), ctypes.c_void_p(p_data), 1))
+        return out
+    data = np.empty(a.nnz, dtype=np.float64)
+    indptr = np.empty(a.n + 1, dtype=np.int32) if pattern else None
+    indices = np.empty(a.nnz, dtype=np.int32) if pattern else None
+    a.synchronize()
+    check(lib().omg_faces_assemble(*a.call, indptr.ctypes.data if pattern else None, indices.ctypes.data if pattern else None,
+                                   data.ctypes.data, 0))
+    return indptr, indices, data
+
+
+def _face_wall_values(what, a, values, named):
+    """The boundary values of faces_rhs / faces_flux for the FaceArgs a — checked (operators.wall_values_arguments), on the
+    coefficients' side like the arrays among `named` = [(name, array or float or None)] — as the C arguments (kinds, scalars,
+    field pointers, their side) and the list of arrays to keep alive."""
+    from . import _devarray, operators
+    values = operators.wall_values_arguments(a.grid, a.walls, values)
+    dev = a.faces_on_device
+    for name, v in list(named) + [("values[%d]" % w, v) for w, v in enumerate(values)]:
+        if v is not None and not isinstance(v, float) and _devarray.is_device_array(v) != dev:
+            raise ValueError("%s: the coefficients, %s and the value fields must all be device arrays or all host arrays; %s is not on "
+                             "the coefficients' side" % (what, named[0][0], name))
+    kinds, scalars, fields, keep = [VALUE_NONE] * 6, [0.0] * 6, [None] * 6, []
+    for w, v in enumerate(values):
+        if v is None:
+            continue
+        if isinstance(v, float):
+            kinds[w], scalars[w] = VALUE_SCALAR, v
+            continue
+        count = int(np.prod([a.grid[axis] for axis in operators.WALL_FACES[w]]))
+        kinds[w], fields[w] = VALUE_FIELD, _side_pointer(dev, v, count, "values[%d]" % w, keep)
+    return ((ctypes.c_int * 6)(*kinds), (ctypes.c_double * 6)(*scalars), (ctypes.c_void_p * 6)(*fields), int(dev)), keep
+
+
+def _side_pointer(on_device, v, count, name, keep):
+    """The address of a float64 array of `count` entries on the given side; a host array is made contiguous and kept."""
+    from . import _devarray
+    if on_device:
+        try:
+            return _devarray.address(v, count, name)
+        except TypeError as e:
+            raise ValueError(str(e))
+    v = np.ascontiguousarray(v, dtype=np.float64)
+    keep.append(v)
+    return v.ctypes.data
+
+
+def faces_rhs(faces, f=None, walls=None, values=None, out=None):
+    """operators.rhs_faces(faces, f, walls, values) made on the device (omg_faces_rhs), bit for bit: the right-hand side that
+    goes with the operator of faces_assemble / Hierarchy.from_faces.  faces (or a FaceArgs), f and the fields among `values`:
+    NumPy arrays or all device arrays; out as kappa_rhs takes it (a device `out` may be f: in place).  Returns b in
+    problemShape (a given `out` as it is).  The coefficients' values are not checked here.  ValueError — before any device
+    work — for what operators.rhs_faces refuses, arrays on both sides, an `out` of the wrong size or side."""
+    from . import _devarray, operators
+    a = FaceArgs(faces, walls)
+    f = operators.source_argument(a.grid, f)
+    wall_values, keep = _face_wall_values("faces_rhs", a, values, [("f", f)])
+    dev, n, grid = a.faces_on_device, a.n, a.grid
+    if out is not None and _devarray.is_device_array(out) != dev:
+        raise ValueError("faces_rhs: `out` must be a device array exactly when the coefficients and f are device arrays")
+    if f is None:
+        f_kind, f_ptr = VALUE_NONE, None
+    elif isinstance(f, float):
+        keep.append(np.array([f], dtype=np.float64))
+        f_kind, f_ptr = VALUE_SCALAR, keep[-1].ctypes.data
+    else:
+        f_kind, f_ptr = VALUE_FIELD, _side_pointer(dev, f, n, "f", keep)
+    if dev:
+        b = _devarray.empty_like(a.faces[0], n).reshape(grid) if out is None else out
+        try:
+            b_ptr = _devarray.address(b, n, "out")
+        except TypeError as e:
+            raise ValueError(str(e))
+        check(lib().omg_device_synchronize())
+    else:
+        if out is None:
+            b = np.empty(grid, dtype=np.float64)
+        elif isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous and out.flags.writeable and out.size == n:
+            b = out
+        else:
+            raise ValueError("out must be a writeable contiguous float64 array of %d entries" % n)
+        b_ptr = b.ctypes.data
+    check(lib().omg_faces_rhs(*a.head, ctypes.c_void_p(f_ptr), f_kind, int(dev and f_kind == VALUE_FIELD), *wall_values,
+                              ctypes.c_void_p(b_ptr), int(dev)))
+    return b
+
+
+def faces_flux(faces, u, walls=None, values=None, out=None, alpha=None):
+    """operators.flux_faces(faces, u, walls, values) made on the device (omg_faces_flux), bit for bit, in one launch: F = C
+    (u_lo - u_hi) on every face with the boundary data `values` of faces_rhs.  faces (or a FaceArgs), u and the value fields:
+    NumPy arrays or all device arrays; out, alpha as kappa_flux takes them (alpha needs `out`: out = out + alpha * F).
+    Returns the three arrays in face shape.  ValueError — before any device work — for what operators.flux_faces refuses,
+    arrays on both sides, outputs of the wrong size or side, alpha without `out` or not finite, an `out` that overlaps u, a
+    coefficient array or another output."""
+    from . import operators
+    a = FaceArgs(faces, walls)
+    u = operators.solution_argument(a.grid, u)
+    dev, n, grid = a.faces_on_device, a.n, a.grid
+    shapes = operators.face_shapes(grid)
+    if alpha is not None:
+        if out is None:
+            raise ValueError("faces_flux: alpha needs `out`, the arrays alpha * F is added to")
+        try:
+            alpha = float(alpha)
+        except (TypeError, ValueError):
+            raise ValueError("faces_flux: alpha must be None or a finite number, not %r" % (alpha,))
+        if not np.isfinite(alpha):
+            raise ValueError("faces_flux: alpha must be finite, not %r" % alpha)
+    wall_values, keep = _face_wall_values("faces_flux", a, values, [("u", u)])
+    u_ptr = _side_pointer(dev, u, n, "u", keep)
+    faces_out, f_ptrs = _face_outputs("faces_flux", out, a.counts, shapes, dev, a.faces[0])
+    spans = [(p, 8 * count) for p, count in zip(f_ptrs, a.counts)]
+    inputs = [(u_ptr, 8 * n)] + [(p, 8 * count) for p, count in zip(a.pointers, a.counts)]
+    for d, span in enumerate(spans):
+        if any(_share_bytes(span, other) for other in inputs):
+            raise ValueError("faces_flux: the face array %s of `out` overlaps u or a coefficient array: the fluxes cannot be made in place" % "zyx"[d])
+        if any(_share_bytes(span, other) for other in spans[:d]):
+            raise ValueError("faces_flux: the face arrays of `out` overlap each other")
+    if dev:
+        check(lib().omg_device_synchronize())
+    check(lib().omg_faces_flux(*a.head, ctypes.c_void_p(u_ptr), int(dev), *wall_values,
+                               None if alpha is None else ctypes.byref(ctypes.c_double(alpha)),
+                               *(ctypes.c_void_p(p) for p in f_ptrs), int(dev)))
+    return faces_out
+
+
 class Hierarchy:
     """Device-resident A/R hierarchy (omg_hierarchy)."""
 
@@ -921,6 +1152,30 @@ class Hierarchy:
         a = KappaArgs(kappa, walls, sigma, scale, spacing)
         a.synchronize()
         check(lib().omg_hierarchy_update_kappa_spaced(self._h, *a.call))
+
+    @classmethod
+    def from_faces(cls, faces, n_restrictions, walls=None, sigma=None, smoother="gs", omega=1.0, dtype="float64", nullspace=None):
+        """from_fine of operators.stencil7_faces(faces, walls, sigma) without that matrix ever being on the host
+        (omg_hierarchy_create_from_faces): level 0 is assembled in HBM from the three face arrays — NumPy arrays or device
+        arrays —, the rest is from_fine's own sequence, the result the same object bit for bit (with periodic walls: the
+        ordinary route's, as from_kappa)."""
+        self = cls._blank(nullspace)
+        a = FaceArgs(faces, walls, sigma)
+        opt, h = self._options(smoother, omega, dtype)
+        self.n_levels = int(n_restrictions) + 1
+        self.sizes = [a.n // 8 ** l for l in range(self.n_levels)]
+        a.synchronize()
+        check(lib().omg_hierarchy_create_from_faces(*a.call, int(n_restrictions), ctypes.byref(opt), ctypes.byref(h)))
+        self._adopt(h)
+        return self
+
+    def update_faces(self, faces, walls=None, sigma=None):
+        """update_fine with the values of operators.stencil7_faces(faces, walls, sigma), made on the device
+        (omg_hierarchy_update_faces): with device arrays nothing crosses to the host.  Takes the hierarchies update_kappa
+        takes (HipError ERR_INVALID otherwise, and for a coefficient or sigma out of range; the hierarchy is then as before)."""
+        a = FaceArgs(faces, walls, sigma)
+        a.synchronize()
+        check(lib().omg_hierarchy_update_faces(self._h, *a.call))
 
     def can_update_fine(self):
         """Whether update_fine takes this hierarchy (omg_hierarchy_can_update_fine)."""

@@ -9,6 +9,8 @@
     b = s.rhs(kappa, f=None, values=None)       # ... and its right-hand side: source, boundary values, fluxes (operators.rhs_kappa)
     Fz, Fy, Fx = s.fluxes(kappa, u, values=None, out=None, alpha=None)     # the face fluxes of a solution (operators.flux_kappa)
     d = s.divergence((Fz, Fy, Fx), out=None)    # ... and the cell balance of face arrays (operators.divergence_faces)
+    s = openmg_amd.Solver.from_faces((Cz, Cy, Cx), parameters, walls, sigma)    # the same line from one coefficient per FACE
+    s.update_faces((Cz, Cy, Cx), sigma=None)    # ... (operators.stencil7_faces); rhs and fluxes then take the three arrays
     y = s.matvec(x, out=None)                   # y = A x on the operator as the hierarchy holds it (b - A u where u lives)
     s = openmg_amd.Solver(A_in, parameters, projection=8)       # every solve starts from its projection onto up to 8 earlier
     x0 = s.project(b); s.projection_size; s.projection_basis(); s.projection_clear()      # ... solutions kept in HBM
@@ -156,8 +158,40 @@ class Solver:
         self._kappa = (source.grid, walls, scale, source.spacing)
         return self
 
+    _faces = None              # from_faces: (problemShape, walls) of construction, else None
+
+    @classmethod
+    def from_faces(cls, faces, parameters, walls=None, sigma=None, *, projection=0):
+        """The Solver of operators.stencil7_faces(faces, walls, sigma) — same bits — from one coefficient per FACE: faces =
+        (Cz, Cy, Cx), float64 arrays of the shapes operators.face_shapes(problemShape) — the arrays fluxes() writes and
+        divergence() reads —, all NumPy arrays or all device arrays; sigma None, a scalar or an array of problemShape.  For
+        callers whose coefficients live on the faces: a MAC grid's 1 / rho from face fractions or an arithmetic mean,
+        orthotropic media (another field per axis), metric factors.  The coefficients carry every factor (the face area over
+        the distance, the time step): there is no scale and no spacing.  A Neumann wall's faces and face e of a periodic axis
+        are never read.  parameters['problemShape'] is taken from the arrays; if given it must agree.  The routes are
+        from_kappa's: on the plain device route level 0 is assembled in HBM and no host matrix is ever made, with any other
+        parameters the operator is assembled on the device into host arrays and the setup runs as for any A_in; periodic
+        walls give the ordinary route's hierarchy, and 'smoother': 'line' and 'coarsening': 'auto' raise HipError
+        (ERR_UNSUPPORTED) on a periodic operator.  ValueError for bad arguments before any device work; a coefficient that is
+        read and is not finite and > 0 (zero, a blocked face, included) or a sigma value out of range: HipError (ERR_INVALID)
+        naming the face."""
+        _projection_of(projection)
+        source = _hip.FaceArgs(faces, walls, sigma)
+        given = dict(parameters)
+        if given.get("problemShape") is not None:
+            try:
+                same = tuple(int(s) for s in given["problemShape"]) == source.grid
+            except TypeError:
+                same = False
+            if not same:
+                raise ValueError("parameters['problemShape'] = %r is not the face arrays' grid %r" % (given["problemShape"], source.grid))
+        given["problemShape"] = source.grid
+        self = cls(source, given, projection=projection)
+        self._faces = (source.grid, walls)
+        return self
+
     def _pattern_of(self, A_in):
-        if isinstance(A_in, _hip.KappaArgs):
+        if isinstance(A_in, (_hip.KappaArgs, _hip.FaceArgs)):
             # (the in-grid 7-point pattern: formed on the host when update(A_new) first asks for it)
             self._shape, self._indptr, self._indices = A_in.shape, None, None
             return
@@ -401,10 +435,17 @@ class Solver:
         Nothing is projected here.  With parameters['nullspace'] = 'constant' (every wall Neumann or periodic, no sigma)
         solve() projects b; the problem itself has a solution only if the data are compatible, sum(b) = 0 — the integral
         of f over the box plus the fluxes into it through the Neumann walls vanish —, which the caller's f and fluxes
-        should meet: what solve() removes otherwise is the part of the data no u can answer."""
+        should meet: what solve() removes otherwise is the part of the data no u can answer.
+
+        On a Solver made by from_faces `kappa` is the three coefficient arrays (Cz, Cy, Cx) and b has the bits of
+        operators.rhs_faces(faces, f, walls, values): a Dirichlet value enters with the wall face's coefficient, a Neumann
+        value is the outward flux through the face already integrated over it and enters with no factor."""
         self._open()
+        if self._faces is not None:
+            b = _hip.faces_rhs(self._own_faces("rhs", kappa), f, self._faces[1], values, out)
+            return b.reshape(-1) if out is None else b
         if self._kappa is None:
-            raise ValueError("Solver.rhs: the solver was not made by Solver.from_kappa")
+            raise ValueError("Solver.rhs: the solver was not made by Solver.from_kappa or Solver.from_faces")
         grid, walls, scale, spacing = self._kappa
         k_shape = tuple(int(s) for s in (kappa.__cuda_array_interface__["shape"] if _devarray.is_device_array(kappa) else np.shape(kappa)))
         if k_shape != tuple(s + 2 for s in grid):
@@ -426,10 +467,16 @@ class Solver:
         fields are NumPy arrays or all device arrays.  out: three arrays to write into, on the same side; alpha (needs
         out): out = out + alpha * F — the velocity correction of a projection step is fluxes(kappa, p, out=W, alpha=-1.0).
         An `out` that overlaps u or kappa is refused.  Nothing is projected, a resident solve is not disturbed and the
-        hierarchy is not touched."""
+        hierarchy is not touched.
+
+        On a Solver made by from_faces `kappa` is the three coefficient arrays (Cz, Cy, Cx) and the result has the bits of
+        operators.flux_faces(faces, u, walls, values) — F = C (u_lo - u_hi), the coefficient loaded from the face's own
+        place; an `out` that overlaps one of them is refused."""
         self._open()
+        if self._faces is not None:
+            return _hip.faces_flux(self._own_faces("fluxes", kappa), u, self._faces[1], values, out, alpha)
         if self._kappa is None:
-            raise ValueError("Solver.fluxes: the solver was not made by Solver.from_kappa")
+            raise ValueError("Solver.fluxes: the solver was not made by Solver.from_kappa or Solver.from_faces")
         grid, walls, scale, spacing = self._kappa
         k_shape = tuple(int(s) for s in (kappa.__cuda_array_interface__["shape"] if _devarray.is_device_array(kappa) else np.shape(kappa)))
         if k_shape != tuple(s + 2 for s in grid):
@@ -439,13 +486,13 @@ class Solver:
     def divergence(self, faces, out=None):
         """The cell balance of three face arrays (Fz, Fy, Fx) of the solver's grid, operators.divergence_faces — same bits —
         made on the device: ((Fz[k+1] - Fz[k]) + (Fy[j+1] - Fy[j])) + (Fx[i+1] - Fx[i]) per cell.  For a Solver made by
-        from_kappa (ValueError otherwise); the arrays are NumPy arrays or all device arrays, `out` an array of n entries on
+        from_kappa or from_faces (ValueError otherwise); the arrays are NumPy arrays or all device arrays, `out` an array of n entries on
         their side.  Returns the balance flattened to n entries in the solver's numbering, ready for solve() — the
         right-hand side of a projection step is divergence(W) of the face velocities times area."""
         self._open()
-        if self._kappa is None:
-            raise ValueError("Solver.divergence: the solver was not made by Solver.from_kappa")
-        grid = tuple(self._kappa[0])
+        if self._kappa is None and self._faces is None:
+            raise ValueError("Solver.divergence: the solver was not made by Solver.from_kappa or Solver.from_faces")
+        grid = tuple((self._kappa or self._faces)[0])
         from . import operators
         try:
             shapes = tuple(tuple(int(s) for s in (a.__cuda_array_interface__["shape"] if _devarray.is_device_array(a) else np.shape(a)))
@@ -470,9 +517,9 @@ class Solver:
         A1 = _hip.as_csr(A_new)
         if self._indptr is None:
             from . import operators
-            grid, walls = self._kappa[:2]
+            grid, walls = (self._kappa or self._faces)[:2]
             if walls is not None and "periodic" in tuple(walls):
-                # (the pattern with the wrapped columns: the definition's own, of a field of ones)
+                # (the pattern with the wrapped columns: the definition's own, of a field of ones; from_faces has the same)
                 P = operators.stencil7_kappa(np.ones(tuple(s + 2 for s in grid)), walls)
             else:
                 P = operators.stencil_poisson(grid)
@@ -505,6 +552,38 @@ class Solver:
                 raise
         self._hierarchy, self.R, self.A, self._basis = fresh, R, A, 0
         h.close()
+
+    def _own_faces(self, what, faces):
+        """`faces` checked as three arrays in the face shapes of the solver's grid (a from_faces solver), as a tuple."""
+        from . import operators
+        grid = self._faces[0]
+        try:
+            faces = tuple(faces)
+            shapes = tuple(tuple(int(s) for s in (a.__cuda_array_interface__["shape"] if _devarray.is_device_array(a) else np.shape(a)))
+                           for a in faces)
+        except TypeError:
+            raise ValueError("Solver.%s: on a solver made by Solver.from_faces the coefficients are three face arrays (Cz, Cy, Cx)" % what)
+        if shapes != operators.face_shapes(grid):
+            raise ValueError("Solver.%s: the coefficient arrays' shapes %r are not the face shapes of the solver's grid %r" % (what, shapes, grid))
+        return faces
+
+    def update_faces(self, faces, sigma=None):
+        """update() with the operator of new face coefficients (and sigma), for a Solver made by from_faces (ValueError
+        otherwise); the walls are those of construction.  Where the hierarchy takes new coefficients in place the values are
+        made on the device and go straight into update_fine — with device arrays nothing crosses to the host; otherwise
+        (periodic walls, 'coarsening', ...) the operator is assembled into host arrays and a new hierarchy built as update()
+        does.  Either way later solves have the bits of a fresh Solver.from_faces(faces, parameters, ...), and the
+        projection set is emptied.  Refused coefficients leave the solver with the old operator."""
+        h = self._open()
+        if self._faces is None:
+            raise ValueError("Solver.update_faces: the solver was not made by Solver.from_faces")
+        grid, walls = self._faces
+        source = _hip.FaceArgs(self._own_faces("update_faces", faces), walls, sigma)
+        if h.can_update_fine():
+            self._basis = 0
+            h.update_faces(source)
+            return
+        self._rebuild(source)
 
     def update_kappa(self, kappa, sigma=None):
         """update() with the operator of a new coefficient field (and sigma), for a Solver made by from_kappa; walls,

@@ -937,6 +937,69 @@ void kappa_flux(const KappaFluxInput &in);
 // out = the cell balance of the three face arrays (n doubles); out overlaps none of them
 void face_divergence(const int64_t *shape, const double *fz, const double *fy, const double *fx, int faces_on_device, double *out,
                      int out_on_device);
+// The 7-point operator of one coefficient per face (kappa.hip): KappaField's twin.  cz, cy, cx: the face
+// arrays (nz + 1) ny nx, nz (ny + 1) nx, nz ny (nx + 1), all in host memory or all in HBM; walls may be null (all Dirichlet).
+struct FacesInput {
+    const int64_t *shape;
+    const double *cz, *cy, *cx;
+    int faces_on_device;
+    const int *walls;
+    const double *sigma;
+    int sigma_kind, sigma_on_device;
+};
+struct FaceField {
+    int nx = 0, ny = 0, nz = 0;
+    const double *c_dev[3] = {nullptr, nullptr, nullptr};      // Cz, Cy, Cx in HBM
+    const double *sigma_dev = nullptr;
+    double sigma_value = 0.0;
+    int sigma_kind = 0;
+    int neumann[6] = {0, 0, 0, 0, 0, 0};
+    int periodic[3] = {0, 0, 0};     // z, y, x
+    bool any_periodic() const { return periodic[0] || periodic[1] || periodic[2]; }
+    DevBuf<double> own_faces, own_sigma;
+    DevBuf<unsigned long long> err;
+    void prepare(const FacesInput &in, hipStream_t s);
+    int64_t rows() const { return int64_t(nx) * ny * nz; }
+    int64_t nnz() const;
+    // as KappaField's; a read coefficient that is not finite and > 0 or a sigma that is not finite and >= 0: OMG_ERR_INVALID
+    // naming one offender — the first array in the order Cz, Cy, Cx, sigma that has one, its smallest flat index
+    void values(double *data, hipStream_t s, const char *entry);
+    void assemble(int32_t *indptr, int32_t *indices, double *data, hipStream_t s, const char *entry);
+    void assemble(DevCsrPlain &A, hipStream_t s, const char *entry);
+};
+// what the callers of omg_faces_rhs and omg_faces_flux name (KappaRhsInput's and KappaFluxInput's twins)
+struct FacesRhsInput {
+    const int64_t *shape;
+    const double *cz, *cy, *cx;
+    int faces_on_device;
+    const int *walls;
+    const double *f;
+    int f_kind, f_on_device;
+    const int *value_kinds;
+    const double *value_scalars;
+    const double *const *value_fields;
+    int values_on_device;
+    double *b;
+    int b_on_device;
+};
+void faces_rhs(const FacesRhsInput &in);
+struct FacesFluxInput {
+    const int64_t *shape;
+    const double *cz, *cy, *cx;
+    int faces_on_device;
+    const int *walls;
+    const double *u;
+    int u_on_device;
+    const int *value_kinds;
+    const double *value_scalars;
+    const double *const *value_fields;
+    int values_on_device;
+    const double *alpha;
+    double *fz, *fy, *fx;
+    int out_on_device;
+};
+// refuses an output that overlaps u, a coefficient array or another output
+void faces_flux(const FacesFluxInput &in);
 // The same chain with a factor (1 or 2) per axis and restriction instead of 2 everywhere (semicoarsening).
 // shape and every factor tuple are in the grid's C order (the last axis has unit stride).  factors: n_restrictions * dim
 // entries, or null = 'auto': per level the couplings kernel, semicoarsen_rule, the restriction kernel, the product.  Auto

@@ -3019,6 +3019,105 @@ int omg_hierarchy_update_kappa_spaced(omg_hierarchy *h, const int64_t *shape, co
     });
 }
 
+// ---- the same from one coefficient per face (FaceField, kappa.hip): the kappa entries' sequences with the other assembly
+int omg_faces_assemble(const int64_t *shape, const double *cz, const double *cy, const double *cx, int faces_on_device, const int *walls,
+                       const double *sigma, int sigma_kind, int sigma_on_device, int32_t *indptr, int32_t *indices, double *data,
+                       int out_on_device) {
+    return guarded([&] {
+        OMG_REQUIRE(data, "omg_faces_assemble: data is null");
+        OMG_REQUIRE(!indptr == !indices, "omg_faces_assemble: indptr and indices are given together or not at all");
+        OneShot one;
+        FaceField F;
+        F.prepare({shape, cz, cy, cx, faces_on_device, walls, sigma, sigma_kind, sigma_on_device}, one.s);
+        const size_t n = size_t(F.rows()), nnz = size_t(F.nnz());
+        DevBuf<double> dv;
+        DevBuf<int32_t> dp, di;
+        if (!out_on_device) {
+            dv.alloc(nnz);
+            if (indptr) { dp.alloc(n + 1); di.alloc(nnz); }
+        }
+        F.assemble(out_on_device ? indptr : dp.p, out_on_device ? indices : di.p, out_on_device ? data : dv.p, one.s, "omg_faces_assemble");
+        if (!out_on_device) {
+            if (indptr) {
+                download_staged(indptr, dp.p, (n + 1) * sizeof(int32_t), one.s);
+                download_staged(indices, di.p, nnz * sizeof(int32_t), one.s);
+            }
+            download_staged(data, dv.p, nnz * sizeof(double), one.s);
+        }
+        OMG_HIP(hipStreamSynchronize(one.s));
+    });
+}
+
+int omg_faces_rhs(const int64_t *shape, const double *cz, const double *cy, const double *cx, int faces_on_device, const int *walls,
+                  const double *f, int f_kind, int f_on_device, const int *value_kinds, const double *value_scalars,
+                  const double *const *value_fields, int values_on_device, double *b, int b_on_device) {
+    return guarded([&] {
+        require_device();
+        faces_rhs({shape, cz, cy, cx, faces_on_device, walls, f, f_kind, f_on_device, value_kinds, value_scalars, value_fields, values_on_device, b,
+                   b_on_device});
+    });
+}
+
+int omg_faces_flux(const int64_t *shape, const double *cz, const double *cy, const double *cx, int faces_on_device, const int *walls,
+                   const double *u, int u_on_device, const int *value_kinds, const double *value_scalars, const double *const *value_fields,
+                   int values_on_device, const double *alpha, double *fz, double *fy, double *fx, int out_on_device) {
+    return guarded([&] {
+        require_device();
+        faces_flux({shape, cz, cy, cx, faces_on_device, walls, u, u_on_device, value_kinds, value_scalars, value_fields, values_on_device, alpha, fz,
+                    fy, fx, out_on_device});
+    });
+}
+
+int omg_hierarchy_create_from_faces(const int64_t *shape, const double *cz, const double *cy, const double *cx, int faces_on_device,
+                                    const int *walls, const double *sigma, int sigma_kind, int sigma_on_device, int n_restrictions,
+                                    const omg_hierarchy_options *opt, omg_hierarchy **out) {
+    return guarded([&] {
+        HostCsr hostA0;
+        omg_csr fine = {};
+        create_handle(opt, out, &fine, [&](auto v, omg_hierarchy &) {
+            DevCsrPlain A0;
+            {
+                OneShot one;
+                FaceField F;
+                F.prepare({shape, cz, cy, cx, faces_on_device, walls, sigma, sigma_kind, sigma_on_device}, one.s);
+                SetupTimer tm("device setup: the fine operator from face coefficients");
+                F.assemble(A0, one.s, "omg_hierarchy_create_from_faces");
+                // (the fp64 outer operator of a mixed hierarchy is coded by the host, as in omg_hierarchy_create_from_kappa)
+                if (opt->dtype == OMG_DTYPE_MIXED) {
+                    hostA0 = download_csr(A0, one.s);
+                    fine = view(hostA0);
+                }
+            }
+            return create_from_fine<decltype(v)>(omg_csr(), 3, shape, n_restrictions, opt->smoother, opt->omega, opt->nullspace, &A0);
+        });
+    });
+}
+
+int omg_hierarchy_update_faces(omg_hierarchy *h, const int64_t *shape, const double *cz, const double *cy, const double *cx,
+                               int faces_on_device, const int *walls, const double *sigma, int sigma_kind, int sigma_on_device) {
+    return guarded([&] {
+        const double *vals = nullptr;
+        int64_t nnz = 0;
+        with(h, [&](auto *hh) {
+            OMG_REQUIRE(shape, "omg_hierarchy_update_faces: shape is null");
+            OMG_REQUIRE(hh->upd7 && shape[0] == hh->g7[2] && shape[1] == hh->g7[1] && shape[2] == hh->g7[0],
+                        "omg_hierarchy_update_faces: needs a hierarchy that omg_hierarchy_update_fine takes (omg_hierarchy_can_update_fine) "
+                        "whose level 0 is the 7-point operator on the grid `shape`");
+            FaceField F;
+            F.prepare({shape, cz, cy, cx, faces_on_device, walls, sigma, sigma_kind, sigma_on_device}, hh->stream);
+            OMG_REQUIRE(!F.any_periodic(), "omg_hierarchy_update_faces: the hierarchy's fine operator has the in-grid pattern, the walls name a periodic axis");
+            nnz = F.nnz();
+            OMG_REQUIRE(nnz == hh->nnz0, "internal: the fine pattern is not the in-grid 7-point pattern");
+            if (hh->kappa_vals.n != size_t(nnz)) hh->kappa_vals.alloc(size_t(nnz));
+            F.values(hh->kappa_vals.p, hh->stream, "omg_hierarchy_update_faces");
+            vals = hh->kappa_vals.p;
+        });
+        // (the one update path: the values are in HBM)
+        const int rc = omg_hierarchy_update_fine(h, vals, nnz, 1);
+        if (rc != OMG_OK) throw Error(rc, g_last_error);
+    });
+}
+
 int omg_hierarchy_can_update_fine(const omg_hierarchy *h, int *yes) {
     return guarded([&] {
         OMG_REQUIRE(yes, "null argument");

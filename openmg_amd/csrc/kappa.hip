@@ -460,18 +460,25 @@ void KappaField::values(double *data, hipStream_t s, const char *entry) {
     throw Error(OMG_ERR_INVALID, std::string(entry) + ": kappa at " + cell + " is not finite and > 0");
 }
 
-void KappaField::assemble(int32_t *indptr, int32_t *indices, double *data, hipStream_t s, const char *entry) {
-    if (indptr) {
-        const KappaGrid g = {nx, ny, nz};
-        const dim3 grid((unsigned)((rows() + 1 + KAPPA_BLOCK - 1) / KAPPA_BLOCK));
-        if (any_periodic()) {
-            const KappaWrap wr = {periodic[0], periodic[1], periodic[2]};
-            hipLaunchKernelGGL(kappa_pattern_wrap_kernel, grid, dim3(KAPPA_BLOCK), 0, s, g, wr, indptr, indices);
-        } else {
-            hipLaunchKernelGGL(kappa_pattern_kernel, grid, dim3(KAPPA_BLOCK), 0, s, g, indptr, indices);
-        }
-        OMG_HIP(hipGetLastError());
+namespace {
+
+// row pointers and columns of the 7-point pattern on a grid, with the wrapped columns of its periodic axes (z, y, x)
+void launch_pattern(const KappaGrid &g, const int *periodic, int32_t *indptr, int32_t *indices, hipStream_t s) {
+    const int64_t n = int64_t(g.nx) * g.ny * g.nz;
+    const dim3 grid((unsigned)((n + 1 + KAPPA_BLOCK - 1) / KAPPA_BLOCK));
+    if (periodic[0] || periodic[1] || periodic[2]) {
+        const KappaWrap wr = {periodic[0], periodic[1], periodic[2]};
+        hipLaunchKernelGGL(kappa_pattern_wrap_kernel, grid, dim3(KAPPA_BLOCK), 0, s, g, wr, indptr, indices);
+    } else {
+        hipLaunchKernelGGL(kappa_pattern_kernel, grid, dim3(KAPPA_BLOCK), 0, s, g, indptr, indices);
     }
+    OMG_HIP(hipGetLastError());
+}
+
+}  // namespace
+
+void KappaField::assemble(int32_t *indptr, int32_t *indices, double *data, hipStream_t s, const char *entry) {
+    if (indptr) launch_pattern({nx, ny, nz}, periodic, indptr, indices, s);
     values(data, s, entry);
 }
 
@@ -1006,6 +1013,537 @@ void face_divergence(const int64_t *shape, const double *fz, const double *fy, c
     hipLaunchKernelGGL(face_divergence_kernel, grid, dim3(KAPPA_BLOCK), 0, s, g, face[0], face[1], face[2], out_dev);
     OMG_HIP(hipGetLastError());
     if (!out_on_device) download_staged(out, own_out.p, size_t(n) * sizeof(double), s);
+    OMG_HIP(hipStreamSynchronize(s));
+}
+
+// ---- the 7-point operator of one coefficient per FACE (operators.stencil7_faces is the definition) ----------
+// Cz (nz + 1, ny, nx), Cy (nz, ny + 1, nx), Cx (nz, ny, nx + 1) in C order — the arrays the flux kernels write and
+// face_divergence_kernel reads; face m of an axis lies between cell m - 1 and cell m.  The row of cell r = (k ny + j) nx + i
+// loads its six coefficients, the low faces at Cz[r], Cy[r + k nx], Cx[r + k ny + j] (the flux kernel's indices), the high
+// ones nx ny, nx and 1 further on: -C off the diagonal, (((((c-K + c-J) + c-I) + c+I) + c+J) + c+K) (+ sigma) on it.  No
+// division and no product: the launch is loads, one sum chain and the stores.  Every face is loaded by the two rows it
+// couples — lane l's +I is lane l + 1's -I in the same line, the J and K partners some other workgroup's —, so HBM gives
+// each coefficient once and the caches the second time.  A Dirichlet wall's face enters the diagonal only; a Neumann wall's
+// face is +0.0 and not read; on a periodic axis the seam's coefficient is C[0], read by the cells at both ends of the line,
+// and C[e] is not read.  Row starts, the slot rule of wrapped columns and the staged store are kappa_values_kernel's; the
+// pattern kernels are used as they are.
+// Validation: every coefficient a thread reads is checked by it (each twice, at no further load); the error word takes the
+// smallest key (array << 40) | flat index with the arrays in the order Cz, Cy, Cx, sigma.
+namespace {
+
+struct FacesValuesArgs {
+    KappaGrid g;
+    const double *c[3];           // Cz, Cy, Cx
+    const double *sigma;          // null: sigma_value (sigma_kind != 0); else one double (kind 1) or one per cell (kind 2)
+    double sigma_value;
+    int sigma_kind;               // OMG_SIGMA_*
+    int neumann[6];               // -z, +z, -y, +y, -x, +x
+    double *data;
+    unsigned long long *err;
+};
+struct FacesWrapArgs : FacesValuesArgs { KappaWrap wrap; };
+template <bool PERIODIC> using faces_args_t = std::conditional_t<PERIODIC, FacesWrapArgs, FacesValuesArgs>;
+
+constexpr int FACES_KEY_SHIFT = 40;                   // (a flat index is below 2^31)
+
+template <bool STAGED, bool PERIODIC>
+__global__ void __launch_bounds__(KAPPA_BLOCK) faces_values_kernel(faces_args_t<PERIODIC> a) {
+    __shared__ double stage[STAGED ? 7 * KAPPA_BLOCK : 1];
+    const KappaGrid g = a.g;
+    const int64_t n = int64_t(g.nx) * g.ny * g.nz;
+    const int64_t r0 = blockIdx.x * int64_t(KAPPA_BLOCK);
+    const int64_t r = r0 + threadIdx.x;
+    int64_t base = 0;
+    if (STAGED) {
+        int i0, j0, k0;
+        cell_of(g, r0, i0, j0, k0);
+        if constexpr (PERIODIC) base = row_start_wrap(g, a.wrap, r0, i0, j0, k0);
+        else base = row_start(g, r0, i0, j0, k0);
+    }
+    if (r < n) {
+        int i, j, k;
+        cell_of(g, r, i, j, k);
+        // by axis z, y, x: the cell's low face in that axis's array, the step to its high face, the extent
+        const int64_t low[3] = {r, r + int64_t(k) * g.nx, r + int64_t(k) * g.ny + j};
+        const int64_t step[3] = {int64_t(g.nx) * g.ny, g.nx, 1};
+        const int extent[3] = {g.nz, g.ny, g.nx};
+        // the six faces in the order of the diagonal's sum: -K, -J, -I, +I, +J, +K
+        const bool inside[6] = {k > 0, j > 0, i > 0, i + 1 < g.nx, j + 1 < g.ny, k + 1 < g.nz};
+        const int wall[6] = {0, 2, 4, 5, 3, 1};
+        const int axis[6] = {0, 1, 2, 2, 1, 0};
+        const bool high[6] = {false, false, false, true, true, true};
+        bool wrapped[6] = {false, false, false, false, false, false};
+        if constexpr (PERIODIC) {
+            const int periodic[3] = {a.wrap.z, a.wrap.y, a.wrap.x};
+#pragma unroll
+            for (int e = 0; e < 6; ++e) wrapped[e] = !inside[e] && periodic[axis[e]];
+        }
+        unsigned long long bad = ~0ull;
+        double w[6];
+#pragma unroll
+        for (int e = 0; e < 6; ++e) {
+            const int ax = axis[e];
+            if (!inside[e] && !wrapped[e] && a.neumann[wall[e]]) { w[e] = 0.0; continue; }
+            int64_t at = low[ax] + (high[e] ? step[ax] : 0);
+            // (PERIODIC: the seam's coefficient is C[0] — the low face of the line's first cell, `extent` faces back from C[e])
+            if constexpr (PERIODIC)
+                if (wrapped[e] && high[e]) at -= extent[ax] * step[ax];
+            const double c = a.c[ax][at];
+            if (!kappa_ok(c)) {
+                const unsigned long long key = ((unsigned long long)ax << FACES_KEY_SHIFT) | (unsigned long long)at;
+                bad = key < bad ? key : bad;
+            }
+            w[e] = c;
+        }
+        double d = __dadd_rn(__dadd_rn(__dadd_rn(__dadd_rn(__dadd_rn(w[0], w[1]), w[2]), w[3]), w[4]), w[5]);
+        if (a.sigma_kind != OMG_SIGMA_NONE) {
+            const double s = a.sigma ? a.sigma[a.sigma_kind == OMG_SIGMA_FIELD ? r : 0] : a.sigma_value;
+            if (!sigma_ok(s)) {
+                const unsigned long long key = (3ull << FACES_KEY_SHIFT) | (unsigned long long)(a.sigma_kind == OMG_SIGMA_FIELD ? r : 0);
+                bad = key < bad ? key : bad;
+            }
+            d = __dadd_rn(d, s);
+        }
+        if (bad != ~0ull) atomicMin(a.err, bad);
+        int64_t p;
+        if constexpr (PERIODIC) p = row_start_wrap(g, a.wrap, r, i, j, k);
+        else p = row_start(g, r, i, j, k);
+        double *out = STAGED ? stage + (p - base) : a.data + p;
+        int q = 0;
+        // (PERIODIC: before an inner entry comes the wrapped one of the opposite face, whose column lies further down; after it, further up)
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+            if constexpr (PERIODIC)
+                if (wrapped[5 - e]) out[q++] = -w[5 - e];
+            if (inside[e]) out[q++] = -w[e];
+        }
+        out[q++] = d;
+#pragma unroll
+        for (int e = 3; e < 6; ++e) {
+            if (inside[e]) out[q++] = -w[e];
+            if constexpr (PERIODIC)
+                if (wrapped[5 - e]) out[q++] = -w[5 - e];
+        }
+    }
+    if (STAGED) {
+        __syncthreads();
+        const int64_t r1 = r0 + KAPPA_BLOCK < n ? r0 + KAPPA_BLOCK : n;
+        int64_t end;
+        if (r1 == n) {
+            if constexpr (PERIODIC) end = nnz_wrap(g, a.wrap);
+            else end = 7 * n - 2 * (int64_t(g.nx) * g.ny + int64_t(g.nx) * g.nz + int64_t(g.ny) * g.nz);
+        } else {
+            int i1, j1, k1;
+            cell_of(g, r1, i1, j1, k1);
+            if constexpr (PERIODIC) end = row_start_wrap(g, a.wrap, r1, i1, j1, k1);
+            else end = row_start(g, r1, i1, j1, k1);
+        }
+        const int count = int(end - base);                      // <= 7 * KAPPA_BLOCK
+        for (int t = threadIdx.x; t < count; t += KAPPA_BLOCK) a.data[base + t] = stage[t];
+    }
+}
+
+// the entries of the three face arrays of a grid
+void face_counts(int nz, int ny, int nx, int64_t count[3]) {
+    const int64_t n = int64_t(nx) * ny * nz;
+    count[0] = n + int64_t(ny) * nx;
+    count[1] = n + int64_t(nz) * nx;
+    count[2] = n + int64_t(nz) * ny;
+}
+
+}  // namespace
+
+int64_t FaceField::nnz() const {
+    return 7 * rows() - 2 * ((periodic[0] ? 0 : int64_t(nx) * ny) + (periodic[1] ? 0 : int64_t(nx) * nz) + (periodic[2] ? 0 : int64_t(ny) * nz));
+}
+
+void FaceField::prepare(const FacesInput &in, hipStream_t s) {
+    const int64_t *const shape = in.shape;
+    const int *const walls = in.walls;
+    OMG_REQUIRE(shape && in.cz && in.cy && in.cx, "faces: null argument");
+    for (int d = 0; d < 3; ++d)
+        OMG_REQUIRE(shape[d] >= 1 && shape[d] < (int64_t(1) << 30), "faces: every extent of the shape must be >= 1");
+    nz = int(shape[0]); ny = int(shape[1]); nx = int(shape[2]);
+    int64_t count[3];
+    face_counts(nz, ny, nx, count);
+    OMG_REQUIRE(7 * int64_t(nx) * ny * nz < (int64_t(1) << 31) - 1 && count[0] < (int64_t(1) << 31) - 1 && count[1] < (int64_t(1) << 31) - 1 &&
+                    count[2] < (int64_t(1) << 31) - 1,
+                "faces: operator too large for int32 indices");
+    for (int f = 0; f < 6; ++f) {
+        const int wv = walls ? walls[f] : OMG_WALL_DIRICHLET;
+        OMG_REQUIRE(wv == OMG_WALL_DIRICHLET || wv == OMG_WALL_NEUMANN || wv == OMG_WALL_PERIODIC,
+                    "faces: a wall must be OMG_WALL_DIRICHLET or OMG_WALL_NEUMANN, or OMG_WALL_PERIODIC on both walls of an axis");
+        neumann[f] = wv == OMG_WALL_NEUMANN;
+    }
+    for (int d = 0; d < 3; ++d) {
+        static const char *const axis_name[3] = {"z", "y", "x"};
+        const bool lo = walls && walls[2 * d] == OMG_WALL_PERIODIC, hi = walls && walls[2 * d + 1] == OMG_WALL_PERIODIC;
+        periodic[d] = lo && hi;
+        if (lo != hi)
+            throw Error(OMG_ERR_INVALID, std::string("faces: OMG_WALL_PERIODIC must be given for both walls of an axis: only one wall of axis ") +
+                                             axis_name[d] + " has it");
+        if (periodic[d] && shape[d] < 3)
+            throw Error(OMG_ERR_INVALID, std::string("faces: a periodic axis needs an extent >= 3: axis ") + axis_name[d] + " has " +
+                                             std::to_string((long long)shape[d]));
+    }
+    const int kind = in.sigma_kind;
+    OMG_REQUIRE(kind == OMG_SIGMA_NONE || kind == OMG_SIGMA_SCALAR || kind == OMG_SIGMA_FIELD, "faces: sigma_kind must be one of OMG_SIGMA_*");
+    OMG_REQUIRE(kind == OMG_SIGMA_NONE || in.sigma, "faces: sigma is null");
+    sigma_kind = kind;
+    sigma_dev = nullptr;
+    sigma_value = 0.0;
+    if (kind == OMG_SIGMA_SCALAR && !in.sigma_on_device) {
+        sigma_value = in.sigma[0];
+        OMG_REQUIRE(sigma_value >= 0.0 && sigma_value < HUGE_VAL, "faces: sigma must be finite and >= 0");
+    } else if (kind != OMG_SIGMA_NONE) {
+        if (in.sigma_on_device) {
+            sigma_dev = in.sigma;
+        } else {
+            own_sigma.alloc(size_t(nx) * ny * nz);
+            own_sigma.upload(in.sigma, size_t(nx) * ny * nz, s);
+            sigma_dev = own_sigma.p;
+        }
+    }
+    const double *const given[3] = {in.cz, in.cy, in.cx};
+    if (in.faces_on_device) {
+        for (int d = 0; d < 3; ++d) c_dev[d] = given[d];
+    } else {                                            // host arrays: one after the other in one array
+        own_faces.alloc(size_t(count[0] + count[1] + count[2]));
+        size_t at = 0;
+        for (int d = 0; d < 3; ++d) {
+            OMG_HIP(hipMemcpyAsync(own_faces.p + at, given[d], size_t(count[d]) * sizeof(double), hipMemcpyHostToDevice, s));
+            c_dev[d] = own_faces.p + at;
+            at += size_t(count[d]);
+        }
+    }
+    if (!err.p) err.alloc(1);
+}
+
+namespace {
+
+template <bool STAGED, bool PERIODIC>
+void launch_face_values(const FaceField &F, double *data, hipStream_t s) {
+    faces_args_t<PERIODIC> a;
+    a.g = {F.nx, F.ny, F.nz};
+    for (int d = 0; d < 3; ++d) a.c[d] = F.c_dev[d];
+    a.sigma = F.sigma_dev;
+    a.sigma_value = F.sigma_value;
+    a.sigma_kind = F.sigma_kind;
+    for (int f = 0; f < 6; ++f) a.neumann[f] = F.neumann[f];
+    a.data = data;
+    a.err = F.err.p;
+    if constexpr (PERIODIC) a.wrap = {F.periodic[0], F.periodic[1], F.periodic[2]};
+    const dim3 grid((unsigned)((F.rows() + KAPPA_BLOCK - 1) / KAPPA_BLOCK));
+    hipLaunchKernelGGL((faces_values_kernel<STAGED, PERIODIC>), grid, dim3(KAPPA_BLOCK), 0, s, a);
+}
+
+}  // namespace
+
+void FaceField::values(double *data, hipStream_t s, const char *entry) {
+    OMG_HIP(hipMemsetAsync(err.p, 0xFF, sizeof(unsigned long long), s));
+    as_constant(kappa_staged(), [&](auto staged) {
+        as_constant(any_periodic(), [&](auto wrap) { launch_face_values<decltype(staged)::value, decltype(wrap)::value>(*this, data, s); });
+    });
+    OMG_HIP(hipGetLastError());
+    unsigned long long e = ~0ull;
+    OMG_HIP(hipMemcpyAsync(&e, err.p, sizeof(e), hipMemcpyDeviceToHost, s));
+    OMG_HIP(hipStreamSynchronize(s));
+    if (e == ~0ull) return;
+    // the key names an array and a flat index in it: as (k, j, i) of that array's own shape
+    const int which = int(e >> FACES_KEY_SHIFT);
+    const int64_t flat = int64_t(e & ((1ull << FACES_KEY_SHIFT) - 1));
+    const int64_t ex = nx + (which == 2 ? 1 : 0), ey = ny + (which == 1 ? 1 : 0);
+    const std::string at = "(" + std::to_string((long long)(flat / (ex * ey))) + ", " + std::to_string((long long)((flat / ex) % ey)) + ", " +
+                           std::to_string((long long)(flat % ex)) + ")";
+    if (which == 3) throw Error(OMG_ERR_INVALID, std::string(entry) + ": sigma at cell " + at + " is not finite and >= 0");
+    static const char *const name[3] = {"Cz", "Cy", "Cx"};
+    throw Error(OMG_ERR_INVALID, std::string(entry) + ": the coefficient " + name[which] + " at face " + at + " is not finite and > 0");
+}
+
+void FaceField::assemble(int32_t *indptr, int32_t *indices, double *data, hipStream_t s, const char *entry) {
+    if (indptr) launch_pattern({nx, ny, nz}, periodic, indptr, indices, s);
+    values(data, s, entry);
+}
+
+void FaceField::assemble(DevCsrPlain &A, hipStream_t s, const char *entry) {
+    A.n_rows = A.n_cols = rows();
+    A.nnz = nnz();
+    A.indptr.alloc(size_t(A.n_rows) + 1);
+    A.indices.alloc(size_t(A.nnz));
+    A.data.alloc(size_t(A.nnz));
+    assemble(A.indptr.p, A.indices.p, A.data.p, s, entry);
+}
+
+// ---- its right-hand side and its face fluxes (operators.rhs_faces, operators.flux_faces) -----------------------------------
+// faces_rhs_kernel: b = ((((((f + t-K) + t-J) + t-I) + t+I) + t+J) + t+K), one thread per cell, f read and b written at unit
+// stride (b may be f: each thread reads its own f first).  t = C_wall g at a Dirichlet wall with a value — the only lanes that
+// read a coefficient —, the value itself at a Neumann wall (the outward flux through the face, already integrated), +0.0 else.
+// faces_flux_kernel: kappa_flux_kernel's thread-to-face mapping — the thread owns the three low faces of its cell, the last
+// layer's cells their high wall face too, cell 0 of a periodic line face e with the bits of face 0 — with the coefficient
+// LOADED from the face's own place instead of computed: F = C (u_lo - u_hi), one subtraction and one multiplication; the
+// coefficient arrays are read and the outputs written at unit stride along x.  ACCUMULATE: out = out + alpha F.
+namespace {
+
+struct FacesRhsArgs {
+    KappaGrid g;
+    const double *__restrict__ c[3];       // Cz, Cy, Cx; read only at Dirichlet walls with a value
+    double f_value;
+    int kind[6];                           // per wall -z, +z, -y, +y, -x, +x: OMG_VALUE_* (a periodic wall: NONE)
+    int neumann[6];
+    double value[6];
+    const double *__restrict__ field[6];   // one per face of the wall: (ny, nx), (nz, nx), (nz, ny)
+};
+
+template <bool F_FIELD>
+__global__ void __launch_bounds__(KAPPA_BLOCK) faces_rhs_kernel(FacesRhsArgs a, const double *f, double *b) {
+    const KappaGrid g = a.g;
+    const int64_t n = int64_t(g.nx) * g.ny * g.nz;
+    const int64_t r = blockIdx.x * int64_t(KAPPA_BLOCK) + threadIdx.x;
+    if (r >= n) return;
+    double v;
+    if constexpr (F_FIELD) v = f[r];
+    else v = a.f_value;                                // (the scalar; +0.0 for no f)
+    int i, j, k;
+    cell_of(g, r, i, j, k);
+    // the six faces in the order of the sum: -K, -J, -I, +I, +J, +K
+    const bool inside[6] = {k > 0, j > 0, i > 0, i + 1 < g.nx, j + 1 < g.ny, k + 1 < g.nz};
+    const int wall[6] = {0, 2, 4, 5, 3, 1};
+    const int axis[6] = {0, 1, 2, 2, 1, 0};
+    const bool high[6] = {false, false, false, true, true, true};
+    bool valued[6], on_wall = false;
+#pragma unroll
+    for (int e = 0; e < 6; ++e) {
+        valued[e] = !inside[e] && a.kind[wall[e]] != OMG_VALUE_NONE;
+        on_wall = on_wall || valued[e];
+    }
+    double t[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (on_wall) {
+        const int64_t low[3] = {r, r + int64_t(k) * g.nx, r + int64_t(k) * g.ny + j};
+        const int64_t step[3] = {int64_t(g.nx) * g.ny, g.nx, 1};
+        // the cell's face on a z, y, x wall: (j, i) of (ny, nx), (k, i) of (nz, nx), (k, j) of (nz, ny)
+        const int64_t at[3] = {int64_t(j) * g.nx + i, int64_t(k) * g.nx + i, int64_t(k) * g.ny + j};
+#pragma unroll
+        for (int e = 0; e < 6; ++e) {
+            if (!valued[e]) continue;
+            const int w = wall[e], ax = axis[e];
+            double val = a.value[w];
+            if (a.kind[w] == OMG_VALUE_FIELD) val = a.field[w][at[ax]];
+            if (a.neumann[w]) {
+                t[e] = val;
+                continue;
+            }
+            t[e] = __dmul_rn(a.c[ax][low[ax] + (high[e] ? step[ax] : 0)], val);
+        }
+    }
+    b[r] = __dadd_rn(__dadd_rn(__dadd_rn(__dadd_rn(__dadd_rn(__dadd_rn(v, t[0]), t[1]), t[2]), t[3]), t[4]), t[5]);
+}
+
+struct FacesFluxArgs {
+    KappaGrid g;
+    KappaWrap wrap;                        // per axis z, y, x: periodic (read by the PERIODIC instantiations)
+    const double *__restrict__ c[3];       // Cz, Cy, Cx
+    const double *__restrict__ u;          // nz ny nx
+    int kind[6];                           // per wall -z, +z, -y, +y, -x, +x: OMG_VALUE_* (a periodic wall: NONE)
+    int neumann[6];
+    double value[6];
+    const double *__restrict__ field[6];
+    double alpha;                          // ACCUMULATE
+    double *fz, *fy, *fx;
+};
+
+template <bool PERIODIC, bool ACCUMULATE>
+__global__ void __launch_bounds__(KAPPA_BLOCK) faces_flux_kernel(FacesFluxArgs a) {
+    const KappaGrid g = a.g;
+    const int64_t n = int64_t(g.nx) * g.ny * g.nz;
+    const int64_t r = blockIdx.x * int64_t(KAPPA_BLOCK) + threadIdx.x;
+    if (r >= n) return;
+    const double uc = a.u[r];
+    int i, j, k;
+    cell_of(g, r, i, j, k);
+    // by axis z, y, x: the cell's coordinate, the extent, the step to the next cell in u — the step to the next face of that
+    // axis in its face array too —, and the cell's low face
+    const int coord[3] = {k, j, i}, extent[3] = {g.nz, g.ny, g.nx};
+    const int64_t ustep[3] = {int64_t(g.nx) * g.ny, g.nx, 1};
+    const int64_t low[3] = {r, r + int64_t(k) * g.nx, r + int64_t(k) * g.ny + j};
+    double *const out[3] = {a.fz, a.fy, a.fx};
+    const int64_t at[3] = {int64_t(j) * g.nx + i, int64_t(k) * g.nx + i, int64_t(k) * g.ny + j};
+    int periodic[3] = {0, 0, 0};
+    if constexpr (PERIODIC) { periodic[0] = a.wrap.z; periodic[1] = a.wrap.y; periodic[2] = a.wrap.x; }
+    // a wall face of the cell: hi = 0 the low wall of the axis, 1 the high wall
+    auto wall_face = [&](int ax, int hi) __attribute__((always_inline)) -> double {
+        const int w = 2 * ax + hi;
+        const int kind = a.kind[w];
+        double val = a.value[w];                           // (+0.0 without a value)
+        if (kind == OMG_VALUE_FIELD) val = a.field[w][at[ax]];
+        if (a.neumann[w]) {
+            if (kind == OMG_VALUE_NONE) return 0.0;
+            return hi ? -val : val;
+        }
+        const double coeff = a.c[ax][hi ? low[ax] + ustep[ax] : low[ax]];
+        return __dmul_rn(coeff, hi ? __dsub_rn(uc, val) : __dsub_rn(val, uc));
+    };
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) {
+        const int m = coord[ax], e = extent[ax];
+        const bool wraps = PERIODIC && periodic[ax];
+        if (m > 0 || wraps) {
+            // the lo cell: one step back, or e - 1 steps on across the seam (whose coefficient is C[0], this cell's low face)
+            const int back = m > 0 ? 1 : -(e - 1);
+            const double ul = a.u[r - back * ustep[ax]];
+            const double F = __dmul_rn(a.c[ax][low[ax]], __dsub_rn(ul, uc));
+            put_face<ACCUMULATE>(out[ax], low[ax], F, a.alpha);
+            if (m == 0) put_face<ACCUMULATE>(out[ax], low[ax] + e * ustep[ax], F, a.alpha);
+        } else {
+            put_face<ACCUMULATE>(out[ax], low[ax], wall_face(ax, 0), a.alpha);
+        }
+        if (m == e - 1 && !wraps) put_face<ACCUMULATE>(out[ax], low[ax] + ustep[ax], wall_face(ax, 1), a.alpha);
+    }
+}
+
+// what omg_faces_rhs and omg_faces_flux check of shape and walls (call_grid's checks, no scale and no widths), the three
+// coefficient arrays in HBM behind it: `given` where they lie there, else staged one after the other in own_faces (`stage`)
+struct FaceGridOnly {
+    KappaGrid g;
+    int neumann[6];
+    double scale[3];
+};
+
+template <typename Args>
+CallGrid face_call_grid(RhsDevice &dev, hipStream_t s, const std::string &entry, const int64_t *shape, const int *walls, Args &a) {
+    FaceGridOnly only;
+    const CallGrid cg = call_grid(dev, s, entry, shape, walls, nullptr, nullptr, nullptr, nullptr, only);
+    a.g = only.g;
+    for (int w = 0; w < 6; ++w) a.neumann[w] = only.neumann[w];
+    int64_t count[3];
+    face_counts(cg.nz, cg.ny, cg.nx, count);
+    for (int d = 0; d < 3; ++d) OMG_REQUIRE(count[d] < (int64_t(1) << 31) - 1, entry + ": face arrays too large for int32 indices");
+    return cg;
+}
+
+void stage_faces(hipStream_t s, const CallGrid &cg, const double *const given[3], int on_device, bool stage, const double *out[3],
+                 DevBuf<double> &own_faces) {
+    int64_t count[3];
+    face_counts(cg.nz, cg.ny, cg.nx, count);
+    size_t at = 0;
+    if (!on_device && stage) own_faces.alloc(size_t(count[0] + count[1] + count[2]));
+    for (int d = 0; d < 3; ++d) {
+        out[d] = on_device ? given[d] : nullptr;
+        if (on_device || !stage) continue;
+        OMG_HIP(hipMemcpyAsync(own_faces.p + at, given[d], size_t(count[d]) * sizeof(double), hipMemcpyHostToDevice, s));
+        out[d] = own_faces.p + at;
+        at += size_t(count[d]);
+    }
+}
+
+}  // namespace
+
+void faces_rhs(const FacesRhsInput &in) {
+    RhsDevice &dev = rhs_device();
+    std::lock_guard<std::mutex> lock(dev.mu);
+    if (!dev.s) OMG_HIP(hipStreamCreateWithFlags(&dev.s, hipStreamNonBlocking));
+    const hipStream_t s = dev.s;
+    const std::string entry = "omg_faces_rhs";
+    OMG_REQUIRE(in.shape && in.b, "omg_faces_rhs: null argument");
+    FacesRhsArgs a;
+    const CallGrid cg = face_call_grid(dev, s, entry, in.shape, in.walls, a);
+    const int64_t n = cg.n;
+    OMG_REQUIRE(in.f_kind == OMG_VALUE_NONE || in.f_kind == OMG_VALUE_SCALAR || in.f_kind == OMG_VALUE_FIELD, "omg_faces_rhs: f_kind must be one of OMG_VALUE_*");
+    OMG_REQUIRE(in.f_kind == OMG_VALUE_NONE || in.f, "omg_faces_rhs: f is null");
+    OMG_REQUIRE(in.f_kind != OMG_VALUE_SCALAR || !in.f_on_device, "omg_faces_rhs: a scalar f is one double in host memory");
+    DevBuf<double> own_f, own_b, own_faces, own_fields;
+    const double *f_dev = nullptr;
+    double *b_dev = nullptr;
+    a.f_value = in.f_kind == OMG_VALUE_SCALAR ? in.f[0] : 0.0;
+    if (in.b_on_device) {
+        b_dev = in.b;
+    } else {
+        own_b.alloc(size_t(n));
+        b_dev = own_b.p;
+    }
+    if (in.f_kind == OMG_VALUE_FIELD) {
+        if (in.f_on_device) {
+            f_dev = in.f;
+        } else if (!in.b_on_device) {
+            own_b.upload(in.f, size_t(n), s);          // (a host f and a host b: staged in one array, in place)
+            f_dev = own_b.p;
+        } else {
+            own_f.alloc(size_t(n));
+            own_f.upload(in.f, size_t(n), s);
+            f_dev = own_f.p;
+        }
+    }
+    const bool reads_faces = call_values(s, entry, cg, in.value_kinds, in.value_scalars, in.value_fields, in.values_on_device, a, own_fields);
+    OMG_REQUIRE(!reads_faces || (in.cz && in.cy && in.cx), "omg_faces_rhs: a coefficient array is null");
+    const double *const given[3] = {in.cz, in.cy, in.cx};
+    const double *c[3];
+    stage_faces(s, cg, given, in.faces_on_device, reads_faces, c, own_faces);
+    for (int d = 0; d < 3; ++d) a.c[d] = reads_faces ? c[d] : nullptr;
+    const dim3 grid((unsigned)((n + KAPPA_BLOCK - 1) / KAPPA_BLOCK));
+    as_constant(f_dev != nullptr, [&](auto field) {
+        hipLaunchKernelGGL((faces_rhs_kernel<decltype(field)::value>), grid, dim3(KAPPA_BLOCK), 0, s, a, f_dev, b_dev);
+    });
+    OMG_HIP(hipGetLastError());
+    if (!in.b_on_device) download_staged(in.b, own_b.p, size_t(n) * sizeof(double), s);
+    OMG_HIP(hipStreamSynchronize(s));
+}
+
+void faces_flux(const FacesFluxInput &in) {
+    RhsDevice &dev = rhs_device();
+    std::lock_guard<std::mutex> lock(dev.mu);
+    if (!dev.s) OMG_HIP(hipStreamCreateWithFlags(&dev.s, hipStreamNonBlocking));
+    const hipStream_t s = dev.s;
+    const std::string entry = "omg_faces_flux";
+    OMG_REQUIRE(in.shape && in.cz && in.cy && in.cx && in.u && in.fz && in.fy && in.fx, "omg_faces_flux: null argument");
+    OMG_REQUIRE(!in.alpha || (*in.alpha - *in.alpha == 0.0), "omg_faces_flux: alpha must be finite");
+    FacesFluxArgs a;
+    const CallGrid cg = face_call_grid(dev, s, entry, in.shape, in.walls, a);
+    const int64_t n = cg.n;
+    int64_t count[3];
+    face_counts(cg.nz, cg.ny, cg.nx, count);
+    // threads read their neighbours' u, and a coefficient is read by the thread of another face's output: nothing in place
+    double *const out[3] = {in.fz, in.fy, in.fx};
+    const double *const given[3] = {in.cz, in.cy, in.cx};
+    for (int d = 0; d < 3; ++d) {
+        OMG_REQUIRE(!(!!in.out_on_device == !!in.u_on_device && overlaps(out[d], count[d], in.u, n)), "omg_faces_flux: an output overlaps u");
+        for (int e = 0; e < 3; ++e)
+            OMG_REQUIRE(!(!!in.out_on_device == !!in.faces_on_device && overlaps(out[d], count[d], given[e], count[e])),
+                        "omg_faces_flux: an output overlaps a coefficient array");
+        for (int e = 0; e < d; ++e) OMG_REQUIRE(!overlaps(out[d], count[d], out[e], count[e]), "omg_faces_flux: the outputs overlap each other");
+    }
+    a.wrap = {cg.periodic[0], cg.periodic[2], cg.periodic[4]};
+    const bool any_periodic = cg.periodic[0] || cg.periodic[2] || cg.periodic[4];
+    a.alpha = in.alpha ? *in.alpha : 0.0;
+    DevBuf<double> own_u, own_faces, own_fields, own_out;
+    call_values(s, entry, cg, in.value_kinds, in.value_scalars, in.value_fields, in.values_on_device, a, own_fields);
+    const double *c[3];
+    stage_faces(s, cg, given, in.faces_on_device, true, c, own_faces);
+    for (int d = 0; d < 3; ++d) a.c[d] = c[d];
+    a.u = in.u;
+    if (!in.u_on_device) {
+        own_u.alloc(size_t(n));
+        own_u.upload(in.u, size_t(n), s);
+        a.u = own_u.p;
+    }
+    double *face[3] = {in.fz, in.fy, in.fx};
+    if (!in.out_on_device) {                            // host outputs: one after the other in one array, with alpha their old values
+        own_out.alloc(size_t(count[0] + count[1] + count[2]));
+        size_t at = 0;
+        for (int d = 0; d < 3; ++d) {
+            face[d] = own_out.p + at;
+            if (in.alpha) OMG_HIP(hipMemcpyAsync(face[d], out[d], size_t(count[d]) * sizeof(double), hipMemcpyHostToDevice, s));
+            at += size_t(count[d]);
+        }
+    }
+    a.fz = face[0]; a.fy = face[1]; a.fx = face[2];
+    const dim3 grid((unsigned)((n + KAPPA_BLOCK - 1) / KAPPA_BLOCK));
+    as_constant(any_periodic, [&](auto wrap) {
+        as_constant(in.alpha != nullptr, [&](auto acc) {
+            hipLaunchKernelGGL((faces_flux_kernel<decltype(wrap)::value, decltype(acc)::value>), grid, dim3(KAPPA_BLOCK), 0, s, a);
+        });
+    });
+    OMG_HIP(hipGetLastError());
+    if (!in.out_on_device)
+        for (int d = 0; d < 3; ++d) download_staged(out[d], face[d], size_t(count[d]) * sizeof(double), s);
     OMG_HIP(hipStreamSynchronize(s));
 }
 

@@ -458,7 +458,7 @@ def unit_scale(scale):
         return False
 
 
-def stencil7_kappa(kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0), spacing=None):
+def stencil7_kappa(kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0), spacing=None, _terms=None):
     """7-point operator of -div(kappa grad u) + sigma u from a coefficient field (NOT in the reference; the definition the
     device assembly — _hip.kappa_assemble, Solver.from_kappa — is pinned to bit for bit): cell-centred finite volumes on a
     box of (nz, ny, nx) cells.  kappa: float64 (nz + 2, ny + 2, nx + 2), the cells and one ghost layer, as
@@ -539,6 +539,15 @@ def stencil7_kappa(kappa, walls=None, sigma=None, scale=(1.0, 1.0, 1.0), spacing
     diag = ((((w[(-1, 0, 0)] + w[(0, -1, 0)]) + w[(0, 0, -1)]) + w[(0, 0, 1)]) + w[(0, 1, 0)]) + w[(1, 0, 0)]
     if sig is not None:
         diag = diag + (sig * ((own[0] * own[1]) * own[2]) if spacing is not None else sig)
+    if _terms is not None:                                # (face_coefficients_kappa: the six face terms as they entered the diagonal)
+        _terms.update(w)
+    return _assemble7(shape, w, diag, periodic)
+
+
+def _assemble7(shape, w, diag, periodic):
+    """The sorted CSR of a 7-point operator from its per-cell face terms w[(dz, dy, dx)] (problemShape arrays; the
+    off-diagonal entry is -w) and its diagonal: an in-grid neighbour per face, along a periodic axis every cell's."""
+    nz, ny, nx = shape
     n = nx * ny * nz
     idx = np.arange(n, dtype=np.int64).reshape(nz, ny, nx)
     rows, cols, vals = [idx.ravel()], [idx.ravel()], [diag.ravel()]
@@ -817,6 +826,191 @@ def grid_of_faces(shapes):
         if min(shape) >= 1 and shapes == face_shapes(shape):
             return shape
     raise ValueError("the face arrays must have the shapes (nz + 1, ny, nx), (nz, ny + 1, nx), (nz, ny, nx + 1) of one grid, not %r" % (shapes,))
+
+
+def faces_arguments(shapes, walls=None, sigma=None):
+    """What stencil7_faces, _hip.FaceArgs and Solver.from_faces check of their arguments besides the arrays' values:
+    (problemShape, wall codes -z +z -y +y -x +x) from the shapes of the three coefficient arrays (Cz, Cy, Cx); ValueError
+    for shapes that are not one grid's face shapes and for what kappa_arguments refuses of walls and sigma."""
+    try:
+        shape = grid_of_faces(shapes)
+    except TypeError:
+        raise ValueError("faces must be three coefficient arrays (Cz, Cy, Cx) in the face shapes of one grid")
+    shape, wall, _ = kappa_arguments(tuple(s + 2 for s in shape), walls, sigma)
+    return shape, wall
+
+
+def _host_faces(faces):
+    """(Cz, Cy, Cx) as float64 NumPy arrays, problemShape; ValueError for another count, dtype or shapes."""
+    try:
+        faces = tuple(faces)
+    except TypeError:
+        raise ValueError("faces must be three coefficient arrays (Cz, Cy, Cx), not %r" % (faces,))
+    if len(faces) != 3:
+        raise ValueError("faces must be three coefficient arrays (Cz, Cy, Cx), not %d" % len(faces))
+    faces = tuple(np.asarray(a) for a in faces)
+    for name, a in zip(("Cz", "Cy", "Cx"), faces):
+        if a.dtype != np.float64:
+            raise ValueError("the face coefficients %s must be float64, not %s" % (name, a.dtype))
+    return faces
+
+
+def _face_layer(axis, m):
+    sel = [slice(None)] * 3
+    sel[axis] = m
+    return tuple(sel)
+
+
+def stencil7_faces(faces, walls=None, sigma=None):
+    """7-point operator from one coefficient per FACE (NOT in the reference; the definition the device assembly —
+    _hip.faces_assemble, Solver.from_faces — is pinned to bit for bit): faces = (Cz, Cy, Cx), float64 arrays of the shapes
+    face_shapes(problemShape) — (nz + 1, ny, nx), (nz, ny + 1, nx), (nz, ny, nx + 1), the arrays flux_kappa writes and
+    divergence_faces reads.  Along an axis of extent e, face m lies between cell m - 1 and cell m.  The coefficients carry
+    every factor (the mean of the medium, the face area over the distance, the time step): there is no scale and no spacing.
+      - an in-grid face, m = 1 .. e - 1: A[lo, hi] = A[hi, lo] = -C[m].
+      - a Dirichlet wall: C[0] and C[e] enter the diagonal of the cell at the wall only.
+      - a Neumann wall: its face contributes +0.0; its entry of C is never read and may hold anything, NaN too.
+      - a periodic axis (both walls, extent >= 3): the seam's coefficient is C[0]; C[e] is never read (flux_kappa writes the
+        same bits to both, so its output can be fed back as it is).
+    The diagonal is (((((c-K + c-J) + c-I) + c+I) + c+J) + c+K), then + sigma, every operation rounded once in double; sigma:
+    None, a scalar or an array of problemShape, >= 0, with no volume factor.  C-order numbering, sorted CSR with int32
+    indices; the pattern is stencil7_kappa's for the same walls.  walls as stencil7_kappa takes them.
+    stencil7_faces(face_coefficients_kappa(kappa, walls, scale, spacing), walls, sigma) is stencil7_kappa(kappa, walls, sigma,
+    scale, spacing) bit for bit (with spacing: sigma * cell_volumes(spacing) in the former).
+
+    ValueError: three arrays that are not one grid's face shapes or not float64; what kappa_arguments refuses of the walls; a
+    coefficient on a face that is read which is not finite and > 0 (zero — a blocked face — included); a sigma that is not
+    finite and >= 0."""
+    F = _host_faces(faces)
+    shape, wall = faces_arguments(tuple(a.shape for a in F), walls, sigma)
+    periodic = periodic_axes(wall)
+    w = {}
+    for axis in range(3):
+        e, C = shape[axis], F[axis]
+        lo, hi = C[_face_layer(axis, slice(0, e))].copy(), C[_face_layer(axis, slice(1, e + 1))].copy()
+        if periodic[axis]:
+            hi[_face_layer(axis, e - 1)] = C[_face_layer(axis, 0)]
+        if wall[2 * axis] == WALL_CODES["neumann"]:
+            lo[_face_layer(axis, 0)] = 0.0
+        if wall[2 * axis + 1] == WALL_CODES["neumann"]:
+            hi[_face_layer(axis, e - 1)] = 0.0
+        for name, a, w_face in (("low", lo, 2 * axis), ("high", hi, 2 * axis + 1)):
+            read = a
+            if wall[w_face] == WALL_CODES["neumann"]:      # (everything but the wall's own layer, which was replaced)
+                read = a[_face_layer(axis, slice(1, e) if w_face % 2 == 0 else slice(0, e - 1))]
+            if not (np.isfinite(read).all() and (read > 0.0).all()):
+                raise ValueError("the face coefficients C%s must be finite and > 0 on every face that is read" % "zyx"[axis])
+        d = [0, 0, 0]
+        d[axis] = -1
+        w[tuple(d)] = lo
+        d[axis] = 1
+        w[tuple(d)] = hi
+    diag = ((((w[(-1, 0, 0)] + w[(0, -1, 0)]) + w[(0, 0, -1)]) + w[(0, 0, 1)]) + w[(0, 1, 0)]) + w[(1, 0, 0)]
+    if sigma is not None:
+        sig = np.asarray(sigma, dtype=np.float64)
+        if not (np.isfinite(sig).all() and (sig >= 0.0).all()):
+            raise ValueError("sigma must be finite and >= 0")
+        diag = diag + sig
+    # (the order of _assemble7's passes over w is stencil7_kappa's: -K, -J, -I, +I, +J, +K)
+    order = [(-1, 0, 0), (0, -1, 0), (0, 0, -1), (0, 0, 1), (0, 1, 0), (1, 0, 0)]
+    return _assemble7(shape, {d: w[d] for d in order}, diag, periodic)
+
+
+def face_coefficients_kappa(kappa, walls=None, scale=(1.0, 1.0, 1.0), spacing=None):
+    """The three face arrays (Cz, Cy, Cx) of stencil7_kappa(kappa, walls, sigma, scale, spacing) (host only): every in-grid,
+    seam and Dirichlet-wall coefficient as that function rounds it — the seam's in both C[0] and C[e] —, +0.0 on the faces of
+    Neumann walls.  stencil7_faces of them (with the spaced sigma as sigma * cell_volumes(spacing)) is that matrix bit for
+    bit: the face expression is symmetric in its two cells and a face's area is the same seen from both."""
+    terms = {}
+    stencil7_kappa(kappa, walls, None, scale, spacing, _terms=terms)
+    shape = tuple(s - 2 for s in np.shape(kappa))
+    out = []
+    for axis, faces in enumerate(face_shapes(shape)):
+        e = shape[axis]
+        d = [0, 0, 0]
+        d[axis] = -1
+        lo = terms[tuple(d)]
+        d[axis] = 1
+        hi = terms[tuple(d)]
+        C = np.zeros(faces)
+        C[_face_layer(axis, slice(1, e + 1))] = hi         # (face m + 1 as its lo cell m rounds it; the last: the wall's or the seam's)
+        C[_face_layer(axis, 0)] = lo[_face_layer(axis, 0)]
+        out.append(C)
+    return tuple(out)
+
+
+def rhs_faces(faces, f=None, walls=None, values=None):
+    """The right-hand side b that goes with stencil7_faces(faces, walls, sigma) (the definition _hip.faces_rhs and Solver.rhs
+    of a from_faces solver are pinned to bit for bit), a float64 array of problemShape: b = ((((((f + t-K) + t-J) + t-I) +
+    t+I) + t+J) + t+K), every operation rounded once.  A Dirichlet wall with the value g contributes C_wall * g to the cell at
+    it (C_wall = C[0] or C[e], the coefficient the diagonal took); a Neumann wall's value is the OUTWARD flux through that
+    face already integrated over it, t = value with no factor (the coefficients carry every factor, so nothing here knows an
+    area); an in-grid face and a wall without a value contribute +0.0.  Only the cells at a Dirichlet wall with a value
+    read a coefficient; the coefficients' values are not checked.  f, values: as rhs_kappa takes them.
+    ValueError: what stencil7_faces refuses of the arrays' shapes, dtype and the walls; what wall_values_arguments and
+    source_argument refuse."""
+    F = _host_faces(faces)
+    shape, wall = faces_arguments(tuple(a.shape for a in F), walls, None)
+    f = source_argument(shape, f)
+    values = wall_values_arguments(shape, wall, values)
+    volume = np.zeros(shape) if f is None else np.broadcast_to(np.asarray(f, dtype=np.float64), shape).copy()
+    terms = {}
+    for face in range(6):
+        axis, hi = face // 2, face % 2
+        t = np.zeros(shape)
+        terms[face] = t
+        if values[face] is None:
+            continue
+        g = np.asarray(values[face], dtype=np.float64)
+        layer = _face_layer(axis, -1 if hi else 0)
+        if wall[face] == WALL_CODES["neumann"]:
+            t[layer] = g
+        else:
+            t[layer] = F[axis][_face_layer(axis, shape[axis] if hi else 0)] * g
+    return (((((volume + terms[0]) + terms[2]) + terms[4]) + terms[5]) + terms[3]) + terms[1]
+
+
+def flux_faces(faces, u, walls=None, values=None):
+    """The face fluxes (Fz, Fy, Fx) of u under stencil7_faces(faces, walls, sigma) with the boundary data of rhs_faces (the
+    definition _hip.faces_flux and Solver.fluxes of a from_faces solver are pinned to bit for bit), one subtraction and one
+    multiplication per face, each rounded once:
+      - an in-grid face: F[m] = C[m] * (u_lo - u_hi).
+      - a periodic axis: F[0] = F[e] = C[0] * (u_{e-1} - u_0).
+      - a Dirichlet wall: F[0] = C[0] * (g - u_0), F[e] = C[e] * (u_{e-1} - g); g = +0.0 where the wall has no value.
+      - a Neumann wall: +0.0 without a value, nothing read; with a value v (rhs_faces' outward flux) F[0] = v, F[e] = -v.
+    For every u, to rounding: divergence_faces(*flux_faces(faces, u, walls, values)) + sigma u = stencil7_faces(faces, walls,
+    sigma) @ u - rhs_faces(faces, None, walls, values).  The coefficients' values are not checked.
+    ValueError: what rhs_faces refuses; a u of another shape."""
+    C = _host_faces(faces)
+    shape, wall = faces_arguments(tuple(a.shape for a in C), walls, None)
+    values = wall_values_arguments(shape, wall, values)
+    u = np.asarray(solution_argument(shape, u), dtype=np.float64).reshape(shape)
+    periodic = periodic_axes(wall)
+    out = []
+    for axis, fshape in enumerate(face_shapes(shape)):
+        e = shape[axis]
+        F = np.zeros(fshape)
+        inner = _face_layer(axis, slice(1, e))
+        F[inner] = C[axis][inner] * (u[_face_layer(axis, slice(0, e - 1))] - u[inner])
+        first, last = _face_layer(axis, 0), _face_layer(axis, e)
+        if periodic[axis]:
+            seam = C[axis][first] * (u[_face_layer(axis, e - 1)] - u[first])
+            F[first] = seam
+            F[last] = seam
+            out.append(F)
+            continue
+        for side, place, cell in ((0, first, 0), (1, last, e - 1)):
+            w = 2 * axis + side
+            at = _face_layer(axis, cell)
+            if wall[w] == WALL_CODES["neumann"]:
+                if values[w] is not None:
+                    t = np.asarray(values[w], dtype=np.float64)
+                    F[place] = -t if side else t
+                continue
+            g = 0.0 if values[w] is None else np.asarray(values[w], dtype=np.float64)
+            F[place] = C[axis][place] * (u[at] - g if side else g - u[at])
+        out.append(F)
+    return tuple(out)
 
 
 def stencil27_variable(shape, seed=2024, rows=None):
