@@ -69,6 +69,15 @@ extern "C" {
 #define OMG_SMOOTH_LINE_X     4
 #define OMG_SMOOTH_LINE_Y     5
 #define OMG_SMOOTH_LINE_Z     6
+/*   LINE_WRAP a flag OR-ed onto one of the four LINE codes (11 .. 14): the smoothed levels may be PERIODIC.  An axis of
+ *             extent e >= 3 and stride s is periodic on a level when row 0 holds column (e - 1) s; its seam rows then hold
+ *             the wrapped neighbour as well, columns ascending.  Across the lines the wrapped coupling is one more cross
+ *             coupling (the extent must be even there, or the two seam lines had one colour: OMG_ERR_UNSUPPORTED); along the
+ *             lines every line is CYCLIC: its block is tridiagonal with two corner entries, factorised once without
+ *             pivoting (a fill row and a fill column; a zero, non-finite or vanishing pivot: OMG_ERR_INVALID).  On operators
+ *             without wrapped rows the flag changes nothing, bit for bit.  The flag on any other code, and code 7, are
+ *             OMG_ERR_INVALID; the entries that refuse the LINE codes refuse these the same way.                       */
+#define OMG_SMOOTH_LINE_WRAP  8
 
 typedef struct {
     int64_t n_rows, n_cols, nnz;

@@ -21,7 +21,16 @@ Extra keys understood in the `parameters` dict (ignored by the reference):
                 with any point smoother; plane smoothing is not here.
                 Works with every 'accel', 'dtype', 'cycle', 'overCorrection', 'nullspace', 'coarsening', device arrays
                 and Solver; single GPU, the lists setup route, set-by-set launches (no fused passes)
-    'lineAxis'  with 'line': None or 'auto' (default: the axis whose couplings of A_in have the largest sum of |a_ij|, ties
+                or 'line-periodic': 'line' for operators with PERIODIC axes (a channel periodic in x and z, a periodic
+                box; Solver.from_kappa(..., walls=<'periodic' ...>) makes them).  An axis of extent >= 3 is periodic on a
+                level when its seam rows hold the wrapped neighbour (columns ascending).  Across the lines the wrapped
+                coupling is one more cross coupling — such an axis must have an EVEN extent on every smoothed level, or
+                HipError (ERR_UNSUPPORTED) names the level and the extent: choose the depth or 'coarsening' accordingly;
+                along the lines every line is cyclic and solved exactly by a factorisation of the tridiagonal block with
+                its two corner entries (a singular block — no cross couplings, no shift: HipError ERR_INVALID).  On an
+                operator without wrapped rows it is 'line', bit for bit; 'coarsening': 'auto' on a periodic operator
+                stays ERR_UNSUPPORTED (named factors work).  'line' itself keeps refusing periodic operators
+    'lineAxis'  with 'line' / 'line-periodic': None or 'auto' (default: the axis whose couplings of A_in have the largest sum of |a_ij|, ties
                 to the unit-stride axis), or an index into 'problemShape' (C order: the last entry is the unit-stride
                 axis).  The same axis on every level.  Anything else raises ValueError before any device work; mgSolve's
                 infoDict['lineAxis'] (and Solver's info) reports the axis used
@@ -136,13 +145,13 @@ _DEFAULT_OMEGA = 2.0 / 3.0
 def _smoother_of(parameters):
     kind = parameters.get("smoother", "gs")
     code = _hip.smoother_code(kind)
-    if code == _hip.SMOOTH_LINE:
-        # 'line': parameters['lineAxis'] picks the code (None / 'auto': the library scans level 0)
+    if _hip.is_line_smoother(code) and code & ~_hip.SMOOTH_LINE_WRAP == _hip.SMOOTH_LINE:
+        # 'line' / 'line-periodic': parameters['lineAxis'] picks the code (None / 'auto': the library scans level 0)
         axis = parameters.get("lineAxis")
         shape = parameters.get("problemShape")
         if shape is None and not (axis is None or (isinstance(axis, str) and axis == "auto")):
             raise ValueError("parameters['lineAxis'] = %r is an index into parameters['problemShape'], which is missing" % (axis,))
-        code = _hip.line_smoother_code(axis, () if shape is None else shape)
+        code = _hip.line_smoother_code(axis, () if shape is None else shape, wrap=bool(code & _hip.SMOOTH_LINE_WRAP))
     omega = float(parameters.get("omega", _DEFAULT_OMEGA if code == _hip.SMOOTH_JACOBI else 1.0))
     return code, omega
 
@@ -402,15 +411,16 @@ def _setup_semicoarsened(A_in, parameters, coarsening, code, omega, nullspace):
         # the rule treats the line axis apart, so it must know it before the hierarchy exists: 'lineAxis' None / 'auto' is
         # resolved here as the library resolves it (the largest sum of |a_ij|, ties to the unit-stride axis) and then NAMED
         # to the library, so that both use the same axis
-        if code == _hip.SMOOTH_LINE:
+        wrap = bool(code & _hip.SMOOTH_LINE_WRAP)           # ('line-periodic': the flag is stripped before the axis is read)
+        if code & ~_hip.SMOOTH_LINE_WRAP == _hip.SMOOTH_LINE:
             sums = _hip.axis_couplings(A_in, problemShape)[0]
             line_axis = dim - 1
             for axis in range(dim - 2, -1, -1):
                 if sums[axis] > sums[line_axis]:
                     line_axis = axis
-            code = _hip.line_smoother_code(line_axis, problemShape)
+            code = _hip.line_smoother_code(line_axis, problemShape, wrap=wrap)
         else:
-            line_axis = dim - 1 - (code - _hip.SMOOTH_LINE_X)
+            line_axis = dim - 1 - ((code & ~_hip.SMOOTH_LINE_WRAP) - _hip.SMOOTH_LINE_X)
     fused_smoother = code == _hip.SMOOTH_GS_COLOUR or (code == _hip.SMOOTH_JACOBI and dim == 2)
     if fused_smoother and not (parameters["giveInfo"] or parameters["verbose"]):
         R = A = None

@@ -17,6 +17,8 @@ ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_SINGULAR, ERR_NO_DIAGONAL, ERR_ALLOC, E
 SMOOTH_GS_LEX, SMOOTH_GS_COLOUR, SMOOTH_JACOBI = 0, 1, 2
 # zebra line smoother: the strongest axis of level 0 (LINE), or lines along the axis named by stride — X unit stride, Z slowest
 SMOOTH_LINE, SMOOTH_LINE_X, SMOOTH_LINE_Y, SMOOTH_LINE_Z = 3, 4, 5, 6
+# ... OR-ed onto one of those four (11 .. 14): the smoothed levels may be periodic — wrapped neighbours across the lines, cyclic lines along them
+SMOOTH_LINE_WRAP = 8
 PROFILE_CLASSES = 7
 PROFILE_NAMES = ("smoother_set_sweep", "residual", "restrict", "prolong_add", "residual_norm", "plane_down", "plane_up")
 
@@ -26,6 +28,7 @@ SMOOTHERS = {
     "red-black": SMOOTH_GS_COLOUR, "multicolour": SMOOTH_GS_COLOUR,
     "jacobi": SMOOTH_JACOBI, "weighted-jacobi": SMOOTH_JACOBI,
     "line": SMOOTH_LINE, "line-gs": SMOOTH_LINE,
+    "line-periodic": SMOOTH_LINE | SMOOTH_LINE_WRAP,
 }
 
 
@@ -290,18 +293,21 @@ def smoother_code(kind):
 
 
 def is_line_smoother(code):
-    return isinstance(code, int) and SMOOTH_LINE <= code <= SMOOTH_LINE_Z
+    """3 .. 6, and those with SMOOTH_LINE_WRAP: 11 .. 14 (7 and 15 are no codes)"""
+    return isinstance(code, int) and not isinstance(code, bool) and 0 <= code < 16 and SMOOTH_LINE <= (code & ~SMOOTH_LINE_WRAP) <= SMOOTH_LINE_Z
 
 
-def line_smoother_code(line_axis, shape):
+def line_smoother_code(line_axis, shape, wrap=False):
     """The OMG_SMOOTH_LINE* code for parameters['lineAxis']: None / 'auto' (the strongest axis of level 0), or an index into
-    problemShape = shape (C order: the last entry is the unit-stride axis X).  ValueError for anything else."""
+    problemShape = shape (C order: the last entry is the unit-stride axis X).  ValueError for anything else.  wrap: with
+    SMOOTH_LINE_WRAP ('line-periodic')."""
+    flag = SMOOTH_LINE_WRAP if wrap else 0
     if line_axis is None or (isinstance(line_axis, str) and line_axis == "auto"):
-        return SMOOTH_LINE
+        return SMOOTH_LINE | flag
     dim = len(tuple(shape))
     if isinstance(line_axis, bool) or not isinstance(line_axis, (int, np.integer)) or not 0 <= int(line_axis) < dim or dim > 3:
         raise ValueError("lineAxis must be None, 'auto' or an index into problemShape (0 .. %d), not %r" % (dim - 1, line_axis))
-    return SMOOTH_LINE_X + (dim - 1 - int(line_axis))
+    return (SMOOTH_LINE_X + (dim - 1 - int(line_axis))) | flag
 
 
 CYCLE_V, CYCLE_F, CYCLE_W = 0, 1, 2

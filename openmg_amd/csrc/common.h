@@ -111,7 +111,11 @@ inline void refuse_nullspace_tail(const omg_hierarchy *tail) {
                                          "and the iterate (single-GPU entries only)");
 }
 // ... and know nothing of the line smoother: a smoother code of theirs, or a tail hierarchy, that names it is refused
-inline bool is_line_smoother(int smoother) { return smoother >= OMG_SMOOTH_LINE && smoother <= OMG_SMOOTH_LINE_Z; }
+// (with or without OMG_SMOOTH_LINE_WRAP: 3 .. 6 and 11 .. 14; the axis of a named one is (code & ~8) - OMG_SMOOTH_LINE_X)
+inline bool is_line_smoother(int smoother) {
+    const int base = smoother & ~OMG_SMOOTH_LINE_WRAP;
+    return smoother >= 0 && smoother <= (OMG_SMOOTH_LINE_Z | OMG_SMOOTH_LINE_WRAP) && base >= OMG_SMOOTH_LINE && base <= OMG_SMOOTH_LINE_Z;
+}
 inline void refuse_line_smoother(int smoother, const char *entry) {
     if (is_line_smoother(smoother))
         throw Error(OMG_ERR_UNSUPPORTED, std::string(entry) + ": the line smoother (OMG_SMOOTH_LINE*) runs in hierarchies made by omg_hierarchy_create* only");
@@ -1262,20 +1266,25 @@ struct LineGeom {
     int ncross = 0;                   // neighbouring lines of a line: 4 (3-D) or 2 (2-D)
     int64_t nl[2] = {0, 0};           // lines per colour
     int64_t base[2] = {0, 0};         // first slot of each colour
+    bool cyclic = false;              // OMG_SMOOTH_LINE_WRAP: the lines' axis is periodic on this level (the lines close on themselves)
 };
 template <typename V>
 struct LinePlan {
     LineGeom g;
     DevBuf<V> cross;                  // [ncross][slot]: couplings to the lines q - 1, q + 1, p - 1, p + 1 (q the faster other axis)
     DevBuf<V> upper, inv_pivot, factor;   // [slot]: the line's super-diagonal, 1 / p_i, f_i = l_i / p_{i-1}
+    DevBuf<V> fill_row, fill_col;     // [slot], cyclic lines only: the last row (h_i) and the last column (g_i) of the block's LU
     DevBuf<int32_t> nbr;              // [colour][ncross][line]: the neighbouring line's rank among the other colour's lines
     // A: the level's operator in natural numbering; axis as LineGeom::axis.  Writes ord.  Throws OMG_ERR_UNSUPPORTED when A is
     // not such a stencil, OMG_ERR_INVALID for a zero or non-finite pivot or an axis the grid does not have.
-    void build(const omg_csr &A, int axis, Ordering &ord, hipStream_t s);
+    // wrap (OMG_SMOOTH_LINE_WRAP): the level may be periodic — an axis of extent e >= 3 and stride s is, when row 0 holds
+    // column (e - 1) s.  Across the lines its extent must be even (OMG_ERR_UNSUPPORTED); along them the lines are cyclic.
+    void build(const omg_csr &A, int axis, Ordering &ord, hipStream_t s, bool wrap = false);
     void sweep(V *x, const V *b, hipStream_t s) const;   // one in-place zebra sweep: two launches
 };
-// the axis (as LineGeom::axis) whose couplings have the largest sum of |a_ij|; ties go to the smaller stride
-int line_auto_axis(const omg_csr &A);
+// the axis (as LineGeom::axis) whose couplings have the largest sum of |a_ij|; ties go to the smaller stride.  wrap: the
+// wrapped couplings of a periodic axis count towards it
+int line_auto_axis(const omg_csr &A, bool wrap = false);
 
 // ---- 27-point grid stencils with per-row coefficients: BASELINE configs[4] (stencil27.hip) ----------------
 // A level whose operator holds, in every row, exactly the in-grid neighbours of a 27-point stencil on a

@@ -1637,7 +1637,10 @@ std::unique_ptr<Hier<V>> create(int n_levels, const omg_csr *A, const omg_csr *R
     using Lv = Level<V>;
     OMG_REQUIRE(n_levels >= 1, "n_levels must be >= 1");
     OMG_REQUIRE(A != nullptr && (n_levels == 1 || R != nullptr), "A / R array is null");
-    OMG_REQUIRE(smoother >= OMG_SMOOTH_GS_LEX && smoother <= OMG_SMOOTH_LINE_Z, "unknown smoother");
+    // (OMG_SMOOTH_LINE_WRAP is a flag on the four line codes alone: 11 .. 14)
+    OMG_REQUIRE((smoother >= OMG_SMOOTH_GS_LEX && smoother <= OMG_SMOOTH_LINE_Z) || is_line_smoother(smoother), "unknown smoother");
+    const bool line_wrap = is_line_smoother(smoother) && (smoother & OMG_SMOOTH_LINE_WRAP) != 0;
+    const int line_code = smoother & ~OMG_SMOOTH_LINE_WRAP;
     for (int l = 0; l < n_levels; ++l) {
         validate_csr(A[l], ("A[" + std::to_string(l) + "]").c_str());
         OMG_REQUIRE(A[l].n_rows == A[l].n_cols, "A[l] must be square");
@@ -1654,7 +1657,7 @@ std::unique_ptr<Hier<V>> create(int n_levels, const omg_csr *A, const omg_csr *R
     // (the line smoother's axis: the caller's, or the strongest of level 0 — before the helper thread starts: a refusal costs nothing)
     if (is_line_smoother(smoother) && n_levels > 1) {
         try {
-            h->line_axis = smoother == OMG_SMOOTH_LINE ? line_auto_axis(A[0]) : smoother - OMG_SMOOTH_LINE_X;
+            h->line_axis = line_code == OMG_SMOOTH_LINE ? line_auto_axis(A[0], line_wrap) : line_code - OMG_SMOOTH_LINE_X;
         } catch (const Error &e) {
             throw Error(e.code, std::string("level 0: ") + e.what());
         }
@@ -1670,7 +1673,7 @@ std::unique_ptr<Hier<V>> create(int n_levels, const omg_csr *A, const omg_csr *R
             SetupTimer tl("line smoother: the level's grid, its ordering, the lines' factorisations");
             std::unique_ptr<LinePlan<V>> plan(new LinePlan<V>);
             try {
-                plan->build(A[l], h->line_axis, L.ord, h->stream);
+                plan->build(A[l], h->line_axis, L.ord, h->stream, line_wrap);
             } catch (const Error &e) {
                 throw Error(e.code, "level " + std::to_string(l) + ": " + e.what());
             }
